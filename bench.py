@@ -3,6 +3,14 @@
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --full ...                               (the headline plus every other leg, see below)
+    python bench.py ... --dump-outputs DIR                   (the last timed step's outputs as DIR/<name>.npy)
+
+A plain run does only what the headline needs: set-up, W warm-up passes (each one runs the pairs a round keeps in flight),
+ONE timed region of exactly K steps, the outputs of its last step if --dump-outputs is given, and the JSON line
+(`value`, `ms_per_step` and the config of the timed command).  Everything else -- the repeated timed region (--reps,
+5 by default under --full), the other f64 mode, loop_ends, single_pair, fixed_work / roofline / roofline_4k, cli, sor,
+occ, cpu_baseline -- runs only with --full; the --no-* options switch single legs of a --full run off.
 
 Workloads (--workload):
   1080p     (default, BASELINE configs[1], the configuration the metric is quoted on)  One "step" = one synthetic
@@ -19,7 +27,7 @@ N > 1: no data-path collective (pairs are independent); the timed region ends wi
 payloads to rank 0.  The pairs of a rank are solved in ROUNDS and the gather of round r runs (asynchronously, RCCL's
 own stream) while round r + 1 computes, so only the last round's transfer is exposed (`gather_ms`).
 
-The line also carries: `fixed_work` (option "fixed_work": every warp runs exactly 300 iterations, SURVEY 8d);
+With --full the line also carries: `fixed_work` (option "fixed_work": every warp runs exactly 300 iterations, SURVEY 8d);
 `roofline` / `roofline_4k` for the dominant kernel k_tvl1_iter2 as the job launches it (one launch = a lockstep group of
 up to 16 pairs), measured on fixed-work passes with HIP events on the library's own stream, with the one-pair launch beside
 it (`single_pair`); `sor` (BASELINE configs 3 / 4: Horn-Schunck and Brox solves, exact and tolerance mode); `occ` (TV-L1 with occlusions); `cpu_baseline` (the compiled
@@ -49,15 +57,25 @@ ARITH = {"strict": "f64 storage and arithmetic, every per-pixel operation in the
                       "reference ~1e-12 px on every BASELINE config (this line's cpu_baseline.gpu_vs_this_reference_run; bar: 1e-4), iteration "
                       "tables equal on all of them"}
 WORKLOADS = {"1080p": (1920, 1080), "4k-batch": (3840, 2160)}
+DUMP_BYTES = 64 * 10 ** 6                                # --dump-outputs: all files together at most this size
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="pairs per rank (1080p, default 64) / pairs of the batch (4k-batch, default 64)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5,
-                    help="repetitions of the timed K-step region (each one bracketed by barrier + sync); the median one is reported")
+    ap.add_argument("--steps", type=int, default=0,
+                    help="timed steps = pairs per rank (1080p, default 64) / pairs of the batch (4k-batch, default 64)")
+    ap.add_argument("--warmup", type=int, default=2,
+                    help="warm-up passes, each over the pairs in flight of a round (contexts x lockstep group, at most K)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline (repetitions, other f64 mode, single_pair, fixed_work / roofline, "
+                         "cli, sor, occ, cpu_baseline); a plain run times the K steps once and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (its .flo payload, float32, and its "
+                         "pixel-iterations, float64) as DIR/<name>.npy, at most 64 MB in all (rank 0)")
+    ap.add_argument("--reps", type=int, default=0,
+                    help="repetitions of the timed K-step region (each one bracketed by barrier + sync); the median one is "
+                         "reported.  0 = 1 on a plain run, 5 with --full")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="1080p")
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64")
     ap.add_argument("--mode", choices=["tolerance", "strict"], default="tolerance",
@@ -138,6 +156,25 @@ def split_rounds(n, rounds, nstreams):
         out.append((first, cnt))
         first += cnt
     return out
+
+
+def dump_outputs(d, flow, pix_iters):
+    """--dump-outputs: the last timed step's results as the caller of ofx_tvl1_batch_dev receives them -- the float32 .flo
+    payload (ny, nx, 2) of that pair and its work in pixel-iterations (float64, shape (1,)).  A payload larger than the
+    budget is written as every s-th row (`flow_rows_stride<s>`, s the smallest stride that fits), the same rows on every
+    run with the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    flow = np.ascontiguousarray(flow, dtype=np.float32)
+    work = np.asarray([pix_iters], dtype=np.float64)
+    name, room = "flow", DUMP_BYTES - work.nbytes - 2 * 128      # .npy headers: 128 bytes each
+    if flow.nbytes > room:
+        stride = -(-flow.nbytes // room)
+        while flow[::stride].nbytes > room:
+            stride += 1
+        name, flow = "flow_rows_stride%d" % stride, np.ascontiguousarray(flow[::stride])
+    np.save(os.path.join(d, name + ".npy"), flow)
+    np.save(os.path.join(d, "pix_iters.npy"), work)
+    return [name, "pix_iters"]
 
 
 def cpu_baseline(synth, nx, ny, pair, gpu_flows=None):
@@ -588,6 +625,7 @@ def occ_leg(ofx_mod, synth, local):
 
 def main():
     a = parse()
+    a.reps = a.reps if a.reps > 0 else (5 if a.full else 1)
     if "RANK" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a))
     import torch
@@ -676,6 +714,8 @@ def main():
     flo = torch.empty((max(slots, in_flight, 1), ny, nx, 2), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
 
+    last_work = [0.0]
+
     def run_pairs(first, cnt):
         """pairs [first, first + cnt) of this rank through the library's batch entry point: cut into lockstep groups of
         `lockstep` pairs that share every kernel launch; group q runs on context q % nstreams (one host thread + one
@@ -686,6 +726,7 @@ def main():
         work = ofx_mod.tvl1_batch_dev(ctxs, [dI0s[var_of(i)].data_ptr() for i in idx],
                                       [dI1s[var_of(i)].data_ptr() for i in idx],
                                       [flo[i % flo.shape[0]].data_ptr() for i in idx], nx, ny, **PAR)
+        last_work[0] = work[-1]                          # work of pair first + cnt - 1 (--dump-outputs)
         return sum(work)
 
     def fence():
@@ -733,8 +774,8 @@ def main():
         el = time.perf_counter() - t0
         return el, (el - t_compute) * 1e3, work
 
-    # The region is short (20 pairs = 57 ms), so it is repeated and the MEDIAN repetition is reported (`value`,
-    # `ms_per_step`, `gather_ms` all from that one repetition); the spread goes into `repetitions`.
+    # A plain run times the K steps once.  With --full (or --reps R) the region is repeated and the MEDIAN repetition is
+    # reported (`value`, `ms_per_step`, `gather_ms` all from that one repetition); the spread goes into `repetitions`.
     reps = [timed_region() for _ in range(max(1, a.reps))]
     if world > 1:
         t = torch.tensor([r_[0] for r_ in reps], dtype=torch.float64, device=dev)
@@ -750,6 +791,10 @@ def main():
         torch.cuda.synchronize()
     log("timed region: %d pairs, %d repetitions %s s -> median %.4f s (exposed gather %.2f ms)"
         % (nsteps, len(reps), [round(x, 4) for x in rep_s], elapsed, gather_ms))
+    if a.dump_outputs and rank == 0 and nsteps > 0:
+        # the last timed step = this rank's last pair, whose payload the timed region left in its slot of `flo`
+        names = dump_outputs(a.dump_outputs, flo[(nsteps - 1) % flo.shape[0]].cpu().numpy(), last_work[0])
+        log("outputs of the last timed step (pair %d): %s in %s" % (mine[nsteps - 1], names, a.dump_outputs))
 
     gather_check = None
     if a.check and world > 1 and rank == 0:
@@ -783,7 +828,7 @@ def main():
     # how the loops of this workload end (one lockstep group, untimed): a loop that stops on the first iteration of a
     # fused pair continues from the stored intermediate state (option store_a) or recomputes that iteration
     odd = None
-    if rank == 0 and nsteps > 0:
+    if a.full and rank == 0 and nsteps > 0:
         gsz = min(lockstep, nsteps)
         st_ = ctx.tvl1_group_dev([dI0s[var_of(i)].data_ptr() for i in range(gsz)], [dI1s[var_of(i)].data_ptr() for i in range(gsz)],
                                  [flo[i].data_ptr() for i in range(gsz)], nx, ny, **PAR)
@@ -797,7 +842,7 @@ def main():
     # ---- the other f64 mode on the same command (same pairs, same grouping, same repetitions) ---------------------------------
     other = None
     other_name = "strict" if a.mode == "tolerance" else "tolerance"
-    if world == 1 and nsteps > 0 and not a.no_other_mode:
+    if a.full and world == 1 and nsteps > 0 and not a.no_other_mode:
         for c_ in ctxs:
             c_.set_option("relaxed_dual", 1 if other_name == "tolerance" else 0)
         run_pairs(0, min(in_flight, max(nsteps, 1)))            # warm
@@ -814,7 +859,7 @@ def main():
 
     # ---- one pair at a time (BASELINE configs[0] / [1] read literally: what bin/tvl1flow runs) ---------------------------
     single = None
-    if rank == 0 and nsteps > 0 and not a.no_single:
+    if a.full and rank == 0 and nsteps > 0 and not a.no_single:
         ctx.set_option("concurrency", 1)
         npair = min(nvar, 8)
         ctx.tvl1_multiscale_dev(dI0s[0].data_ptr(), dI1s[0].data_ptr(), flo[0].data_ptr(), nx, ny, **PAR)    # warm
@@ -852,7 +897,7 @@ def main():
 
     # ---- fixed-work pass + roofline (rank 0's numbers are reported; every rank runs it to stay in step) ----
     fixed, roof, roof4k = None, None, None
-    if a.fixed_steps > 0 and nsteps > 0:
+    if a.full and a.fixed_steps > 0 and nsteps > 0:
         # (a) throughput of the fixed-work job with the same number of pairs in flight as the headline
         for c_ in ctxs:
             c_.set_option("fixed_work", 1)
@@ -909,19 +954,19 @@ def main():
             roof4k = None
 
     cli = None
-    if rank == 0 and world == 1 and not a.no_cli:
+    if a.full and rank == 0 and world == 1 and not a.no_cli:
         cli = cli_leg(synth, local)
         log("cli leg done")
     sor = None
-    if rank == 0 and world == 1 and not a.no_sor:
+    if a.full and rank == 0 and world == 1 and not a.no_sor:
         sor = sor_leg(ofx_mod, synth, local, dev, with_cpu=not a.no_cpu)
         log("sor leg done")
     occ = None
-    if rank == 0 and world == 1 and not a.no_occ:
+    if a.full and rank == 0 and world == 1 and not a.no_occ:
         occ = occ_leg(ofx_mod, synth, local)
         log("occ leg done")
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cnx, cny = WORKLOADS["1080p"] if strong else (nx, ny)
 
         def gpu_flows(k, I0, I1):

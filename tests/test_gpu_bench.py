@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,7 +33,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_one_gpu_line_has_roofline_keys():
-    d = run_bench(["--gpus", "1", "--steps", "8"] + SMALL)
+    d = run_bench(["--full", "--gpus", "1", "--steps", "8"] + SMALL)
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 8 and d["scaling"] == "weak" and d["value"] > 0
@@ -80,10 +81,40 @@ def test_bench_4k_batch_workload_shards_pairs_over_ranks():
 def test_bench_4k_batch_workload_on_one_gpu_at_full_size():
     """`bench.py --workload 4k-batch --steps 4 --gpus 1`: BASELINE config 5's size (3840x2160) on the one GPU, the launch
     shape roofline_4k quotes (lockstep groups, non-temporal stores); the line must carry the contract keys and a roofline."""
-    d = run_bench(["--gpus", "1", "--workload", "4k-batch", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-sor", "--no-cli", "--no-occ",
-                   "--fixed-steps", "1"])
+    d = run_bench(["--full", "--gpus", "1", "--workload", "4k-batch", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-sor", "--no-cli",
+                   "--no-occ", "--fixed-steps", "1"])
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["workload_name"] == "4k-batch" and "3840x2160" in d["config"]["workload"]
     assert 0 < d["roofline"]["frac"] <= 1.0 and "3840x2160" in d["roofline"]["kernel"]
+
+
+# what only `--full` measures: a plain run must not spend time on any of it
+FULL_ONLY = ("strict", "tolerance", "single_pair", "loop_ends", "fixed_work", "roofline", "roofline_4k", "sor", "cli", "occ",
+             "cpu_baseline")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_bench_plain_run_times_k_steps_once_and_dumps_the_last_step(tmp_path, orc, synth):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline alone, ONE timed region of exactly K steps,
+    and the .flo payload of the last step (pair K - 1 of the cycled variants) with its work -- the same bytes on a second run
+    with the same arguments, and the flow of that pair as the oracle computes it."""
+    args = ["--gpus", "1", "--steps", "11", "--warmup", "1", "--nx", "320", "--ny", "240"]
+    d = run_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    for k in CONTRACT:
+        assert k in d, k
+    assert not [k for k in FULL_ONLY if k in d], [k for k in FULL_ONLY if k in d]
+    assert d["steps"] == 11 and d["repetitions"]["n"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["ms_per_step"] * 11 - d["repetitions"]["seconds"][0] * 1e3) < 0.01 * d["ms_per_step"] * 11 + 0.01
+    assert sorted(os.listdir(tmp_path / "a")) == ["flow.npy", "pix_iters.npy"]
+    flow, work = np.load(tmp_path / "a" / "flow.npy"), np.load(tmp_path / "a" / "pix_iters.npy")
+    assert flow.dtype == np.float32 and flow.shape == (240, 320, 2) and np.isfinite(flow).all()
+    assert work.dtype == np.float64 and work.shape == (1,) and work[0] > 0
+    I0, I1 = synth.pair("P1", 320, 240, 10 % 8)                   # step 10 of rank 0: variant 10 mod 8
+    uo, vo, _, _ = orc.tvl1_multiscale(I0, I1, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5, epsilon=0.01)
+    assert float(np.mean(np.hypot(flow[..., 0] - uo, flow[..., 1] - vo))) < 1e-4
+    run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    for f in ("flow.npy", "pix_iters.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

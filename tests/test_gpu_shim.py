@@ -1,6 +1,7 @@
 """Link compatibility: tests/shim/shim_driver.cpp is a caller written against the reference's own headers and
-function names; its definitions come from include/ofx_reference_shim.hpp + libofx.so.  Built in the build container
-(tests/shim/Makefile, needs /root/reference for the headers), run here on the GPU and compared with the oracle."""
+function names; its definitions come from include/ofx_reference_shim.hpp + libofx.so.  Built by build() where the
+reference's headers are (oracle/Makefile, target `shim`, into oracle/_ref/ with the compiled reference), run here on the
+GPU and compared with the oracle."""
 import os
 import struct
 import subprocess
@@ -12,11 +13,11 @@ from conftest import require_or_skip
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "tests", "shim", "_build", "shim_driver")
+DRIVER = os.path.join(ROOT, "oracle", "_ref", "shim_driver")
 
 
 def test_reference_prototypes_through_the_shim(orc, synth, tmp_path):
-    require_or_skip(os.path.exists(DRIVER), "tests/shim/_build/shim_driver not built (needs /root/reference headers at build time)")
+    require_or_skip(os.path.exists(DRIVER), "oracle/_ref/shim_driver not built (needs the reference's headers at build time)")
     nx, ny, frames = 96, 64, 4
     seq = synth.sequence(nx, ny, frames)
     with open(tmp_path / "in.bin", "wb") as f:

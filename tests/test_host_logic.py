@@ -407,3 +407,21 @@ def test_staging_route_of_the_cross_gpu_batch():
     assert f(0, -1, 1) == 1 and f(0, -1, 0) == 1           # host memory: one copy
     assert f(0, 1, 1) == 1                                 # another GPU, peer access: one copy over xGMI
     assert f(0, 1, 0) == 2 and f(5, 2, 0) == 2             # no peer access: through a host bounce buffer
+
+
+def test_bench_dump_outputs_files_types_and_budget(tmp_path):
+    """bench.py --dump-outputs: float32 payload + float64 work as .npy; a payload over the 64 MB budget (3840x2160, the
+    4k-batch workload) is written as every s-th row, s the smallest stride that fits, the same rows every time."""
+    import bench
+    small = np.arange(48 * 64 * 2, dtype=np.float32).reshape(48, 64, 2)
+    assert bench.dump_outputs(str(tmp_path / "s"), small, 1234.0) == ["flow", "pix_iters"]
+    assert np.array_equal(np.load(tmp_path / "s" / "flow.npy"), small)
+    w = np.load(tmp_path / "s" / "pix_iters.npy")
+    assert w.dtype == np.float64 and w.tolist() == [1234.0]
+    big = np.random.default_rng(5).standard_normal((2160, 3840, 2)).astype(np.float32)
+    names = bench.dump_outputs(str(tmp_path / "b"), big, 7.0)
+    assert names == ["flow_rows_stride2", "pix_iters"]
+    got = np.load(tmp_path / "b" / "flow_rows_stride2.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, big[::2])
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= bench.DUMP_BYTES

@@ -28,7 +28,7 @@ for r in range(rounds):
                 env[k] = v.replace(";", ",")
             else:
                 opts += ["--opt", o]
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"] + extra.split() + opts
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5"] + extra.split() + opts
         p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
         if p.returncode:
             print(name, "FAILED", p.stderr[-500:])

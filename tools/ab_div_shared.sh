@@ -16,6 +16,6 @@ echo "== shared-denominator division"
 OFX_LIB_PATH=$R/variants/libofx_div_shared.so timeout -k 10 300 python tools/tune_iter.py --quick 2>&1 | grep -v amdgpu.ids
 for v in production div_shared; do
   L=$R/optical-flow-1_amd/libofx.so; [ $v = div_shared ] && L=$R/variants/libofx_div_shared.so
-  OFX_LIB_PATH=$L timeout -k 10 300 python bench.py --no-cpu --no-sor --no-4k > /tmp/ab_$v.json 2> /tmp/ab_$v.err
+  OFX_LIB_PATH=$L timeout -k 10 300 python bench.py --full --no-cpu --no-sor --no-4k > /tmp/ab_$v.json 2> /tmp/ab_$v.err
   python -c "import json;d=json.load(open('/tmp/ab_$v.json'));print('$v: value',d['value'],'fixed',d['fixed_work']['value'],'launch us',d['roofline']['avg_launch_us'])"
 done

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for pass in "$@"; do
   rm -rf /tmp/pmck
-  timeout -k 10 250 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d /tmp/pmck -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --fixed-steps 0 --streams 1 --lockstep 1 > /tmp/pmck.json 2> /tmp/pmck.err
+  timeout -k 10 250 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d /tmp/pmck -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --fixed-steps 0 --streams 1 --lockstep 1 > /tmp/pmck.json 2> /tmp/pmck.err
   python3 - "$pat" "$gx" <<'PY'
 import collections, csv, glob, sys
 pat, gx = sys.argv[1], int(sys.argv[2])
