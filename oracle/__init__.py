@@ -327,6 +327,61 @@ class Oracle(_Lib):
                         C.c_double, C.c_int)(u1, u2, p11, p12, p21, p22, _f64(I1wx), _f64(I1wy), _f64(rho_c),
                                              _f64(grad), nx, ny, tau, lam, theta, n_iter)
 
+    # ---- the HIP path's non-strict modes restated (checker aids; relaxed = store_f32 = 0 is the reference) ----------
+    def tvl1_iterations_mode(self, u1, u2, p11, p12, p21, p22, I1wx, I1wy, rho_c, grad, tau, lam, theta, n_iter, relaxed=0,
+                             store_f32=0):
+        """tvl1_iterations in the f64 tolerance mode (relaxed = 1) and / or float storage (store_f32 = 1: the six state
+        arrays are rounded to float in place first, grad is recomputed from the rounded I1wx / I1wy)."""
+        ny, nx = u1.shape
+        g = np.zeros((ny, nx)) if grad is None else grad
+        return self._fn("tvl1_iterations_mode", C.c_double, *([_dp] * 10), C.c_int, C.c_int, C.c_double, C.c_double,
+                        C.c_double, C.c_int, C.c_int, C.c_int)(u1, u2, p11, p12, p21, p22, _f64(I1wx), _f64(I1wy), _f64(rho_c),
+                                                               _f64(g), nx, ny, tau, lam, theta, n_iter, int(relaxed),
+                                                               int(store_f32))
+
+    def tvl1_single_scale_mode(self, I0, I1, u1, u2, tau=0.25, lam=0.15, theta=0.3, warps=5, epsilon=0.01, verbose=0,
+                               relaxed=0):
+        ny, nx = I0.shape
+        u1, u2 = _f64(u1).copy(), _f64(u2).copy()
+        iters = (C.c_int * warps)()
+        errs = np.zeros(warps)
+        self._fn("tvl1_single_scale_mode", None, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double,
+                 C.c_double, C.c_int, C.c_double, C.c_int, _ip, _dp, C.c_int)(
+            _f64(I0), _f64(I1), u1, u2, nx, ny, tau, lam, theta, warps, epsilon, verbose, iters, errs, int(relaxed))
+        return u1, u2, list(iters), errs
+
+    def tvl1_multiscale_mode(self, I0, I1, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5,
+                             epsilon=0.01, verbose=0, relaxed=0):
+        ny, nx = I0.shape
+        u1, u2 = np.zeros((ny, nx)), np.zeros((ny, nx))
+        iters = (C.c_int * (warps * nscales))()
+        errs = np.zeros(warps * nscales)
+        rc = self._fn("tvl1_multiscale_mode", C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double,
+                      C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _ip, _dp, C.c_int)(
+            _f64(I0), _f64(I1), u1, u2, nx, ny, tau, lam, theta, nscales, zfactor, warps, epsilon, verbose,
+            iters, errs, int(relaxed))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return u1, u2, np.array(list(iters)).reshape(nscales, warps), errs.reshape(nscales, warps)
+
+    def gaussian_mode(self, I, sigma, store_f32=0):
+        ny, nx = I.shape
+        out = _f64(I).copy()
+        rc = self._fn("gaussian_mode", C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int)(out, nx, ny, sigma, int(store_f32))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return out
+
+    def zoom_out_mode(self, I, factor, store_f32=0):
+        ny, nx = I.shape
+        nxx, nyy = self.zoom_size(nx, ny, factor)
+        out = np.empty((nyy, nxx))
+        rc = self._fn("zoom_out_mode", C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int)(
+            _f64(I), out, nx, ny, factor, int(store_f32))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return out
+
     def hs_single_scale(self, I1, I2, u, v, alpha=7.0, warps=10, TOL=1e-4, maxiter=150, verbose=0):
         ny, nx = I1.shape
         u, v = _f64(u).copy(), _f64(v).copy()

@@ -31,6 +31,9 @@
 #define BROX_SOR_W            1.9      /* src/brox_optic_flow_spatial.cpp:25 */
 #define BROX_SIGMA            0.8      /* src/brox_optic_flow_spatial.cpp:26 */
 
+/* (double)(float) x: a value stored in the HIP path's float storage (rnd_to<float>, csrc/ofx_tvl1.hip) */
+static inline double rnd_f32(double x) { return (double) (float) x; }
+
 static double *dalloc(size_t n)
 {
     double *p = (double *) malloc((n ? n : 1) * sizeof(double));
@@ -200,7 +203,9 @@ static inline int gauss_reflect(int t, int n)
     return t < 0 ? -t : (t >= n ? 2 * n - 1 - t : t);
 }
 
-int orc_gaussian(double *I, int nx, int ny, double sigma)
+/* store_f32: the HIP path's float storage (op_gaussian<float>, csrc/ofx_ops.hip) -- the row pass is stored into a float
+ * plane before the column pass reads it, and the result is stored as float */
+static int gaussian(double *I, int nx, int ny, double sigma, int store_f32)
 {
     double *B;
     const int size = gauss_taps(sigma, &B);
@@ -216,7 +221,7 @@ int orc_gaussian(double *I, int nx, int ny, double sigma)
             double sum = B[0] * row[x];
             for (int j = 1; j < size; j++)
                 sum += B[j] * (row[gauss_reflect(x - j, nx)] + row[gauss_reflect(x + j, nx)]);
-            line[x] = sum;
+            line[x] = store_f32 ? rnd_f32(sum) : sum;
         }
         memcpy(row, line, (size_t) nx * sizeof(double));
     }
@@ -226,13 +231,26 @@ int orc_gaussian(double *I, int nx, int ny, double sigma)
             for (int j = 1; j < size; j++)
                 sum += B[j] * (I[(size_t) gauss_reflect(y - j, ny) * nx + k] +
                                I[(size_t) gauss_reflect(y + j, ny) * nx + k]);
-            line[y] = sum;
+            line[y] = store_f32 ? rnd_f32(sum) : sum;
         }
         for (int y = 0; y < ny; y++) I[(size_t) y * nx + k] = line[y];
     }
     free(line);
     free(B);
     return 0;
+}
+
+int orc_gaussian(double *I, int nx, int ny, double sigma)
+{
+    return gaussian(I, nx, ny, sigma, 0);
+}
+
+/* store_f32: the input is rounded to float first (it is uploaded into a float plane) */
+int orc_gaussian_mode(double *I, int nx, int ny, double sigma, int store_f32)
+{
+    if (store_f32)
+        for (size_t i = 0; i < (size_t) nx * ny; i++) I[i] = rnd_f32(I[i]);
+    return gaussian(I, nx, ny, sigma, store_f32);
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -301,23 +319,35 @@ void orc_zoom_size(int nx, int ny, int *nxx, int *nyy, double factor)
     *nyy = (int) (ny * factor + 0.5);
 }
 
-/* src/zoom.cpp:41-78 */
-int orc_zoom_out(const double *I, double *Iout, int nx, int ny, double factor)
+/* src/zoom.cpp:41-78.  store_f32: op_zoom_out<float> (csrc/ofx_ops.hip) -- float input, the smoothed image as
+ * op_gaussian<float> stores it, the output stored as float. */
+static int zoom_out(const double *I, double *Iout, int nx, int ny, double factor, int store_f32)
 {
     double *Is = dalloc((size_t) nx * ny);
     memcpy(Is, I, (size_t) nx * ny * sizeof(double));
     int nxx, nyy;
     orc_zoom_size(nx, ny, &nxx, &nyy, factor);
     const double sigma = ZOOM_SIGMA_ZERO * sqrt(1.0 / (factor * factor) - 1.0);
-    if (orc_gaussian(Is, nx, ny, sigma)) { free(Is); return 1; }
+    if (store_f32 ? orc_gaussian_mode(Is, nx, ny, sigma, 1) : orc_gaussian(Is, nx, ny, sigma)) { free(Is); return 1; }
     #pragma omp parallel for
     for (int i1 = 0; i1 < nyy; i1++)
         for (int j1 = 0; j1 < nxx; j1++) {
             const double i2 = i1 / factor, j2 = j1 / factor;
-            Iout[i1 * nxx + j1] = orc_bicubic_at(Is, j2, i2, nx, ny, 0);
+            const double o = orc_bicubic_at(Is, j2, i2, nx, ny, 0);
+            Iout[i1 * nxx + j1] = store_f32 ? rnd_f32(o) : o;
         }
     free(Is);
     return 0;
+}
+
+int orc_zoom_out(const double *I, double *Iout, int nx, int ny, double factor)
+{
+    return zoom_out(I, Iout, nx, ny, factor, 0);
+}
+
+int orc_zoom_out_mode(const double *I, double *Iout, int nx, int ny, double factor, int store_f32)
+{
+    return zoom_out(I, Iout, nx, ny, factor, store_f32);
 }
 
 /* src/zoom.cpp:132-155 */
@@ -375,10 +405,18 @@ static void tvl1_scratch_free(tvl1_scratch *s)
     free(s->u1x); free(s->u1y); free(s->u2x); free(s->u2y);
 }
 
+/* relaxed = 0, store_f32 = 0 is the reference's iteration.  The two switches restate the HIP path's non-strict modes
+ * (csrc/ofx_tvl1.hip, tvl1_primal / tvl1_dual<T, false>) with exact arithmetic where the kernels take one refinement
+ * step on the hardware estimates (sqrt_tol, rcp_tol):
+ *   relaxed:   primal fi = -rho * (1 / grad); dual g = sqrt(max(x^2 + y^2, 2^-600)), i = 1 / (1 + taut g),
+ *              p = (p + taut u') i
+ *   store_f32: u rounded to float after the primal stage and p after the dual stage (the stores of T = float); the
+ *              error is taken from the rounded u. */
 static double tvl1_one_iteration(double *u1, double *u2, double *p11, double *p12, double *p21,
                                  double *p22, const double *I1wx, const double *I1wy,
                                  const double *rho_c, const double *grad, tvl1_scratch *s,
-                                 int nx, int ny, double tau, double theta, double l_t)
+                                 int nx, int ny, double tau, double theta, double l_t,
+                                 int relaxed, int store_f32)
 {
     const int size = nx * ny;
     double *v1 = s->v1, *v2 = s->v2;
@@ -397,7 +435,7 @@ static double tvl1_one_iteration(double *u1, double *u2, double *p11, double *p1
         } else if (grad[i] < TVL1_GRAD_IS_ZERO) {
             d1 = d2 = 0;
         } else {
-            const double fi = -rho / grad[i];
+            const double fi = relaxed ? -rho * (1.0 / grad[i]) : -rho / grad[i];
             d1 = fi * I1wx[i];
             d2 = fi * I1wy[i];
         }
@@ -415,6 +453,7 @@ static double tvl1_one_iteration(double *u1, double *u2, double *p11, double *p1
         const double u1k = u1[i], u2k = u2[i];
         u1[i] = v1[i] + theta * s->div_p1[i];
         u2[i] = v2[i] + theta * s->div_p2[i];
+        if (store_f32) { u1[i] = rnd_f32(u1[i]); u2[i] = rnd_f32(u2[i]); }
         error += (u1[i] - u1k) * (u1[i] - u1k) + (u2[i] - u2k) * (u2[i] - u2k);
     }
     error /= size;
@@ -426,14 +465,30 @@ static double tvl1_one_iteration(double *u1, double *u2, double *p11, double *p1
     #pragma omp parallel for
     for (int i = 0; i < size; i++) {
         const double taut = tau / theta;
-        const double g1 = hypot(s->u1x[i], s->u1y[i]);
-        const double g2 = hypot(s->u2x[i], s->u2y[i]);
-        const double ng1 = 1.0 + taut * g1;
-        const double ng2 = 1.0 + taut * g2;
-        p11[i] = (p11[i] + taut * s->u1x[i]) / ng1;
-        p12[i] = (p12[i] + taut * s->u1y[i]) / ng1;
-        p21[i] = (p21[i] + taut * s->u2x[i]) / ng2;
-        p22[i] = (p22[i] + taut * s->u2y[i]) / ng2;
+        if (relaxed) {
+            const double u1x = s->u1x[i], u1y = s->u1y[i], u2x = s->u2x[i], u2y = s->u2y[i];
+            const double g1 = sqrt(fmax(u1x * u1x + u1y * u1y, 0x1p-600));
+            const double g2 = sqrt(fmax(u2x * u2x + u2y * u2y, 0x1p-600));
+            const double i1 = 1.0 / (1.0 + taut * g1);
+            const double i2 = 1.0 / (1.0 + taut * g2);
+            p11[i] = (p11[i] + taut * u1x) * i1;
+            p12[i] = (p12[i] + taut * u1y) * i1;
+            p21[i] = (p21[i] + taut * u2x) * i2;
+            p22[i] = (p22[i] + taut * u2y) * i2;
+        } else {
+            const double g1 = hypot(s->u1x[i], s->u1y[i]);
+            const double g2 = hypot(s->u2x[i], s->u2y[i]);
+            const double ng1 = 1.0 + taut * g1;
+            const double ng2 = 1.0 + taut * g2;
+            p11[i] = (p11[i] + taut * s->u1x[i]) / ng1;
+            p12[i] = (p12[i] + taut * s->u1y[i]) / ng1;
+            p21[i] = (p21[i] + taut * s->u2x[i]) / ng2;
+            p22[i] = (p22[i] + taut * s->u2y[i]) / ng2;
+        }
+        if (store_f32) {
+            p11[i] = rnd_f32(p11[i]); p12[i] = rnd_f32(p12[i]);
+            p21[i] = rnd_f32(p21[i]); p22[i] = rnd_f32(p22[i]);
+        }
     }
     return error;
 }
@@ -448,15 +503,49 @@ double orc_tvl1_iterations(double *u1, double *u2, double *p11, double *p12, dou
     double error = INFINITY;
     for (int n = 0; n < n_iter; n++)
         error = tvl1_one_iteration(u1, u2, p11, p12, p21, p22, I1wx, I1wy, rho_c, grad, &s,
-                                   nx, ny, tau, theta, lambda * theta);
+                                   nx, ny, tau, theta, lambda * theta, 0, 0);
     tvl1_scratch_free(&s);
     return error;
 }
 
+/* The same sweep in one of the HIP path's non-strict modes (tvl1_one_iteration).  With store_f32 the state and the
+ * linearisation are first rounded to float, as ofx_tvl1_iterations uploads them into T = float, and grad is recomputed
+ * from the rounded I1wx / I1wy (the kernels recompute it from the stored A): the `grad` argument is then unused. */
+double orc_tvl1_iterations_mode(double *u1, double *u2, double *p11, double *p12, double *p21, double *p22,
+                                const double *I1wx, const double *I1wy, const double *rho_c,
+                                const double *grad, int nx, int ny, double tau, double lambda,
+                                double theta, int n_iter, int relaxed, int store_f32)
+{
+    const size_t n = (size_t) nx * ny;
+    double *ax = NULL, *ay = NULL, *r = NULL, *g = NULL;
+    if (store_f32) {
+        ax = dalloc(n); ay = dalloc(n); r = dalloc(n); g = dalloc(n);
+        double *st[6] = { u1, u2, p11, p12, p21, p22 };
+        for (int k = 0; k < 6; k++)
+            for (size_t i = 0; i < n; i++) st[k][i] = rnd_f32(st[k][i]);
+        for (size_t i = 0; i < n; i++) {
+            ax[i] = rnd_f32(I1wx[i]);
+            ay[i] = rnd_f32(I1wy[i]);
+            r[i] = rnd_f32(rho_c[i]);
+            g[i] = ax[i] * ax[i] + ay[i] * ay[i];
+        }
+        I1wx = ax; I1wy = ay; rho_c = r; grad = g;
+    }
+    tvl1_scratch s;
+    tvl1_scratch_alloc(&s, n);
+    double error = INFINITY;
+    for (int k = 0; k < n_iter; k++)
+        error = tvl1_one_iteration(u1, u2, p11, p12, p21, p22, I1wx, I1wy, rho_c, grad, &s,
+                                   nx, ny, tau, theta, lambda * theta, relaxed, store_f32);
+    tvl1_scratch_free(&s);
+    free(ax); free(ay); free(r); free(g);
+    return error;
+}
+
 /* src/tvl1flow.cpp:46-212 */
-void orc_tvl1_single_scale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
-                           double tau, double lambda, double theta, int warps, double epsilon,
-                           int verbose, int *iters, double *errs)
+static void tvl1_single_scale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                              double tau, double lambda, double theta, int warps, double epsilon,
+                              int verbose, int *iters, double *errs, int relaxed)
 {
     const int size = nx * ny;
     const size_t n = (size_t) size;
@@ -488,7 +577,7 @@ void orc_tvl1_single_scale(const double *I0, const double *I1, double *u1, doubl
         while (error > epsilon * epsilon && it < TVL1_MAX_ITERATIONS) {  /* :113 */
             it++;
             error = tvl1_one_iteration(u1, u2, p11, p12, p21, p22, I1wx, I1wy, rho_c, grad, &s,
-                                       nx, ny, tau, theta, l_t);
+                                       nx, ny, tau, theta, l_t, relaxed, 0);
         }
         if (verbose)
             fprintf(stderr, "Warping: %d, Iterations: %d, Error: %f\n", w, it, error);  /* :184-188 */
@@ -499,6 +588,21 @@ void orc_tvl1_single_scale(const double *I0, const double *I1, double *u1, doubl
     tvl1_scratch_free(&s);
     free(I1x); free(I1y); free(I1w); free(I1wx); free(I1wy); free(rho_c); free(grad);
     free(p11); free(p12); free(p21); free(p22);
+}
+
+void orc_tvl1_single_scale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                           double tau, double lambda, double theta, int warps, double epsilon,
+                           int verbose, int *iters, double *errs)
+{
+    tvl1_single_scale(I0, I1, u1, u2, nx, ny, tau, lambda, theta, warps, epsilon, verbose, iters, errs, 0);
+}
+
+/* relaxed = 1: the HIP path's f64 tolerance mode (option relaxed_dual), which changes the inner iteration only */
+void orc_tvl1_single_scale_mode(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                                double tau, double lambda, double theta, int warps, double epsilon,
+                                int verbose, int *iters, double *errs, int relaxed)
+{
+    tvl1_single_scale(I0, I1, u1, u2, nx, ny, tau, lambda, theta, warps, epsilon, verbose, iters, errs, relaxed);
 }
 
 /* Shared pyramid prologue: src/tvl1flow.cpp:236-280, horn_schunck_pyramidal.cpp:279-323,
@@ -563,21 +667,37 @@ static void pyramid_free(pyramid *P)
 }
 
 /* src/tvl1flow.cpp:219-328 */
-int orc_tvl1_multiscale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
-                        double tau, double lambda, double theta, int nscales, double zfactor,
-                        int warps, double epsilon, int verbose, int *iters, double *errs)
+static int tvl1_multiscale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                           double tau, double lambda, double theta, int nscales, double zfactor,
+                           int warps, double epsilon, int verbose, int *iters, double *errs, int relaxed)
 {
     pyramid P;
     int rc = pyramid_build(&P, I0, I1, u1, u2, nx, ny, nscales, zfactor, TVL1_PRESMOOTH_SIGMA);
     for (int s = nscales - 1; s >= 0 && !rc; s--) {
         if (verbose) fprintf(stderr, "Scale %d: %dx%d\n", s, P.nx[s], P.ny[s]);
-        orc_tvl1_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], tau, lambda, theta,
-                              warps, epsilon, verbose, iters ? iters + s * warps : NULL,
-                              errs ? errs + s * warps : NULL);
+        tvl1_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], tau, lambda, theta,
+                          warps, epsilon, verbose, iters ? iters + s * warps : NULL,
+                          errs ? errs + s * warps : NULL, relaxed);
         if (s) pyramid_upsample(&P, s, zfactor);
     }
     pyramid_free(&P);
     return rc;
+}
+
+int orc_tvl1_multiscale(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                        double tau, double lambda, double theta, int nscales, double zfactor,
+                        int warps, double epsilon, int verbose, int *iters, double *errs)
+{
+    return tvl1_multiscale(I0, I1, u1, u2, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon, verbose,
+                           iters, errs, 0);
+}
+
+int orc_tvl1_multiscale_mode(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                             double tau, double lambda, double theta, int nscales, double zfactor,
+                             int warps, double epsilon, int verbose, int *iters, double *errs, int relaxed)
+{
+    return tvl1_multiscale(I0, I1, u1, u2, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon, verbose,
+                           iters, errs, relaxed);
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -63,6 +63,27 @@ double orc_tvl1_iterations(double *u1, double *u2, double *p11, double *p12, dou
                            const double *grad, int nx, int ny, double tau, double lambda,
                            double theta, int n_iter);
 
+/* The HIP path's two non-strict modes, restated with exact arithmetic (ofx_oracle.c, tvl1_one_iteration).  These are
+ * checker aids of this project, not the reference: with both switches 0 each equals its counterpart above bit for bit.
+ *   relaxed   = 1: the f64 tolerance mode (option relaxed_dual) -- fi = -rho * (1 / grad), the dual update with
+ *                  sqrt(max(x^2 + y^2, 2^-600)) and one reciprocal per denominator;
+ *   store_f32 = 1: float storage (OFX_F32) -- state, linearisation and every stored u / p rounded to float, grad from
+ *                  the rounded I1wx / I1wy (the `grad` argument is unused).  f32 runs the relaxed algebra too. */
+double orc_tvl1_iterations_mode(double *u1, double *u2, double *p11, double *p12, double *p21, double *p22,
+                                const double *I1wx, const double *I1wy, const double *rho_c,
+                                const double *grad, int nx, int ny, double tau, double lambda,
+                                double theta, int n_iter, int relaxed, int store_f32);
+void orc_tvl1_single_scale_mode(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                                double tau, double lambda, double theta, int warps, double epsilon,
+                                int verbose, int *iters, double *errs, int relaxed);
+int  orc_tvl1_multiscale_mode(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
+                              double tau, double lambda, double theta, int nscales, double zfactor,
+                              int warps, double epsilon, int verbose, int *iters, double *errs, int relaxed);
+/* store_f32 = 1: op_gaussian<float> / op_zoom_out<float> -- input, intermediate of the two passes, smoothed image and
+ * output rounded to float where the GPU stores them */
+int  orc_gaussian_mode(double *I, int nx, int ny, double sigma, int store_f32);
+int  orc_zoom_out_mode(const double *I, double *Iout, int nx, int ny, double factor, int store_f32);
+
 /* checker aids, see ofx_oracle.c: 0 = reference sweep order (default), 1 = the HIP path's colour order,
  * 2 = the HIP path's exact hyperplane-pipelined schedule (bit-identical to 0 by construction) */
 void orc_set_sor_order(int order);

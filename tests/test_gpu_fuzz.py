@@ -221,17 +221,32 @@ def test_tvl1occ_random_lockstep_groups(ofx_mod, gpu64, orc, synth, seed):
     c["nx"], c["ny"], c["pair"], c["kw"]["nscales"], c["kw"]["warps"], c["kw"]["zfactor"], c["kw"]["epsilon"]))
 def test_tolerance_mode_random_configurations(gpu64, orc, synth, c):
     """option relaxed_dual = 1 on random sizes / parameters: north_star's bar (AEPE < 1e-4 px) against the oracle, iteration
-    counts within a few per loop (they are equal on every BASELINE config; tiny images sit closer to the threshold)"""
+    counts within a few per loop (they are equal on every BASELINE config; tiny images sit closer to the threshold) -- and
+    against the oracle's restatement of the tolerance arithmetic (relaxed = 1): iteration tables equal (a differing table is
+    reported with both errors and the threshold), flows to 1e-9 and errors to 1e-9 relative as in the strict test above --
+    unless the solve itself amplifies last-bit differences further: then at most 10x the distance between the two
+    correctly rounded restatements (strict and relaxed oracle).  Measured on an MI355X: 198x68-P1-ns2-w4-z0.75 differs from the
+    restatement by 2.2e-9 while the two restatements differ by 7.5e-10 (on 43 of its 13464 pixels: a discrete decision, a
+    thresholding branch or a bicubic tap, moved by the last bit); every other case stays below 1e-9."""
     I0, I1 = synth.pair(c["pair"], c["nx"], c["ny"], c["k"])
-    uo, vo, it_o, _ = orc.tvl1_multiscale(I0, I1, **c["kw"])
+    uo, vo, it_o, err_o = orc.tvl1_multiscale(I0, I1, **c["kw"])
     gpu64.set_option("relaxed_dual", 1)
     try:
         ug, vg = gpu64.tvl1_multiscale(I0, I1, **c["kw"])
-        it_g = gpu64.stats().iterations().copy()
+        st = gpu64.stats()
+        it_g = st.iterations().copy()
     finally:
         gpu64.set_option("relaxed_dual", 0)
     assert float(np.mean(np.hypot(ug - uo, vg - vo))) < 1e-4
     assert np.abs(it_g - np.asarray(it_o)).max() <= 4
+    ur, vr, it_r, err_r = orc.tvl1_multiscale_mode(I0, I1, relaxed=1, **c["kw"])
+    bad = np.argwhere(it_g != it_r)
+    assert bad.size == 0, ("iteration tables differ at", bad.tolist(), it_g[tuple(bad.T)], it_r[tuple(bad.T)], "errors gpu",
+                           st.errors()[tuple(bad.T)], "oracle", err_r[tuple(bad.T)], "threshold", c["kw"]["epsilon"] ** 2)
+    cond = max(np.abs(uo - ur).max(), np.abs(vo - vr).max())                  # the two restatements
+    cond_err = float((np.abs(err_o - err_r) / np.maximum(np.abs(err_r), 1e-300)).max())
+    assert max(np.abs(ug - ur).max(), np.abs(vg - vr).max()) < max(1e-9, 10 * cond), cond
+    assert np.allclose(st.errors(), err_r, rtol=max(1e-9, 10 * cond_err), atol=1e-300), cond_err
 
 
 FUZZ_REXPO = int(os.environ.get("OFX_FUZZ_REXPO", "6"))
