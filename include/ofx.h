@@ -309,14 +309,35 @@ int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, 
 
 /* ---- robust_expo_methods (replace src/robust_expo_methods.h:21-38) -----------------------------------*/
 /* Brox's scheme with an image-driven weight in the smoothness term: method_type 1 = exp(-lambda |grad I1|), 2 = the same
- * + 0.001, 3 = lambda chosen per pixel from alpha and the gradient distribution.  The reference's argument order.  nzz must
- * be 1 (OFX_ERR_ARG otherwise): for colour images the reference's pyramid reads beyond its scratch copy (zoom.cpp:96-118).
- * Kept quirks of the source: the presmoothing is gaussian(I, nx, ny, nzz, 0.8), i.e. sigma = nzz = 1 with the DIRICHLET
- * boundary (robust_expo_methods.cpp:497-498), and alpha * nzz is truncated to an int (:529).  SOR sweeps run in the
- * reference's order (windowed exact schedule, option sor_exact = 1); bit-identical to the reference on one thread. */
+ * + 0.001, 3 = lambda chosen per pixel from alpha and the gradient distribution.  The reference's argument order.
+ * I1, I2: nxx * nyy * nzz doubles, channels interleaved (element (i * nxx + j) * nzz + k); u, v: nxx * nyy.
+ * nzz = 1: any number of scales.  nzz = 2 .. OFX_REXPO_MAX_CHANNELS: nscales must be 1 (OFX_ERR_ARG otherwise): the
+ * reference's colour pyramid reads beyond its scratch copy (zoom.cpp:96-118), its colour solver at one scale is defined.
+ * Other nzz: OFX_ERR_ARG.  Levels smaller than 3x3 and option sor_exact != 1: OFX_ERR_ARG.
+ * Kept quirks of the source:
+ *  - the presmoothing is gaussian(I, nxx, nyy, nzz, 0.8) against (I, xdim, ydim, sigma, boundary, window)
+ *    (robust_expo_methods.cpp:497-498): sigma = nzz, the DIRICHLET boundary, and the buffer taken for one nxx x nyy plane, so
+ *    for nzz > 1 only the first nxx * nyy elements of the interleaved image are smoothed;
+ *  - alpha * nzz is truncated to an int (:527);
+ *  - the SOR stopping value is sqrt(error / (nx ny nz)) (:400);
+ *  - for nzz > 1 the first row of the derivative arrays: centered_gradient and the 3x3 masks address it by the column alone
+ *    (operators.cpp:176, :363-364), so elements 1 .. nx - 2 hold the last channel's stencil of "column k", the corner
+ *    elements their own values and the rest of the row is never written -- 0 here, as in the reference built with zeroed
+ *    arrays, which is the build this library is checked against; and the right-hand tap of the masks in the last row is
+ *    read one ELEMENT further instead of one pixel (:189).
+ * SOR sweeps run in the reference's order (windowed exact schedule, option sor_exact = 1); sweep counts equal to the
+ * reference's on one thread, flows to 1e-11 (the order of the stopping sum). */
+#define OFX_REXPO_MAX_CHANNELS 4
 int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
                     int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                     int inner_iter, int outer_iter, int verbose);
+/* The reference's single-scale overload (robust_expo_methods.cpp:162-178, declared in none of its headers): the solver of one
+ * level with no normalisation, no presmoothing and alpha as given; u, v are READ as the initial flow and overwritten with
+ * the result -- what a caller needs to run colour on a pyramid of their own.  nz in 1 .. OFX_REXPO_MAX_CHANNELS, images
+ * interleaved as above.  number_of_threads is accepted for the argument order's sake and ignored.  ofx_get_stats: scale 0. */
+int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
+                                 int method_type, double alpha, double gamma, double lambda, double TOL, int inner_iter,
+                                 int outer_iter, int number_of_threads, int verbose);
 
 /* ---- Brox temporal (replace src/brox_optic_flow.h:41-55) ---------------------------*/
 /* I: `frames` images of nx*ny, frame-major; u, v: frames - 1 flow fields (u[f] takes frame f to frame f + 1).

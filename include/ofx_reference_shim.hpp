@@ -97,13 +97,23 @@ void brox_optic_flow_spatial(const ofpix_t *I1, const ofpix_t *I2, ofpix_t *u, o
     ofx_shim::check(ofx_brox_spatial(ofx_shim::ctx(), I1, I2, u, v, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter,
                                      verbose));
 }
-// ---- src/robust_expo_methods.h:21-38 (one channel; nzz != 1 -> std::runtime_error with the library's message) -----------
+// ---- src/robust_expo_methods.h:21-38 (one channel at any number of scales, nzz = 2..4 channels with nscales = 1; anything
+// else -> std::runtime_error with the library's message) --------------------------------------------------------------------
 void robust_expo_methods(const ofpix_t *I1, const ofpix_t *I2, ofpix_t *u, ofpix_t *v, const int nxx, const int nyy, const int nzz,
                          const int method_type, const double alpha, const double gamma, const double lambda, const int nscales,
                          const double nu, const double TOL, const int inner_iter, const int outer_iter, const bool verbose)
 {
     ofx_shim::check(ofx_robust_expo(ofx_shim::ctx(), I1, I2, u, v, nxx, nyy, nzz, method_type, alpha, gamma, lambda, nscales, nu,
                                     TOL, inner_iter, outer_iter, verbose));
+}
+// the single-scale overload of src/robust_expo_methods.cpp:162-178: an EXTRA, the reference declares it in none of its headers
+// (a caller that used it declared it itself); u, v are the initial flow on entry, number_of_threads is ignored
+void robust_expo_methods(const ofpix_t *I1, const ofpix_t *I2, ofpix_t *u, ofpix_t *v, const int nx, const int ny, const int nz,
+                         const int method_type, const double alpha, const double gamma, const double lambda, const double TOL,
+                         const int inner_iter, const int outer_iter, const int number_of_threads, const bool verbose)
+{
+    ofx_shim::check(ofx_robust_expo_single_scale(ofx_shim::ctx(), I1, I2, u, v, nx, ny, nz, method_type, alpha, gamma, lambda, TOL,
+                                                 inner_iter, outer_iter, number_of_threads, verbose));
 }
 void brox_optic_flow_temporal(const ofpix_t *I, ofpix_t *u, ofpix_t *v, const int nxx, const int nyy, const int frames,
                               const double alpha, const double gamma, const int nscales, const double nu, const double TOL,

@@ -94,6 +94,7 @@ def lib():
         "ofx_bicubic_at": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i]),
         "ofx_hypot": (_i, [_vp, _dp, _dp, _dp, _i]),
         "ofx_robust_expo": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _i, _i, _i]),
+        "ofx_robust_expo_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _i, _i]),
         "ofx_bicubic_warp": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_zoom_size": (None, [_i, _i, C.POINTER(_i), C.POINTER(_i), _d]),
         "ofx_zoom_out": (_i, [_vp, _dp, _dp, _i, _i, _d]),
@@ -305,12 +306,40 @@ class Ofx:
         self._ck(self.L.ofx_bicubic_at(self.h, _f64(I), uu, vv, out, uu.size, nx, ny, int(border_out)))
         return out
 
+    @staticmethod
+    def _colour_shape(I1, I2, nz):
+        """(ny, nx, nz) of a robust_expo input: (ny, nx) planes or (ny, nx, nz) interleaved images; an explicit `nz` must agree"""
+        if I1.shape != I2.shape or I1.ndim not in (2, 3):
+            raise ValueError("robust_expo: images of shape %s and %s" % (I1.shape, I2.shape))
+        if I1.ndim == 3:
+            if nz is not None and nz != I1.shape[2]:
+                raise ValueError("robust_expo: nz = %d for images of shape %s" % (nz, I1.shape))
+            return I1.shape
+        return I1.shape[0], I1.shape[1], (1 if nz is None else nz)
+
     def robust_expo(self, I1, I2, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4, inner=1, outer=15,
-                    verbose=0, nz=1):
-        ny, nx = I1.shape
+                    verbose=0, nz=None):
+        """I1, I2: (ny, nx) planes, or (ny, nx, nz) colour images (channels interleaved; nscales must then be 1) -> u, v"""
+        ny, nx, nz = self._colour_shape(I1, I2, nz)
+        if I1.ndim == 2 and nz > 1 and nscales == 1:    # planes cannot stand for nz channels; with nscales != 1 the library refuses
+            raise ValueError("robust_expo: nz = %d needs (ny, nx, nz) images" % nz)
         u, v = np.zeros((ny, nx)), np.zeros((ny, nx))
         self._ck(self.L.ofx_robust_expo(self.h, _f64(I1), _f64(I2), u, v, nx, ny, nz, method, alpha, gamma, lam, nscales, nu, TOL,
                                         inner, outer, verbose))
+        return u, v
+
+    def robust_expo_single_scale(self, I1, I2, u, v, method=1, alpha=50.0, gamma=10.0, lam=1.0, TOL=1e-4, inner=1, outer=15,
+                                 verbose=0, nz=None):
+        """One level of robust_expo_methods with no normalisation or presmoothing: (u, v) is the initial flow, the refined flow
+        is returned (the arguments are not modified).  I1, I2: (ny, nx) or (ny, nx, nz) as robust_expo."""
+        ny, nx, nz = self._colour_shape(I1, I2, nz)
+        if I1.ndim == 2 and nz != 1:
+            raise ValueError("robust_expo_single_scale: nz = %d needs (ny, nx, nz) images" % nz)
+        u, v = np.array(u, dtype=np.float64, order="C"), np.array(v, dtype=np.float64, order="C")
+        if u.shape != (ny, nx) or v.shape != (ny, nx):
+            raise ValueError("robust_expo_single_scale: flow of shape %s, %s for %dx%d images" % (u.shape, v.shape, nx, ny))
+        self._ck(self.L.ofx_robust_expo_single_scale(self.h, _f64(I1), _f64(I2), u, v, nx, ny, nz, method, alpha, gamma, lam, TOL,
+                                                     inner, outer, 1, verbose))
         return u, v
 
     def hypot(self, x, y):

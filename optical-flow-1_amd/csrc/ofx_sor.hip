@@ -1733,11 +1733,252 @@ __global__ void k_brox_add(typename Pix<T>::v2 *__restrict__ U, const typename P
     stn2(U + i, make_double2(u.x + d.x, u.y + d.y));
 }
 
+// ============================================================================================
+// robust_expo_methods on nz interleaved channels (src/robust_expo_methods.cpp:162-455)
+// ============================================================================================
+// Device layout: channel-planar packs.  Channel c of I1, (I1x, I1y), (I2, I2x, I2y, I2xx), (I2xy, I2yy) and of their warps
+// lies at element c * nx * ny of the level's I1, G1, PA, PB, WA, WB; the C ABI keeps the reference's interleaved order.
+
+// The five derivatives the reference leaves at FLAT element k = (i * nx + j) * nz + c of its derivative arrays
+// (centered_gradient, Dxx, Dyy, Dxy with nz channels, src/operators.cpp:132-406).  Below the first row they are the clamped
+// one-channel stencils applied to channel c, with one exception: in the last row the right-hand tap of the mask is read at
+// k + 1 instead of k + nz (:189).  In the FIRST row the source's loops address their output by the column alone
+// (dx[j], output[j], :176, :363-364), so for nz > 1 flat elements 1 .. nx - 2 receive the stencil of "column k" of the last
+// channel -- its second-row taps read at nx * nz + k (:172-174) --, the corner elements that are written afterwards keep
+// their own values, and every other element of the row is never written.  The compiled reference allocates zeroed arrays, so
+// those read 0; that is what is reproduced.  For nz = 1 all of this reduces to the one-channel operators.
+struct RexpoDerivs { double x, y, xx, xy, yy; };
+template <typename T>
+OFX_DEV RexpoDerivs rexpo_derivs_proper(const T *__restrict__ in, int i, int j, int c, int nx, int ny, int nz)
+{
+    const int jl = j > 0 ? j - 1 : 0, jr = j < nx - 1 ? j + 1 : nx - 1;
+    const int iu = i > 0 ? i - 1 : 0, id = i < ny - 1 ? i + 1 : ny - 1;
+#define RX_P(ii, jj) ldw(in + ((size_t) (ii) * nx + (jj)) * nz + c)
+    // the mask's right-hand tap of the last row, :189
+    const bool odd = i == ny - 1 && j > 0 && j < nx - 1;
+    const double rgt = odd ? ldw(in + ((size_t) i * nx + j) * nz + c + 1) : RX_P(i, jr);
+    RexpoDerivs d;
+    d.x = 0.5 * (RX_P(i, jr) - RX_P(i, jl));
+    d.y = 0.5 * (RX_P(id, j) - RX_P(iu, j));
+    if (j == 0) d.xx = RX_P(i, j) * -1.0 + RX_P(i, j + 1);
+    else if (j == nx - 1) d.xx = RX_P(i, j - 1) + RX_P(i, j) * -1.0;
+    else d.xx = RX_P(i, j - 1) + RX_P(i, j) * -2.0 + rgt;
+    if (i == 0) d.yy = RX_P(i, j) * -1.0 + RX_P(i + 1, j);
+    else if (i == ny - 1) d.yy = RX_P(i - 1, j) + RX_P(i, j) * -1.0;
+    else d.yy = RX_P(i - 1, j) + RX_P(i, j) * -2.0 + RX_P(i + 1, j);
+    d.xy = RX_P(iu, jl) * 0.25 + RX_P(iu, jr) * -0.25 + RX_P(id, jl) * -0.25 + (odd ? rgt : RX_P(id, jr)) * 0.25;
+#undef RX_P
+    return d;
+}
+template <typename T>
+OFX_DEV RexpoDerivs rexpo_derivs(const T *__restrict__ in, int i, int j, int c, int nx, int ny, int nz)
+{
+    if (i > 0) return rexpo_derivs_proper(in, i, j, c, nx, ny, nz);
+    const int f = j * nz + c;                                    // flat element of the first row
+    const bool row_loop = f >= 1 && f <= nx - 2;                 // written as dx[f] / output[f] by every channel's pass
+    if (f < nz && !(row_loop && f < nz - 1)) return rexpo_derivs_proper(in, 0, 0, f, nx, ny, nz);     // corner (0, 0) of channel f
+    if (row_loop) {                                              // the last channel's pass wins
+        const size_t idx = (size_t) f * nz + (nz - 1), row1 = (size_t) nx * nz + f;
+        RexpoDerivs d;
+        d.x = 0.5 * (ldw(in + idx + nz) - ldw(in + idx - nz));
+        d.y = 0.5 * (ldw(in + idx + (size_t) nx * nz) - ldw(in + idx));
+        d.xx = ldw(in + idx - nz) + ldw(in + idx) * -2.0 + ldw(in + idx + nz);
+        d.yy = ldw(in + idx) * -1.0 + ldw(in + row1);
+        d.xy = ldw(in + idx - nz) * 0.25 + ldw(in + idx + nz) * -0.25 + ldw(in + row1 - nz) * -0.25 + ldw(in + row1 + nz) * 0.25;
+        return d;
+    }
+    if (f >= (nx - 1) * nz) return rexpo_derivs_proper(in, 0, nx - 1, f - (nx - 1) * nz, nx, ny, nz);   // corner (0, nx - 1)
+    return RexpoDerivs{0.0, 0.0, 0.0, 0.0, 0.0};                 // never written by the source
+}
+
+// :221-227: gradient of I1; I2 with its first and second derivatives; interleaved in, channel-planar packs out
+// (blockIdx.z = channel).  Needs nx, ny >= 3.
+template <typename T>
+__global__ void k_rexpo_prepare_c(const T *__restrict__ I1i, const T *__restrict__ I2i, T *__restrict__ I1,
+                                  typename Pix<T>::v2 *__restrict__ G1, typename Pix<T>::v4 *__restrict__ PA,
+                                  typename Pix<T>::v2 *__restrict__ PB, int nx, int ny, int nz)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    const int c = blockIdx.z;
+    if (j >= nx || i >= ny) return;
+    const size_t p = (size_t) i * nx + j, q = (size_t) c * nx * ny + p;
+    const RexpoDerivs a = rexpo_derivs(I1i, i, j, c, nx, ny, nz), b = rexpo_derivs(I2i, i, j, c, nx, ny, nz);
+    stn(I1 + q, ldw(I1i + p * nz + c));
+    stn2(G1 + q, make_double2(a.x, a.y));
+    stn4(PA + q, make_double4(ldw(I2i + p * nz + c), b.x, b.y, b.xx));
+    stn2(PB + q, make_double2(b.xy, b.yy));
+}
+
+// max_gradients (src/robust_expo_smoothness.cpp:51-73): the largest gradient magnitude of a pixel's channels
+template <typename T>
+__global__ void k_rexpo_maxgrad(const typename Pix<T>::v2 *__restrict__ G1, double *__restrict__ Mg, int n, int nz)
+{
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t) n) return;
+    double2 g = ldw2(G1 + i);
+    double m = sqrt(g.x * g.x + g.y * g.y);
+    for (int c = 1; c < nz; c++) {
+        g = ldw2(G1 + (size_t) c * n + i);
+        const double gc = sqrt(g.x * g.x + g.y * g.y);
+        if (m < gc) m = gc;
+    }
+    Mg[i] = m;
+}
+
+// :236-241: the six warps of every channel with the pixel's one set of bicubic taps
+template <typename T>
+__global__ void k_rexpo_warp_c(const typename Pix<T>::v4 *__restrict__ PA, const typename Pix<T>::v2 *__restrict__ PB,
+                               const typename Pix<T>::v2 *__restrict__ U, typename Pix<T>::v4 *__restrict__ WA,
+                               typename Pix<T>::v2 *__restrict__ WB, int nx, int ny, int nz)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (j >= nx || i >= ny) return;
+    const size_t n = (size_t) nx * ny, p = (size_t) i * nx + j;
+    const double2 u = ldw2(U + p);
+    const BicubicTaps t = bicubic_taps(j + u.x, i + u.y, nx, ny);
+    for (int ch = 0; ch < nz; ch++) {
+        const typename Pix<T>::v4 *__restrict__ pa = PA + ch * n;
+        const typename Pix<T>::v2 *__restrict__ pb = PB + ch * n;
+        double4 wa = make_double4(0.0, 0.0, 0.0, 0.0);
+        double2 wb = make_double2(0.0, 0.0);
+        if (!t.out) {
+            double c[6][4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                double4 a[4];
+                double2 b[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    a[r] = ldw4(pa + (size_t) t.row[r] * nx + t.col[k]);
+                    b[r] = ldw2(pb + (size_t) t.row[r] * nx + t.col[k]);
+                }
+                c[0][k] = cubic_cell(a[0].x, a[1].x, a[2].x, a[3].x, t.fy);
+                c[1][k] = cubic_cell(a[0].y, a[1].y, a[2].y, a[3].y, t.fy);
+                c[2][k] = cubic_cell(a[0].z, a[1].z, a[2].z, a[3].z, t.fy);
+                c[3][k] = cubic_cell(a[0].w, a[1].w, a[2].w, a[3].w, t.fy);
+                c[4][k] = cubic_cell(b[0].x, b[1].x, b[2].x, b[3].x, t.fy);
+                c[5][k] = cubic_cell(b[0].y, b[1].y, b[2].y, b[3].y, t.fy);
+            }
+            wa.x = cubic_cell(c[0][0], c[0][1], c[0][2], c[0][3], t.fx);
+            wa.y = cubic_cell(c[1][0], c[1][1], c[1][2], c[1][3], t.fx);
+            wa.z = cubic_cell(c[2][0], c[2][1], c[2][2], c[2][3], t.fx);
+            wa.w = cubic_cell(c[3][0], c[3][1], c[3][2], c[3][3], t.fx);
+            wb.x = cubic_cell(c[4][0], c[4][1], c[4][2], c[4][3], t.fx);
+            wb.y = cubic_cell(c[5][0], c[5][1], c[5][2], c[5][3], t.fx);
+        }
+        stn4(WA + ch * n + p, wa);
+        stn2(WB + ch * n + p, wb);
+    }
+}
+
+// psi_data, psi_gradient and the constant parts of the scheme for nz channels (:53-63, :92-104, :276-318): every sum over the
+// channels runs in ascending order onto 0, psi multiplies the finished sums (k_brox_coeff's rx branch is the nz = 1 form)
+template <typename T>
+__global__ void k_rexpo_coeff_c(const T *__restrict__ I1, const typename Pix<T>::v2 *__restrict__ G1,
+                                const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
+                                const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
+                                const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n, int nz,
+                                double alpha, double gamma)
+{
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t) n) return;
+    const double2 d = ldw2(DU + i);
+    const double eps2 = BROX_EPSILON * BROX_EPSILON;
+    double sd = 0.0, sg = 0.0, BNu = 0.0, BNv = 0.0, BDu = 0.0, BDv = 0.0, DI_Data = 0.0;
+    double GNu = 0.0, GNv = 0.0, GDu = 0.0, GDv = 0.0, DI_Gradient = 0.0;
+    for (int c = 0; c < nz; c++) {
+        const size_t q = (size_t) c * n + i;
+        const double i1 = ldw(I1 + q);
+        const double2 g1 = ldw2(G1 + q);
+        const double4 wa = ldw4(WA + q);
+        const double2 wb = ldw2(WB + q);
+        const double I2w = wa.x, I2wx = wa.y, I2wy = wa.z, I2wxx = wa.w, I2wxy = wb.x, I2wyy = wb.y;
+        const double dI = I2w + I2wx * d.x + I2wy * d.y - i1;
+        sd += dI * dI;
+        const double dIx = I2wx + I2wxx * d.x + I2wxy * d.y - g1.x;
+        const double dIy = I2wy + I2wxy * d.x + I2wyy * d.y - g1.y;
+        sg += dIx * dIx + dIy * dIy;
+        const double dif = I2w - i1;
+        BNu += dif * I2wx;
+        BNv += dif * I2wy;
+        BDu += I2wx * I2wx;
+        BDv += I2wy * I2wy;
+        DI_Data += (I2wy * I2wx);
+        const double dx = (I2wx - g1.x), dy = (I2wy - g1.y);
+        GNu += (dx * I2wxx + dy * I2wxy);
+        GNv += (dx * I2wxy + dy * I2wyy);
+        GDu += (I2wxx * I2wxx + I2wxy * I2wxy);
+        GDv += (I2wyy * I2wyy + I2wxy * I2wxy);
+        DI_Gradient += (I2wxx + I2wyy) * I2wxy;
+    }
+    const double psid = rnd_to<T>(1. / sqrt(sd + eps2));
+    const double psig = rnd_to<T>(1. / sqrt(sg + eps2));
+    const double g = gamma * psig;
+    BNu = -psid * BNu; BNv = -psid * BNv; BDu = psid * BDu; BDv = psid * BDv;
+    GNu = -g * GNu; GNv = -g * GNv; GDu = g * GDu; GDv = g * GDv;
+    const double2 dvv = ldw2(DV + i);
+    const double dd = ldw(Dd + i);
+    stn4(CO + i, make_double4(BNu + GNu + alpha * dvv.x, BNv + GNv + alpha * dvv.y, BDu + GDu + dd, BDv + GDv + dd));
+    stn(Dm + i, psid * DI_Data + g * DI_Gradient);
+}
+
+// image_normalization_2_color (src/utils.cpp:334-406) on device data: per channel the joint minimum / maximum of both images
+// (exact, order-independent), then 255 (x - min) / den, or a copy when den <= 0
+#define RX_MM_BLOCKS 64
+__global__ __launch_bounds__(256) void k_rexpo_mm_partial(const double *__restrict__ a, const double *__restrict__ b, size_t npix,
+                                                          int nz, double *__restrict__ part /* [nz][2][RX_MM_BLOCKS] */)
+{
+    const int c = blockIdx.y;
+    double lo = a[c], hi = lo;
+    for (size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x; t < npix; t += (size_t) gridDim.x * blockDim.x) {
+        const double x = a[t * nz + c], y = b[t * nz + c];
+        lo = x < lo ? x : lo; hi = x > hi ? x : hi;
+        lo = y < lo ? y : lo; hi = y > hi ? y : hi;
+    }
+    __shared__ double slo[256], shi[256];
+    slo[threadIdx.x] = lo;
+    shi[threadIdx.x] = hi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int) threadIdx.x < s) {
+            const double l2 = slo[threadIdx.x + s], h2 = shi[threadIdx.x + s];
+            if (l2 < slo[threadIdx.x]) slo[threadIdx.x] = l2;
+            if (h2 > shi[threadIdx.x]) shi[threadIdx.x] = h2;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[((size_t) c * 2 + 0) * RX_MM_BLOCKS + blockIdx.x] = slo[0];
+        part[((size_t) c * 2 + 1) * RX_MM_BLOCKS + blockIdx.x] = shi[0];
+    }
+}
+template <typename T>
+__global__ void k_rexpo_norm_map(const double *__restrict__ a, const double *__restrict__ b, T *__restrict__ oa, T *__restrict__ ob,
+                                 size_t n, int nz, const double *__restrict__ part, int nblocks)
+{
+    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int c = (int) (e % nz);
+    const double *pl = part + ((size_t) c * 2 + 0) * RX_MM_BLOCKS, *ph = part + ((size_t) c * 2 + 1) * RX_MM_BLOCKS;
+    double lo = pl[0], hi = ph[0];
+    for (int k = 1; k < nblocks; k++) { lo = pl[k] < lo ? pl[k] : lo; hi = ph[k] > hi ? ph[k] : hi; }
+    const double den = hi - lo;
+    stn(oa + e, den > 0 ? 255.0 * (a[e] - lo) / den : a[e]);
+    stn(ob + e, den > 0 ? 255.0 * (b[e] - lo) / den : b[e]);
+}
+
 // One level of a lockstep group: every array holds G pairs back to back (pair g at element g * nx * ny).
 template <typename T> struct BroxLevel {
     using v2 = typename Pix<T>::v2;
     using v4 = typename Pix<T>::v4;
     int nx, ny, G;
+    // robust_expo on colour: nz > 1 channels; I1, G1, PA, PB, WA, WB then hold nz channel planes each, I1c / I2c the interleaved
+    // images the level starts from and Mg the largest gradient magnitude of each pixel's channels
+    int nz = 1;
+    T *I1c = nullptr, *I2c = nullptr;
+    double *Mg = nullptr;
     T *I1, *I2, *Psis, *Dd, *Dm;
     v2 *G1, *PB, *WB, *U, *DV, *DU, *DUck;
     v4 *PA, *WA, *CO;
@@ -1755,26 +1996,27 @@ template <typename T> struct BroxLevel {
     size_t n() const { return (size_t) nx * ny; }
 };
 
-template <typename T> static int brox_level_alloc(ofx_ctx *ctx, BroxLevel<T> &L, int nx, int ny, int G)
+template <typename T> static int brox_level_alloc(ofx_ctx *ctx, BroxLevel<T> &L, int nx, int ny, int G, int nz = 1)
 {
-    const size_t n = (size_t) nx * ny * G;
+    const size_t n = (size_t) nx * ny * G, nc = n * nz;
     L.nx = nx;
     L.ny = ny;
     L.G = G;
-    OFX_TRY(ofx_alloc(ctx, n, &L.I1));
+    L.nz = nz;
+    OFX_TRY(ofx_alloc(ctx, nc, &L.I1));
     OFX_TRY(ofx_alloc(ctx, n, &L.I2));
     OFX_TRY(ofx_alloc(ctx, n, &L.Psis));
     OFX_TRY(ofx_alloc(ctx, n, &L.Dd));
     OFX_TRY(ofx_alloc(ctx, n, &L.Dm));
-    OFX_TRY(ofx_alloc(ctx, n, &L.G1));
-    OFX_TRY(ofx_alloc(ctx, n, &L.PB));
-    OFX_TRY(ofx_alloc(ctx, n, &L.WB));
+    OFX_TRY(ofx_alloc(ctx, nc, &L.G1));
+    OFX_TRY(ofx_alloc(ctx, nc, &L.PB));
+    OFX_TRY(ofx_alloc(ctx, nc, &L.WB));
     OFX_TRY(ofx_alloc(ctx, n, &L.U));
     OFX_TRY(ofx_alloc(ctx, n, &L.DV));
     OFX_TRY(ofx_alloc(ctx, n, &L.DU));
     OFX_TRY(ofx_alloc(ctx, n, &L.DUck));
-    OFX_TRY(ofx_alloc(ctx, n, &L.PA));
-    OFX_TRY(ofx_alloc(ctx, n, &L.WA));
+    OFX_TRY(ofx_alloc(ctx, nc, &L.PA));
+    OFX_TRY(ofx_alloc(ctx, nc, &L.WA));
     OFX_TRY(ofx_alloc(ctx, n, &L.CO));
     L.Snap = L.DUs = nullptr;
     L.COs = nullptr;
@@ -1803,14 +2045,23 @@ template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L,
 {
     const size_t n = L.n();
     if (!L.Expo) OFX_TRY(ofx_alloc(ctx, n, &L.Expo));
-    std::vector<typename Pix<T>::v2> g1(n);
     std::vector<T> expo(n);
-    OFX_HIP(ctx, hipMemcpyAsync(g1.data(), L.G1, n * sizeof(typename Pix<T>::v2), hipMemcpyDeviceToHost, ctx->stream));
-    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<double> mg(n);
-    for (size_t i = 0; i < n; i++) {
-        const double ix = (double) g1[i].x, iy = (double) g1[i].y;
-        mg[i] = sqrt(ix * ix + iy * iy);
+    if (L.nz > 1) {
+        // colour: the largest magnitude of the pixel's channels (k_rexpo_maxgrad; IEEE sqrt on either side)
+        if (!L.Mg) OFX_TRY(ofx_alloc(ctx, n, &L.Mg));
+        hipLaunchKernelGGL(k_rexpo_maxgrad<T>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, L.G1, L.Mg, (int) n, L.nz);
+        OFX_LAUNCH_CHECK(ctx);
+        OFX_HIP(ctx, hipMemcpyAsync(mg.data(), L.Mg, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        std::vector<typename Pix<T>::v2> g1(n);
+        OFX_HIP(ctx, hipMemcpyAsync(g1.data(), L.G1, n * sizeof(typename Pix<T>::v2), hipMemcpyDeviceToHost, ctx->stream));
+        OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < n; i++) {
+            const double ix = (double) g1[i].x, iy = (double) g1[i].y;
+            mg[i] = sqrt(ix * ix + iy * iy);
+        }
     }
     if (P.method == 1 || P.method == 2) {
         const double beta = P.method == 2 ? 0.001 : 0.0;
@@ -1856,15 +2107,27 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
     const int rx = P.robust;
     if (rx && (!windowed || G != 1))
         return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs sor_exact = 1 and levels of at least 3x3 (%dx%d)", nx, ny);
+    const int nz = L.nz;                                         // > 1: robust_expo on colour (channel-planar packs)
+    if (nz > 1 && (!rx || !L.I1c || !L.I2c)) return ofx_fail(ctx, OFX_ERR_ARG, "brox: only robust_expo takes %d channels", nz);
+    if (nz > 1)
+        hipLaunchKernelGGL(k_rexpo_prepare_c<T>, dim3(g.x, g.y, nz), b, 0, ctx->stream, (const T *) L.I1c, (const T *) L.I2c, L.I1, L.G1,
+                           L.PA, L.PB, nx, ny, nz);
+    else
     hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) L.I1, (const T *) L.I2, L.G1, L.PA, L.PB, nx, ny);
     OFX_LAUNCH_CHECK(ctx);
     if (rx) OFX_TRY(rexpo_level_expo<T>(ctx, L, P));                                              // robust_expo_methods.cpp:231
     for (int no = 0; no < P.outer_iter; no++) {                                                   // :244
+        if (nz > 1) hipLaunchKernelGGL(k_rexpo_warp_c<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny, nz);
+        else
         hipLaunchKernelGGL(k_brox_warp<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny);
         hipLaunchKernelGGL(k_brox_psis<T>, g, b, 0, ctx->stream, L.U, L.Psis, nx, ny, (const T *) (rx ? L.Expo : nullptr));
         hipLaunchKernelGGL(k_brox_div<T>, g, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, P.alpha, rx);
         OFX_LAUNCH_CHECK(ctx);
         for (int ni = 0; ni < P.inner_iter; ni++) {                                               // :277
+            if (nz > 1)
+                hipLaunchKernelGGL(k_rexpo_coeff_c<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
+                                   (const T *) L.Dd, L.CO, L.Dm, n, nz, P.alpha, P.gamma);
+            else
             hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
                                (const T *) L.Dd, L.CO, L.Dm, (int) (npix * G), P.alpha, P.gamma, rx);
             OFX_LAUNCH_CHECK(ctx);
@@ -1960,7 +2223,8 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
                                                 hipMemcpyDeviceToDevice, ctx->stream));
                     return OFX_OK;
                 };
-                OFX_TRY(sor_window_loop(ctx, G, n, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
+                // robust_expo_methods.cpp:400: the stopping value divides by nx * ny * nz
+                OFX_TRY(sor_window_loop(ctx, G, n * nz, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
                                         take, nsor, error, 1, &L.sweep_hint, 0));
                 OFX_TRY((op_skew<typename Pix<T>::v2, false>(ctx, L.DUs, L.DU, nx, ny, BROX_PLANE_C_SKEW, G)));
             } else if (ctx->sor_exact && nx >= 3 && ny >= 3) {
@@ -2119,26 +2383,119 @@ extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2
     return s;
 }
 
-// robust_expo_methods (src/robust_expo_methods.h:21-38), one channel
+// robust_expo_methods on ONE level of nz interleaved channels, both public entries:
+//   presmooth = true : the multiscale overload called with nscales = 1 (src/robust_expo_methods.cpp:462-566):
+//                      image_normalization_2_color, its Gaussian call and a zero flow in front of the level solver
+//   presmooth = false: the single-scale overload itself (:162-178): the images as they come, (u, v) is the initial flow
+// nz = 1 runs the one-channel kernels of the level solver, nz > 1 the channel-planar ones.
+template <typename T>
+static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
+                            const BroxParams &P, bool presmooth)
+{
+    if (nx < 1 || ny < 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: bad size %dx%d", nx, ny);
+    const size_t n = (size_t) nx * ny, nc = n * nz;
+    if ((long long) nc >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: more than 2^31 image elements");
+    sor_stats_begin(&ctx->stats, 1, P.inner_iter * P.outer_iter);
+    ctx->stats.nx[0] = nx;
+    ctx->stats.ny[0] = ny;
+    BroxLevel<T> L;
+    OFX_TRY(brox_level_alloc<T>(ctx, L, nx, ny, 1, nz));
+    T *A, *B;
+    if (presmooth) {
+        double *a, *b, *part;
+        T *tmp;
+        OFX_TRY(ofx_alloc(ctx, nc, &a));
+        OFX_TRY(ofx_alloc(ctx, nc, &b));
+        OFX_TRY(ofx_alloc(ctx, nc, &A));
+        OFX_TRY(ofx_alloc(ctx, nc, &B));
+        OFX_TRY(ofx_alloc(ctx, (size_t) nz * 2 * RX_MM_BLOCKS, &part));
+        OFX_TRY(ofx_alloc(ctx, n, &tmp));
+        OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        int nb = (int) ((n + 255) / 256);
+        if (nb > RX_MM_BLOCKS) nb = RX_MM_BLOCKS;
+        hipLaunchKernelGGL(k_rexpo_mm_partial, dim3(nb, nz), dim3(256), 0, ctx->stream, (const double *) a, (const double *) b, n, nz, part);
+        OFX_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(k_rexpo_norm_map<T>, dim3((unsigned) ((nc + 255) / 256)), dim3(256), 0, ctx->stream, (const double *) a,
+                           (const double *) b, A, B, nc, nz, (const double *) part, nb);
+        OFX_LAUNCH_CHECK(ctx);
+        // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
+        // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
+        // so only the first nx * ny elements of the interleaved image are smoothed (across pixels and channels alike)
+        OFX_TRY(op_gaussian<T>(ctx, A, tmp, nx, ny, (double) nz, 1));
+        OFX_TRY(op_gaussian<T>(ctx, B, tmp, nx, ny, (double) nz, 1));
+        OFX_TRY(op_fill2<T>(ctx, L.U, n));                                                         // :522-524
+    } else {
+        double *du, *dv;
+        OFX_TRY(upload_plane<T>(ctx, I1, nc, &A));
+        OFX_TRY(upload_plane<T>(ctx, I2, nc, &B));
+        OFX_TRY(ofx_alloc(ctx, n, &du));
+        OFX_TRY(ofx_alloc(ctx, n, &dv));
+        OFX_HIP(ctx, hipMemcpyAsync(du, u, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        OFX_HIP(ctx, hipMemcpyAsync(dv, v, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        OFX_TRY(op_interleave2<T>(ctx, du, dv, L.U, n));
+    }
+    if (nz > 1) { L.I1c = A; L.I2c = B; }
+    else { L.I1 = A; L.I2 = B; }
+    if (P.verbose && presmooth) { printf("Scale: 0\n"); fflush(stdout); }
+    OFX_TRY(brox_single_scale_dev<T>(ctx, L, P, 0, &ctx->stats));
+    return download_flow<T>(ctx, L.U, u, v, n);
+}
+
+static int rexpo_check_args(ofx_ctx *ctx, const double *I1, const double *I2, const double *u, const double *v, int nz, int method_type,
+                            int inner_iter, int outer_iter)
+{
+    if (!I1 || !I2 || !u || !v) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
+    if (nz < 1 || nz > OFX_REXPO_MAX_CHANNELS)
+        return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: nz=%d (1..%d channels)", nz, OFX_REXPO_MAX_CHANNELS);
+    if (method_type < 1 || method_type > 3) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: method_type=%d (1, 2 or 3)", method_type);
+    if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: negative iteration count");
+    if (ctx->sor_exact != 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs the default option sor_exact = 1");
+    return OFX_OK;
+}
+
+// robust_expo_methods (src/robust_expo_methods.h:21-38): one channel at any number of scales, colour at one scale
 extern "C" int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
                                int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                                int inner_iter, int outer_iter, int verbose)
 {
     OFX_ENTER(ctx);
-    if (!I1 || !I2 || !u || !v) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
-    if (nzz != 1)
-        return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: nzz=%d (one channel only: for colour the reference's pyramid reads beyond its "
-                                          "scratch copy, zoom.cpp:96-118)", nzz);
-    if (method_type < 1 || method_type > 3) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: method_type=%d (1, 2 or 3)", method_type);
-    if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: negative iteration count");
-    if (ctx->sor_exact != 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs the default option sor_exact = 1");
+    OFX_TRY(rexpo_check_args(ctx, I1, I2, u, v, nzz, method_type, inner_iter, outer_iter));
+    if (nzz != 1 && nscales != 1)
+        return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: nzz=%d with nscales=%d (colour at one scale only: the reference's colour pyramid "
+                                          "reads beyond its scratch copy, zoom.cpp:96-118)", nzz, nscales);
     const double t0 = ofx_now_ms();
-    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, verbose};     // :529: alpha * nzz as an int
+    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, verbose};     // :527: alpha * nzz as an int
     P.robust = 1;
     P.method = method_type;
     P.lambda = lambda;
-    int s = ctx->precision == OFX_F64 ? brox_spatial_host<double>(ctx, I1, I2, u, v, nxx, nyy, P, nscales, nu)
+    int s;
+    if (nzz == 1)
+        s = ctx->precision == OFX_F64 ? brox_spatial_host<double>(ctx, I1, I2, u, v, nxx, nyy, P, nscales, nu)
                                       : brox_spatial_host<float>(ctx, I1, I2, u, v, nxx, nyy, P, nscales, nu);
+    else
+        s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true)
+                                      : rexpo_level_host<float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true);
+    ctx->stats.total_ms = ofx_now_ms() - t0;
+    return s;
+}
+
+// the single-scale overload (src/robust_expo_methods.cpp:162-178): no normalisation, no presmoothing, alpha as given, and
+// (u, v) is read as the initial flow
+extern "C" int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                                            int nz, int method_type, double alpha, double gamma, double lambda, double TOL,
+                                            int inner_iter, int outer_iter, int number_of_threads, int verbose)
+{
+    OFX_ENTER(ctx);
+    (void) number_of_threads;
+    OFX_TRY(rexpo_check_args(ctx, I1, I2, u, v, nz, method_type, inner_iter, outer_iter));
+    const double t0 = ofx_now_ms();
+    BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, verbose};
+    P.robust = 1;
+    P.method = method_type;
+    P.lambda = lambda;
+    int s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nx, ny, nz, P, false)
+                                      : rexpo_level_host<float>(ctx, I1, I2, u, v, nx, ny, nz, P, false);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
 }

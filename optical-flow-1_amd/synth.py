@@ -56,6 +56,21 @@ def pair(name, nx, ny, k=0):
     raise ValueError(name)
 
 
+def colour_pair(name, nx, ny, nz=3, k=0):
+    """pair(name, nx, ny, k) as two (ny, nx, nz) images, channels interleaved (the layout of the colour entries): channel 0 is the
+    plane itself, the others are made from it with + - * / only (exactly rounded operations, so the images are bit-equal wherever
+    pair() is): an inverted, compressed copy, a gamma-like square, a mix of the two."""
+    I0, I1 = pair(name, nx, ny, k)
+    if not 1 <= nz <= 4:
+        raise ValueError("nz = %d" % nz)
+
+    def channels(p):
+        ch = [p, 0.6 * (255.0 - p) + 20.0, p * p / 255.0, 0.5 * p + 0.25 * (255.0 - p * p / 255.0)]
+        return np.ascontiguousarray(np.stack(ch[:nz], axis=-1))
+
+    return channels(I0), channels(I1)
+
+
 def sequence(nx, ny, frames, k=0):
     """`frames` images of the P1 scene in uniform motion (frame t = background moved by t * flow, foreground
     rectangle moved by t * (mx, my)): input of the temporal Brox method.  Shape (frames, ny, nx)."""
