@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OFX_VERSION 100
+#define OFX_VERSION 101
 
 /* status codes */
 #define OFX_OK          0
@@ -78,6 +78,8 @@ typedef struct ofx_stats {
     int    fused[OFX_MAX_SCALES];                     /* TV-L1: iterations per iteration launch at each level
                                                          (1, 2, 3, or the tile kernel's 4 | 6); odd_stops then
                                                          counts the loops that ended inside such a launch unit  */
+    double pyramid_ms;                                /* ofx_robust_expo_pyramid: HIP-event time from the upload of the
+                                                         images to the last level of both pyramids (0 unless profiling) */
 } ofx_stats;
 
 /* ---- context ---------------------------------------------------------------------------------*/
@@ -91,7 +93,8 @@ int   ofx_ctx_precision(const ofx_ctx *ctx);
 int   ofx_ctx_synchronize(ofx_ctx *ctx);
 int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
 /* options (value 0 = default / automatic unless noted):
- *   "profile"        0/1  bracket the inner-iteration launches with HIP events -> stats.iter_ms
+ *   "profile"        0/1  bracket the inner-iteration launches with HIP events -> stats.iter_ms (and the pyramid phase of
+ *                         ofx_robust_expo_pyramid -> stats.pyramid_ms)
  *   "fixed_work"     0/1  TV-L1: every warp runs exactly OFX_TVL1_MAX_ITERATIONS iterations (stopping
  *                         test disabled; the reference with epsilon = 0)
  *   "sor_exact"      HS / Brox: 1 (default) = the reference's sweep order, bit-identical results, K time steps
@@ -190,6 +193,14 @@ int  ofx_zoom_in(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, in
 /* zoom_out_color (src/zoom.h:44-55).  The reference is only defined for nz = 1 (for nz > 1 it reads beyond its
  * nx*ny scratch copy, src/zoom.cpp:96-118); nz = 1 is zoom_out, any other nz is OFX_ERR_ARG. */
 int  ofx_zoom_out_color(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, int nz, double factor);
+/* zoom_out of nz interleaved channels as the IPOL ORIGINAL of robust_expo_methods defines it
+ * (3rdparty/ipoldfmethods_20160307/zoom.h:45-85 with gaussian.h:23-168): all nx*ny*nz elements are smoothed, one separable
+ * reflecting Gaussian per channel, and every channel is sampled with the same bicubic -- channel k of the result is
+ * ofx_zoom_out of channel k, nz = 1 is ofx_zoom_out bit for bit.  This is NOT a reference prototype: ofx_zoom_out_color above
+ * keeps the reference's name and keeps refusing nz > 1, where the reference is undefined.
+ * I: element (i * nx + j) * nz + k; Iout: nxx * nyy * nz with (nxx, nyy) from ofx_zoom_size.  nz in 1 .. OFX_REXPO_MAX_CHANNELS
+ * (OFX_ERR_ARG otherwise); OFX_ERR_SIGMA under ofx_zoom_out's rule (kernel radius >= width or height). */
+int  ofx_zoom_out_channels(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, int nz, double factor);
 
 /* ---- normalisation (replace src/utils.h:27-32) -----------------------------------------------*/
 int ofx_image_normalization_2(ofx_ctx *ctx, const double *I1, const double *I2, double *I1n, double *I2n,
@@ -331,6 +342,21 @@ int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, 
 int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
                     int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                     int inner_iter, int outer_iter, int verbose);
+/* Colour on a pyramid: ofx_robust_expo's argument list, any nzz in 1 .. OFX_REXPO_MAX_CHANNELS with any nscales >= 1.
+ * The REFERENCE's: the multiscale driver (robust_expo_methods.cpp:482-566) step for step with every quirk listed above, and
+ * the level solver.  The IPOL ORIGINAL's: the one call that builds level s from level s - 1, ofx_zoom_out_channels
+ * (3rdparty/ipoldfmethods_20160307/zoom.h:45-85) in place of the reference's zoom_out_color (zoom.cpp:85-125), which reads
+ * beyond its scratch copy for nzz > 1.  ofx_robust_expo and ofx_zoom_out_color keep the reference's names and keep refusing
+ * there; this entry is an extra under a name of its own.
+ * In f64 storage nzz = 1 gives ofx_robust_expo's result at the same nscales bit for bit (in f32 storage the one-channel entry
+ * rounds the planes to float BEFORE the normalisation, this one after it, so the two may differ there); nscales = 1 gives
+ * ofx_robust_expo's colour result bit for bit in either storage.  Against the reference's entry points composed the same way on one thread: equal sweep counts, flows to 1e-11.
+ * Errors, all found before any work (no flow is written): OFX_ERR_ARG as ofx_robust_expo, and for a level smaller than 3x3;
+ * OFX_ERR_SIGMA for a level too small for the zoom Gaussian.  ofx_get_stats: the level sizes, sweeps and stopping values per
+ * level and solve; with verbose the reference's "Scale: s" lines. */
+int ofx_robust_expo_pyramid(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
+                            int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
+                            int inner_iter, int outer_iter, int verbose);
 /* The reference's single-scale overload (robust_expo_methods.cpp:162-178, declared in none of its headers): the solver of one
  * level with no normalisation, no presmoothing and alpha as given; u, v are READ as the initial flow and overwritten with
  * the result -- what a caller needs to run colour on a pyramid of their own.  nz in 1 .. OFX_REXPO_MAX_CHANNELS, images

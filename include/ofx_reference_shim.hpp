@@ -106,6 +106,7 @@ void robust_expo_methods(const ofpix_t *I1, const ofpix_t *I2, ofpix_t *u, ofpix
     ofx_shim::check(ofx_robust_expo(ofx_shim::ctx(), I1, I2, u, v, nxx, nyy, nzz, method_type, alpha, gamma, lambda, nscales, nu,
                                     TOL, inner_iter, outer_iter, verbose));
 }
+// colour at more than one scale has no reference name to stand under: see ofx_robust_expo_pyramid in ofx.h
 // the single-scale overload of src/robust_expo_methods.cpp:162-178: an EXTRA, the reference declares it in none of its headers
 // (a caller that used it declared it itself); u, v are the initial flow on entry, number_of_threads is ignored
 void robust_expo_methods(const ofpix_t *I1, const ofpix_t *I2, ofpix_t *u, ofpix_t *v, const int nx, const int ny, const int nz,

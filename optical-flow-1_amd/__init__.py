@@ -39,7 +39,8 @@ class Stats(C.Structure):
                 ("iter_ms", C.c_double * MAX_SCALES),
                 ("iter_launches", C.c_longlong * MAX_SCALES),
                 ("work_pix_iters", C.c_double), ("total_ms", C.c_double),
-                ("odd_stops", C.c_int), ("odd_stops_stored", C.c_int), ("fused", C.c_int * MAX_SCALES)]
+                ("odd_stops", C.c_int), ("odd_stops_stored", C.c_int), ("fused", C.c_int * MAX_SCALES),
+                ("pyramid_ms", C.c_double)]
 
     def iterations(self):
         return np.array([[self.iters[s][w] for w in range(min(self.nsolves, MAX_SOLVES))]
@@ -95,6 +96,7 @@ def lib():
         "ofx_hypot": (_i, [_vp, _dp, _dp, _dp, _i]),
         "ofx_robust_expo": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _i, _i, _i]),
         "ofx_robust_expo_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _d, _d, _d, _d, _i, _i, _i, _i]),
+        "ofx_robust_expo_pyramid": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _d, _d, _d, _i, _d, _d, _i, _i, _i]),
         "ofx_bicubic_warp": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_zoom_size": (None, [_i, _i, C.POINTER(_i), C.POINTER(_i), _d]),
         "ofx_zoom_out": (_i, [_vp, _dp, _dp, _i, _i, _d]),
@@ -105,6 +107,7 @@ def lib():
         "ofx_centered_gradient3": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_bicubic_at_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i]),
         "ofx_zoom_out_color": (_i, [_vp, _dp, _dp, _i, _i, _i, _d]),
+        "ofx_zoom_out_channels": (_i, [_vp, _dp, _dp, _i, _i, _i, _d]),
         "ofx_tvl1_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _d, _d, _i, _d, _i]),
         "ofx_tvl1_multiscale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _d, _d, _i, _d, _i, _d, _i]),
         "ofx_tvl1_multiscale_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _d, _i, _d, _i, _d, _i]),
@@ -328,6 +331,18 @@ class Ofx:
                                         inner, outer, verbose))
         return u, v
 
+    def robust_expo_pyramid(self, I1, I2, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4, inner=1, outer=15,
+                            verbose=0, nz=None):
+        """robust_expo on a pyramid of (ny, nx) planes or (ny, nx, nz) colour images, nz = 1..4 at any nscales: the levels are
+        built with zoom_out_channels -> u, v"""
+        ny, nx, nz = self._colour_shape(I1, I2, nz)
+        if I1.ndim == 2 and nz != 1:
+            raise ValueError("robust_expo_pyramid: nz = %d needs (ny, nx, nz) images" % nz)
+        u, v = np.zeros((ny, nx)), np.zeros((ny, nx))
+        self._ck(self.L.ofx_robust_expo_pyramid(self.h, _f64(I1), _f64(I2), u, v, nx, ny, nz, method, alpha, gamma, lam, nscales, nu,
+                                                TOL, inner, outer, verbose))
+        return u, v
+
     def robust_expo_single_scale(self, I1, I2, u, v, method=1, alpha=50.0, gamma=10.0, lam=1.0, TOL=1e-4, inner=1, outer=15,
                                  verbose=0, nz=None):
         """One level of robust_expo_methods with no normalisation or presmoothing: (u, v) is the initial flow, the refined flow
@@ -480,6 +495,14 @@ class Ofx:
         nxx, nyy = zoom_size(nx, ny, factor)
         out = np.empty((nyy, nxx, nz))
         self._ck(self.L.ofx_zoom_out_color(self.h, _f64(I), out, nx, ny, nz, factor))
+        return out
+
+    def zoom_out_channels(self, I, factor):
+        """I: (ny, nx, nz) interleaved channels, nz = 1..4 -> (nyy, nxx, nz), every channel as zoom_out of that channel"""
+        ny, nx, nz = I.shape
+        nxx, nyy = zoom_size(nx, ny, factor)
+        out = np.empty((nyy, nxx, nz))
+        self._ck(self.L.ofx_zoom_out_channels(self.h, _f64(I), out, nx, ny, nz, factor))
         return out
 
     def image_normalization_1(self, I):

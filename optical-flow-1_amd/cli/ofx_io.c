@@ -152,8 +152,9 @@ static const struct ofx_png_api *png_api(void)
     return &api;
 }
 
-/* f is positioned at the start of the file.  Returns gray samples as double, or NULL. */
-static double *read_png(FILE *f, int *w, int *h)
+/* f is positioned at the start of the file.  c == NULL: gray samples as double (ofx_read_image_double); otherwise the
+ * file's 1..4 channels of 8 or 16 bits interleaved, *c = their number.  NULL on failure. */
+static double *read_png(FILE *f, int *w, int *h, int *c)
 {
     const struct ofx_png_api *P = png_api();
     if (!P) {
@@ -176,6 +177,23 @@ static double *read_png(FILE *f, int *w, int *h)
     const uint32_t ww = P->get_image_width(pp, pi), hh = P->get_image_height(pp, pi);
     const int ch = P->get_channels(pp, pi), depth = P->get_bit_depth(pp, pi);
     unsigned char **rows = P->get_rows(pp, pi);
+    if (c) {                                               /* every sample as it is stored, no collapse to gray */
+        const int okv = rows && ww > 0 && hh > 0 && ch >= 1 && ch <= 4 && (depth == 8 || depth == 16);
+        if (!okv) fprintf(stderr, "PNG with %d channel(s) of %d bits: not supported\n", ch, depth);
+        if (okv) out = (double *) malloc((size_t) ww * hh * ch * sizeof(double));
+        if (okv && out) {
+            for (uint32_t j = 0; j < hh; j++)
+                for (size_t e = 0; e < (size_t) ww * ch; e++) {
+                    const unsigned char *b = rows[j] + e * (depth / 8);
+                    out[(size_t) j * ww * ch + e] = depth == 16 ? (double) (uint16_t) ((b[0] << 8) | b[1]) : (double) b[0];
+                }
+            *w = (int) ww;
+            *h = (int) hh;
+            *c = ch;
+        }
+        P->destroy_read_struct(&pp, &pi, NULL);
+        return out;
+    }
     const int ok = rows && ww > 0 && hh > 0 && ((depth == 8 && (ch == 1 || ch == 3)) || (depth == 16 && ch == 1));
     if (!ok) fprintf(stderr, "PNG with %d channel(s) of %d bits: not a scalar image for the reference either\n", ch, depth);
     if (ok) out = (double *) malloc((size_t) ww * hh * sizeof(double));
@@ -204,7 +222,7 @@ double *ofx_read_image_double(const char *fname, int *w, int *h)
     float *data = NULL;
     if (c1 == 0x89 && c2 == 'P') {                          /* PNG signature 89 50 4E 47 ... */
         rewind(f);
-        double *png = read_png(f, w, h);
+        double *png = read_png(f, w, h, NULL);
         fclose(f);
         return png;
     }
@@ -222,6 +240,34 @@ double *ofx_read_image_double(const char *fname, int *w, int *h)
         } else {
             out[i] = data[i];
         }
+    }
+    free(data);
+    return out;
+}
+
+/* the channels as they are stored (the IPOL original reads with iio_read_image_float_vec, main.cpp:43-48): PGM / Pf one
+ * channel, PPM / PF three interleaved, PNG the file's 1..4; the float samples widened to double */
+double *ofx_read_image_double_vec(const char *fname, int *w, int *h, int *c)
+{
+    FILE *f = fopen(fname, "rb");
+    if (!f) return NULL;
+    int c1 = fgetc(f), c2 = fgetc(f), pd = 1;
+    float *data = NULL;
+    if (c1 == 0x89 && c2 == 'P') {
+        rewind(f);
+        double *png = read_png(f, w, h, c);
+        fclose(f);
+        return png;
+    }
+    if (c1 == 'P' && c2 >= '2' && c2 <= '6' && c2 != '4') data = read_pnm(f, c2 - '0', w, h, &pd);
+    else if (c1 == 'P' && (c2 == 'f' || c2 == 'F')) data = read_pfm(f, c2 == 'F', w, h, &pd);
+    fclose(f);
+    if (!data) return NULL;
+    const size_t n = (size_t) *w * *h * pd;
+    double *out = (double *) malloc(n * sizeof(double));
+    if (out) {
+        for (size_t i = 0; i < n; i++) out[i] = data[i];
+        *c = pd;
     }
     free(data);
     return out;

@@ -20,6 +20,9 @@ extern "C" {
 
 /* returns a malloc'ed w*h double image (caller frees) or NULL */
 double *ofx_read_image_double(const char *fname, int *w, int *h);
+/* the same files with their channels kept: a malloc'ed w*h*c double image, channels interleaved, *c = 1 (PGM, Pf), 3 (PPM,
+ * PF: NO collapse to gray) or the PNG's 1..4; or NULL */
+double *ofx_read_image_double_vec(const char *fname, int *w, int *h, int *c);
 /* uv = w*h interleaved (u,v) pairs; returns 0 on success */
 int ofx_write_flo(const char *fname, const float *uv, int w, int h);
 /* one-channel float image whose samples are all bytes (iio_save_image_float, src/iio.cpp:3698-3710): .png -> 8-bit gray PNG

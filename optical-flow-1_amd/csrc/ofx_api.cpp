@@ -147,6 +147,23 @@ template <typename T> int zoom_out_t(ofx_ctx *ctx, const double *I, double *Iout
     return h.sync();
 }
 
+template <typename T> int zoom_out_channels_t(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, int nz, double factor)
+{
+    HostOp<T> h{ctx};
+    const size_t n = (size_t) nx * ny * nz;
+    int nxx, nyy;
+    ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
+    if (nxx < 1 || nyy < 1) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: empty output");
+    T *a, *o, *t1, *t2;
+    OFX_TRY(h.in(I, &a, n));
+    OFX_TRY(h.out_alloc(&o, (size_t) nxx * nyy * nz));
+    OFX_TRY(h.out_alloc(&t1, n));
+    OFX_TRY(h.out_alloc(&t2, n));
+    OFX_TRY(op_zoom_out_channels<T>(ctx, a, o, t1, t2, nx, ny, nz, factor));
+    OFX_TRY(h.out(o, Iout, (size_t) nxx * nyy * nz));
+    return h.sync();
+}
+
 template <typename T> int zoom_in_t(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, int nxx, int nyy)
 {
     HostOp<T> h{ctx};
@@ -372,6 +389,20 @@ int ofx_zoom_out_color(ofx_ctx *ctx, const double *I, double *Iout, int nx, int 
     if (!ctx) return OFX_ERR_ARG;
     if (nz != 1) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_color: nz=%d (the reference is only defined for nz = 1)", nz);
     return ofx_zoom_out(ctx, I, Iout, nx, ny, factor);
+}
+
+int ofx_zoom_out_channels(ofx_ctx *ctx, const double *I, double *Iout, int nx, int ny, int nz, double factor)
+{
+    // the zoom_out of the IPOL original (3rdparty/ipoldfmethods_20160307/zoom.h:45-85): every one of the nx*ny*nz elements is
+    // copied and smoothed, so each channel is zoom_out of that channel -- the function src/zoom.cpp:85-125 was derived from
+    OFX_ENTER(ctx);
+    if (!I || !Iout) return ofx_fail(ctx, OFX_ERR_ARG, "NULL pointer");
+    if (nz < 1 || nz > OFX_REXPO_MAX_CHANNELS)
+        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: nz=%d (1..%d channels)", nz, OFX_REXPO_MAX_CHANNELS);
+    if (!(factor > 0) || !(factor < 1)) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor=%g", factor);
+    OFX_TRY(check_dims(ctx, nx, ny));
+    if ((long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "bad image size %dx%dx%d", nx, ny, nz);
+    return DISPATCH(ctx, zoom_out_channels_t, ctx, I, Iout, nx, ny, nz, factor);
 }
 
 int ofx_image_normalization_1(ofx_ctx *ctx, const double *I, double *In, int size)

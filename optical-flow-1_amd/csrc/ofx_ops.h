@@ -43,6 +43,10 @@ template <typename T> int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v
 // zoom_out (src/zoom.cpp:41-78): tmpA, tmpB are nx*ny scratch images
 template <typename T> int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny,
                                       double factor);
+// zoom_out of nz interleaved channels, each channel as zoom_out (the IPOL original of robust_expo_methods, zoom.h:45-85):
+// tmpA, tmpB are nx*ny*nz scratch images; OFX_ERR_SIGMA under zoom_out's rule, before anything is launched
+template <typename T> int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz,
+                                               double factor);
 
 // planar operators for the operator-level API
 template <typename T> int op_divergence(ofx_ctx *ctx, const T *v1, const T *v2, T *div, int nx, int ny);

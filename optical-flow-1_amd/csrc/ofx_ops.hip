@@ -550,6 +550,71 @@ int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int
     return op_resample<T>(ctx, tmpA, Iout, nx, ny, nxx, nyy, factor, factor);
 }
 
+// ---- zoom_out of nz interleaved channels (IPOL original of robust_expo_methods, zoom.h:45-85 with gaussian.h:23-168) ----
+// Channel k of the result is zoom_out of channel k: per pixel the sums and the cubics of k_gauss_pass / bicubic_sample in the
+// same order, on the interleaved image itself.
+// Row pass: a row is nx * nz contiguous elements, one lane per ELEMENT (a wave loads 64 consecutive elements per tap); the
+// taps are nz elements apart and the reflection is taken on the pixel index.  The column pass is k_gauss_pass<T, false> on an
+// image of nx * nz columns: the channels of a column are independent columns there.
+template <typename T>
+__global__ void k_gauss_row_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, GaussTaps taps)
+{
+    const int e = blockIdx.x * BX + threadIdx.x;
+    const int i = blockIdx.y * BY + threadIdx.y;
+    if (e >= nx * nz || i >= ny) return;
+    const int j = e / nz, k = e - j * nz;
+    const T *row = in + (size_t) i * nx * nz + k;
+    double sum = taps.B[0] * ldw(row + (size_t) j * nz);
+    for (int t = 1; t < taps.size; t++)
+        sum += taps.B[t] * (ldw(row + (size_t) gauss_reflect(j - t, nx) * nz) + ldw(row + (size_t) gauss_reflect(j + t, nx) * nz));
+    stn(out + (size_t) i * nx * nz + e, sum);
+}
+
+// Sample stage: the 16 tap indices of an output pixel once, then one bicubic per channel from them
+template <typename T>
+__global__ void k_resample_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, int nxx, int nyy, double factor)
+{
+    const int j1 = blockIdx.x * BX + threadIdx.x;
+    const int i1 = blockIdx.y * BY + threadIdx.y;
+    if (j1 >= nxx || i1 >= nyy) return;
+    const double i2 = i1 / factor, j2 = j1 / factor;
+    const BicubicTaps t = bicubic_taps(j2, i2, nx, ny);
+    size_t tap[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) tap[r][q] = ((size_t) t.row[r] * nx + t.col[q]) * nz;
+    T *o = out + ((size_t) i1 * nxx + j1) * nz;
+    for (int k = 0; k < nz; k++) {
+        double c[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            c[q] = cubic_cell(ldw(in + tap[0][q] + k), ldw(in + tap[1][q] + k), ldw(in + tap[2][q] + k), ldw(in + tap[3][q] + k), t.fy);
+        stn(o + k, cubic_cell(c[0], c[1], c[2], c[3], t.fx));
+    }
+}
+
+template <typename T>
+int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz, double factor)
+{
+    int nxx, nyy;
+    ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
+    const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.h:21,66
+    GaussTaps taps;
+    if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
+    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
+    if (taps.size >= nx || taps.size >= ny)                               // op_gaussian's rule
+        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    hipLaunchKernelGGL(k_gauss_row_ch<T>, grid2d(nx * nz, ny), block2d(), 0, ctx->stream, I, tmpA, nx, ny, nz, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_gauss_pass<T, false>), grid2d(nx * nz, ny), block2d(), 0, ctx->stream, (const T *) tmpA, tmpB, nx * nz, ny, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_resample_ch<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, (const T *) tmpB, Iout, nx, ny, nz, nxx, nyy, factor);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
 // ---- planar stencil operators (operator-level API) --------------------------------------------------
 template <typename T>
 __global__ void k_divergence(const T *__restrict__ v1, const T *__restrict__ v2, T *__restrict__ div, int nx, int ny)
@@ -961,6 +1026,7 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
     template int op_resample<T>(ofx_ctx *, const T *, T *, int, int, int, int, double, double);                       \
     template int op_zoom_in_flow<T>(ofx_ctx *, const Pix<T>::v2 *, Pix<T>::v2 *, int, int, int, int, double);         \
     template int op_zoom_out<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, double);                               \
+    template int op_zoom_out_channels<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, int, double);                 \
     template int op_divergence<T>(ofx_ctx *, const T *, const T *, T *, int, int);                                    \
     template int op_forward_gradient<T>(ofx_ctx *, const T *, T *, T *, int, int);                                    \
     template int op_centered_gradient<T>(ofx_ctx *, const T *, T *, T *, int, int);                                   \

@@ -2383,6 +2383,38 @@ extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2
     return s;
 }
 
+// The head of the multiscale overload (src/robust_expo_methods.cpp:494-498) on host images of nz interleaved channels:
+// image_normalization_2_color and the source's Gaussian call; *A, *B = the level-0 images on the device, allocated here unless
+// the caller hands in arrays of nx * ny * nz elements
+template <typename T>
+static int rexpo_normalise_presmooth(ofx_ctx *ctx, const double *I1, const double *I2, int nx, int ny, int nz, T **A, T **B)
+{
+    const size_t n = (size_t) nx * ny, nc = n * nz;
+    double *a, *b, *part;
+    T *tmp;
+    OFX_TRY(ofx_alloc(ctx, nc, &a));
+    OFX_TRY(ofx_alloc(ctx, nc, &b));
+    if (!*A) OFX_TRY(ofx_alloc(ctx, nc, A));
+    if (!*B) OFX_TRY(ofx_alloc(ctx, nc, B));
+    OFX_TRY(ofx_alloc(ctx, (size_t) nz * 2 * RX_MM_BLOCKS, &part));
+    OFX_TRY(ofx_alloc(ctx, n, &tmp));
+    OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    int nb = (int) ((n + 255) / 256);
+    if (nb > RX_MM_BLOCKS) nb = RX_MM_BLOCKS;
+    hipLaunchKernelGGL(k_rexpo_mm_partial, dim3(nb, nz), dim3(256), 0, ctx->stream, (const double *) a, (const double *) b, n, nz, part);
+    OFX_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_rexpo_norm_map<T>, dim3((unsigned) ((nc + 255) / 256)), dim3(256), 0, ctx->stream, (const double *) a,
+                       (const double *) b, *A, *B, nc, nz, (const double *) part, nb);
+    OFX_LAUNCH_CHECK(ctx);
+    // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
+    // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
+    // so only the first nx * ny elements of the interleaved image are smoothed (across pixels and channels alike)
+    OFX_TRY(op_gaussian<T>(ctx, *A, tmp, nx, ny, (double) nz, 1));
+    OFX_TRY(op_gaussian<T>(ctx, *B, tmp, nx, ny, (double) nz, 1));
+    return OFX_OK;
+}
+
 // robust_expo_methods on ONE level of nz interleaved channels, both public entries:
 //   presmooth = true : the multiscale overload called with nscales = 1 (src/robust_expo_methods.cpp:462-566):
 //                      image_normalization_2_color, its Gaussian call and a zero flow in front of the level solver
@@ -2400,30 +2432,9 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
     ctx->stats.ny[0] = ny;
     BroxLevel<T> L;
     OFX_TRY(brox_level_alloc<T>(ctx, L, nx, ny, 1, nz));
-    T *A, *B;
+    T *A = nz == 1 ? L.I1 : nullptr, *B = nz == 1 ? L.I2 : nullptr;      // one channel: the level's own planes
     if (presmooth) {
-        double *a, *b, *part;
-        T *tmp;
-        OFX_TRY(ofx_alloc(ctx, nc, &a));
-        OFX_TRY(ofx_alloc(ctx, nc, &b));
-        OFX_TRY(ofx_alloc(ctx, nc, &A));
-        OFX_TRY(ofx_alloc(ctx, nc, &B));
-        OFX_TRY(ofx_alloc(ctx, (size_t) nz * 2 * RX_MM_BLOCKS, &part));
-        OFX_TRY(ofx_alloc(ctx, n, &tmp));
-        OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        int nb = (int) ((n + 255) / 256);
-        if (nb > RX_MM_BLOCKS) nb = RX_MM_BLOCKS;
-        hipLaunchKernelGGL(k_rexpo_mm_partial, dim3(nb, nz), dim3(256), 0, ctx->stream, (const double *) a, (const double *) b, n, nz, part);
-        OFX_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(k_rexpo_norm_map<T>, dim3((unsigned) ((nc + 255) / 256)), dim3(256), 0, ctx->stream, (const double *) a,
-                           (const double *) b, A, B, nc, nz, (const double *) part, nb);
-        OFX_LAUNCH_CHECK(ctx);
-        // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
-        // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
-        // so only the first nx * ny elements of the interleaved image are smoothed (across pixels and channels alike)
-        OFX_TRY(op_gaussian<T>(ctx, A, tmp, nx, ny, (double) nz, 1));
-        OFX_TRY(op_gaussian<T>(ctx, B, tmp, nx, ny, (double) nz, 1));
+        OFX_TRY(rexpo_normalise_presmooth<T>(ctx, I1, I2, nx, ny, nz, &A, &B));
         OFX_TRY(op_fill2<T>(ctx, L.U, n));                                                         // :522-524
     } else {
         double *du, *dv;
@@ -2440,6 +2451,80 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
     if (P.verbose && presmooth) { printf("Scale: 0\n"); fflush(stdout); }
     OFX_TRY(brox_single_scale_dev<T>(ctx, L, P, 0, &ctx->stats));
     return download_flow<T>(ctx, L.U, u, v, n);
+}
+
+// The multiscale overload (src/robust_expo_methods.cpp:482-566) on nz interleaved channels at any number of scales, with ONE
+// call replaced: the levels come from op_zoom_out_channels -- the zoom_out of the IPOL original, each channel as zoom_out --
+// where the reference's zoom_out_color reads beyond its scratch copy (zoom.cpp:96-118).  Everything else is the driver as
+// ofx_robust_expo runs it: the head above, a zero flow at the coarsest level, brox_single_scale_dev and op_zoom_in_flow per
+// level (the loop of brox_spatial_dev).  All levels are checked before anything is uploaded.
+template <typename T>
+static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
+                              const BroxParams &P, int nscales, double nu)
+{
+    std::vector<int> nxs, nys;
+    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, nu, nxs, nys));
+    const size_t n = (size_t) nx * ny, nc = n * nz;
+    if ((long long) nc >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: more than 2^31 image elements");
+    if (nscales > 1) {
+        GaussTaps taps;
+        if (ofx_gauss_taps(0.6 * sqrt(1.0 / (nu * nu) - 1.0), &taps) != OFX_OK)
+            return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: zoom factor %g needs more than %d taps", nu, OFX_GAUSS_MAX_TAPS);
+        for (int s = 0; s + 1 < nscales; s++)
+            if (taps.size >= nxs[s] || taps.size >= nys[s])
+                return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, scale %d is %dx%d)", taps.size, s,
+                                nxs[s], nys[s]);
+    }
+    for (int s = 0; s < nscales; s++)
+        if (nxs[s] < 3 || nys[s] < 3)
+            return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs levels of at least 3x3 (scale %d is %dx%d)", s, nxs[s], nys[s]);
+    sor_stats_begin(&ctx->stats, nscales, P.inner_iter * P.outer_iter);
+    for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { ctx->stats.nx[s] = nxs[s]; ctx->stats.ny[s] = nys[s]; }
+    std::vector<BroxLevel<T>> lv(nscales);
+    std::vector<T *> lA(nscales), lB(nscales);
+    for (int s = 0; s < nscales; s++) {
+        OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], 1, nz));
+        if (nz == 1) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }                   // one channel: the level's own planes
+        else {
+            lA[s] = lB[s] = nullptr;
+            if (s) {
+                OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s] * nz, &lA[s]));
+                OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s] * nz, &lB[s]));
+            }
+        }
+    }
+    if (ctx->profile) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    OFX_TRY(rexpo_normalise_presmooth<T>(ctx, I1, I2, nx, ny, nz, &lA[0], &lB[0]));               // :494-498
+    {
+        T *tmpA = nullptr, *tmpB = nullptr;
+        if (nscales > 1) {
+            OFX_TRY(ofx_alloc(ctx, nc, &tmpA));
+            OFX_TRY(ofx_alloc(ctx, nc, &tmpB));
+        }
+        for (int s = 1; s < nscales; s++) {                                                        // :512-520
+            OFX_TRY(op_zoom_out_channels<T>(ctx, lA[s - 1], lA[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
+            OFX_TRY(op_zoom_out_channels<T>(ctx, lB[s - 1], lB[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
+        }
+    }
+    double pyramid_ms = 0.0;
+    if (ctx->profile) {
+        float ms;
+        OFX_HIP(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_t1));
+        OFX_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+        pyramid_ms = ms;
+    }
+    if (nz > 1)
+        for (int s = 0; s < nscales; s++) { lv[s].I1c = lA[s]; lv[s].I2c = lB[s]; }
+    OFX_TRY(op_fill2<T>(ctx, lv[nscales - 1].U, lv[nscales - 1].n()));                             // :522-524
+    for (int s = nscales - 1; s >= 0; s--) {                                                      // :530
+        if (P.verbose) { printf("Scale: %d\n", s); fflush(stdout); }
+        OFX_TRY(brox_single_scale_dev<T>(ctx, lv[s], P, s, &ctx->stats));
+        if (s)
+            OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U, lv[s - 1].U, lv[s].nx, lv[s].ny, lv[s - 1].nx, lv[s - 1].ny, 1.0 / nu));
+    }
+    ctx->stats.pyramid_ms = pyramid_ms;
+    return download_flow<T>(ctx, lv[0].U, u, v, n);
 }
 
 static int rexpo_check_args(ofx_ctx *ctx, const double *I1, const double *I2, const double *u, const double *v, int nz, int method_type,
@@ -2476,6 +2561,26 @@ extern "C" int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2,
     else
         s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true)
                                       : rexpo_level_host<float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true);
+    ctx->stats.total_ms = ofx_now_ms() - t0;
+    return s;
+}
+
+// ofx_robust_expo's argument list, any nzz in 1 .. OFX_REXPO_MAX_CHANNELS at any number of scales: the reference's driver on
+// levels built by the per-channel zoom-out of the IPOL original (rexpo_pyramid_host).  nzz = 1 is ofx_robust_expo's result,
+// nscales = 1 ofx_robust_expo's colour result.
+extern "C" int ofx_robust_expo_pyramid(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy,
+                                       int nzz, int method_type, double alpha, double gamma, double lambda, int nscales, double nu,
+                                       double TOL, int inner_iter, int outer_iter, int verbose)
+{
+    OFX_ENTER(ctx);
+    OFX_TRY(rexpo_check_args(ctx, I1, I2, u, v, nzz, method_type, inner_iter, outer_iter));
+    const double t0 = ofx_now_ms();
+    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, verbose};     // :527: alpha * nzz as an int
+    P.robust = 1;
+    P.method = method_type;
+    P.lambda = lambda;
+    int s = ctx->precision == OFX_F64 ? rexpo_pyramid_host<double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu)
+                                      : rexpo_pyramid_host<float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
 }

@@ -1,0 +1,308 @@
+"""robust_expo_methods on colour images over a pyramid: ofx_zoom_out_channels, ofx_robust_expo_pyramid and the
+robust_expo_methods front-end, against the compiled reference's entry points composed as its multiscale driver with every
+level zoomed out channel by channel (tests/rexpo_pyramid_ref.py), live and through recorded fixtures.
+
+The bound on the flows is BOUND of tests/test_gpu_rexpo_color.py, 1e-11: the one the one-channel pyramid is held to in
+tests/test_gpu_sor.py -- the sweep tables are equal and the order of the stopping sum is the only difference.
+
+Every comparison prints its max |du|, max |dv| before it asserts (run with -s to keep them)."""
+import ctypes as C
+import importlib.util
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_gpu_relaxed_modes import same_bits
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+GOLDEN = os.path.join(HERE, "golden")
+BIN = os.path.join(ROOT, "optical-flow-1_amd", "bin")
+BOUND = 1e-11
+
+
+def _load(name, path):
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+H = _load("rexpo_pyramid_ref", os.path.join(HERE, "rexpo_pyramid_ref.py"))
+CASES = json.load(open(os.path.join(GOLDEN, "cases_color_pyramid.json")))
+
+
+def _report(tag, ug, vg, ur, vr):
+    du, dv = float(np.abs(ug - ur).max()), float(np.abs(vg - vr).max())
+    print("%s: max|du| = %.3g, max|dv| = %.3g" % (tag, du, dv))
+    return du, dv
+
+
+def _solve(gpu, c):
+    I1, I2 = H.inputs(c)
+    return gpu.robust_expo_pyramid(I1, I2, nscales=c["nscales"], nu=c["nu"], **c["params"])
+
+
+# ---- 5. the operator --------------------------------------------------------------------------------------------------------
+def _image(seed, ny, nx, nz):
+    return np.random.default_rng(seed).standard_normal((ny, nx, nz)) * 50 + 100
+
+
+@pytest.mark.parametrize("factor", [0.5, 0.7])
+@pytest.mark.parametrize("nx,ny,nzs", [(64, 48, (1, 2, 3, 4)), (131, 67, (1, 2, 3, 4)), (33, 21, (1, 2, 3, 4)), (640, 480, (3,))])
+def test_zoom_out_channels_is_zoom_out_per_channel(gpu64, ref, nx, ny, nzs, factor):
+    for nz in nzs:
+        a = _image(nz, ny, nx, nz)
+        got = gpu64.zoom_out_channels(a, factor)
+        assert got.shape == gpu64.zoom_out(np.ascontiguousarray(a[..., 0]), factor).shape + (nz,)
+        for k in range(nz):
+            assert np.array_equal(got[..., k], ref.zoom_out(np.ascontiguousarray(a[..., k]), factor)), (nz, k)
+        if nz == 1:
+            assert np.array_equal(got[..., 0], gpu64.zoom_out(np.ascontiguousarray(a[..., 0]), factor))
+
+
+@pytest.mark.parametrize("factor", [0.5, 0.7])
+@pytest.mark.parametrize("nx,ny,nz", [(64, 48, 3), (131, 67, 4), (33, 21, 2), (47, 33, 1), (640, 480, 3)])
+def test_zoom_out_channels_f32_storage_bit_for_bit(gpu32, orc, nx, ny, nz, factor):
+    a = _image(7, ny, nx, nz)
+    got = gpu32.zoom_out_channels(a, factor)
+    for k in range(nz):
+        plane = np.ascontiguousarray(a[..., k])
+        assert same_bits(got[..., k], orc.zoom_out_mode(plane, factor, 1)), k
+        if nz == 1:
+            assert same_bits(got[..., 0], gpu32.zoom_out(plane, factor))
+
+
+def test_zoom_out_channels_errors(gpu64, ofx_mod):
+    with pytest.raises(ofx_mod.OfxError) as e:
+        gpu64.zoom_out_channels(_image(1, 12, 5, 3), 0.5)           # radius 6 reaches the width
+    assert e.value.status == 2
+    with pytest.raises(ofx_mod.OfxError) as e:
+        gpu64.zoom_out_channels(_image(1, 5, 12, 1), 0.5)
+    assert e.value.status == 2
+    a, out = _image(1, 24, 32, 4), np.full((12, 16, 4), -7.0)
+    for nz in (0, 5, -1):
+        assert gpu64.L.ofx_zoom_out_channels(gpu64.h, a, out, 32, 24, nz, 0.5) == 1
+    for factor in (0.0, 1.0, -0.5):
+        assert gpu64.L.ofx_zoom_out_channels(gpu64.h, a, out, 32, 24, 4, factor) == 1
+    assert gpu64.L.ofx_zoom_out_channels(gpu64.h, a, out, 1, 24, 4, 0.5) == 1
+    assert (out == -7.0).all()
+    assert gpu64.zoom_out_channels(a, 0.5).shape == (12, 16, 4)     # the context still works
+
+
+# ---- 6. the fixtures ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_fixture(gpu64, name):
+    c, g = CASES[name], np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    u, v = _solve(gpu64, c)
+    st = gpu64.stats()
+    got = st.iterations()
+    print(name, "sweeps", got.tolist(), "recorded", g["iters"].tolist())
+    du, dv = _report(name, u, v, g["u"], g["v"])
+    assert st.nscales == c["nscales"] and got.shape == g["iters"].shape
+    assert np.array_equal(got, g["iters"])
+    assert du < BOUND and dv < BOUND
+
+
+# ---- 7. live against the composition -----------------------------------------------------------------------------------------
+LIVE = [
+    ("P1", 320, 240, 3, 4, dict(method=1, alpha=50.0, gamma=10.0, lam=0.1, outer=4)),
+    ("P1", 320, 240, 3, 4, dict(method=2, alpha=50.0, gamma=10.0, lam=0.1, outer=4)),
+    ("P1", 320, 240, 3, 4, dict(method=3, alpha=50.0, gamma=10.0, lam=0.1, outer=4)),
+    ("P0", 131, 67, 4, 3, dict(method=3, alpha=30.0, gamma=10.0, lam=1.0, outer=4)),
+    ("P1", 640, 480, 3, 5, dict(method=1, alpha=50.0, gamma=10.0, lam=0.1, outer=4)),
+]
+
+
+@pytest.mark.parametrize("pair,nx,ny,nz,nscales,kw", LIVE, ids=["%s-%dx%dx%d-s%d-m%d" % (c[0], c[1], c[2], c[3], c[4], c[5]["method"]) for c in LIVE])
+def test_live_against_the_composition(gpu64, ref, pair, nx, ny, nz, nscales, kw):
+    c = dict(pair=pair, nx=nx, ny=ny, nz=nz, nscales=nscales, nu=0.5, params=kw)
+    ur, vr = H.run_case(ref, c)
+    ug, vg = _solve(gpu64, c)
+    st = gpu64.stats()
+    du, dv = _report("live %s %dx%dx%d, %d scales, method %d" % (pair, nx, ny, nz, nscales, kw["method"]), ug, vg, ur, vr)
+    assert np.isfinite(ur).all() and np.isfinite(vr).all() and np.abs(ur).max() > 0.1
+    assert st.nscales == nscales and (st.nx[0], st.ny[0]) == (nx, ny)
+    assert du < BOUND and dv < BOUND
+
+
+# ---- 8. the two identities ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pair,nx,ny,kw", [("P1", 96, 64, dict(method=1, alpha=50.7, gamma=10.0, lam=0.1, outer=4)),
+                                           ("P0", 131, 67, dict(method=3, alpha=30.2, gamma=5.0, lam=1.0, outer=3, inner=2))])
+def test_one_channel_is_robust_expo(gpu64, synth, pair, nx, ny, kw):
+    I1, I2 = synth.pair(pair, nx, ny)
+    ua, va = gpu64.robust_expo(I1, I2, nscales=3, **kw)
+    sa = gpu64.stats()
+    ub, vb = gpu64.robust_expo_pyramid(I1, I2, nscales=3, **kw)
+    sb = gpu64.stats()
+    assert np.array_equal(ua, ub) and np.array_equal(va, vb)
+    assert sa.nscales == sb.nscales == 3 and sa.nsolves == sb.nsolves
+    assert list(sa.nx[:3]) == list(sb.nx[:3]) and list(sa.ny[:3]) == list(sb.ny[:3])
+    assert np.array_equal(sa.iterations(), sb.iterations()) and np.array_equal(sa.errors(), sb.errors())
+    assert sa.work_pix_iters == sb.work_pix_iters
+    uc, vc = gpu64.robust_expo_pyramid(I1[..., None], I2[..., None], nscales=3, **kw)       # a (ny, nx, 1) image is the plane
+    assert np.array_equal(ua, uc) and np.array_equal(va, vc)
+
+
+@pytest.mark.parametrize("pair,nx,ny,nz,kw", [("P1", 96, 64, 3, dict(method=1, alpha=50.0, gamma=10.0, lam=0.1, outer=4)),
+                                              ("P0", 33, 21, 4, dict(method=2, alpha=7.9, gamma=4.0, lam=0.3, outer=5))])
+def test_one_scale_is_robust_expo_on_colour(gpu64, synth, pair, nx, ny, nz, kw):
+    I1, I2 = synth.colour_pair(pair, nx, ny, nz)
+    ua, va = gpu64.robust_expo(I1, I2, nscales=1, **kw)
+    ita = gpu64.stats().iterations().copy()
+    ub, vb = gpu64.robust_expo_pyramid(I1, I2, nscales=1, **kw)
+    assert np.array_equal(ua, ub) and np.array_equal(va, vb)
+    assert np.array_equal(ita, gpu64.stats().iterations())
+
+
+# ---- 9. errors, and the workspace afterwards ----------------------------------------------------------------------------------
+def test_errors_leave_the_context_usable(gpu64, ofx_mod, synth):
+    I1, I2 = synth.colour_pair("P1", 32, 24, 3)
+    z = np.zeros((24, 32))
+    L, h = gpu64.L, gpu64.h
+    dp = C.POINTER(C.c_double)
+
+    def raw(a, b, u, v, nx, ny, nz, method=1, nscales=2, nu=0.5, inner=1, outer=2):
+        return L.ofx_robust_expo_pyramid(h, a, b, u, v, nx, ny, nz, method, 50.0, 10.0, 0.1, nscales, nu, 1e-4, inner, outer, 0)
+
+    u, v = z.copy(), z.copy()
+    for nz in (0, 5, -1):
+        assert raw(I1, I2, u, v, 32, 24, nz) == 1
+    for method in (0, 4):
+        assert raw(I1, I2, u, v, 32, 24, 3, method=method) == 1
+    assert raw(I1, I2, u, v, 32, 24, 3, inner=-1) == 1 and raw(I1, I2, u, v, 32, 24, 3, outer=-1) == 1
+    assert raw(I1, I2, u, v, 32, 24, 3, nscales=0) == 1
+    for nu in (0.0, 1.0):
+        assert raw(I1, I2, u, v, 32, 24, 3, nu=nu) == 1
+    assert raw(I1, I2, u, v, 2, 2, 3, nscales=1) == 1                 # the coarsest (only) level is under 3x3
+    assert "3x3" in L.ofx_last_error(h).decode()
+    assert raw(I1, I2, u, v, 32, 6, 3, nscales=2) == 2                # radius 6 of the zoom Gaussian reaches the height of level 0
+    assert raw(I1, I2, u, v, 32, 24, 3, nscales=4) == 2               # ... of level 2: 32x24 -> 16x12 -> 8x6, which cannot be built on
+    assert raw(I1, I2, u, v, 32, 24, 3, nscales=9) == 2
+    gpu64.set_option("sor_exact", 0)
+    try:
+        assert raw(I1, I2, u, v, 32, 24, 3) == 1
+        with pytest.raises(ofx_mod.OfxError) as e:
+            gpu64.robust_expo_pyramid(I1, I2, nscales=2, outer=2)
+        assert e.value.status == 1
+    finally:
+        gpu64.set_option("sor_exact", 1)
+    fn = L.ofx_robust_expo_pyramid
+    saved = fn.argtypes
+    try:
+        fn.argtypes = [C.c_void_p, dp, dp, dp, dp] + list(saved[5:])
+        ptr = [x.ctypes.data_as(dp) for x in (np.ascontiguousarray(I1), np.ascontiguousarray(I2), u, v)]
+        for k in range(4):
+            args = list(ptr)
+            args[k] = None
+            assert fn(h, *args, 32, 24, 3, 1, 50.0, 10.0, 0.1, 2, 0.5, 1e-4, 1, 2, 0) == 1
+    finally:
+        fn.argtypes = saved
+    assert np.array_equal(u, z) and np.array_equal(v, z)              # no failed call wrote a flow
+    with pytest.raises(ofx_mod.OfxError) as e:
+        gpu64.robust_expo_pyramid(I1, I2, nscales=4, outer=2)
+    assert e.value.status == 2
+    # the next valid call is served
+    assert raw(I1, I2, u, v, 32, 24, 3, nscales=2) == 0 and np.abs(u).max() > 0
+    name = "rexpocp_m1_p1_96x64x3_s3"
+    c, g = CASES[name], np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    ug, vg = _solve(gpu64, c)
+    assert np.abs(ug - g["u"]).max() < BOUND and np.abs(vg - g["v"]).max() < BOUND
+
+
+def test_workspace_reuse_after_a_colour_pyramid(gpu64, ofx_mod, synth):
+    """after a colour pyramid, a one-channel robust_expo and a brox_spatial on the same context are bit-equal to a fresh context's"""
+    P1, P2 = synth.pair("P1", 96, 64)
+    C1, C2 = synth.colour_pair("P0", 131, 67, 4)
+    kw = dict(method=1, alpha=50.0, gamma=10.0, lam=0.1, nscales=3, outer=4)
+    fresh = ofx_mod.Ofx(0, ofx_mod.F64)
+    ur, vr = fresh.robust_expo(P1, P2, **kw)
+    ub, vb = fresh.brox_spatial(P1, P2, nscales=3, outer=3)
+    uc, vc = fresh.robust_expo_pyramid(C1, C2, nscales=3, method=2, alpha=20.0, lam=0.1, outer=3)
+    del fresh
+    u0, v0 = gpu64.robust_expo_pyramid(C1, C2, nscales=3, method=2, alpha=20.0, lam=0.1, outer=3)
+    assert np.array_equal(u0, uc) and np.array_equal(v0, vc)
+    u1, v1 = gpu64.robust_expo(P1, P2, **kw)
+    assert np.array_equal(u1, ur) and np.array_equal(v1, vr)
+    gpu64.robust_expo_pyramid(C1, C2, nscales=2, method=3, alpha=60.0, outer=2)
+    u2, v2 = gpu64.brox_spatial(P1, P2, nscales=3, outer=3)
+    assert np.array_equal(u2, ub) and np.array_equal(v2, vb)
+    u3, v3 = gpu64.robust_expo_pyramid(C1, C2, nscales=3, method=2, alpha=20.0, lam=0.1, outer=3)
+    assert np.array_equal(u3, uc) and np.array_equal(v3, vc)
+
+
+# ---- 10. the front-end ---------------------------------------------------------------------------------------------------------
+def write_pnm(path, img):
+    img = np.asarray(img)
+    with open(path, "wb") as f:
+        f.write(b"%s\n%d %d\n255\n" % (b"P6" if img.ndim == 3 else b"P5", img.shape[1], img.shape[0]))
+        f.write(img.astype(np.uint8).tobytes())
+
+
+def read_flo(path):
+    raw = open(path, "rb").read()
+    assert raw[:4] == b"PIEH"
+    w, h = np.frombuffer(raw[4:12], dtype=np.uint32)
+    return raw[12:], int(w), int(h)
+
+
+def run_front_end(*args):
+    """each run under a time limit of its own"""
+    return subprocess.run(["timeout", "-k", "10", "300", os.path.join(BIN, "robust_expo_methods")] + [str(a) for a in args],
+                          capture_output=True, text=True)
+
+
+def front_end_nscales(nx, ny, nscales=10, zfactor=0.5):
+    N = 1 + np.log(min(nx, ny) / 16.) / np.log(1. / zfactor)
+    return min(nscales, int(N))
+
+
+def test_front_end_colour_and_gray(gpu64, synth, tmp_path):
+    nx, ny = 96, 64
+    I1, I2 = synth.colour_pair("P1", nx, ny, 3)
+    b1, b2 = I1.astype(np.uint8), I2.astype(np.uint8)                      # what a PPM holds
+    write_pnm(tmp_path / "a.ppm", b1)
+    write_pnm(tmp_path / "b.ppm", b2)
+    ns = front_end_nscales(nx, ny)
+    assert ns == 3
+    # defaults: flow.flo 1 1 50 10 0.2 10 0.5 0.0001 1 15 0
+    r = run_front_end(tmp_path / "a.ppm", tmp_path / "b.ppm", tmp_path / "o.flo")
+    assert r.returncode == 0, r.stderr
+    assert " ncores:1 method_type:1 alpha:50 gamma:10 lambda:0.2 scales:3 nu:0.5 TOL:0.0001 inner:1 outer:15" in r.stdout
+    u, v = gpu64.robust_expo_pyramid(b1.astype(np.float64), b2.astype(np.float64), method=1, alpha=50.0, gamma=10.0, lam=0.2, nscales=ns,
+                                     nu=0.5, TOL=1e-4, inner=1, outer=15)
+    payload, w, h = read_flo(tmp_path / "o.flo")
+    assert (w, h) == (nx, ny)
+    assert payload == np.stack([u, v], axis=-1).astype(np.float32).tobytes()
+    # out-of-range values fall back to the defaults; verbose prints the reference's scale lines
+    r = run_front_end(tmp_path / "a.ppm", tmp_path / "b.ppm", tmp_path / "o2.flo", 0, 7, -1, -1, -1, 0, 1.5, 0, 0, 0, 1)
+    assert r.returncode == 0, r.stderr
+    assert " ncores:0 method_type:1 alpha:50 gamma:10 lambda:0.2 scales:3 nu:0.5 TOL:0.0001 inner:1 outer:15" in r.stdout
+    assert [ln for ln in r.stdout.splitlines() if ln.startswith("Scale: ")] == ["Scale: 2", "Scale: 1", "Scale: 0"]
+    assert read_flo(tmp_path / "o2.flo")[0] == payload
+    # a PGM pair: the one-channel solve
+    write_pnm(tmp_path / "a.pgm", b1[..., 0])
+    write_pnm(tmp_path / "b.pgm", b2[..., 0])
+    r = run_front_end(tmp_path / "a.pgm", tmp_path / "b.pgm", tmp_path / "g.flo", 1, 2, 30, 5, 0.1, 2, 0.5, 0.0001, 1, 4, 0)
+    assert r.returncode == 0, r.stderr
+    assert " method_type:2 alpha:30 gamma:5 lambda:0.1 scales:2 " in r.stdout
+    u, v = gpu64.robust_expo(b1[..., 0].astype(np.float64), b2[..., 0].astype(np.float64), method=2, alpha=30.0, gamma=5.0, lam=0.1,
+                             nscales=2, nu=0.5, TOL=1e-4, inner=1, outer=4)
+    assert read_flo(tmp_path / "g.flo")[0] == np.stack([u, v], axis=-1).astype(np.float32).tobytes()
+
+
+def test_front_end_refuses_mismatched_images(synth, tmp_path):
+    I1, I2 = synth.colour_pair("P1", 48, 32, 3)
+    write_pnm(tmp_path / "a.ppm", I1)
+    write_pnm(tmp_path / "b.pgm", I2[..., 0])
+    write_pnm(tmp_path / "c.ppm", I2[:30])
+    for other in ("b.pgm", "c.ppm", "missing.ppm"):
+        r = run_front_end(tmp_path / "a.ppm", tmp_path / other, tmp_path / "o.flo")
+        assert r.returncode not in (0, 124, 137), (other, r.returncode)
+        assert "Cannot read the images or the size of the images are not equal" in r.stderr
+        assert not (tmp_path / "o.flo").exists()
