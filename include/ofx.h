@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OFX_VERSION 101
+#define OFX_VERSION 102
 
 /* status codes */
 #define OFX_OK          0
@@ -94,7 +94,7 @@ int   ofx_ctx_synchronize(ofx_ctx *ctx);
 int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
 /* options (value 0 = default / automatic unless noted):
  *   "profile"        0/1  bracket the inner-iteration launches with HIP events -> stats.iter_ms (and the pyramid phase of
- *                         ofx_robust_expo_pyramid -> stats.pyramid_ms)
+ *                         ofx_robust_expo_pyramid / _group_dev -> stats.pyramid_ms; _group_dev: iter_ms on the host's clock)
  *   "fixed_work"     0/1  TV-L1: every warp runs exactly OFX_TVL1_MAX_ITERATIONS iterations (stopping
  *                         test disabled; the reference with epsilon = 0)
  *   "sor_exact"      HS / Brox: 1 (default) = the reference's sweep order, bit-identical results, K time steps
@@ -357,6 +357,49 @@ int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2, double *u,
 int ofx_robust_expo_pyramid(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
                             int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                             int inner_iter, int outer_iter, int verbose);
+/* ofx_robust_expo_pyramid for the pairs of a lockstep group / of a batch, on device-resident images; the conventions of
+ * ofx_brox_group_dev and ofx_brox_batch_dev: n_pairs in 1..16 for a group, the pairs of a group share every launch (the pair is
+ * a grid dimension) and each keeps its own stopping test; dI1, dI2, d_flo are arrays of n_pairs device pointers; stats_out is
+ * NULL or n_pairs records; the call is asynchronous on the context's stream (ofx_ctx_synchronize).  A batch is cut into groups
+ * by the rule of the other SOR batches (option "lockstep" of ctxs[0], else as large as possible and evened out over the
+ * contexts), group q runs on ctxs[q % n_ctx] on a worker thread of its own, work_pix_iters (NULL or n_pairs doubles) receives
+ * sum sweeps * nx_s * ny_s per pair, and n_pairs = 0 is OFX_OK.
+ * dI1[g], dI2[g]: nxx * nyy * nzz elements of the context's storage precision (double | float), channels interleaved, element
+ * (i * nxx + j) * nzz + k.  d_flo[g]: the .flo payload, nxx * nyy interleaved (u, v) float32.
+ * Every pair gets what ofx_robust_expo_pyramid computes for that pair alone -- any nzz in 1 .. OFX_REXPO_MAX_CHANNELS at any
+ * nscales >= 1, with every quirk listed above.  In f64 storage the payload of pair g is bit-identical to float32 of the flow
+ * that entry returns for the pair, and the pair's sweep table and stopping values equal that solve's.  In f32 storage the same
+ * holds whenever the input values are exactly representable in float: the lone entry receives doubles and rounds to float AFTER
+ * the normalisation, the device images here are float already, and the two coincide on such inputs (8-bit or 16-bit image
+ * data, for instance); on other inputs the group sees the rounded images.
+ * (The stopping values depend on options sor_window / sor_rows in their last bits: the stopping sum is associated along the
+ * window geometry.  The groups therefore keep the lone entry's defaults, 8 steps and 64 rows, also where Brox groups of >= 4
+ * pairs switch to 4 steps and 125 rows, and the equality holds whenever both calls run under the same options.  One limit, of
+ * the lone entry as well: the sum of a sweep is kept in 64 shards, one per wave of a row block, so with more than 16 row
+ * blocks -- levels of more than 1024 rows at the default 64 rows per block -- two blocks add atomically into one shard and
+ * the last bits of a stopping value are not reproducible from run to run, for two lone solves as little as for a group.)
+ * The `expo` weights of a level are evaluated on the host (libm's exp / log, std::sort), all pairs of the group from one
+ * download, on up to 16 / concurrency threads per context; results do not depend on the thread count.
+ * Errors, all found before any work (no d_flo element is written): those of ofx_robust_expo_pyramid -- nzz, method_type,
+ * negative iteration counts, option sor_exact != 1, a level smaller than 3x3 (OFX_ERR_ARG), a level too small for the zoom
+ * Gaussian (OFX_ERR_SIGMA) -- and those of ofx_brox_group_dev: n_pairs outside 1..16, a NULL array or a NULL pointer at pair g.
+ * Option "profile": pyramid_ms = the group's pyramid phase (normalisation to the last level of all 2 n_pairs pyramids), in every
+ * record of the group; iter_ms[s] = the SOR windows of level s on the HOST's clock, between two drains of the stream that only
+ * this entry adds under "profile": wall time with the polls of the stopping test, not kernel time (the lone robust_expo
+ * entries leave iter_ms 0); ofx_ctx_expo_host_ms = the host part of the expo stage. */
+int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2, void *const *d_flo,
+                              int nxx, int nyy, int nzz, int method_type, double alpha, double gamma, double lambda,
+                              int nscales, double nu, double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out);
+int ofx_robust_expo_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                              void *const *d_flo, int n_pairs, int nxx, int nyy, int nzz, int method_type, double alpha,
+                              double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
+                              double *work_pix_iters);
+/* milliseconds the host spent evaluating `expo` (without the transfers), all levels, during the LAST API call on this context:
+ * every solver and operator entry zeroes it on entry (the ofx_ctx_* calls and ofx_set_option do not), so it is non-zero only
+ * straight after a robust_expo entry
+ * (ofx_robust_expo, _single_scale, _pyramid, _group_dev; after ofx_robust_expo_batch_dev each context holds its last group's).
+ * Measured always; NULL reads 0. */
+double ofx_ctx_expo_host_ms(const ofx_ctx *ctx);
 /* The reference's single-scale overload (robust_expo_methods.cpp:162-178, declared in none of its headers): the solver of one
  * level with no normalisation, no presmoothing and alpha as given; u, v are READ as the initial flow and overwritten with
  * the result -- what a caller needs to run colour on a pyramid of their own.  nz in 1 .. OFX_REXPO_MAX_CHANNELS, images

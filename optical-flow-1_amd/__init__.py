@@ -128,6 +128,11 @@ def lib():
                                     _i, C.POINTER(Stats)]),
         "ofx_brox_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, _i,
                                     _d, _d, _i, _i, C.POINTER(_d)]),
+        "ofx_robust_expo_group_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _d, _d, _d, _i,
+                                           _d, _d, _i, _i, C.POINTER(Stats)]),
+        "ofx_robust_expo_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i,
+                                           _d, _d, _d, _i, _d, _d, _i, _i, C.POINTER(_d)]),
+        "ofx_ctx_expo_host_ms": (_d, [_vp]),
         "ofx_bicubic_warp_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i]),
         "ofx_image_normalization_2_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i]),
         "ofx_image_normalization_3": (_i, [_vp, _dp, _dp, _dp, _i]),
@@ -198,6 +203,14 @@ def hs_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0
 def brox_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1, outer=15):
     """ofx_brox_batch_dev (see hs_batch_dev)"""
     return _batch_call(lib().ofx_brox_batch_dev, ctxs, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
+
+
+def robust_expo_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4,
+                          inner=1, outer=15):
+    """ofx_robust_expo_batch_dev (see hs_batch_dev): the images are (ny, nx, nz) device arrays of the contexts' storage type,
+    channels interleaved; the per-pair result is robust_expo_pyramid's"""
+    return _batch_call(lib().ofx_robust_expo_batch_dev, ctxs, dI1, dI2, d_flo, nx, ny, nz, method, alpha, gamma, lam, nscales, nu,
+                       TOL, inner, outer)
 
 
 def tvl1occ_batch(ctxs, triples, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3, zfactor=0.5, warps=2, epsilon=0.01, out=None):
@@ -436,6 +449,18 @@ class Ofx:
     def brox_group_dev(self, dI1, dI2, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1, outer=15):
         """ofx_brox_group_dev (see hs_group_dev)"""
         return self._group_call(self.L.ofx_brox_group_dev, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
+
+    def robust_expo_group_dev(self, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5,
+                              TOL=1e-4, inner=1, outer=15):
+        """ofx_robust_expo_group_dev (see hs_group_dev): robust_expo_pyramid for every pair of the group; the images are
+        (ny, nx, nz) device arrays of the context's storage type, channels interleaved"""
+        return self._group_call(self.L.ofx_robust_expo_group_dev, dI1, dI2, d_flo, nx, ny, nz, method, alpha, gamma, lam, nscales,
+                                nu, TOL, inner, outer)
+
+    def expo_host_ms(self):
+        """ofx_ctx_expo_host_ms: host milliseconds of robust_expo's expo stage during the last API call on this context (every
+        entry zeroes it on entry, so read it straight after a robust_expo call)"""
+        return self.L.ofx_ctx_expo_host_ms(self.h)
 
     def tvl1_iterations(self, u1, u2, p11, p12, p21, p22, I1wx, I1wy, rho_c, tau, lam, theta, n_iter):
         """In place on the six state arrays (float64, C-contiguous); returns the last error."""

@@ -112,6 +112,7 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->mem_budget = 0;
     ctx->poll_seq = 0;
     ctx->errmsg[0] = 0;
+    ctx->expo_host_ms = 0.0;
     memset(&ctx->stats, 0, sizeof(ctx->stats));
 
     ctx->stream = nullptr;

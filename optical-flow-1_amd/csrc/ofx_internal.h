@@ -119,6 +119,7 @@ struct ofx_ctx {
     unsigned long long poll_seq;
 
     ofx_stats stats;
+    double expo_host_ms;    // robust_expo: host time of the `expo` stage, all levels; OFX_ENTER of EVERY entry zeroes it (ofx_ctx_expo_host_ms)
     char errmsg[256];
 };
 
@@ -167,6 +168,7 @@ static inline int ofx_cdiv(int a, int b) { return (a + b - 1) / b; }
         if (hipSetDevice((ctx)->device) != hipSuccess)                                           \
             return ofx_fail((ctx), OFX_ERR_NODEV, "hipSetDevice(%d) failed", (ctx)->device);     \
         (ctx)->errmsg[0] = 0;                                                                    \
+        (ctx)->expo_host_ms = 0.0;                                                               \
         ofx_arena_reset(ctx);                                                                    \
     } while (0)
 

@@ -38,8 +38,9 @@ template <typename T> int op_gaussian(ofx_ctx *ctx, T *I, T *tmp, int nx, int ny
 template <typename T> int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx, int ny, int nxx, int nyy,
                                       double fx, double fy);
 // zoom_in of an interleaved flow field + `*= scale` (src/tvl1flow.cpp:302-309)
+// G > 1: the G flow fields of a lockstep group, back to back in U and Uout, in one launch
 template <typename T> int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, typename Pix<T>::v2 *Uout,
-                                          int nx, int ny, int nxx, int nyy, double scale);
+                                          int nx, int ny, int nxx, int nyy, double scale, int G = 1);
 // zoom_out (src/zoom.cpp:41-78): tmpA, tmpB are nx*ny scratch images
 template <typename T> int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny,
                                       double factor);
@@ -47,6 +48,14 @@ template <typename T> int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA
 // tmpA, tmpB are nx*ny*nz scratch images; OFX_ERR_SIGMA under zoom_out's rule, before anything is launched
 template <typename T> int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz,
                                                double factor);
+// the same for the 2 G images of a lockstep group, one launch per stage: A / B = the G first / second images back to back
+// (nx*ny*nz elements each), oA / oB the results likewise, tmpA / tmpB scratch for 2 G images
+template <typename T> int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB,
+                                                     int nx, int ny, int nz, double factor);
+// op_gaussian on the first nx*ny elements of 2 G images, one launch per pass: image g of A / B lies `stride` elements after
+// image g - 1, tmp holds 2 G planes of nx*ny
+template <typename T> int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma,
+                                            int dirichlet = 0);
 
 // planar operators for the operator-level API
 template <typename T> int op_divergence(ofx_ctx *ctx, const T *v1, const T *v2, T *div, int nx, int ny);

@@ -470,6 +470,30 @@ template <typename T> int op_gaussian(ofx_ctx *ctx, T *I, T *tmp, int nx, int ny
     return OFX_OK;
 }
 
+// op_gaussian on the first nx * ny elements of the 2 G images of a lockstep group, one launch per pass (blockIdx.z = image):
+// image g of A / B starts `stride` elements after image g - 1; tmp holds 2 G planes of nx * ny.  Per pixel k_gauss_pass.
+template <typename T>
+int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
+{
+    GaussTaps taps;
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: group of %d", G);
+    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+        return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
+    taps.dirichlet = dirichlet != 0;
+    if (!dirichlet && (taps.size >= nx || taps.size >= ny))           // op_gaussian's rule
+        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    const size_t n = (size_t) nx * ny;
+    dim3 g = grid2d(nx, ny);
+    g.z = 2 * G;
+    hipLaunchKernelGGL((k_gauss_pass_g<T, true>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, G, stride},
+                       OfxPlanes2<T>{tmp, tmp + (size_t) G * n, G, n}, nx, ny, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmp, tmp + (size_t) G * n, G, n},
+                       OfxPlanes2<T>{A, B, G, stride}, nx, ny, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
 // ---- bicubic resampling: zoom_out / zoom_in (src/zoom.cpp:41-78,132-155) ---------------------------
 template <typename T>
 OFX_DEV void resample_px(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nxx, int nyy, double fx, double fy)
@@ -500,6 +524,8 @@ __global__ void k_zoom_in_flow(const typename Pix<T>::v2 *__restrict__ U, typena
     const int j1 = blockIdx.x * BX + threadIdx.x;
     const int i1 = blockIdx.y * BY + threadIdx.y;
     if (j1 >= nxx || i1 >= nyy) return;
+    U += (size_t) blockIdx.z * nx * ny;                          // pair of a lockstep group
+    Uout += (size_t) blockIdx.z * nxx * nyy;
     const double i2 = i1 / fy, j2 = j1 / fx;
     const BicubicTaps t = bicubic_taps(j2, i2, nx, ny);
     double c1[4], c2[4];
@@ -530,11 +556,12 @@ int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx, int ny, int nxx, int 
 
 template <typename T>
 int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, typename Pix<T>::v2 *Uout, int nx, int ny,
-                    int nxx, int nyy, double scale)
+                    int nxx, int nyy, double scale, int G)
 {
     const double fx = ((double) nxx / nx), fy = ((double) nyy / ny);     // zoom.cpp:141-142
-    hipLaunchKernelGGL(k_zoom_in_flow<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, U, Uout, nx, ny, nxx, nyy,
-                       fx, fy, scale);
+    dim3 g = grid2d(nxx, nyy);
+    g.z = G;
+    hipLaunchKernelGGL(k_zoom_in_flow<T>, g, block2d(), 0, ctx->stream, U, Uout, nx, ny, nxx, nyy, fx, fy, scale);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -557,7 +584,7 @@ int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int
 // taps are nz elements apart and the reflection is taken on the pixel index.  The column pass is k_gauss_pass<T, false> on an
 // image of nx * nz columns: the channels of a column are independent columns there.
 template <typename T>
-__global__ void k_gauss_row_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, GaussTaps taps)
+OFX_DEV void gauss_row_ch_px(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, const GaussTaps &taps)
 {
     const int e = blockIdx.x * BX + threadIdx.x;
     const int i = blockIdx.y * BY + threadIdx.y;
@@ -569,10 +596,20 @@ __global__ void k_gauss_row_ch(const T *__restrict__ in, T *__restrict__ out, in
         sum += taps.B[t] * (ldw(row + (size_t) gauss_reflect(j - t, nx) * nz) + ldw(row + (size_t) gauss_reflect(j + t, nx) * nz));
     stn(out + (size_t) i * nx * nz + e, sum);
 }
+template <typename T>
+__global__ void k_gauss_row_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, GaussTaps taps)
+{
+    gauss_row_ch_px<T>(in, out, nx, ny, nz, taps);
+}
+template <typename T>
+__global__ void k_gauss_row_ch_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, int nz, GaussTaps taps)
+{
+    gauss_row_ch_px<T>(in.at(blockIdx.z), out.at(blockIdx.z), nx, ny, nz, taps);
+}
 
 // Sample stage: the 16 tap indices of an output pixel once, then one bicubic per channel from them
 template <typename T>
-__global__ void k_resample_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, int nxx, int nyy, double factor)
+OFX_DEV void resample_ch_px(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, int nxx, int nyy, double factor)
 {
     const int j1 = blockIdx.x * BX + threadIdx.x;
     const int i1 = blockIdx.y * BY + threadIdx.y;
@@ -593,6 +630,16 @@ __global__ void k_resample_ch(const T *__restrict__ in, T *__restrict__ out, int
         stn(o + k, cubic_cell(c[0], c[1], c[2], c[3], t.fx));
     }
 }
+template <typename T>
+__global__ void k_resample_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, int nxx, int nyy, double factor)
+{
+    resample_ch_px<T>(in, out, nx, ny, nz, nxx, nyy, factor);
+}
+template <typename T>
+__global__ void k_resample_ch_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, int nz, int nxx, int nyy, double factor)
+{
+    resample_ch_px<T>(in.at(blockIdx.z), out.at(blockIdx.z), nx, ny, nz, nxx, nyy, factor);
+}
 
 template <typename T>
 int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz, double factor)
@@ -611,6 +658,41 @@ int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, in
     hipLaunchKernelGGL((k_gauss_pass<T, false>), grid2d(nx * nz, ny), block2d(), 0, ctx->stream, (const T *) tmpA, tmpB, nx * nz, ny, taps);
     OFX_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_resample_ch<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, (const T *) tmpB, Iout, nx, ny, nz, nxx, nyy, factor);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+// op_zoom_out_channels for the 2 G images of a lockstep group, one launch per stage (blockIdx.z = image; the counterpart of
+// op_build_pyramid_group for interleaved channels): A / B hold the G first / second images back to back, nx * ny * nz elements
+// each, oA / oB the zoomed ones likewise; tmpA, tmpB are scratch for 2 G images of nx * ny * nz.  Every image is computed by
+// the single-image path's per-pixel code.
+template <typename T>
+int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB, int nx, int ny, int nz,
+                               double factor)
+{
+    int nxx, nyy;
+    ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
+    const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.h:21,66
+    GaussTaps taps;
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: group of %d", G);
+    if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
+    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
+    if (taps.size >= nx || taps.size >= ny)                               // op_gaussian's rule
+        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    const size_t st = (size_t) nx * ny * nz, sto = (size_t) nxx * nyy * nz;
+    dim3 g = grid2d(nx * nz, ny);
+    g.z = 2 * G;
+    hipLaunchKernelGGL(k_gauss_row_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, G, st},
+                       OfxPlanes2<T>{tmpA, tmpA + (size_t) G * st, G, st}, nx, ny, nz, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpA, tmpA + (size_t) G * st, G, st},
+                       OfxPlanes2<T>{tmpB, tmpB + (size_t) G * st, G, st}, nx * nz, ny, taps);
+    OFX_LAUNCH_CHECK(ctx);
+    g = grid2d(nxx, nyy);
+    g.z = 2 * G;
+    hipLaunchKernelGGL(k_resample_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpB, tmpB + (size_t) G * st, G, st},
+                       OfxPlanes2<T>{oA, oB, G, sto}, nx, ny, nz, nxx, nyy, factor);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -1024,7 +1106,9 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
     template int op_normalize2<T>(ofx_ctx *, const T *, const T *, T *, T *, int, double *);                          \
     template int op_gaussian<T>(ofx_ctx *, T *, T *, int, int, double, int);                                          \
     template int op_resample<T>(ofx_ctx *, const T *, T *, int, int, int, int, double, double);                       \
-    template int op_zoom_in_flow<T>(ofx_ctx *, const Pix<T>::v2 *, Pix<T>::v2 *, int, int, int, int, double);         \
+    template int op_zoom_in_flow<T>(ofx_ctx *, const Pix<T>::v2 *, Pix<T>::v2 *, int, int, int, int, double, int);    \
+    template int op_gaussian_group<T>(ofx_ctx *, int, T *, T *, size_t, T *, int, int, double, int);                   \
+    template int op_zoom_out_channels_group<T>(ofx_ctx *, int, const T *, const T *, T *, T *, T *, T *, int, int, int, double); \
     template int op_zoom_out<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, double);                               \
     template int op_zoom_out_channels<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, int, double);                 \
     template int op_divergence<T>(ofx_ctx *, const T *, const T *, T *, int, int);                                    \

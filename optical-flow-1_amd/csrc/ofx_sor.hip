@@ -26,6 +26,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <new>
 #include <thread>
 
 #define HS_SOR_W 1.9                 // src/horn_schunck_pyramidal.cpp:21
@@ -552,7 +553,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
 template <class WindowFn, class TakeFn>
 static int sor_window_loop(ofx_ctx *ctx, int G, int size, int ny, double TOL, int maxiter, int qmax, int C, int batch,
                            WindowFn launch, TakeFn take, int *n_out, double *err_out, int nz = 1, int *hint = nullptr,
-                           int Kdef = 0)          // Kdef: the caller's default steps per launch (0 = the rule below)
+                           int Kdef = 0, int Rdef = 0)   // Kdef, Rdef: the caller's default steps per launch / rows per block (0 = the rule below)
 {
     // G problems in lockstep (SorGrp): launch(w, blocks, sweeps, runmask, err_stride) serves every problem whose bit
     // is set; take(g, n) makes snapshot n - 1 of problem g its current state.  All problems start together, so the
@@ -564,7 +565,7 @@ static int sor_window_loop(ofx_ctx *ctx, int G, int size, int ny, double TOL, in
     // 4 for the 4-neighbour stencil in a group (its sweeps are spaced C = 2 apart, so the 2 K lag dominates the pipeline).
     SorWin w;
     w.K = ctx->sor_window > 0 ? ctx->sor_window : (Kdef > 0 ? Kdef : ((G >= 4 && C <= 2) ? 4 : 8));
-    w.R = ctx->sor_rows > 0 ? ctx->sor_rows : (G >= 4 ? 125 : 64);
+    w.R = ctx->sor_rows > 0 ? ctx->sor_rows : (Rdef > 0 ? Rdef : (G >= 4 ? 125 : 64));
     if (w.R < 2) w.R = 2;
     if (w.R > 1021) w.R = 1021;                                  // R + 3 threads per workgroup
     const int B = ofx_cdiv(ny, w.R);
@@ -1736,8 +1737,10 @@ __global__ void k_brox_add(typename Pix<T>::v2 *__restrict__ U, const typename P
 // ============================================================================================
 // robust_expo_methods on nz interleaved channels (src/robust_expo_methods.cpp:162-455)
 // ============================================================================================
-// Device layout: channel-planar packs.  Channel c of I1, (I1x, I1y), (I2, I2x, I2y, I2xx), (I2xy, I2yy) and of their warps
-// lies at element c * nx * ny of the level's I1, G1, PA, PB, WA, WB; the C ABI keeps the reference's interleaved order.
+// Device layout: channel-planar packs, pair-major in a lockstep group.  Channel c of pair g of I1, (I1x, I1y),
+// (I2, I2x, I2y, I2xx), (I2xy, I2yy) and of their warps lies at element (g * nz + c) * nx * ny of the level's I1, G1, PA, PB,
+// WA, WB; the one-plane arrays (U, DU, DV, Dd, CO, Dm, Psis, Expo, Mg) keep pair g at g * nx * ny, and the interleaved images
+// a level starts from lie back to back, pair g at g * nx * ny * nz.  The C ABI keeps the reference's interleaved order.
 
 // The five derivatives the reference leaves at FLAT element k = (i * nx + j) * nz + c of its derivative arrays
 // (centered_gradient, Dxx, Dyy, Dxy with nz channels, src/operators.cpp:132-406).  Below the first row they are the clamped
@@ -1792,7 +1795,7 @@ OFX_DEV RexpoDerivs rexpo_derivs(const T *__restrict__ in, int i, int j, int c, 
 }
 
 // :221-227: gradient of I1; I2 with its first and second derivatives; interleaved in, channel-planar packs out
-// (blockIdx.z = channel).  Needs nx, ny >= 3.
+// (blockIdx.z = pair * nz + channel).  Needs nx, ny >= 3.
 template <typename T>
 __global__ void k_rexpo_prepare_c(const T *__restrict__ I1i, const T *__restrict__ I2i, T *__restrict__ I1,
                                   typename Pix<T>::v2 *__restrict__ G1, typename Pix<T>::v4 *__restrict__ PA,
@@ -1800,9 +1803,11 @@ __global__ void k_rexpo_prepare_c(const T *__restrict__ I1i, const T *__restrict
 {
     const int j = blockIdx.x * 64 + threadIdx.x;
     const int i = blockIdx.y * 4 + threadIdx.y;
-    const int c = blockIdx.z;
+    const int pair = blockIdx.z / nz, c = blockIdx.z - pair * nz;
     if (j >= nx || i >= ny) return;
-    const size_t p = (size_t) i * nx + j, q = (size_t) c * nx * ny + p;
+    const size_t p = (size_t) i * nx + j, q = (size_t) blockIdx.z * nx * ny + p;
+    I1i += (size_t) pair * nx * ny * nz;
+    I2i += (size_t) pair * nx * ny * nz;
     const RexpoDerivs a = rexpo_derivs(I1i, i, j, c, nx, ny, nz), b = rexpo_derivs(I2i, i, j, c, nx, ny, nz);
     stn(I1 + q, ldw(I1i + p * nz + c));
     stn2(G1 + q, make_double2(a.x, a.y));
@@ -1811,11 +1816,14 @@ __global__ void k_rexpo_prepare_c(const T *__restrict__ I1i, const T *__restrict
 }
 
 // max_gradients (src/robust_expo_smoothness.cpp:51-73): the largest gradient magnitude of a pixel's channels
+// (blockIdx.y = pair)
 template <typename T>
 __global__ void k_rexpo_maxgrad(const typename Pix<T>::v2 *__restrict__ G1, double *__restrict__ Mg, int n, int nz)
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t) n) return;
+    G1 += (size_t) blockIdx.y * nz * n;
+    Mg += (size_t) blockIdx.y * n;
     double2 g = ldw2(G1 + i);
     double m = sqrt(g.x * g.x + g.y * g.y);
     for (int c = 1; c < nz; c++) {
@@ -1826,7 +1834,7 @@ __global__ void k_rexpo_maxgrad(const typename Pix<T>::v2 *__restrict__ G1, doub
     Mg[i] = m;
 }
 
-// :236-241: the six warps of every channel with the pixel's one set of bicubic taps
+// :236-241: the six warps of every channel with the pixel's one set of bicubic taps (blockIdx.z = pair)
 template <typename T>
 __global__ void k_rexpo_warp_c(const typename Pix<T>::v4 *__restrict__ PA, const typename Pix<T>::v2 *__restrict__ PB,
                                const typename Pix<T>::v2 *__restrict__ U, typename Pix<T>::v4 *__restrict__ WA,
@@ -1836,7 +1844,9 @@ __global__ void k_rexpo_warp_c(const typename Pix<T>::v4 *__restrict__ PA, const
     const int i = blockIdx.y * 4 + threadIdx.y;
     if (j >= nx || i >= ny) return;
     const size_t n = (size_t) nx * ny, p = (size_t) i * nx + j;
-    const double2 u = ldw2(U + p);
+    const size_t go = (size_t) blockIdx.z * nz * n;              // pair of a lockstep group
+    PA += go; PB += go; WA += go; WB += go;
+    const double2 u = ldw2(U + (size_t) blockIdx.z * n + p);
     const BicubicTaps t = bicubic_taps(j + u.x, i + u.y, nx, ny);
     for (int ch = 0; ch < nz; ch++) {
         const typename Pix<T>::v4 *__restrict__ pa = PA + ch * n;
@@ -1874,22 +1884,24 @@ __global__ void k_rexpo_warp_c(const typename Pix<T>::v4 *__restrict__ PA, const
 }
 
 // psi_data, psi_gradient and the constant parts of the scheme for nz channels (:53-63, :92-104, :276-318): every sum over the
-// channels runs in ascending order onto 0, psi multiplies the finished sums (k_brox_coeff's rx branch is the nz = 1 form)
+// channels runs in ascending order onto 0, psi multiplies the finished sums (k_brox_coeff's rx branch is the nz = 1 form).
+// One lane per pixel of the G pairs; n = pixels of ONE pair.
 template <typename T>
 __global__ void k_rexpo_coeff_c(const T *__restrict__ I1, const typename Pix<T>::v2 *__restrict__ G1,
                                 const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
                                 const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
                                 const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n, int nz,
-                                double alpha, double gamma)
+                                int G, double alpha, double gamma)
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t) n) return;
+    if (i >= (size_t) n * G) return;
+    const size_t pair = i / (size_t) n, c0 = pair * nz * n + (i - pair * n);     // channel 0 of this pixel
     const double2 d = ldw2(DU + i);
     const double eps2 = BROX_EPSILON * BROX_EPSILON;
     double sd = 0.0, sg = 0.0, BNu = 0.0, BNv = 0.0, BDu = 0.0, BDv = 0.0, DI_Data = 0.0;
     double GNu = 0.0, GNv = 0.0, GDu = 0.0, GDv = 0.0, DI_Gradient = 0.0;
     for (int c = 0; c < nz; c++) {
-        const size_t q = (size_t) c * n + i;
+        const size_t q = (size_t) c * n + c0;
         const double i1 = ldw(I1 + q);
         const double2 g1 = ldw2(G1 + q);
         const double4 wa = ldw4(WA + q);
@@ -1924,16 +1936,20 @@ __global__ void k_rexpo_coeff_c(const T *__restrict__ I1, const typename Pix<T>:
     stn(Dm + i, psid * DI_Data + g * DI_Gradient);
 }
 
-// image_normalization_2_color (src/utils.cpp:334-406) on device data: per channel the joint minimum / maximum of both images
-// (exact, order-independent), then 255 (x - min) / den, or a copy when den <= 0
+// image_normalization_2_color (src/utils.cpp:334-406) on device data: per pair and channel the joint minimum / maximum of
+// both images (exact, order-independent), then 255 (x - min) / den, or a copy when den <= 0.  S = the type the images come in
+// (double: host images uploaded as they are; the storage type: the device images of a group), converted exactly to double;
+// blockIdx.z / blockIdx.y of the two kernels = pair.
 #define RX_MM_BLOCKS 64
-__global__ __launch_bounds__(256) void k_rexpo_mm_partial(const double *__restrict__ a, const double *__restrict__ b, size_t npix,
-                                                          int nz, double *__restrict__ part /* [nz][2][RX_MM_BLOCKS] */)
+template <typename S>
+__global__ __launch_bounds__(256) void k_rexpo_mm_partial(OfxGroupPtrs P, size_t npix, int nz,
+                                                          double *__restrict__ part /* [G][nz][2][RX_MM_BLOCKS] */)
 {
-    const int c = blockIdx.y;
-    double lo = a[c], hi = lo;
+    const int c = blockIdx.y, pair = blockIdx.z;
+    const S *__restrict__ a = (const S *) P.a[pair], *__restrict__ b = (const S *) P.b[pair];
+    double lo = (double) a[c], hi = lo;
     for (size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x; t < npix; t += (size_t) gridDim.x * blockDim.x) {
-        const double x = a[t * nz + c], y = b[t * nz + c];
+        const double x = (double) a[t * nz + c], y = (double) b[t * nz + c];
         lo = x < lo ? x : lo; hi = x > hi ? x : hi;
         lo = y < lo ? y : lo; hi = y > hi ? y : hi;
     }
@@ -1950,23 +1966,25 @@ __global__ __launch_bounds__(256) void k_rexpo_mm_partial(const double *__restri
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        part[((size_t) c * 2 + 0) * RX_MM_BLOCKS + blockIdx.x] = slo[0];
-        part[((size_t) c * 2 + 1) * RX_MM_BLOCKS + blockIdx.x] = shi[0];
+        part[(((size_t) pair * nz + c) * 2 + 0) * RX_MM_BLOCKS + blockIdx.x] = slo[0];
+        part[(((size_t) pair * nz + c) * 2 + 1) * RX_MM_BLOCKS + blockIdx.x] = shi[0];
     }
 }
-template <typename T>
-__global__ void k_rexpo_norm_map(const double *__restrict__ a, const double *__restrict__ b, T *__restrict__ oa, T *__restrict__ ob,
-                                 size_t n, int nz, const double *__restrict__ part, int nblocks)
+// n = elements of ONE image; the images of pair g go to oa + g * n, ob + g * n
+template <typename T, typename S>
+__global__ void k_rexpo_norm_map(OfxGroupPtrs P, T *__restrict__ oa, T *__restrict__ ob, size_t n, int nz,
+                                 const double *__restrict__ part, int nblocks)
 {
     const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    const int c = (int) (e % nz);
-    const double *pl = part + ((size_t) c * 2 + 0) * RX_MM_BLOCKS, *ph = part + ((size_t) c * 2 + 1) * RX_MM_BLOCKS;
+    const int c = (int) (e % nz), pair = blockIdx.y;
+    const double *pl = part + (((size_t) pair * nz + c) * 2 + 0) * RX_MM_BLOCKS, *ph = pl + RX_MM_BLOCKS;
     double lo = pl[0], hi = ph[0];
     for (int k = 1; k < nblocks; k++) { lo = pl[k] < lo ? pl[k] : lo; hi = ph[k] > hi ? ph[k] : hi; }
     const double den = hi - lo;
-    stn(oa + e, den > 0 ? 255.0 * (a[e] - lo) / den : a[e]);
-    stn(ob + e, den > 0 ? 255.0 * (b[e] - lo) / den : b[e]);
+    const double a = (double) ((const S *) P.a[pair])[e], b = (double) ((const S *) P.b[pair])[e];
+    stn(oa + (size_t) pair * n + e, den > 0 ? 255.0 * (a - lo) / den : a);
+    stn(ob + (size_t) pair * n + e, den > 0 ? 255.0 * (b - lo) / den : b);
 }
 
 // One level of a lockstep group: every array holds G pairs back to back (pair g at element g * nx * ny).
@@ -2033,6 +2051,7 @@ struct BroxParams {
     // summation orders (the kernels' rx / RX variants); 0 = Brox
     int robust = 0, method = 1;
     double lambda = 0.0;
+    int time_windows = 0;     // ofx_robust_expo_group_dev under option "profile": iter_ms = the host's clock around the windows
 };
 
 // src/brox_optic_flow_spatial.cpp:179-444 on device data for the G pairs of a lockstep group; stats[g] = record of pair g
@@ -2041,34 +2060,15 @@ struct BroxParams {
 // magnitudes.  Evaluated on the HOST once per level: the reference calls libm's exp and log, whose last bit the device's
 // math library does not promise to share, and method 3 sorts the level (std::sort there, here).  The gradient comes from the
 // level's (I1x, I1y) pairs the prepare kernel has just written.
-template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams &P)
+// One pair: mg = its n gradient magnitudes, expo = its n weights, ord = n doubles of scratch for method 3's sort.
+template <typename T> static void rexpo_pair_expo(const double *mg, T *expo, double *ord, size_t n, const BroxParams &P)
 {
-    const size_t n = L.n();
-    if (!L.Expo) OFX_TRY(ofx_alloc(ctx, n, &L.Expo));
-    std::vector<T> expo(n);
-    std::vector<double> mg(n);
-    if (L.nz > 1) {
-        // colour: the largest magnitude of the pixel's channels (k_rexpo_maxgrad; IEEE sqrt on either side)
-        if (!L.Mg) OFX_TRY(ofx_alloc(ctx, n, &L.Mg));
-        hipLaunchKernelGGL(k_rexpo_maxgrad<T>, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, L.G1, L.Mg, (int) n, L.nz);
-        OFX_LAUNCH_CHECK(ctx);
-        OFX_HIP(ctx, hipMemcpyAsync(mg.data(), L.Mg, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    } else {
-        std::vector<typename Pix<T>::v2> g1(n);
-        OFX_HIP(ctx, hipMemcpyAsync(g1.data(), L.G1, n * sizeof(typename Pix<T>::v2), hipMemcpyDeviceToHost, ctx->stream));
-        OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < n; i++) {
-            const double ix = (double) g1[i].x, iy = (double) g1[i].y;
-            mg[i] = sqrt(ix * ix + iy * iy);
-        }
-    }
     if (P.method == 1 || P.method == 2) {
         const double beta = P.method == 2 ? 0.001 : 0.0;
         for (size_t i = 0; i < n; i++) expo[i] = (T) (exp(-P.lambda * mg[i]) + beta);
     } else {
-        std::vector<double> ord(mg);
-        std::sort(ord.begin(), ord.end());
+        std::copy(mg, mg + n, ord);
+        std::sort(ord, ord + n);
         const double c = -log(0.05) + log(P.alpha);
         long pos_ref = (long) (int) (0.94 * (double) (int) n);
         double lambda_omega;
@@ -2082,7 +2082,63 @@ template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L,
             expo[i] = (T) exp(-lambda_pi * mg[i]);
         }
     }
-    OFX_HIP(ctx, hipMemcpyAsync(L.Expo, expo.data(), n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+}
+
+// The G pairs of a lockstep group: ONE download of all gradient magnitudes, the pairs evaluated independently (method 3 sorts
+// and takes its quantile per pair) on up to 16 / concurrency host threads -- sor_batch_run sets `concurrency` to the number of
+// contexts working at once, so a batch runs at most 16 of them --, ONE upload.  A pair is evaluated by one thread in pixel
+// order whatever the thread count, so the result does not depend on it.  Levels of fewer than RX_EXPO_SERIAL pixels over all
+// pairs (the coarse ones, where starting a thread costs more than the pair's exp calls) are evaluated by the caller alone.
+// Every buffer is allocated here, before a thread starts: the workers allocate nothing.
+#define RX_EXPO_SERIAL 32768
+template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams &P, double *host_ms)
+{
+    const size_t n = L.n(), ng = n * L.G;
+    const int G = L.G;
+    if (!L.Expo) OFX_TRY(ofx_alloc(ctx, ng, &L.Expo));
+    std::vector<T> expo;
+    std::vector<double> mg, ord;
+    std::vector<typename Pix<T>::v2> g1;
+    try {
+        expo.resize(ng);
+        mg.resize(ng);
+        if (P.method == 3) ord.resize(ng);
+        if (L.nz == 1) g1.resize(ng);
+    } catch (const std::bad_alloc &) {
+        return ofx_fail(ctx, OFX_ERR_NOMEM, "robust_expo: no host memory for the expo stage of %zu pixels", ng);
+    }
+    if (L.nz > 1) {
+        // colour: the largest magnitude of the pixel's channels (k_rexpo_maxgrad; IEEE sqrt on either side)
+        if (!L.Mg) OFX_TRY(ofx_alloc(ctx, ng, &L.Mg));
+        hipLaunchKernelGGL(k_rexpo_maxgrad<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, L.G1, L.Mg, (int) n,
+                           L.nz);
+        OFX_LAUNCH_CHECK(ctx);
+        OFX_HIP(ctx, hipMemcpyAsync(mg.data(), L.Mg, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        OFX_HIP(ctx, hipMemcpyAsync(g1.data(), L.G1, ng * sizeof(typename Pix<T>::v2), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double t0 = ofx_now_ms();
+    auto pairs = [&](int first, int step) {
+        for (int q = first; q < G; q += step) {
+            double *m = mg.data() + q * n;
+            if (L.nz == 1)
+                for (size_t i = 0; i < n; i++) {
+                    const double ix = (double) g1[q * n + i].x, iy = (double) g1[q * n + i].y;
+                    m[i] = sqrt(ix * ix + iy * iy);
+                }
+            rexpo_pair_expo<T>(m, expo.data() + q * n, ord.data() + (ord.empty() ? 0 : q * n), n, P);
+        }
+    };
+    int nt = 16 / (ctx->concurrency > 1 ? ctx->concurrency : 1);
+    if (nt > G) nt = G;
+    if (nt < 1 || ng < RX_EXPO_SERIAL) nt = 1;
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(pairs, t, nt);
+    pairs(0, nt);
+    for (auto &t : th) t.join();
+    if (host_ms) *host_ms += ofx_now_ms() - t0;
+    OFX_HIP(ctx, hipMemcpyAsync(L.Expo, expo.data(), ng * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));               // `expo` is a local
     return OFX_OK;
 }
@@ -2105,17 +2161,17 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
         return ofx_fail(ctx, OFX_ERR_ARG, "brox: lockstep groups need sor_exact = 1 (levels of at least 3x3, this one %dx%d) or the tile sweeps of sor_exact = 0", nx, ny);
     int solve = 0;
     const int rx = P.robust;
-    if (rx && (!windowed || G != 1))
+    if (rx && !windowed)
         return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs sor_exact = 1 and levels of at least 3x3 (%dx%d)", nx, ny);
     const int nz = L.nz;                                         // > 1: robust_expo on colour (channel-planar packs)
     if (nz > 1 && (!rx || !L.I1c || !L.I2c)) return ofx_fail(ctx, OFX_ERR_ARG, "brox: only robust_expo takes %d channels", nz);
     if (nz > 1)
-        hipLaunchKernelGGL(k_rexpo_prepare_c<T>, dim3(g.x, g.y, nz), b, 0, ctx->stream, (const T *) L.I1c, (const T *) L.I2c, L.I1, L.G1,
+        hipLaunchKernelGGL(k_rexpo_prepare_c<T>, dim3(g.x, g.y, G * nz), b, 0, ctx->stream, (const T *) L.I1c, (const T *) L.I2c, L.I1, L.G1,
                            L.PA, L.PB, nx, ny, nz);
     else
     hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) L.I1, (const T *) L.I2, L.G1, L.PA, L.PB, nx, ny);
     OFX_LAUNCH_CHECK(ctx);
-    if (rx) OFX_TRY(rexpo_level_expo<T>(ctx, L, P));                                              // robust_expo_methods.cpp:231
+    if (rx) OFX_TRY(rexpo_level_expo<T>(ctx, L, P, &ctx->expo_host_ms));                          // robust_expo_methods.cpp:231
     for (int no = 0; no < P.outer_iter; no++) {                                                   // :244
         if (nz > 1) hipLaunchKernelGGL(k_rexpo_warp_c<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny, nz);
         else
@@ -2126,7 +2182,7 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
         for (int ni = 0; ni < P.inner_iter; ni++) {                                               // :277
             if (nz > 1)
                 hipLaunchKernelGGL(k_rexpo_coeff_c<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
-                                   (const T *) L.Dd, L.CO, L.Dm, n, nz, P.alpha, P.gamma);
+                                   (const T *) L.Dd, L.CO, L.Dm, n, nz, G, P.alpha, P.gamma);
             else
             hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
                                (const T *) L.Dd, L.CO, L.Dm, (int) (npix * G), P.alpha, P.gamma, rx);
@@ -2223,9 +2279,23 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
                                                 hipMemcpyDeviceToDevice, ctx->stream));
                     return OFX_OK;
                 };
-                // robust_expo_methods.cpp:400: the stopping value divides by nx * ny * nz
+                // the robust_expo group entry under option "profile": the windows of this solve between two drained streams, on
+                // the host's clock (so with the polls of the stopping test); every other entry keeps its schedule
+                double tw = 0.0;
+                if (P.time_windows) {
+                    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                    tw = ofx_now_ms();
+                }
+                // robust_expo_methods.cpp:400: the stopping value divides by nx * ny * nz.  A robust_expo group promises each pair
+                // the lone solve's stopping VALUES, and the association of the stopping sum follows the window geometry (a
+                // thread's K steps, then the row block's waves): its groups keep the lone geometry, 8 steps and 64 rows, where
+                // Brox groups of >= 4 pairs switch to 125 rows.  Options sor_window / sor_rows still override both alike.
                 OFX_TRY(sor_window_loop(ctx, G, n * nz, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
-                                        take, nsor, error, 1, &L.sweep_hint, 0));
+                                        take, nsor, error, 1, &L.sweep_hint, rx ? 8 : 0, rx ? 64 : 0));
+                if (P.time_windows) {
+                    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                    ms = (float) (ofx_now_ms() - tw);
+                }
                 OFX_TRY((op_skew<typename Pix<T>::v2, false>(ctx, L.DUs, L.DU, nx, ny, BROX_PLANE_C_SKEW, G)));
             } else if (ctx->sor_exact && nx >= 3 && ny >= 3) {
                 const size_t ub = (size_t) n * sizeof(typename Pix<T>::v2);
@@ -2383,36 +2453,55 @@ extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2
     return s;
 }
 
-// The head of the multiscale overload (src/robust_expo_methods.cpp:494-498) on host images of nz interleaved channels:
-// image_normalization_2_color and the source's Gaussian call; *A, *B = the level-0 images on the device, allocated here unless
-// the caller hands in arrays of nx * ny * nz elements
-template <typename T>
-static int rexpo_normalise_presmooth(ofx_ctx *ctx, const double *I1, const double *I2, int nx, int ny, int nz, T **A, T **B)
+// The head of the multiscale overload (src/robust_expo_methods.cpp:494-498) for the G pairs of a lockstep group, every launch
+// for all of them: image_normalization_2_color and the source's Gaussian call.  src = the G image pairs on the device in type
+// S, nz interleaved channels each; A, B = the level-0 images, G * nx * ny * nz elements each, pair g at g * nx * ny * nz.
+template <typename T, typename S>
+static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nx, int ny, int nz, T *A, T *B)
 {
     const size_t n = (size_t) nx * ny, nc = n * nz;
-    double *a, *b, *part;
+    double *part;
     T *tmp;
-    OFX_TRY(ofx_alloc(ctx, nc, &a));
-    OFX_TRY(ofx_alloc(ctx, nc, &b));
-    if (!*A) OFX_TRY(ofx_alloc(ctx, nc, A));
-    if (!*B) OFX_TRY(ofx_alloc(ctx, nc, B));
-    OFX_TRY(ofx_alloc(ctx, (size_t) nz * 2 * RX_MM_BLOCKS, &part));
-    OFX_TRY(ofx_alloc(ctx, n, &tmp));
-    OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    OFX_TRY(ofx_alloc(ctx, (size_t) G * nz * 2 * RX_MM_BLOCKS, &part));
+    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * n, &tmp));
     int nb = (int) ((n + 255) / 256);
     if (nb > RX_MM_BLOCKS) nb = RX_MM_BLOCKS;
-    hipLaunchKernelGGL(k_rexpo_mm_partial, dim3(nb, nz), dim3(256), 0, ctx->stream, (const double *) a, (const double *) b, n, nz, part);
+    hipLaunchKernelGGL(k_rexpo_mm_partial<S>, dim3(nb, nz, G), dim3(256), 0, ctx->stream, src, n, nz, part);
     OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_rexpo_norm_map<T>, dim3((unsigned) ((nc + 255) / 256)), dim3(256), 0, ctx->stream, (const double *) a,
-                       (const double *) b, *A, *B, nc, nz, (const double *) part, nb);
+    hipLaunchKernelGGL((k_rexpo_norm_map<T, S>), dim3((unsigned) ((nc + 255) / 256), G), dim3(256), 0, ctx->stream, src, A, B, nc, nz,
+                       (const double *) part, nb);
     OFX_LAUNCH_CHECK(ctx);
     // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
     // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
-    // so only the first nx * ny elements of the interleaved image are smoothed (across pixels and channels alike)
-    OFX_TRY(op_gaussian<T>(ctx, *A, tmp, nx, ny, (double) nz, 1));
-    OFX_TRY(op_gaussian<T>(ctx, *B, tmp, nx, ny, (double) nz, 1));
+    // so only the first nx * ny elements of each interleaved image are smoothed (across pixels and channels alike)
+    return op_gaussian_group<T>(ctx, G, A, B, nc, tmp, nx, ny, (double) nz, 1);
+}
+
+// host images: uploaded as doubles, so that the float mode rounds after the normalisation
+static int rexpo_upload_pair(ofx_ctx *ctx, const double *I1, const double *I2, size_t nc, OfxGroupPtrs *src)
+{
+    double *a, *b;
+    OFX_TRY(ofx_alloc(ctx, nc, &a));
+    OFX_TRY(ofx_alloc(ctx, nc, &b));
+    OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    memset(src, 0, sizeof(*src));
+    src->a[0] = a;
+    src->b[0] = b;
     return OFX_OK;
+}
+
+// the same on one pair of host images; *A, *B = the level-0 images on the device, allocated here unless the caller hands in
+// arrays of nx * ny * nz elements
+template <typename T>
+static int rexpo_normalise_presmooth(ofx_ctx *ctx, const double *I1, const double *I2, int nx, int ny, int nz, T **A, T **B)
+{
+    const size_t nc = (size_t) nx * ny * nz;
+    OfxGroupPtrs src;
+    if (!*A) OFX_TRY(ofx_alloc(ctx, nc, A));
+    if (!*B) OFX_TRY(ofx_alloc(ctx, nc, B));
+    OFX_TRY(rexpo_upload_pair(ctx, I1, I2, nc, &src));
+    return rexpo_normalise_presmooth_dev<T, double>(ctx, 1, src, nx, ny, nz, *A, *B);
 }
 
 // robust_expo_methods on ONE level of nz interleaved channels, both public entries:
@@ -2457,15 +2546,14 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
 // call replaced: the levels come from op_zoom_out_channels -- the zoom_out of the IPOL original, each channel as zoom_out --
 // where the reference's zoom_out_color reads beyond its scratch copy (zoom.cpp:96-118).  Everything else is the driver as
 // ofx_robust_expo runs it: the head above, a zero flow at the coarsest level, brox_single_scale_dev and op_zoom_in_flow per
-// level (the loop of brox_spatial_dev).  All levels are checked before anything is uploaded.
-template <typename T>
-static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
-                              const BroxParams &P, int nscales, double nu)
+// level (the loop of brox_spatial_dev).
+
+// Every level of G pairs is checked here, before anything is uploaded or launched.
+static int rexpo_pyramid_check(ofx_ctx *ctx, int G, int nx, int ny, int nz, int nscales, double nu, std::vector<int> &nxs,
+                               std::vector<int> &nys)
 {
-    std::vector<int> nxs, nys;
     OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, nu, nxs, nys));
-    const size_t n = (size_t) nx * ny, nc = n * nz;
-    if ((long long) nc >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: more than 2^31 image elements");
+    if ((long long) nx * ny * nz * G >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: more than 2^31 image elements");
     if (nscales > 1) {
         GaussTaps taps;
         if (ofx_gauss_taps(0.6 * sqrt(1.0 / (nu * nu) - 1.0), &taps) != OFX_OK)
@@ -2478,33 +2566,39 @@ static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, 
     for (int s = 0; s < nscales; s++)
         if (nxs[s] < 3 || nys[s] < 3)
             return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs levels of at least 3x3 (scale %d is %dx%d)", s, nxs[s], nys[s]);
-    sor_stats_begin(&ctx->stats, nscales, P.inner_iter * P.outer_iter);
-    for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { ctx->stats.nx[s] = nxs[s]; ctx->stats.ny[s] = nys[s]; }
-    std::vector<BroxLevel<T>> lv(nscales);
+    return OFX_OK;
+}
+
+// The G pairs of a lockstep group (src: their images on the device in type S, see rexpo_normalise_presmooth_dev); every launch
+// serves all of them.  nxs, nys come from rexpo_pyramid_check; on success lv[0].U holds the G flows, stats[g] the record of pair g.
+template <typename T, typename S>
+static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nz, const BroxParams &P, int nscales, double nu,
+                             const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxLevel<T>> &lv,
+                             ofx_stats *stats, bool t0_recorded = false)   // the caller has started the pyramid phase's clock
+{
+    const size_t nc = (size_t) nxs[0] * nys[0] * nz;
+    for (int g = 0; g < G; g++) {
+        sor_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
+        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
+    }
+    lv.resize(nscales);
     std::vector<T *> lA(nscales), lB(nscales);
     for (int s = 0; s < nscales; s++) {
-        OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], 1, nz));
+        OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, nz));
         if (nz == 1) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }                   // one channel: the level's own planes
         else {
-            lA[s] = lB[s] = nullptr;
-            if (s) {
-                OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s] * nz, &lA[s]));
-                OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s] * nz, &lB[s]));
-            }
+            OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lA[s]));
+            OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lB[s]));
         }
     }
-    if (ctx->profile) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    OFX_TRY(rexpo_normalise_presmooth<T>(ctx, I1, I2, nx, ny, nz, &lA[0], &lB[0]));               // :494-498
-    {
-        T *tmpA = nullptr, *tmpB = nullptr;
-        if (nscales > 1) {
-            OFX_TRY(ofx_alloc(ctx, nc, &tmpA));
-            OFX_TRY(ofx_alloc(ctx, nc, &tmpB));
-        }
-        for (int s = 1; s < nscales; s++) {                                                        // :512-520
-            OFX_TRY(op_zoom_out_channels<T>(ctx, lA[s - 1], lA[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
-            OFX_TRY(op_zoom_out_channels<T>(ctx, lB[s - 1], lB[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
-        }
+    if (ctx->profile && !t0_recorded) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    OFX_TRY((rexpo_normalise_presmooth_dev<T, S>(ctx, G, src, nxs[0], nys[0], nz, lA[0], lB[0])));  // :494-498
+    if (nscales > 1) {
+        T *tmpA, *tmpB;                                   // all 2 G images of a level per launch
+        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nc, &tmpA));
+        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nc, &tmpB));
+        for (int s = 1; s < nscales; s++)                                                          // :512-520
+            OFX_TRY(op_zoom_out_channels_group<T>(ctx, G, lA[s - 1], lB[s - 1], lA[s], lB[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
     }
     double pyramid_ms = 0.0;
     if (ctx->profile) {
@@ -2516,27 +2610,60 @@ static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, 
     }
     if (nz > 1)
         for (int s = 0; s < nscales; s++) { lv[s].I1c = lA[s]; lv[s].I2c = lB[s]; }
-    OFX_TRY(op_fill2<T>(ctx, lv[nscales - 1].U, lv[nscales - 1].n()));                             // :522-524
+    OFX_TRY(op_fill2<T>(ctx, lv[nscales - 1].U, lv[nscales - 1].n() * G));                         // :522-524
     for (int s = nscales - 1; s >= 0; s--) {                                                      // :530
-        if (P.verbose) { printf("Scale: %d\n", s); fflush(stdout); }
-        OFX_TRY(brox_single_scale_dev<T>(ctx, lv[s], P, s, &ctx->stats));
+        if (P.verbose && G == 1) { printf("Scale: %d\n", s); fflush(stdout); }
+        OFX_TRY(brox_single_scale_dev<T>(ctx, lv[s], P, s, stats));
         if (s)
-            OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U, lv[s - 1].U, lv[s].nx, lv[s].ny, lv[s - 1].nx, lv[s - 1].ny, 1.0 / nu));
+            OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U, lv[s - 1].U, lv[s].nx, lv[s].ny, lv[s - 1].nx, lv[s - 1].ny, 1.0 / nu, G));
     }
-    ctx->stats.pyramid_ms = pyramid_ms;
+    for (int g = 0; g < G; g++) stats[g].pyramid_ms = pyramid_ms;
+    return OFX_OK;
+}
+
+template <typename T>
+static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
+                              const BroxParams &P, int nscales, double nu)
+{
+    std::vector<int> nxs, nys;
+    OFX_TRY(rexpo_pyramid_check(ctx, 1, nx, ny, nz, nscales, nu, nxs, nys));
+    const size_t n = (size_t) nx * ny;
+    OfxGroupPtrs src;
+    std::vector<BroxLevel<T>> lv;
+    if (ctx->profile) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    OFX_TRY(rexpo_upload_pair(ctx, I1, I2, n * nz, &src));
+    OFX_TRY((rexpo_pyramid_dev<T, double>(ctx, 1, src, nz, P, nscales, nu, nxs, nys, lv, &ctx->stats, true)));
     return download_flow<T>(ctx, lv[0].U, u, v, n);
 }
 
-static int rexpo_check_args(ofx_ctx *ctx, const double *I1, const double *I2, const double *u, const double *v, int nz, int method_type,
-                            int inner_iter, int outer_iter)
+template <typename T>
+static int rexpo_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo,
+                              int nz, const BroxParams &P, int nscales, double nu, const std::vector<int> &nxs,
+                              const std::vector<int> &nys, ofx_stats *stats)
 {
-    if (!I1 || !I2 || !u || !v) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
+    OfxGroupPtrs src;
+    for (int g = 0; g < OFX_MAX_GROUP; g++) { src.a[g] = g < G ? dI1[g] : nullptr; src.b[g] = g < G ? dI2[g] : nullptr; }
+    std::vector<BroxLevel<T>> lv;
+    OFX_TRY((rexpo_pyramid_dev<T, T>(ctx, G, src, nz, P, nscales, nu, nxs, nys, lv, stats)));
+    const size_t n = (size_t) nxs[0] * nys[0];
+    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) d_flo[g], n));
+    return OFX_OK;
+}
+
+static int rexpo_check_params(ofx_ctx *ctx, int nz, int method_type, int inner_iter, int outer_iter)
+{
     if (nz < 1 || nz > OFX_REXPO_MAX_CHANNELS)
         return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: nz=%d (1..%d channels)", nz, OFX_REXPO_MAX_CHANNELS);
     if (method_type < 1 || method_type > 3) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: method_type=%d (1, 2 or 3)", method_type);
     if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: negative iteration count");
     if (ctx->sor_exact != 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs the default option sor_exact = 1");
     return OFX_OK;
+}
+static int rexpo_check_args(ofx_ctx *ctx, const double *I1, const double *I2, const double *u, const double *v, int nz, int method_type,
+                            int inner_iter, int outer_iter)
+{
+    if (!I1 || !I2 || !u || !v) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
+    return rexpo_check_params(ctx, nz, method_type, inner_iter, outer_iter);
 }
 
 // robust_expo_methods (src/robust_expo_methods.h:21-38): one channel at any number of scales, colour at one scale
@@ -2628,6 +2755,38 @@ extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *
     return s;
 }
 
+// ofx_robust_expo_pyramid for the pairs of a lockstep group on device-resident images (include/ofx.h)
+extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                                         void *const *d_flo, int nxx, int nyy, int nzz, int method_type, double alpha,
+                                         double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter,
+                                         int outer_iter, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
+    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
+    for (int g = 0; g < n_pairs; g++)
+        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer (pair %d)", g);
+    OFX_TRY(rexpo_check_params(ctx, nzz, method_type, inner_iter, outer_iter));
+    std::vector<int> nxs, nys;
+    OFX_TRY(rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys));
+    const double t0 = ofx_now_ms();
+    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, 0};           // :527: alpha * nzz as an int
+    P.robust = 1;
+    P.method = method_type;
+    P.lambda = lambda;
+    P.time_windows = ctx->profile;
+    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    int s = ctx->precision == OFX_F64
+                ? rexpo_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st)
+                : rexpo_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st);
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
+    ctx->stats = st[0];
+    return s;
+}
+
 // ---- batches of pairs for the SOR solvers: lockstep groups, one worker thread per context (as ofx_tvl1_batch_dev) ----
 template <class GroupFn>
 static int sor_batch_run(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, int G, double *work_pix_iters, GroupFn group)
@@ -2707,6 +2866,21 @@ extern "C" int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
     });
 }
 
+extern "C" int ofx_robust_expo_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                         void *const *d_flo, int n_pairs, int nxx, int nyy, int nzz, int method_type,
+                                         double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
+                                         int inner_iter, int outer_iter, double *work_pix_iters)
+{
+    OFX_TRY(sor_batch_check(ctxs, n_ctx, n_pairs, dI1, dI2, d_flo));
+    if (n_pairs == 0) return OFX_OK;
+    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
+    return sor_batch_run(ctxs, n_ctx, n_pairs, G, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+        return ofx_robust_expo_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nxx, nyy, nzz, method_type, alpha, gamma,
+                                         lambda, nscales, nu, TOL, inner_iter, outer_iter, st);
+    });
+}
+
+extern "C" double ofx_ctx_expo_host_ms(const ofx_ctx *ctx) { return ctx ? ctx->expo_host_ms : 0.0; }
 
 // ============================================================================================
 // Brox temporal: src/brox_optic_flow_temporal.cpp, src/brox_temporal_mask.cpp
