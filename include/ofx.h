@@ -78,7 +78,7 @@ typedef struct ofx_stats {
     int    fused[OFX_MAX_SCALES];                     /* TV-L1: iterations per iteration launch at each level
                                                          (1, 2, 3, or the tile kernel's 4 | 6); odd_stops then
                                                          counts the loops that ended inside such a launch unit  */
-    double pyramid_ms;                                /* ofx_robust_expo_pyramid: HIP-event time from the upload of the
+    double pyramid_ms;                                /* ofx_robust_expo, _pyramid: HIP-event time from the upload of the
                                                          images to the last level of both pyramids (0 unless profiling) */
 } ofx_stats;
 
@@ -94,7 +94,7 @@ int   ofx_ctx_synchronize(ofx_ctx *ctx);
 int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
 /* options (value 0 = default / automatic unless noted):
  *   "profile"        0/1  bracket the inner-iteration launches with HIP events -> stats.iter_ms (and the pyramid phase of
- *                         ofx_robust_expo_pyramid / _group_dev -> stats.pyramid_ms; _group_dev: iter_ms on the host's clock)
+ *                         ofx_robust_expo / _pyramid / _group_dev -> stats.pyramid_ms; _group_dev: iter_ms on the host's clock)
  *   "fixed_work"     0/1  TV-L1: every warp runs exactly OFX_TVL1_MAX_ITERATIONS iterations (stopping
  *                         test disabled; the reference with epsilon = 0)
  *   "sor_exact"      HS / Brox: 1 (default) = the reference's sweep order, bit-identical results, K time steps
@@ -324,7 +324,8 @@ int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, 
  * I1, I2: nxx * nyy * nzz doubles, channels interleaved (element (i * nxx + j) * nzz + k); u, v: nxx * nyy.
  * nzz = 1: any number of scales.  nzz = 2 .. OFX_REXPO_MAX_CHANNELS: nscales must be 1 (OFX_ERR_ARG otherwise): the
  * reference's colour pyramid reads beyond its scratch copy (zoom.cpp:96-118), its colour solver at one scale is defined.
- * Other nzz: OFX_ERR_ARG.  Levels smaller than 3x3 and option sor_exact != 1: OFX_ERR_ARG.
+ * Other nzz: OFX_ERR_ARG.  Levels smaller than 3x3 and option sor_exact != 1: OFX_ERR_ARG; a level too small for the zoom
+ * Gaussian: OFX_ERR_SIGMA; all found before any work.  One driver serves this entry and ofx_robust_expo_pyramid.
  * Kept quirks of the source:
  *  - the presmoothing is gaussian(I, nxx, nyy, nzz, 0.8) against (I, xdim, ydim, sigma, boundary, window)
  *    (robust_expo_methods.cpp:497-498): sigma = nzz, the DIRICHLET boundary, and the buffer taken for one nxx x nyy plane, so

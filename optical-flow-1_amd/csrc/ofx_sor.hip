@@ -1175,6 +1175,39 @@ __global__ void k_brox_prepare(const T *__restrict__ I1, const T *__restrict__ I
     stn2(PB + p, make_double2(d2xy(I2, i, j, nx, ny), d2yy(I2, i, j, nx, ny)));
 }
 
+// the six fields (I2, I2x, I2y, I2xx | I2xy, I2yy) of one image or channel at a pixel's bicubic taps; 0 when the taps lie outside
+template <typename T>
+OFX_DEV void bicubic_cell6(const BicubicTaps &t, const typename Pix<T>::v4 *__restrict__ PA,
+                           const typename Pix<T>::v2 *__restrict__ PB, int nx, double4 &wa, double2 &wb)
+{
+    wa = make_double4(0.0, 0.0, 0.0, 0.0);
+    wb = make_double2(0.0, 0.0);
+    if (t.out) return;
+    double c[6][4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        double4 a[4];
+        double2 b[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            a[r] = ldw4(PA + (size_t) t.row[r] * nx + t.col[k]);
+            b[r] = ldw2(PB + (size_t) t.row[r] * nx + t.col[k]);
+        }
+        c[0][k] = cubic_cell(a[0].x, a[1].x, a[2].x, a[3].x, t.fy);
+        c[1][k] = cubic_cell(a[0].y, a[1].y, a[2].y, a[3].y, t.fy);
+        c[2][k] = cubic_cell(a[0].z, a[1].z, a[2].z, a[3].z, t.fy);
+        c[3][k] = cubic_cell(a[0].w, a[1].w, a[2].w, a[3].w, t.fy);
+        c[4][k] = cubic_cell(b[0].x, b[1].x, b[2].x, b[3].x, t.fy);
+        c[5][k] = cubic_cell(b[0].y, b[1].y, b[2].y, b[3].y, t.fy);
+    }
+    wa.x = cubic_cell(c[0][0], c[0][1], c[0][2], c[0][3], t.fx);
+    wa.y = cubic_cell(c[1][0], c[1][1], c[1][2], c[1][3], t.fx);
+    wa.z = cubic_cell(c[2][0], c[2][1], c[2][2], c[2][3], t.fx);
+    wa.w = cubic_cell(c[3][0], c[3][1], c[3][2], c[3][3], t.fx);
+    wb.x = cubic_cell(c[4][0], c[4][1], c[4][2], c[4][3], t.fx);
+    wb.y = cubic_cell(c[5][0], c[5][1], c[5][2], c[5][3], t.fx);
+}
+
 // six bicubic warps with one set of taps, :246-251
 template <typename T>
 __global__ void k_brox_warp(const typename Pix<T>::v4 *__restrict__ PA, const typename Pix<T>::v2 *__restrict__ PB,
@@ -1189,33 +1222,9 @@ __global__ void k_brox_warp(const typename Pix<T>::v4 *__restrict__ PA, const ty
     const size_t p = (size_t) i * nx + j;
     const double2 u = ldw2(U + p);
     const BicubicTaps t = bicubic_taps(j + u.x, i + u.y, nx, ny);
-    double4 wa = make_double4(0.0, 0.0, 0.0, 0.0);
-    double2 wb = make_double2(0.0, 0.0);
-    if (!t.out) {
-        double c[6][4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            double4 a[4];
-            double2 b[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                a[r] = ldw4(PA + (size_t) t.row[r] * nx + t.col[k]);
-                b[r] = ldw2(PB + (size_t) t.row[r] * nx + t.col[k]);
-            }
-            c[0][k] = cubic_cell(a[0].x, a[1].x, a[2].x, a[3].x, t.fy);
-            c[1][k] = cubic_cell(a[0].y, a[1].y, a[2].y, a[3].y, t.fy);
-            c[2][k] = cubic_cell(a[0].z, a[1].z, a[2].z, a[3].z, t.fy);
-            c[3][k] = cubic_cell(a[0].w, a[1].w, a[2].w, a[3].w, t.fy);
-            c[4][k] = cubic_cell(b[0].x, b[1].x, b[2].x, b[3].x, t.fy);
-            c[5][k] = cubic_cell(b[0].y, b[1].y, b[2].y, b[3].y, t.fy);
-        }
-        wa.x = cubic_cell(c[0][0], c[0][1], c[0][2], c[0][3], t.fx);
-        wa.y = cubic_cell(c[1][0], c[1][1], c[1][2], c[1][3], t.fx);
-        wa.z = cubic_cell(c[2][0], c[2][1], c[2][2], c[2][3], t.fx);
-        wa.w = cubic_cell(c[3][0], c[3][1], c[3][2], c[3][3], t.fx);
-        wb.x = cubic_cell(c[4][0], c[4][1], c[4][2], c[4][3], t.fx);
-        wb.y = cubic_cell(c[5][0], c[5][1], c[5][2], c[5][3], t.fx);
-    }
+    double4 wa;
+    double2 wb;
+    bicubic_cell6<T>(t, PA, PB, nx, wa, wb);
     stn4(WA + p, wa);
     stn2(WB + p, wb);
 }
@@ -1339,7 +1348,7 @@ __global__ void k_brox_coeff(const T *__restrict__ I1, const typename Pix<T>::v2
                              const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
                              const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
                              const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n,
-                             double alpha, double gamma, int rx = 0)
+                             double alpha, double gamma)
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t) n) return;
@@ -1350,30 +1359,6 @@ __global__ void k_brox_coeff(const T *__restrict__ I1, const typename Pix<T>::v2
     const double2 d = ldw2(DU + i);
     const double I2w = wa.x, I2wx = wa.y, I2wy = wa.z, I2wxx = wa.w, I2wxy = wb.x, I2wyy = wb.y;
     const double eps2 = BROX_EPSILON * BROX_EPSILON;
-    if (rx) {
-        // robust_expo_methods.cpp:48-60, :85-102, :279-322 for one channel: the motion terms are added before I1 is subtracted,
-        // every per-channel sum is accumulated onto 0, and psi multiplies the finished sums
-        const double dI = I2w + I2wx * d.x + I2wy * d.y - i1;
-        const double psid = rnd_to<T>(1. / sqrt((0.0 + dI * dI) + eps2));
-        const double dIx = I2wx + I2wxx * d.x + I2wxy * d.y - g1.x;
-        const double dIy = I2wy + I2wxy * d.x + I2wyy * d.y - g1.y;
-        const double psig = rnd_to<T>(1. / sqrt((0.0 + (dIx * dIx + dIy * dIy)) + eps2));
-        const double dif = I2w - i1;
-        double BNu = 0.0 + dif * I2wx, BNv = 0.0 + dif * I2wy, BDu = 0.0 + I2wx * I2wx, BDv = 0.0 + I2wy * I2wy;
-        const double DI_Data = 0.0 + (I2wy * I2wx);
-        const double dx = (I2wx - g1.x), dy = (I2wy - g1.y);
-        double GNu = 0.0 + (dx * I2wxx + dy * I2wxy), GNv = 0.0 + (dx * I2wxy + dy * I2wyy);
-        double GDu = 0.0 + (I2wxx * I2wxx + I2wxy * I2wxy), GDv = 0.0 + (I2wyy * I2wyy + I2wxy * I2wxy);
-        const double DI_Gradient = 0.0 + (I2wxx + I2wyy) * I2wxy;
-        const double g = gamma * psig;
-        BNu = -psid * BNu; BNv = -psid * BNv; BDu = psid * BDu; BDv = psid * BDv;
-        GNu = -g * GNu; GNv = -g * GNv; GDu = g * GDu; GDv = g * GDv;
-        const double2 dvv = ldw2(DV + i);
-        const double dd = ldw(Dd + i);
-        stn4(CO + i, make_double4(BNu + GNu + alpha * dvv.x, BNv + GNv + alpha * dvv.y, BDu + GDu + dd, BDv + GDv + dd));
-        stn(Dm + i, psid * DI_Data + g * DI_Gradient);
-        return;
-    }
     const double dI = I2w - i1 + I2wx * d.x + I2wy * d.y;                              // psi_data :51
     const double psid = rnd_to<T>(1. / sqrt(dI * dI + eps2));
     const double dIx = I2wx - g1.x + I2wxx * d.x + I2wxy * d.y;                        // psi_gradient :86-87
@@ -1749,7 +1734,7 @@ __global__ void k_brox_add(typename Pix<T>::v2 *__restrict__ U, const typename P
 // (dx[j], output[j], :176, :363-364), so for nz > 1 flat elements 1 .. nx - 2 receive the stencil of "column k" of the last
 // channel -- its second-row taps read at nx * nz + k (:172-174) --, the corner elements that are written afterwards keep
 // their own values, and every other element of the row is never written.  The compiled reference allocates zeroed arrays, so
-// those read 0; that is what is reproduced.  For nz = 1 all of this reduces to the one-channel operators.
+// those read 0; that is what is reproduced.  For nz = 1 all of this is cdx, cdy, d2xx, d2yy, d2xy of the Brox section.
 struct RexpoDerivs { double x, y, xx, xy, yy; };
 template <typename T>
 OFX_DEV RexpoDerivs rexpo_derivs_proper(const T *__restrict__ in, int i, int j, int c, int nx, int ny, int nz)
@@ -1849,42 +1834,16 @@ __global__ void k_rexpo_warp_c(const typename Pix<T>::v4 *__restrict__ PA, const
     const double2 u = ldw2(U + (size_t) blockIdx.z * n + p);
     const BicubicTaps t = bicubic_taps(j + u.x, i + u.y, nx, ny);
     for (int ch = 0; ch < nz; ch++) {
-        const typename Pix<T>::v4 *__restrict__ pa = PA + ch * n;
-        const typename Pix<T>::v2 *__restrict__ pb = PB + ch * n;
-        double4 wa = make_double4(0.0, 0.0, 0.0, 0.0);
-        double2 wb = make_double2(0.0, 0.0);
-        if (!t.out) {
-            double c[6][4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                double4 a[4];
-                double2 b[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    a[r] = ldw4(pa + (size_t) t.row[r] * nx + t.col[k]);
-                    b[r] = ldw2(pb + (size_t) t.row[r] * nx + t.col[k]);
-                }
-                c[0][k] = cubic_cell(a[0].x, a[1].x, a[2].x, a[3].x, t.fy);
-                c[1][k] = cubic_cell(a[0].y, a[1].y, a[2].y, a[3].y, t.fy);
-                c[2][k] = cubic_cell(a[0].z, a[1].z, a[2].z, a[3].z, t.fy);
-                c[3][k] = cubic_cell(a[0].w, a[1].w, a[2].w, a[3].w, t.fy);
-                c[4][k] = cubic_cell(b[0].x, b[1].x, b[2].x, b[3].x, t.fy);
-                c[5][k] = cubic_cell(b[0].y, b[1].y, b[2].y, b[3].y, t.fy);
-            }
-            wa.x = cubic_cell(c[0][0], c[0][1], c[0][2], c[0][3], t.fx);
-            wa.y = cubic_cell(c[1][0], c[1][1], c[1][2], c[1][3], t.fx);
-            wa.z = cubic_cell(c[2][0], c[2][1], c[2][2], c[2][3], t.fx);
-            wa.w = cubic_cell(c[3][0], c[3][1], c[3][2], c[3][3], t.fx);
-            wb.x = cubic_cell(c[4][0], c[4][1], c[4][2], c[4][3], t.fx);
-            wb.y = cubic_cell(c[5][0], c[5][1], c[5][2], c[5][3], t.fx);
-        }
+        double4 wa;
+        double2 wb;
+        bicubic_cell6<T>(t, PA + ch * n, PB + ch * n, nx, wa, wb);
         stn4(WA + ch * n + p, wa);
         stn2(WB + ch * n + p, wb);
     }
 }
 
 // psi_data, psi_gradient and the constant parts of the scheme for nz channels (:53-63, :92-104, :276-318): every sum over the
-// channels runs in ascending order onto 0, psi multiplies the finished sums (k_brox_coeff's rx branch is the nz = 1 form).
+// channels runs in ascending order onto 0, psi multiplies the finished sums.
 // One lane per pixel of the G pairs; n = pixels of ONE pair.
 template <typename T>
 __global__ void k_rexpo_coeff_c(const T *__restrict__ I1, const typename Pix<T>::v2 *__restrict__ G1,
@@ -1992,8 +1951,9 @@ template <typename T> struct BroxLevel {
     using v2 = typename Pix<T>::v2;
     using v4 = typename Pix<T>::v4;
     int nx, ny, G;
-    // robust_expo on colour: nz > 1 channels; I1, G1, PA, PB, WA, WB then hold nz channel planes each, I1c / I2c the interleaved
-    // images the level starts from and Mg the largest gradient magnitude of each pixel's channels
+    // robust_expo: nz >= 1 channels; I1, G1, PA, PB, WA, WB hold nz channel planes each, I1c / I2c the interleaved images the
+    // level starts from (rexpo_level_host, rexpo_pyramid_dev) and Mg the largest gradient magnitude of each pixel's channels.  Brox: nz = 1 and the
+    // level starts from the planes I1 and I2.
     int nz = 1;
     T *I1c = nullptr, *I2c = nullptr;
     double *Mg = nullptr;
@@ -2054,12 +2014,11 @@ struct BroxParams {
     int time_windows = 0;     // ofx_robust_expo_group_dev under option "profile": iter_ms = the host's clock around the windows
 };
 
-// src/brox_optic_flow_spatial.cpp:179-444 on device data for the G pairs of a lockstep group; stats[g] = record of pair g
-// robust_expo_exponential_calculation (src/robust_expo_smoothness.cpp:128-187, one channel): expo = exp(-lambda |grad I1|)
+// robust_expo_exponential_calculation (src/robust_expo_smoothness.cpp:128-187): expo = exp(-lambda |grad I1|)
 // (+ 0.001 for method 2), method 3 with a per-pixel lambda bounded by the value at the 0.94 quantile of the sorted gradient
 // magnitudes.  Evaluated on the HOST once per level: the reference calls libm's exp and log, whose last bit the device's
-// math library does not promise to share, and method 3 sorts the level (std::sort there, here).  The gradient comes from the
-// level's (I1x, I1y) pairs the prepare kernel has just written.
+// math library does not promise to share, and method 3 sorts the level (std::sort there, here).  |grad I1| is the largest
+// magnitude of the pixel's channels (k_rexpo_maxgrad on the (I1x, I1y) pairs the prepare kernel has just written).
 // One pair: mg = its n gradient magnitudes, expo = its n weights, ord = n doubles of scratch for method 3's sort.
 template <typename T> static void rexpo_pair_expo(const double *mg, T *expo, double *ord, size_t n, const BroxParams &P)
 {
@@ -2098,37 +2057,22 @@ template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L,
     if (!L.Expo) OFX_TRY(ofx_alloc(ctx, ng, &L.Expo));
     std::vector<T> expo;
     std::vector<double> mg, ord;
-    std::vector<typename Pix<T>::v2> g1;
     try {
         expo.resize(ng);
         mg.resize(ng);
         if (P.method == 3) ord.resize(ng);
-        if (L.nz == 1) g1.resize(ng);
     } catch (const std::bad_alloc &) {
         return ofx_fail(ctx, OFX_ERR_NOMEM, "robust_expo: no host memory for the expo stage of %zu pixels", ng);
     }
-    if (L.nz > 1) {
-        // colour: the largest magnitude of the pixel's channels (k_rexpo_maxgrad; IEEE sqrt on either side)
-        if (!L.Mg) OFX_TRY(ofx_alloc(ctx, ng, &L.Mg));
-        hipLaunchKernelGGL(k_rexpo_maxgrad<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, L.G1, L.Mg, (int) n,
-                           L.nz);
-        OFX_LAUNCH_CHECK(ctx);
-        OFX_HIP(ctx, hipMemcpyAsync(mg.data(), L.Mg, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        OFX_HIP(ctx, hipMemcpyAsync(g1.data(), L.G1, ng * sizeof(typename Pix<T>::v2), hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (!L.Mg) OFX_TRY(ofx_alloc(ctx, ng, &L.Mg));
+    hipLaunchKernelGGL(k_rexpo_maxgrad<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, L.G1, L.Mg, (int) n, L.nz);
+    OFX_LAUNCH_CHECK(ctx);
+    OFX_HIP(ctx, hipMemcpyAsync(mg.data(), L.Mg, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double t0 = ofx_now_ms();
     auto pairs = [&](int first, int step) {
-        for (int q = first; q < G; q += step) {
-            double *m = mg.data() + q * n;
-            if (L.nz == 1)
-                for (size_t i = 0; i < n; i++) {
-                    const double ix = (double) g1[q * n + i].x, iy = (double) g1[q * n + i].y;
-                    m[i] = sqrt(ix * ix + iy * iy);
-                }
-            rexpo_pair_expo<T>(m, expo.data() + q * n, ord.data() + (ord.empty() ? 0 : q * n), n, P);
-        }
+        for (int q = first; q < G; q += step)
+            rexpo_pair_expo<T>(mg.data() + q * n, expo.data() + q * n, ord.data() + (ord.empty() ? 0 : q * n), n, P);
     };
     int nt = 16 / (ctx->concurrency > 1 ? ctx->concurrency : 1);
     if (nt > G) nt = G;
@@ -2143,6 +2087,8 @@ template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L,
     return OFX_OK;
 }
 
+// src/brox_optic_flow_spatial.cpp:179-444 on device data for the G pairs of a lockstep group; stats[g] = record of pair g.
+// P.robust: src/robust_expo_methods.cpp:162-455 on the level's nz >= 1 interleaved channels (the k_rexpo_* kernels)
 template <typename T>
 static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams &P, int scale, ofx_stats *stats)
 {
@@ -2163,29 +2109,29 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
     const int rx = P.robust;
     if (rx && !windowed)
         return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: needs sor_exact = 1 and levels of at least 3x3 (%dx%d)", nx, ny);
-    const int nz = L.nz;                                         // > 1: robust_expo on colour (channel-planar packs)
-    if (nz > 1 && (!rx || !L.I1c || !L.I2c)) return ofx_fail(ctx, OFX_ERR_ARG, "brox: only robust_expo takes %d channels", nz);
-    if (nz > 1)
+    const int nz = L.nz;                                         // robust_expo: channels (channel-planar packs)
+    if (nz > 1 && !rx) return ofx_fail(ctx, OFX_ERR_ARG, "brox: only robust_expo takes %d channels", nz);
+    if (rx && (!L.I1c || !L.I2c)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: level without its interleaved images");
+    if (rx)
         hipLaunchKernelGGL(k_rexpo_prepare_c<T>, dim3(g.x, g.y, G * nz), b, 0, ctx->stream, (const T *) L.I1c, (const T *) L.I2c, L.I1, L.G1,
                            L.PA, L.PB, nx, ny, nz);
     else
-    hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) L.I1, (const T *) L.I2, L.G1, L.PA, L.PB, nx, ny);
+        hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) L.I1, (const T *) L.I2, L.G1, L.PA, L.PB, nx, ny);
     OFX_LAUNCH_CHECK(ctx);
     if (rx) OFX_TRY(rexpo_level_expo<T>(ctx, L, P, &ctx->expo_host_ms));                          // robust_expo_methods.cpp:231
     for (int no = 0; no < P.outer_iter; no++) {                                                   // :244
-        if (nz > 1) hipLaunchKernelGGL(k_rexpo_warp_c<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny, nz);
-        else
-        hipLaunchKernelGGL(k_brox_warp<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny);
+        if (rx) hipLaunchKernelGGL(k_rexpo_warp_c<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny, nz);
+        else hipLaunchKernelGGL(k_brox_warp<T>, g, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny);
         hipLaunchKernelGGL(k_brox_psis<T>, g, b, 0, ctx->stream, L.U, L.Psis, nx, ny, (const T *) (rx ? L.Expo : nullptr));
         hipLaunchKernelGGL(k_brox_div<T>, g, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, P.alpha, rx);
         OFX_LAUNCH_CHECK(ctx);
         for (int ni = 0; ni < P.inner_iter; ni++) {                                               // :277
-            if (nz > 1)
+            if (rx)
                 hipLaunchKernelGGL(k_rexpo_coeff_c<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
                                    (const T *) L.Dd, L.CO, L.Dm, n, nz, G, P.alpha, P.gamma);
             else
-            hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
-                               (const T *) L.Dd, L.CO, L.Dm, (int) (npix * G), P.alpha, P.gamma, rx);
+                hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I1, L.G1, L.WA, L.WB, L.DU, L.DV,
+                                   (const T *) L.Dd, L.CO, L.Dm, (int) (npix * G), P.alpha, P.gamma);
             OFX_LAUNCH_CHECK(ctx);
             int nsor[OFX_MAX_GROUP] = {0};
             double error[OFX_MAX_GROUP];
@@ -2385,18 +2331,6 @@ static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
         OFX_TRY(ofx_alloc(ctx, (size_t) G * op_pyramid_scratch_doubles(), &scr));
         std::vector<T *> lA(nscales), lB(nscales);
         for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }
-        if (P.robust) {
-            // robust_expo_methods.cpp:494-525 for one channel: image_normalization_2_color == image_normalization_2, then
-            // gaussian(I, nx, ny, nzz, GAUSSIAN_SIGMA) -- i.e. sigma = the number of channels = 1 and boundary condition
-            // (int) 0.8 = BOUNDARY_CONDITION_DIRICHLET --, then zoom_out_color == zoom_out
-            OFX_TRY(op_normalize2<T>(ctx, dI1[0], dI2[0], lA[0], lB[0], nx * ny, scr));
-            OFX_TRY(op_gaussian<T>(ctx, lA[0], tmpA, nx, ny, 1.0, 1));
-            OFX_TRY(op_gaussian<T>(ctx, lB[0], tmpA, nx, ny, 1.0, 1));
-            for (int s = 1; s < nscales; s++) {
-                OFX_TRY(op_zoom_out<T>(ctx, lA[s - 1], lA[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nu));
-                OFX_TRY(op_zoom_out<T>(ctx, lB[s - 1], lB[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nu));
-            }
-        } else
         OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI1, (const void *const *) dI2, nscales, nu,
                                           BROX_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr));
     }
@@ -2477,41 +2411,11 @@ static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs
     return op_gaussian_group<T>(ctx, G, A, B, nc, tmp, nx, ny, (double) nz, 1);
 }
 
-// host images: uploaded as doubles, so that the float mode rounds after the normalisation
-static int rexpo_upload_pair(ofx_ctx *ctx, const double *I1, const double *I2, size_t nc, OfxGroupPtrs *src)
-{
-    double *a, *b;
-    OFX_TRY(ofx_alloc(ctx, nc, &a));
-    OFX_TRY(ofx_alloc(ctx, nc, &b));
-    OFX_HIP(ctx, hipMemcpyAsync(a, I1, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    OFX_HIP(ctx, hipMemcpyAsync(b, I2, nc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    memset(src, 0, sizeof(*src));
-    src->a[0] = a;
-    src->b[0] = b;
-    return OFX_OK;
-}
-
-// the same on one pair of host images; *A, *B = the level-0 images on the device, allocated here unless the caller hands in
-// arrays of nx * ny * nz elements
-template <typename T>
-static int rexpo_normalise_presmooth(ofx_ctx *ctx, const double *I1, const double *I2, int nx, int ny, int nz, T **A, T **B)
-{
-    const size_t nc = (size_t) nx * ny * nz;
-    OfxGroupPtrs src;
-    if (!*A) OFX_TRY(ofx_alloc(ctx, nc, A));
-    if (!*B) OFX_TRY(ofx_alloc(ctx, nc, B));
-    OFX_TRY(rexpo_upload_pair(ctx, I1, I2, nc, &src));
-    return rexpo_normalise_presmooth_dev<T, double>(ctx, 1, src, nx, ny, nz, *A, *B);
-}
-
-// robust_expo_methods on ONE level of nz interleaved channels, both public entries:
-//   presmooth = true : the multiscale overload called with nscales = 1 (src/robust_expo_methods.cpp:462-566):
-//                      image_normalization_2_color, its Gaussian call and a zero flow in front of the level solver
-//   presmooth = false: the single-scale overload itself (:162-178): the images as they come, (u, v) is the initial flow
-// nz = 1 runs the one-channel kernels of the level solver, nz > 1 the channel-planar ones.
+// the single-scale overload itself (src/robust_expo_methods.cpp:162-178) on ONE level of nz interleaved channels: the images
+// as they come, (u, v) is the initial flow
 template <typename T>
 static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
-                            const BroxParams &P, bool presmooth)
+                            const BroxParams &P)
 {
     if (nx < 1 || ny < 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: bad size %dx%d", nx, ny);
     const size_t n = (size_t) nx * ny, nc = n * nz;
@@ -2521,32 +2425,23 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
     ctx->stats.ny[0] = ny;
     BroxLevel<T> L;
     OFX_TRY(brox_level_alloc<T>(ctx, L, nx, ny, 1, nz));
-    T *A = nz == 1 ? L.I1 : nullptr, *B = nz == 1 ? L.I2 : nullptr;      // one channel: the level's own planes
-    if (presmooth) {
-        OFX_TRY(rexpo_normalise_presmooth<T>(ctx, I1, I2, nx, ny, nz, &A, &B));
-        OFX_TRY(op_fill2<T>(ctx, L.U, n));                                                         // :522-524
-    } else {
-        double *du, *dv;
-        OFX_TRY(upload_plane<T>(ctx, I1, nc, &A));
-        OFX_TRY(upload_plane<T>(ctx, I2, nc, &B));
-        OFX_TRY(ofx_alloc(ctx, n, &du));
-        OFX_TRY(ofx_alloc(ctx, n, &dv));
-        OFX_HIP(ctx, hipMemcpyAsync(du, u, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        OFX_HIP(ctx, hipMemcpyAsync(dv, v, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        OFX_TRY(op_interleave2<T>(ctx, du, dv, L.U, n));
-    }
-    if (nz > 1) { L.I1c = A; L.I2c = B; }
-    else { L.I1 = A; L.I2 = B; }
-    if (P.verbose && presmooth) { printf("Scale: 0\n"); fflush(stdout); }
+    double *du, *dv;
+    OFX_TRY(upload_plane<T>(ctx, I1, nc, &L.I1c));
+    OFX_TRY(upload_plane<T>(ctx, I2, nc, &L.I2c));
+    OFX_TRY(ofx_alloc(ctx, n, &du));
+    OFX_TRY(ofx_alloc(ctx, n, &dv));
+    OFX_HIP(ctx, hipMemcpyAsync(du, u, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    OFX_HIP(ctx, hipMemcpyAsync(dv, v, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    OFX_TRY(op_interleave2<T>(ctx, du, dv, L.U, n));
     OFX_TRY(brox_single_scale_dev<T>(ctx, L, P, 0, &ctx->stats));
     return download_flow<T>(ctx, L.U, u, v, n);
 }
 
 // The multiscale overload (src/robust_expo_methods.cpp:482-566) on nz interleaved channels at any number of scales, with ONE
 // call replaced: the levels come from op_zoom_out_channels -- the zoom_out of the IPOL original, each channel as zoom_out --
-// where the reference's zoom_out_color reads beyond its scratch copy (zoom.cpp:96-118).  Everything else is the driver as
-// ofx_robust_expo runs it: the head above, a zero flow at the coarsest level, brox_single_scale_dev and op_zoom_in_flow per
-// level (the loop of brox_spatial_dev).
+// where the reference's zoom_out_color reads beyond its scratch copy (zoom.cpp:96-118).  Everything else is the reference's
+// driver: the head above, a zero flow at the coarsest level, brox_single_scale_dev and op_zoom_in_flow per level.  Every
+// robust_expo entry but the single-scale one runs it.
 
 // Every level of G pairs is checked here, before anything is uploaded or launched.
 static int rexpo_pyramid_check(ofx_ctx *ctx, int G, int nx, int ny, int nz, int nscales, double nu, std::vector<int> &nxs,
@@ -2582,23 +2477,20 @@ static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int n
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
-    std::vector<T *> lA(nscales), lB(nscales);
     for (int s = 0; s < nscales; s++) {
         OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, nz));
-        if (nz == 1) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }                   // one channel: the level's own planes
-        else {
-            OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lA[s]));
-            OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lB[s]));
-        }
+        OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lv[s].I1c));
+        OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lv[s].I2c));
     }
     if (ctx->profile && !t0_recorded) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    OFX_TRY((rexpo_normalise_presmooth_dev<T, S>(ctx, G, src, nxs[0], nys[0], nz, lA[0], lB[0])));  // :494-498
+    OFX_TRY((rexpo_normalise_presmooth_dev<T, S>(ctx, G, src, nxs[0], nys[0], nz, lv[0].I1c, lv[0].I2c)));  // :494-498
     if (nscales > 1) {
         T *tmpA, *tmpB;                                   // all 2 G images of a level per launch
         OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nc, &tmpA));
         OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nc, &tmpB));
         for (int s = 1; s < nscales; s++)                                                          // :512-520
-            OFX_TRY(op_zoom_out_channels_group<T>(ctx, G, lA[s - 1], lB[s - 1], lA[s], lB[s], tmpA, tmpB, nxs[s - 1], nys[s - 1], nz, nu));
+            OFX_TRY(op_zoom_out_channels_group<T>(ctx, G, lv[s - 1].I1c, lv[s - 1].I2c, lv[s].I1c, lv[s].I2c, tmpA, tmpB, nxs[s - 1],
+                                                  nys[s - 1], nz, nu));
     }
     double pyramid_ms = 0.0;
     if (ctx->profile) {
@@ -2608,8 +2500,6 @@ static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int n
         OFX_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
         pyramid_ms = ms;
     }
-    if (nz > 1)
-        for (int s = 0; s < nscales; s++) { lv[s].I1c = lA[s]; lv[s].I2c = lB[s]; }
     OFX_TRY(op_fill2<T>(ctx, lv[nscales - 1].U, lv[nscales - 1].n() * G));                         // :522-524
     for (int s = nscales - 1; s >= 0; s--) {                                                      // :530
         if (P.verbose && G == 1) { printf("Scale: %d\n", s); fflush(stdout); }
@@ -2621,18 +2511,37 @@ static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int n
     return OFX_OK;
 }
 
-template <typename T>
+// One host image on the device in type S: the storage type through upload_plane, doubles copied as they are
+template <typename S> static int rexpo_upload(ofx_ctx *ctx, const double *h, size_t n, S **out)
+{
+    return upload_plane<S>(ctx, h, n, out);
+}
+template <> int rexpo_upload<double>(ofx_ctx *ctx, const double *h, size_t n, double **out)
+{
+    OFX_TRY(ofx_alloc(ctx, n, out));
+    OFX_HIP(ctx, hipMemcpyAsync(*out, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return OFX_OK;
+}
+
+// One pair of host images, uploaded in type S: double, so that the float mode rounds after the normalisation, or the storage
+// type, which rounds the images as they come
+template <typename T, typename S>
 static int rexpo_pyramid_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny, int nz,
                               const BroxParams &P, int nscales, double nu)
 {
     std::vector<int> nxs, nys;
     OFX_TRY(rexpo_pyramid_check(ctx, 1, nx, ny, nz, nscales, nu, nxs, nys));
     const size_t n = (size_t) nx * ny;
+    S *a, *b;
     OfxGroupPtrs src;
     std::vector<BroxLevel<T>> lv;
     if (ctx->profile) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    OFX_TRY(rexpo_upload_pair(ctx, I1, I2, n * nz, &src));
-    OFX_TRY((rexpo_pyramid_dev<T, double>(ctx, 1, src, nz, P, nscales, nu, nxs, nys, lv, &ctx->stats, true)));
+    OFX_TRY(rexpo_upload<S>(ctx, I1, n * nz, &a));
+    OFX_TRY(rexpo_upload<S>(ctx, I2, n * nz, &b));
+    memset(&src, 0, sizeof(src));
+    src.a[0] = a;
+    src.b[0] = b;
+    OFX_TRY((rexpo_pyramid_dev<T, S>(ctx, 1, src, nz, P, nscales, nu, nxs, nys, lv, &ctx->stats, true)));
     return download_flow<T>(ctx, lv[0].U, u, v, n);
 }
 
@@ -2666,7 +2575,21 @@ static int rexpo_check_args(ofx_ctx *ctx, const double *I1, const double *I2, co
     return rexpo_check_params(ctx, nz, method_type, inner_iter, outer_iter);
 }
 
-// robust_expo_methods (src/robust_expo_methods.h:21-38): one channel at any number of scales, colour at one scale
+// the parameter set of every robust_expo entry; alpha as the level solver takes it
+static BroxParams rexpo_params(int method_type, double alpha, double gamma, double lambda, double TOL, int inner_iter, int outer_iter,
+                               int verbose)
+{
+    BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, verbose};
+    P.robust = 1;
+    P.method = method_type;
+    P.lambda = lambda;
+    return P;
+}
+// the multiscale overload's alpha (:527): alpha * nzz as an int
+static double rexpo_multiscale_alpha(double alpha, int nzz) { return (double) (int) (alpha * nzz); }
+
+// robust_expo_methods (src/robust_expo_methods.h:21-38): one channel at any number of scales, colour at one scale.
+// One channel is rounded to the storage type as it comes, before the normalisation; colour after it.
 extern "C" int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int nzz,
                                int method_type, double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                                int inner_iter, int outer_iter, int verbose)
@@ -2677,24 +2600,19 @@ extern "C" int ofx_robust_expo(ofx_ctx *ctx, const double *I1, const double *I2,
         return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: nzz=%d with nscales=%d (colour at one scale only: the reference's colour pyramid "
                                           "reads beyond its scratch copy, zoom.cpp:96-118)", nzz, nscales);
     const double t0 = ofx_now_ms();
-    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, verbose};     // :527: alpha * nzz as an int
-    P.robust = 1;
-    P.method = method_type;
-    P.lambda = lambda;
+    const BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter,
+                                      verbose);
     int s;
-    if (nzz == 1)
-        s = ctx->precision == OFX_F64 ? brox_spatial_host<double>(ctx, I1, I2, u, v, nxx, nyy, P, nscales, nu)
-                                      : brox_spatial_host<float>(ctx, I1, I2, u, v, nxx, nyy, P, nscales, nu);
-    else
-        s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true)
-                                      : rexpo_level_host<float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, true);
+    if (ctx->precision == OFX_F64) s = rexpo_pyramid_host<double, double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
+    else if (nzz == 1) s = rexpo_pyramid_host<float, float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
+    else s = rexpo_pyramid_host<float, double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
 }
 
 // ofx_robust_expo's argument list, any nzz in 1 .. OFX_REXPO_MAX_CHANNELS at any number of scales: the reference's driver on
-// levels built by the per-channel zoom-out of the IPOL original (rexpo_pyramid_host).  nzz = 1 is ofx_robust_expo's result,
-// nscales = 1 ofx_robust_expo's colour result.
+// levels built by the per-channel zoom-out of the IPOL original.  Every channel count is rounded to the storage type after the
+// normalisation.
 extern "C" int ofx_robust_expo_pyramid(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx, int nyy,
                                        int nzz, int method_type, double alpha, double gamma, double lambda, int nscales, double nu,
                                        double TOL, int inner_iter, int outer_iter, int verbose)
@@ -2702,12 +2620,10 @@ extern "C" int ofx_robust_expo_pyramid(ofx_ctx *ctx, const double *I1, const dou
     OFX_ENTER(ctx);
     OFX_TRY(rexpo_check_args(ctx, I1, I2, u, v, nzz, method_type, inner_iter, outer_iter));
     const double t0 = ofx_now_ms();
-    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, verbose};     // :527: alpha * nzz as an int
-    P.robust = 1;
-    P.method = method_type;
-    P.lambda = lambda;
-    int s = ctx->precision == OFX_F64 ? rexpo_pyramid_host<double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu)
-                                      : rexpo_pyramid_host<float>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
+    const BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter,
+                                      verbose);
+    int s = ctx->precision == OFX_F64 ? rexpo_pyramid_host<double, double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu)
+                                      : rexpo_pyramid_host<float, double>(ctx, I1, I2, u, v, nxx, nyy, nzz, P, nscales, nu);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
 }
@@ -2722,12 +2638,9 @@ extern "C" int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, cons
     (void) number_of_threads;
     OFX_TRY(rexpo_check_args(ctx, I1, I2, u, v, nz, method_type, inner_iter, outer_iter));
     const double t0 = ofx_now_ms();
-    BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, verbose};
-    P.robust = 1;
-    P.method = method_type;
-    P.lambda = lambda;
-    int s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nx, ny, nz, P, false)
-                                      : rexpo_level_host<float>(ctx, I1, I2, u, v, nx, ny, nz, P, false);
+    const BroxParams P = rexpo_params(method_type, alpha, gamma, lambda, TOL, inner_iter, outer_iter, verbose);
+    int s = ctx->precision == OFX_F64 ? rexpo_level_host<double>(ctx, I1, I2, u, v, nx, ny, nz, P)
+                                      : rexpo_level_host<float>(ctx, I1, I2, u, v, nx, ny, nz, P);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
 }
@@ -2771,10 +2684,7 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
     std::vector<int> nxs, nys;
     OFX_TRY(rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys));
     const double t0 = ofx_now_ms();
-    BroxParams P = {(double) (int) (alpha * nzz), gamma, TOL, inner_iter, outer_iter, 0};           // :527: alpha * nzz as an int
-    P.robust = 1;
-    P.method = method_type;
-    P.lambda = lambda;
+    BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter, 0);
     P.time_windows = ctx->profile;
     std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
     ofx_stats *st = stats_out ? stats_out : local.data();

@@ -160,6 +160,63 @@ def test_one_scale_is_robust_expo_on_colour(gpu64, synth, pair, nx, ny, nz, kw):
     assert np.array_equal(ita, gpu64.stats().iterations())
 
 
+def test_one_channel_f32_rounds_before_it_normalises(gpu32, synth):
+    """f32 storage: ofx_robust_expo rounds a one-channel image to float as it comes, BEFORE the normalisation, so the images
+    and their float roundings give the same bits; ofx_robust_expo_pyramid rounds after it, and on float-representable images,
+    where the order cannot matter, the two entries agree.  synth.pair is integer-valued, which every float holds, so the pair
+    is divided by 3: two thirds of its values then differ from their float roundings."""
+    I1, I2 = (a / 3.0 for a in synth.pair("P1", 64, 48))
+    kw = dict(nscales=2, method=2, alpha=18.7, gamma=5.0, lam=0.05, outer=3)
+    assert not np.array_equal(I1, I1.astype(np.float32)) and not np.array_equal(I2, I2.astype(np.float32))
+    R1, R2 = I1.astype(np.float32).astype(np.float64), I2.astype(np.float32).astype(np.float64)
+    ua, va = gpu32.robust_expo(I1, I2, **kw)
+    ita = gpu32.stats().iterations().copy()
+    ub, vb = gpu32.robust_expo(R1, R2, **kw)
+    itb = gpu32.stats().iterations().copy()
+    assert np.array_equal(ua, ub) and np.array_equal(va, vb) and np.array_equal(ita, itb)
+    uc, vc = gpu32.robust_expo_pyramid(R1, R2, **kw)
+    assert np.array_equal(ub, uc) and np.array_equal(vb, vc) and np.array_equal(itb, gpu32.stats().iterations())
+
+
+MKC = _load("make_golden_color", os.path.join(GOLDEN, "make_golden_color.py"))
+
+
+@pytest.mark.parametrize("nx,ny", [(3, 3), (5, 3), (4, 4), (33, 21), (64, 48)],
+                         ids=["3x3", "5x3", "4x4", "33x21", "recorded-64x48"])
+def test_one_channel_level_at_the_row_rules(gpu64, ref, nx, ny):
+    """One channel through the level kernels where the first-row and last-row rules of the channel derivatives bite: (ny, nx)
+    planes and the same data as (ny, nx, 1) are one solve, and the compiled reference's single-scale overload agrees to
+    < 1e-11.  3x3, the smallest level the solver takes, is all corners and one element of the first-row loop.  Under 4 rows or
+    columns no pixel has its bicubic taps inside and the warps are 0, so the initial flow is not constant: its smoothing is
+    weighed by expo, i.e. by the derivatives of I1, and the result depends on them at every size; from 4x4 on the warps read
+    I2's derivatives of both rows as well.  The oracle has no single-scale form and the reference reports its sweep counts only
+    as text, so the sweep table is compared where it is recorded: fixture rexpoc_ss_p1_64x48x1, at its size and parameters."""
+    if (nx, ny) == (64, 48):
+        c = json.load(open(os.path.join(GOLDEN, "cases_color.json")))["rexpoc_ss_p1_64x48x1"]
+        g = np.load(os.path.join(GOLDEN, "rexpoc_ss_p1_64x48x1.npz"), allow_pickle=False)
+        I1, I2, u0, v0 = MKC.inputs(c)
+        ur, vr, iters = g["u"], g["v"], g["iters"]
+    else:
+        c = dict(pair="P1", nx=nx, ny=ny, nz=1, params=dict(method=3, alpha=37.5, gamma=10.0, lam=0.1, inner=2, outer=2))
+        I1, I2, _, _ = MKC.inputs(c)
+        x, y = np.meshgrid(np.arange(nx) / (nx - 1.0), np.arange(ny) / (ny - 1.0))
+        u0, v0 = 0.3 + 0.4 * x - 0.3 * y * y, -0.2 + 0.5 * x * y - 0.3 * x
+        ur, vr = MKC.ref_single(ref.lib, I1, I2, u0, v0, **c["params"])
+        iters = None
+        assert np.abs(ur - u0).max() > 0.01 and np.abs(vr - v0).max() > 0.01     # the solve moves the flow
+    assert I1.shape == (ny, nx, 1)
+    ua, va = gpu64.robust_expo_single_scale(I1[..., 0], I2[..., 0], u0, v0, **c["params"])
+    ita = gpu64.stats().iterations()[0, :c["params"]["inner"] * c["params"]["outer"]].copy()
+    ub, vb = gpu64.robust_expo_single_scale(I1, I2, u0, v0, **c["params"])
+    itb = gpu64.stats().iterations()[0, :len(ita)]
+    du, dv = _report("one channel %dx%d" % (nx, ny), ua, va, ur, vr)
+    print("sweeps", ita.tolist(), "recorded", None if iters is None else iters.tolist())
+    assert np.array_equal(ua, ub) and np.array_equal(va, vb) and np.array_equal(ita, itb)
+    assert iters is None or np.array_equal(ita, iters)
+    assert np.isfinite(ur).all() and np.isfinite(vr).all()
+    assert du < BOUND and dv < BOUND
+
+
 # ---- 9. errors, and the workspace afterwards ----------------------------------------------------------------------------------
 def test_errors_leave_the_context_usable(gpu64, ofx_mod, synth):
     I1, I2 = synth.colour_pair("P1", 32, 24, 3)

@@ -2,7 +2,7 @@
 """Cost of robust_expo on a colour pair at one scale: one 1280x720x3 pair (method 1, nscales = 1, the
 reference's defaults otherwise) through ofx_robust_expo, next to
   (a) the compiled reference on ONE thread on the same input (skipped where oracle/_ref/libofref.so is absent), and
-  (b) the one-channel solve of the same size at nscales = 1 (channel 0; the one-channel path is the code of the parent commit).
+  (b) the one-channel solve of the same size at nscales = 1 (channel 0; the same driver and level kernels with nz = 1).
 Prints one JSON line; --out FILE also writes it there.
 
     python tools/bench_rexpo_color.py [--nx 1280 --ny 720 --nz 3 --reps 3 --no-ref --out profiles/rexpo_color_1280x720.json]
