@@ -439,6 +439,10 @@ __global__ __launch_bounds__(MAXT) void k_hs_window(typename Pix<T>::v2 *Ug, typ
 template <typename T, int KW> struct HsWinLds {
     static constexpr int NH = KW + 10;          // hyperplanes of unknowns in the window
     static constexpr int BACK = 7;              // window starts at q0 - BACK
+    static size_t bytes(int nr, int nt)
+    {
+        return (size_t) nr * NH * sizeof(double2) + (size_t) nt * KW * (sizeof(double2) + sizeof(double));
+    }
 };
 template <typename T, bool SNAP> struct ULds {
     typename Pix<T>::v2 *U, *snap;               // global arrays (hyperplane-major), written through
@@ -542,6 +546,13 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(1, 2))) vo
     loop_accumulate(err, s, e, b * 4 + (t >> 6));
 }
 
+// the stopping test of every SOR loop of this file: sqrt(sum of squared updates / size) > TOL.  max_iter -- and chunk and
+// fixed in the colour-order loops, which poll -- are the caller's.
+static LoopSpec sor_loop_spec(int size, double TOL)
+{
+    return LoopSpec{/* max_iter */ 0, size, TOL, OFX_CRIT_SQRT_MEAN, /* chunk */ 0, /* fixed */ false, /* pairs */ false};
+}
+
 // Batch driver of the windowed exact mode.  launch(w, blocks, sweeps) enqueues one window over `blocks` row
 // blocks x `sweeps` sweeps starting at w.s_first; take(n) makes snapshot n - 1 the current state.  Same contract
 // as sor_exact_loop.  Spacing: lag_b = K between the row blocks of a sweep, lag_s = 2 K + C between sweeps (K + C
@@ -574,13 +585,7 @@ static int sor_window_loop(ofx_ctx *ctx, int G, int size, int ny, double TOL, in
     w.lag_s = (B > 1 ? 2 * w.K : w.K) + C + w.lag_f * (nz - 1);
     const int per = batch + 1;                                   // error slots per problem
     OFX_TRY(ofx_loop_reserve(ctx, G * per));
-    LoopSpec LS;
-    LS.size = size;
-    LS.thr = TOL;
-    LS.crit = OFX_CRIT_SQRT_MEAN;
-    LS.chunk = 0;
-    LS.fixed = false;
-    LS.pairs = false;
+    LoopSpec LS = sor_loop_spec(size, TOL);
     // Every sweep of a batch costs lag_s steps of pipeline whether it is needed or not, so batches are sized, not
     // maximal (`batch` is the snapshot capacity): the first one from the sweep count of the previous solve at this level
     // (*hint = the largest of the group; consecutive warps / outer iterations converge in similar, usually decreasing,
@@ -649,13 +654,7 @@ static int sor_exact_loop(ofx_ctx *ctx, int size, double TOL, int maxiter, int q
     double error = 1000;
     const int batch = ctx->sor_batch > 0 ? ctx->sor_batch : 64;
     OFX_TRY(ofx_loop_reserve(ctx, batch + 1));
-    LoopSpec LS;
-    LS.size = size;
-    LS.thr = TOL;
-    LS.crit = OFX_CRIT_SQRT_MEAN;
-    LS.chunk = 0;
-    LS.fixed = false;
-    LS.pairs = false;
+    LoopSpec LS = sor_loop_spec(size, TOL);
     auto run_batch = [&](int ns, OfxIterState *out) -> int {
         OFX_TRY(ofx_loop_clear(ctx, (size_t) ns));
         const int tmax = qmax + C * (ns - 1);
@@ -721,9 +720,8 @@ static int sor_pick_batch(const ofx_ctx *ctx, size_t npix, size_t elem_bytes, in
 // one store drain + barrier per step for all of them -- run at 0.66x / 0.47x the throughput of 1 (HS 23.9k -> 15.7k ->
 // 11.2k Mpix*sweeps/s): the operands of two updates take 151 VGPRs = 3 waves per SIMD instead of 8 at 64, and the
 // per-step latency is hidden by resident waves, not by instruction-level parallelism inside one.
-static int sor_pick_spw(const ofx_ctx *ctx, int G)
+static int sor_pick_spw(const ofx_ctx *ctx)
 {
-    (void) G;
     if (ctx->sor_spw == 1 || ctx->sor_spw == 2 || ctx->sor_spw == 4) return ctx->sor_spw;
     return 1;
 }
@@ -735,14 +733,150 @@ static int sor_pick_spw(const ofx_ctx *ctx, int G)
 // 572 -> 537 ms with 8 steps per launch (16: 617), lockstep groups of 16 81 -> 147 ms per pair (116 since idle units leave at
 // once, profiles/r03_n_hs_window_kernels_counters.txt: 800 resident waves against 2400); Brox lone solves 255 -> 297 ms.
 // A step is bound by the ~200 dependent instructions of a lone wave, not by the round trip the window removes.
-static bool sor_use_lds(const ofx_ctx *ctx, int G, bool brox = false)
+// lds_for_small_groups: whether sor_lds = 1 takes the LDS window for groups of fewer than 4 (Horn-Schunck does, Brox does not)
+static bool sor_use_lds(const ofx_ctx *ctx, int G, bool lds_for_small_groups)
 {
-    return ctx->sor_lds == 2 || (ctx->sor_lds == 1 && G < 4 && !brox);
+    return ctx->sor_lds == 2 || (ctx->sor_lds == 1 && G < 4 && lds_for_small_groups);
 }
 static int sor_window_threads(int n_items)
 {
     const int t = ofx_cdiv(n_items, 64) * 64;
     return t > 1024 ? 1024 : t;
+}
+
+// makes *snap hold `batch` snapshot planes of `plane` elements for each of G problems
+template <typename V> static int sor_snap_reserve(ofx_ctx *ctx, V **snap, int *planes, size_t plane, int batch, int G)
+{
+    if (*planes >= batch) return OFX_OK;
+    OFX_TRY(ofx_alloc(ctx, plane * batch * G, snap));
+    *planes = batch;
+    return OFX_OK;
+}
+
+// one finished solve (number `solve` of level `scale`) in the work records of the G problems that ran it
+static void sor_record_solve(ofx_stats *stats, int G, int scale, int solve, const int *niter, const double *error, float ms,
+                             double pixels)
+{
+    for (int g = 0; g < G; g++) {
+        ofx_stats &S = stats[g];
+        if (scale < OFX_MAX_SCALES) {
+            if (solve < OFX_MAX_SOLVES) { S.iters[scale][solve] = niter[g]; S.error[scale][solve] = error[g]; }
+            S.iter_ms[scale] += ms;
+            S.iter_launches[scale] += niter[g];
+        }
+        S.work_pix_iters += (double) niter[g] * pixels;
+    }
+}
+
+// ---- the exact-mode solve, once for both stencils (S: HsExact, BroxExact) ------------------------------------------------------
+
+// one launch of an exact-mode kernel; dynamic LDS beyond 64 KiB has to be granted to the kernel first
+template <class... KA, class... A>
+static int sor_launch(ofx_ctx *ctx, void (*kernel)(KA...), dim3 grid, dim3 blk, size_t lds, A... args)
+{
+    if (lds > 64 * 1024)
+        OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int) lds));
+    hipLaunchKernelGGL(kernel, grid, blk, lds, ctx->stream, args...);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+// the LDS window of KW steps, if that is the launch's length and its footprint fits the 160 KiB of a CU (*done: launched)
+template <class S, int KW>
+static int sor_window_lds(ofx_ctx *ctx, const S &st, const SorWin &w, const SorGrp &grp, dim3 grid, dim3 blk, int sweeps, bool *done)
+{
+    const size_t lds = S::template Lds<KW>::bytes(w.R + 3, (int) blk.x);
+    *done = w.K == KW && lds <= 160 * 1024;
+    return *done ? st.launch(ctx, S::template window_lds<KW>, grid, blk, lds, w, grp, sweeps) : OFX_OK;
+}
+
+// One window of `sweeps` sweeps x `blocks` row blocks x G problems: the launch window staged in LDS (one sweep per workgroup,
+// steps on LDS only) where sor_use_lds asks for it and a kernel of w.K steps exists, up to 253 rows fit its 256 threads and the
+// footprint fits the LDS; else the global kernel with option sor_spw's sweeps per workgroup.
+template <class S>
+static int sor_window_launch(ofx_ctx *ctx, const S &st, const SorWin &w, const SorGrp &grp, int blocks, int sweeps, int G)
+{
+    const dim3 blk(sor_window_threads(w.R + 3));
+    if constexpr (S::ONE_KERNEL) {
+        return st.launch(ctx, S::template window<1, 1024>, dim3(blocks, sweeps, G), blk, 0, w, grp, sweeps);
+    } else {
+        if (sor_use_lds(ctx, G, S::LDS_FOR_SMALL_GROUPS) && w.R + 3 <= 256) {
+            const dim3 grid(blocks, sweeps, G);
+            bool done = false;
+            int s = sor_window_lds<S, S::LDS_K[0]>(ctx, st, w, grp, grid, blk, sweeps, &done);
+            if (!done) s = sor_window_lds<S, S::LDS_K[1]>(ctx, st, w, grp, grid, blk, sweeps, &done);
+            if (!done) s = sor_window_lds<S, S::LDS_K[2]>(ctx, st, w, grp, grid, blk, sweeps, &done);
+            if (done) return s;
+        }
+        const int spw = sor_pick_spw(ctx);
+        // workgroups of up to 128 threads (the default geometries) are compiled without the 128-VGPR cap that a 1024-thread
+        // bound implies: two sweeps per workgroup keep their operands in registers instead of spilling.  One sweep per
+        // workgroup: the 64-VGPR build, 8 waves per SIMD.
+        const bool small = blk.x <= 128;
+        const auto k = spw == 4   ? (small ? S::template window<4, 128> : S::template window<4, 1024>)
+                       : spw == 2 ? (small ? S::template window<2, 128> : S::template window<2, 1024>)
+                                  : S::template window<1, 1024>;
+        return st.launch(ctx, k, dim3(blocks, ofx_cdiv(sweeps, spw), G), blk, 0, w, grp, sweeps);
+    }
+}
+
+// sor_exact_solve<S> runs one solve of the G problems of a lockstep group in the reference's sweep order: option sor_exact = 1
+// on hyperplane-major copies through sor_window_loop, anything else one launch per time step through sor_exact_loop (lone
+// problems).  S -- HsExact, BroxExact -- is bound to a level and carries what differs between the solvers:
+//   SKEW, C         hyperplane of pixel (i, j) = SKEW i + j (LaySkew; the stencil skew of sor_unit_idle); steps between sweeps
+//   qmax(nx, ny)    the last step of a sweep
+//   LDS_K, Lds<KW>  the window lengths k_*_window_lds is instantiated for and the footprint Lds<KW>::bytes(rows + 3, threads)
+//   LDS_FOR_SMALL_GROUPS   whether option sor_lds = 1 takes the LDS window for groups of fewer than 4 (sor_use_lds)
+//   ONE_KERNEL      robust_expo: k_brox_window<T, 1, 1024, true> whatever sor_lds and sor_spw say
+//   u(), us(), ck() the unknowns row-major, hyperplane-major, and the checkpoint of the one-launch-per-step path
+//   skew_in()       allocates the level's hyperplane-major planes on first use (it writes L.Us, ...) and copies every operand in
+//   window<SPW, MAXT>, window_lds<KW>, launch(); plane()   the window kernels and their launcher; the plane kernel's launcher
+// size: pixels the stopping sum is divided by; Kdef, Rdef: see sor_window_loop; niter[g], error[g]: sweeps and last stopping
+// value of problem g; ms (windowed only), when given: the windows of this solve between two drained streams on the host's clock
+// (so with the polls of the stopping test) -- every other caller keeps its schedule
+template <class S>
+static int sor_exact_solve(ofx_ctx *ctx, const S &st, int G, int size, double TOL, int maxiter, int Kdef, int Rdef, int *niter,
+                           double *error, float *ms)
+{
+    using v2 = typename S::v2;
+    auto &L = st.L;
+    const int nx = L.nx, ny = L.ny, qmax = S::qmax(nx, ny);
+    if (ctx->sor_exact != 1) {
+        // one launch per time step (option sor_exact = 2): the reference implementation of the exact schedule
+        const size_t ub = (size_t) nx * ny * sizeof(v2);
+        auto plane = [&](int t, int s_lo, int s_cnt) -> int { return st.plane(ctx, t, s_lo, s_cnt); };
+        auto copy = [&](v2 *dst, const v2 *src) -> int {
+            OFX_HIP(ctx, hipMemcpyAsync(dst, src, ub, hipMemcpyDeviceToDevice, ctx->stream));
+            return OFX_OK;
+        };
+        return sor_exact_loop(ctx, size, TOL, maxiter, qmax, S::C, plane, [&] { return copy(st.ck(), st.u()); },
+                              [&] { return copy(st.u(), st.ck()); }, niter, error);
+    }
+    // windowed (default): the sweeps run on hyperplane-major copies of the unknowns and the constant operands
+    const size_t ps = skew_plane_elems(nx, ny, S::SKEW);
+    const int batch = sor_pick_batch(ctx, ps, sizeof(v2), maxiter, G);
+    OFX_TRY(st.skew_in(ctx, ps, G));
+    OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, ps, batch, G));
+    const size_t snap_stride = ps * L.snap_planes;
+    auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned runmask, int err_stride) -> int {
+        const SorGrp grp = {runmask, err_stride, ps, snap_stride};
+        return sor_window_launch(ctx, st, w, grp, blocks, sweeps, G);
+    };
+    auto take = [&](int g, int n) -> int {
+        OFX_HIP(ctx, hipMemcpyAsync(st.us() + g * ps, L.Snap + g * snap_stride + (size_t) (n - 1) * ps, ps * sizeof(v2),
+                                    hipMemcpyDeviceToDevice, ctx->stream));
+        return OFX_OK;
+    };
+    if (ms) OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double t0 = ofx_now_ms();
+    OFX_TRY(sor_window_loop(ctx, G, size, ny, TOL, maxiter, qmax, S::C, batch, window, take, niter, error, 1, &L.sweep_hint, Kdef,
+                            Rdef));
+    if (ms) {
+        OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *ms = (float) (ofx_now_ms() - t0);
+    }
+    return op_skew<v2, false>(ctx, st.us(), st.u(), nx, ny, S::SKEW, G);
 }
 
 // One level of a lockstep group: every array holds G pairs back to back (pair g at element g * nx * ny).
@@ -794,6 +928,45 @@ struct HsParams {
     int warps, maxiter, verbose;
 };
 
+// Horn-Schunck's side of sor_exact_solve: unknowns U, constant operands A, Dif, alpha^2 as the kernels' scalar.  L is the
+// level itself, not a copy: skew_in() gives it its hyperplane-major planes (Us, As, Difs), the driver its snapshot planes
+template <typename T> struct HsExact {
+    using v2 = typename Pix<T>::v2;
+    static constexpr int SKEW = HS_PLANE_C_SKEW, C = HS_PLANE_C;
+    static constexpr int LDS_K[3] = {8, 16, 24};
+    static constexpr bool LDS_FOR_SMALL_GROUPS = true, ONE_KERNEL = false;
+    template <int KW> using Lds = HsWinLds<T, KW>;
+    static int qmax(int nx, int ny) { return 2 * ny + nx - 2; }
+    HsLevel<T> &L;
+    double alpha2;
+    v2 *u() const { return L.U; }
+    v2 *us() const { return L.Us; }
+    v2 *ck() const { return L.Uck; }
+    int skew_in(ofx_ctx *ctx, size_t ps, int G) const
+    {
+        if (!L.Us) {
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.Us));
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.As));
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.Difs));
+        }
+        OFX_TRY((op_skew<v2, true>(ctx, L.U, L.Us, L.nx, L.ny, SKEW, G)));
+        OFX_TRY((op_skew<v2, true>(ctx, L.A, L.As, L.nx, L.ny, SKEW, G)));
+        return op_skew<T, true>(ctx, L.Dif, L.Difs, L.nx, L.ny, SKEW, G);
+    }
+    template <int SPW, int MAXT> static constexpr auto window = k_hs_window<T, SPW, MAXT>;
+    template <int KW> static constexpr auto window_lds = k_hs_window_lds<T, KW, 256>;
+    template <class Kernel>
+    int launch(ofx_ctx *ctx, Kernel k, dim3 grid, dim3 blk, size_t lds, const SorWin &w, const SorGrp &grp, int sweeps) const
+    {
+        return sor_launch(ctx, k, grid, blk, lds, L.Us, L.Snap, L.As, L.Difs, ctx->d_err, w, grp, sweeps, L.nx, L.ny, alpha2);
+    }
+    int plane(ofx_ctx *ctx, int t, int s_lo, int s_cnt) const
+    {
+        return sor_launch(ctx, k_hs_plane<T>, dim3(ofx_cdiv(L.ny + 3, 64), s_cnt), dim3(64), 0, L.U, L.A, L.Dif, ctx->d_err, t, s_lo,
+                          L.nx, L.ny, alpha2);
+    }
+};
+
 // src/horn_schunck_pyramidal.cpp:78-249 on device data for the G pairs of a lockstep group; L.U holds the incoming
 // flows; stats[g] = work record of pair g.
 template <typename T>
@@ -825,105 +998,13 @@ static int hs_single_scale_dev(ofx_ctx *ctx, HsLevel<T> &L, const HsParams &P, i
         if (tiled) {
             OFX_TRY(ofx_hs_tile_solve<T>(ctx, G, L.U, L.Uck, &L.cur, L.A, (const T *) L.Dif, nx, ny, alpha2, P.TOL, P.maxiter,
                                          ctx->sor_fuse, niter, error, ctx->profile ? &ms : nullptr));
-        } else if (windowed) {
-            // windowed exact mode (default): the sweeps run on hyperplane-major copies of U, A, Dif
-            const size_t ps = skew_plane_elems(nx, ny, HS_PLANE_C_SKEW);
-            const size_t ub = ps * sizeof(typename Pix<T>::v2);
-            const int batch = sor_pick_batch(ctx, ps, sizeof(typename Pix<T>::v2), P.maxiter, G);
-            if (!L.Us) {
-                OFX_TRY(ofx_alloc(ctx, ps * G, &L.Us));
-                OFX_TRY(ofx_alloc(ctx, ps * G, &L.As));
-                OFX_TRY(ofx_alloc(ctx, ps * G, &L.Difs));
-            }
-            if (L.snap_planes < batch) {
-                OFX_TRY(ofx_alloc(ctx, ps * batch * G, &L.Snap));
-                L.snap_planes = batch;
-            }
-            OFX_TRY((op_skew<typename Pix<T>::v2, true>(ctx, L.U, L.Us, nx, ny, HS_PLANE_C_SKEW, G)));
-            OFX_TRY((op_skew<typename Pix<T>::v2, true>(ctx, L.A, L.As, nx, ny, HS_PLANE_C_SKEW, G)));
-            OFX_TRY((op_skew<T, true>(ctx, L.Dif, L.Difs, nx, ny, HS_PLANE_C_SKEW, G)));
-            const size_t snap_stride = ps * L.snap_planes;
-            auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned runmask, int err_stride) -> int {
-                const SorGrp grp = {runmask, err_stride, ps, snap_stride};
-                const int spw = sor_pick_spw(ctx, G);
-                const size_t lds_need = (size_t) (w.R + 3) * (w.K + 10) * sizeof(double2) +
-                                        (size_t) sor_window_threads(w.R + 3) * w.K * (sizeof(double2) + sizeof(double));
-                if (sor_use_lds(ctx, G) && (w.K == 8 || w.K == 16 || w.K == 24) && w.R + 3 <= 256 && lds_need <= 160 * 1024) {
-                    // the launch window staged in LDS (k_hs_window_lds): one sweep per workgroup, steps on LDS only
-                    const dim3 grid(blocks, sweeps, G), blk(sor_window_threads(w.R + 3));
-                    const int nr = w.R + 3;
-#define OFX_HS_WINL(K_)                                                                                                        \
-    do {                                                                                                                       \
-        const size_t lds = (size_t) nr * HsWinLds<T, K_>::NH * sizeof(double2) + (size_t) blk.x * K_ * (sizeof(double2) + sizeof(double)); \
-        if (lds > 160 * 1024) return ofx_fail(ctx, OFX_ERR_ARG, "hs: window of %d steps x %d rows does not fit the LDS", K_, w.R); \
-        if (lds > 64 * 1024)                                                                                                   \
-            OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_hs_window_lds<T, K_, 256>),                      \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                          \
-        hipLaunchKernelGGL((k_hs_window_lds<T, K_, 256>), grid, blk, lds, ctx->stream, L.Us, L.Snap, L.As, (const T *) L.Difs, \
-                           ctx->d_err, w, grp, sweeps, nx, ny, alpha2);                                                        \
-    } while (0)
-                    if (w.K == 8) OFX_HS_WINL(8);
-                    else if (w.K == 16) OFX_HS_WINL(16);
-                    else OFX_HS_WINL(24);
-#undef OFX_HS_WINL
-                    OFX_LAUNCH_CHECK(ctx);
-                    return OFX_OK;
-                }
-                const dim3 grid(blocks, ofx_cdiv(sweeps, spw), G), blk(sor_window_threads(w.R + 3));
-                // workgroups of up to 128 threads (the default geometries) are compiled without the 128-VGPR cap that a
-                // 1024-thread bound implies: two sweeps per workgroup keep their operands in registers instead of spilling
-#define OFX_HS_WIN(SPW_, MAXT_)                                                                                          \
-    hipLaunchKernelGGL((k_hs_window<T, SPW_, MAXT_>), grid, blk, 0, ctx->stream, L.Us, L.Snap, L.As, (const T *) L.Difs, \
-                       ctx->d_err, w, grp, sweeps, nx, ny, alpha2)
-                if (blk.x <= 128 && spw > 1) {
-                    if (spw == 4) OFX_HS_WIN(4, 128);
-                    else OFX_HS_WIN(2, 128);
-                } else {                                         // one sweep per workgroup: the 64-VGPR build, 8 waves per SIMD
-                    if (spw == 4) OFX_HS_WIN(4, 1024);
-                    else if (spw == 2) OFX_HS_WIN(2, 1024);
-                    else OFX_HS_WIN(1, 1024);
-                }
-#undef OFX_HS_WIN
-                OFX_LAUNCH_CHECK(ctx);
-                return OFX_OK;
-            };
-            auto take = [&](int g, int n) -> int {
-                OFX_HIP(ctx, hipMemcpyAsync(L.Us + g * ps, L.Snap + g * snap_stride + (size_t) (n - 1) * ps, ub,
-                                            hipMemcpyDeviceToDevice, ctx->stream));
-                return OFX_OK;
-            };
-            OFX_TRY(sor_window_loop(ctx, G, nx * ny, ny, P.TOL, P.maxiter, 2 * ny + nx - 2, HS_PLANE_C, batch, window, take,
-                                    niter, error, 1, &L.sweep_hint, 0));
-            OFX_TRY((op_skew<typename Pix<T>::v2, false>(ctx, L.Us, L.U, nx, ny, HS_PLANE_C_SKEW, G)));
         } else if (ctx->sor_exact && nx >= 3 && ny >= 3) {
-            // one launch per time step (option sor_exact = 2): the reference implementation of the exact schedule
-            const size_t ub = (size_t) nx * ny * sizeof(typename Pix<T>::v2);
-            const dim3 gp(ofx_cdiv(ny + 3, 64), 1), bp(64);
-            auto plane = [&](int t, int s_lo, int s_cnt) -> int {
-                hipLaunchKernelGGL(k_hs_plane<T>, dim3(gp.x, s_cnt), bp, 0, ctx->stream, L.U, L.A, (const T *) L.Dif,
-                                   ctx->d_err, t, s_lo, nx, ny, alpha2);
-                OFX_LAUNCH_CHECK(ctx);
-                return OFX_OK;
-            };
-            auto save = [&]() -> int {
-                OFX_HIP(ctx, hipMemcpyAsync(L.Uck, L.U, ub, hipMemcpyDeviceToDevice, ctx->stream));
-                return OFX_OK;
-            };
-            auto restore = [&]() -> int {
-                OFX_HIP(ctx, hipMemcpyAsync(L.U, L.Uck, ub, hipMemcpyDeviceToDevice, ctx->stream));
-                return OFX_OK;
-            };
-            OFX_TRY(sor_exact_loop(ctx, nx * ny, P.TOL, P.maxiter, 2 * ny + nx - 2, HS_PLANE_C, plane, save, restore,
-                                   &niter[0], &error[0]));
+            OFX_TRY(sor_exact_solve(ctx, HsExact<T>{L, alpha2}, G, nx * ny, P.TOL, P.maxiter, 0, 0, niter, error, nullptr));
         } else if (P.maxiter > 0 && error[0] > P.TOL) {
-            LoopSpec LS;
+            LoopSpec LS = sor_loop_spec(nx * ny, P.TOL);
             LS.max_iter = P.maxiter;
-            LS.size = nx * ny;
-            LS.thr = P.TOL;
-            LS.crit = OFX_CRIT_SQRT_MEAN;
             LS.chunk = sor_pick_chunk(ctx, nx, ny, 4);
             LS.fixed = ctx->fixed_work != 0;
-            LS.pairs = false;
             auto launch = [&](int k, int, double thr) -> int {
                 for (int col = 0; col < 4; col++)
                     hipLaunchKernelGGL(k_hs_sor<T>, gc, b2d(), 0, ctx->stream, L.U, L.A, (const T *) L.Dif, ctx->d_err, k,
@@ -934,15 +1015,7 @@ static int hs_single_scale_dev(ofx_ctx *ctx, HsLevel<T> &L, const HsParams &P, i
             OFX_TRY(ofx_run_loop(ctx, LS, launch, [](int) { return OFX_OK; }, &niter[0], &error[0], ctx->profile ? &ms : nullptr));
         }
         if (P.verbose && G == 1) fprintf(stderr, "Iterations %d (%g)\n", niter[0], error[0]);   // :233-235
-        for (int g = 0; g < G; g++) {
-            ofx_stats &S = stats[g];
-            if (scale < OFX_MAX_SCALES) {
-                if (w < OFX_MAX_SOLVES) { S.iters[scale][w] = niter[g]; S.error[scale][w] = error[g]; }
-                S.iter_ms[scale] += ms;
-                S.iter_launches[scale] += niter[g];
-            }
-            S.work_pix_iters += (double) niter[g] * nx * ny;
-        }
+        sor_record_solve(stats, G, scale, w, niter, error, ms, (double) nx * ny);
     }
     return OFX_OK;
 }
@@ -1056,6 +1129,28 @@ static int hs_pyramidal_host(ofx_ctx *ctx, const double *I1, const double *I2, d
     return download_flow<T>(ctx, lv[0].flow(0), u, v, n);
 }
 
+// What the three ofx_*_group_dev entries share: the checks of the pointer tables and the group size, then the solver's own
+// (check), then solve(st) on the caller's records or, without stats_out, on local ones; pair 0's record stays in the context.
+template <class CheckFn, class SolveFn>
+static int sor_group_entry(ofx_ctx *ctx, const char *who, int n_pairs, const void *const *dI1, const void *const *dI2,
+                           void *const *d_flo, ofx_stats *stats_out, CheckFn check, SolveFn solve)
+{
+    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer", who);
+    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "%s: a lockstep group holds 1..%d pairs (got %d)", who, OFX_MAX_GROUP, n_pairs);
+    for (int g = 0; g < n_pairs; g++)
+        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer (pair %d)", who, g);
+    OFX_TRY(check());
+    const double t0 = ofx_now_ms();
+    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    const int s = solve(st);
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
+    ctx->stats = st[0];
+    return s;
+}
+
 template <typename T>
 static int hs_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx,
                            int ny, const HsParams &P, int nscales, double zfactor, ofx_stats *stats)
@@ -1103,23 +1198,16 @@ extern "C" int ofx_hs_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI
                                 double TOL, int maxiter, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
-    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "hs: NULL pointer");
-    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "hs: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
-    for (int g = 0; g < n_pairs; g++)
-        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "hs: NULL pointer (pair %d)", g);
-    if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", warps);
-    if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
-    const double t0 = ofx_now_ms();
     const HsParams P = {alpha, TOL, warps, maxiter, 0};
-    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    int s = ctx->precision == OFX_F64 ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st)
-                                      : hs_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    auto check = [&]() -> int {
+        if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", warps);
+        if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
+        return OFX_OK;
+    };
+    return sor_group_entry(ctx, "hs", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64 ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st)
+                                         : hs_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st);
+    });
 }
 
 // ============================================================================================
@@ -2087,6 +2175,49 @@ template <typename T> static int rexpo_level_expo(ofx_ctx *ctx, BroxLevel<T> &L,
     return OFX_OK;
 }
 
+// Brox's side of sor_exact_solve: unknowns DU, constant operands CO, Dm, psi_s, alpha as the kernels' scalar.  RX: robust_expo,
+// the global window kernel with that source's summation order and nothing else.  L is the level itself, as in HsExact:
+// skew_in() gives it DUs, COs, Dms, Psiss
+template <typename T, bool RX> struct BroxExact {
+    using v2 = typename Pix<T>::v2;
+    using v4 = typename Pix<T>::v4;
+    static constexpr int SKEW = BROX_PLANE_C_SKEW, C = BROX_PLANE_C;
+    static constexpr int LDS_K[3] = {4, 8, 16};
+    static constexpr bool LDS_FOR_SMALL_GROUPS = false, ONE_KERNEL = RX;
+    template <int KW> using Lds = BroxWinLds<T, KW>;
+    static int qmax(int nx, int ny) { return ny + nx - 2; }
+    BroxLevel<T> &L;
+    double alpha;
+    v2 *u() const { return L.DU; }
+    v2 *us() const { return L.DUs; }
+    v2 *ck() const { return L.DUck; }
+    int skew_in(ofx_ctx *ctx, size_t ps, int G) const
+    {
+        if (!L.DUs) {
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.DUs));
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.COs));
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.Dms));
+            OFX_TRY(ofx_alloc(ctx, ps * G, &L.Psiss));
+        }
+        OFX_TRY((op_skew<v2, true>(ctx, L.DU, L.DUs, L.nx, L.ny, SKEW, G)));
+        OFX_TRY((op_skew<v4, true>(ctx, L.CO, L.COs, L.nx, L.ny, SKEW, G)));
+        OFX_TRY((op_skew<T, true>(ctx, L.Dm, L.Dms, L.nx, L.ny, SKEW, G)));
+        return op_skew<T, true>(ctx, L.Psis, L.Psiss, L.nx, L.ny, SKEW, G);
+    }
+    template <int SPW, int MAXT> static constexpr auto window = k_brox_window<T, SPW, MAXT, RX>;
+    template <int KW> static constexpr auto window_lds = k_brox_window_lds<T, KW, 256>;
+    template <class Kernel>
+    int launch(ofx_ctx *ctx, Kernel k, dim3 grid, dim3 blk, size_t lds, const SorWin &w, const SorGrp &grp, int sweeps) const
+    {
+        return sor_launch(ctx, k, grid, blk, lds, L.DUs, L.Snap, L.COs, L.Dms, L.Psiss, ctx->d_err, w, grp, sweeps, L.nx, L.ny, alpha);
+    }
+    int plane(ofx_ctx *ctx, int t, int s_lo, int s_cnt) const
+    {
+        return sor_launch(ctx, k_brox_plane<T>, dim3(ofx_cdiv(L.ny + 3, 64), s_cnt), dim3(64), 0, L.DU, L.CO, L.Dm, L.Psis,
+                          ctx->d_err, t, s_lo, L.nx, L.ny, alpha);
+    }
+};
+
 // src/brox_optic_flow_spatial.cpp:179-444 on device data for the G pairs of a lockstep group; stats[g] = record of pair g.
 // P.robust: src/robust_expo_methods.cpp:162-455 on the level's nz >= 1 interleaved channels (the k_rexpo_* kernels)
 template <typename T>
@@ -2153,129 +2284,27 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
                 OFX_TRY(ofx_brox_wave_solve<T>(ctx, G, L.DUb, L.COb, (const T *) L.Dmb, (const T *) L.Psb, nx, ny, P.alpha, P.TOL,
                                                OFX_BROX_MAX_ITERATIONS, nsor, error, ctx->profile ? &ms : nullptr));
                 OFX_TRY((ofx_band_copy<typename Pix<T>::v2, false>(ctx, L.DUb, L.DU, nx, ny, G)));
-            } else if (windowed) {
-                // the sweeps run on hyperplane-major copies of DU, CO, Dm, psi_s
-                const size_t ps = skew_plane_elems(nx, ny, BROX_PLANE_C_SKEW);
-                const size_t ub = ps * sizeof(typename Pix<T>::v2);
-                const int batch = sor_pick_batch(ctx, ps, sizeof(typename Pix<T>::v2), OFX_BROX_MAX_ITERATIONS, G);
-                if (!L.DUs) {
-                    OFX_TRY(ofx_alloc(ctx, ps * G, &L.DUs));
-                    OFX_TRY(ofx_alloc(ctx, ps * G, &L.COs));
-                    OFX_TRY(ofx_alloc(ctx, ps * G, &L.Dms));
-                    OFX_TRY(ofx_alloc(ctx, ps * G, &L.Psiss));
-                }
-                if (L.snap_planes < batch) {
-                    OFX_TRY(ofx_alloc(ctx, ps * batch * G, &L.Snap));
-                    L.snap_planes = batch;
-                }
-                OFX_TRY((op_skew<typename Pix<T>::v2, true>(ctx, L.DU, L.DUs, nx, ny, BROX_PLANE_C_SKEW, G)));
-                OFX_TRY((op_skew<typename Pix<T>::v4, true>(ctx, L.CO, L.COs, nx, ny, BROX_PLANE_C_SKEW, G)));
-                OFX_TRY((op_skew<T, true>(ctx, L.Dm, L.Dms, nx, ny, BROX_PLANE_C_SKEW, G)));
-                OFX_TRY((op_skew<T, true>(ctx, L.Psis, L.Psiss, nx, ny, BROX_PLANE_C_SKEW, G)));
-                const size_t snap_stride = ps * L.snap_planes;
-                auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned runmask, int err_stride) -> int {
-                    const SorGrp grp = {runmask, err_stride, ps, snap_stride};
-                    if (rx) {                                    // robust_expo: the global window kernel with its summation order
-                        hipLaunchKernelGGL((k_brox_window<T, 1, 1024, true>), dim3(blocks, sweeps, G), dim3(sor_window_threads(w.R + 3)),
-                                           0, ctx->stream, L.DUs, L.Snap, L.COs, (const T *) L.Dms, (const T *) L.Psiss, ctx->d_err, w,
-                                           grp, sweeps, nx, ny, P.alpha);
-                        OFX_LAUNCH_CHECK(ctx);
-                        return OFX_OK;
-                    }
-                    const int spw = sor_pick_spw(ctx, G);
-                    const size_t lds_need = (size_t) sor_window_threads(w.R + 3) * w.K * (sizeof(double4) + sizeof(double)) +
-                                            (size_t) (w.R + 3) * (w.K + 5) * (sizeof(double2) + sizeof(double));
-                    if (sor_use_lds(ctx, G, true) && (w.K == 4 || w.K == 8 || w.K == 16) && w.R + 3 <= 256 && lds_need <= 160 * 1024) {
-                        const dim3 grid(blocks, sweeps, G), blk(sor_window_threads(w.R + 3));
-#define OFX_BROX_WINL(K_)                                                                                                      \
-    do {                                                                                                                       \
-        const size_t lds = BroxWinLds<T, K_>::bytes(w.R + 3, (int) blk.x);                                                     \
-        if (lds > 160 * 1024) return ofx_fail(ctx, OFX_ERR_ARG, "brox: window of %d steps x %d rows does not fit the LDS", K_, w.R); \
-        if (lds > 64 * 1024)                                                                                                   \
-            OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_brox_window_lds<T, K_, 256>),                    \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));                          \
-        hipLaunchKernelGGL((k_brox_window_lds<T, K_, 256>), grid, blk, lds, ctx->stream, L.DUs, L.Snap, L.COs, (const T *) L.Dms, \
-                           (const T *) L.Psiss, ctx->d_err, w, grp, sweeps, nx, ny, P.alpha);                                  \
-    } while (0)
-                        if (w.K == 4) OFX_BROX_WINL(4);
-                        else if (w.K == 8) OFX_BROX_WINL(8);
-                        else OFX_BROX_WINL(16);
-#undef OFX_BROX_WINL
-                        OFX_LAUNCH_CHECK(ctx);
-                        return OFX_OK;
-                    }
-                    const dim3 grid(blocks, ofx_cdiv(sweeps, spw), G), blk(sor_window_threads(w.R + 3));
-#define OFX_BROX_WIN(SPW_, MAXT_)                                                                                        \
-    hipLaunchKernelGGL((k_brox_window<T, SPW_, MAXT_>), grid, blk, 0, ctx->stream, L.DUs, L.Snap, L.COs, (const T *) L.Dms, \
-                       (const T *) L.Psiss, ctx->d_err, w, grp, sweeps, nx, ny, P.alpha)
-                    if (blk.x <= 128 && spw > 1) {
-                        if (spw == 4) OFX_BROX_WIN(4, 128);
-                        else OFX_BROX_WIN(2, 128);
-                    } else {
-                        if (spw == 4) OFX_BROX_WIN(4, 1024);
-                        else if (spw == 2) OFX_BROX_WIN(2, 1024);
-                        else OFX_BROX_WIN(1, 1024);
-                    }
-#undef OFX_BROX_WIN
-                    OFX_LAUNCH_CHECK(ctx);
-                    return OFX_OK;
-                };
-                auto take = [&](int q, int k) -> int {
-                    OFX_HIP(ctx, hipMemcpyAsync(L.DUs + q * ps, L.Snap + q * snap_stride + (size_t) (k - 1) * ps, ub,
-                                                hipMemcpyDeviceToDevice, ctx->stream));
-                    return OFX_OK;
-                };
-                // the robust_expo group entry under option "profile": the windows of this solve between two drained streams, on
-                // the host's clock (so with the polls of the stopping test); every other entry keeps its schedule
-                double tw = 0.0;
-                if (P.time_windows) {
-                    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    tw = ofx_now_ms();
-                }
+            } else if (ctx->sor_exact && nx >= 3 && ny >= 3) {
                 // robust_expo_methods.cpp:400: the stopping value divides by nx * ny * nz.  A robust_expo group promises each pair
                 // the lone solve's stopping VALUES, and the association of the stopping sum follows the window geometry (a
                 // thread's K steps, then the row block's waves): its groups keep the lone geometry, 8 steps and 64 rows, where
                 // Brox groups of >= 4 pairs switch to 125 rows.  Options sor_window / sor_rows still override both alike.
-                OFX_TRY(sor_window_loop(ctx, G, n * nz, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
-                                        take, nsor, error, 1, &L.sweep_hint, rx ? 8 : 0, rx ? 64 : 0));
-                if (P.time_windows) {
-                    OFX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    ms = (float) (ofx_now_ms() - tw);
-                }
-                OFX_TRY((op_skew<typename Pix<T>::v2, false>(ctx, L.DUs, L.DU, nx, ny, BROX_PLANE_C_SKEW, G)));
-            } else if (ctx->sor_exact && nx >= 3 && ny >= 3) {
-                const size_t ub = (size_t) n * sizeof(typename Pix<T>::v2);
-                const unsigned gpx = ofx_cdiv(ny + 3, 64);
-                auto plane = [&](int t, int s_lo, int s_cnt) -> int {
-                    hipLaunchKernelGGL(k_brox_plane<T>, dim3(gpx, s_cnt), dim3(64), 0, ctx->stream, L.DU, L.CO,
-                                       (const T *) L.Dm, (const T *) L.Psis, ctx->d_err, t, s_lo, nx, ny, P.alpha);
-                    OFX_LAUNCH_CHECK(ctx);
-                    return OFX_OK;
+                // time_windows: the robust_expo group entry under option "profile"
+                auto exact = [&](auto st, int Kdef, int Rdef) -> int {
+                    return sor_exact_solve(ctx, st, G, n * nz, P.TOL, OFX_BROX_MAX_ITERATIONS, Kdef, Rdef, nsor, error,
+                                           P.time_windows ? &ms : nullptr);
                 };
-                auto save = [&]() -> int {
-                    OFX_HIP(ctx, hipMemcpyAsync(L.DUck, L.DU, ub, hipMemcpyDeviceToDevice, ctx->stream));
-                    return OFX_OK;
-                };
-                auto restore = [&]() -> int {
-                    OFX_HIP(ctx, hipMemcpyAsync(L.DU, L.DUck, ub, hipMemcpyDeviceToDevice, ctx->stream));
-                    return OFX_OK;
-                };
-                OFX_TRY(sor_exact_loop(ctx, n, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, plane, save,
-                                       restore, &nsor[0], &error[0]));
+                OFX_TRY(rx ? exact(BroxExact<T, true>{L, P.alpha}, 8, 64) : exact(BroxExact<T, false>{L, P.alpha}, 0, 0));
             } else if (tol_mode && ctx->sor_fuse != 9) {
                 // the coarser levels of the tolerance mode: red-black, K sweeps per launch on LDS tiles (k_brox_tile; sor_fuse = 9:
                 // the two launches per sweep of k_brox_sor below, for A/B)
                 OFX_TRY(ofx_brox_tile_solve<T>(ctx, G, L.DU, L.DUck, L.CO, (const T *) L.Dm, (const T *) L.Psis, nx, ny, P.alpha, P.TOL,
                                                OFX_BROX_MAX_ITERATIONS, ctx->sor_fuse, nsor, error, ctx->profile ? &ms : nullptr));
             } else if (error[0] > P.TOL) {
-                LoopSpec LS;
+                LoopSpec LS = sor_loop_spec(n, P.TOL);
                 LS.max_iter = OFX_BROX_MAX_ITERATIONS;
-                LS.size = n;
-                LS.thr = P.TOL;
-                LS.crit = OFX_CRIT_SQRT_MEAN;
                 LS.chunk = sor_pick_chunk(ctx, nx, ny, 2);
                 LS.fixed = ctx->fixed_work != 0;
-                LS.pairs = false;
                 const int err_stride = (LS.max_iter + 1) * OFX_NSHARD;
                 const dim3 gcg(gc.x, gc.y, G);
                 auto launch = [&](int k, int, double thr) -> int {
@@ -2292,16 +2321,7 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
                 else printf("Iterations: %d\n", nsor[0]);
                 fflush(stdout);
             }
-            for (int q = 0; q < G; q++) {
-                ofx_stats &S = stats[q];
-                if (scale < OFX_MAX_SCALES) {
-                    if (solve < OFX_MAX_SOLVES) { S.iters[scale][solve] = nsor[q]; S.error[scale][solve] = error[q]; }
-                    S.iter_ms[scale] += ms;
-                    S.iter_launches[scale] += nsor[q];
-                }
-                S.work_pix_iters += (double) nsor[q] * n;
-            }
-            solve++;
+            sor_record_solve(stats, G, scale, solve++, nsor, error, ms, (double) n);
         }
         hipLaunchKernelGGL(k_brox_add<T>, g1, b1, 0, ctx->stream, L.U, L.DU, (int) (npix * G));   // :398-401
         OFX_LAUNCH_CHECK(ctx);
@@ -2650,22 +2670,15 @@ extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *
                                   double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
-    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "brox: NULL pointer");
-    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "brox: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
-    for (int g = 0; g < n_pairs; g++)
-        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "brox: NULL pointer (pair %d)", g);
-    if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
-    const double t0 = ofx_now_ms();
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
-    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    int s = ctx->precision == OFX_F64 ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st)
-                                      : brox_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    auto check = [&]() -> int {
+        if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
+        return OFX_OK;
+    };
+    return sor_group_entry(ctx, "brox", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64 ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st)
+                                         : brox_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st);
+    });
 }
 
 // ofx_robust_expo_pyramid for the pairs of a lockstep group on device-resident images (include/ofx.h)
@@ -2675,26 +2688,17 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
                                          int outer_iter, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
-    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer");
-    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
-    for (int g = 0; g < n_pairs; g++)
-        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: NULL pointer (pair %d)", g);
-    OFX_TRY(rexpo_check_params(ctx, nzz, method_type, inner_iter, outer_iter));
     std::vector<int> nxs, nys;
-    OFX_TRY(rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys));
-    const double t0 = ofx_now_ms();
-    BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter, 0);
-    P.time_windows = ctx->profile;
-    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    int s = ctx->precision == OFX_F64
-                ? rexpo_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st)
-                : rexpo_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    auto check = [&]() -> int {
+        OFX_TRY(rexpo_check_params(ctx, nzz, method_type, inner_iter, outer_iter));
+        return rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys);
+    };
+    return sor_group_entry(ctx, "robust_expo", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
+        BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter, 0);
+        P.time_windows = ctx->profile;
+        return ctx->precision == OFX_F64 ? rexpo_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st)
+                                         : rexpo_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st);
+    });
 }
 
 // ---- batches of pairs for the SOR solvers: lockstep groups, one worker thread per context (as ofx_tvl1_batch_dev) ----
@@ -3001,7 +3005,6 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
     if (nx < 3 || ny < 3) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: level %dx%d has no interior", nx, ny);
     const dim3 g = g2d(nx, ny), b = b2d(), g3(g.x, g.y, nz);
     const dim3 g1((unsigned) ((n1 + 255) / 256)), b1(256);
-    ofx_stats &S = ctx->stats;
     int solve = 0;
     for (int f = 0; f < nz; f++) {                                                                   // :346-355
         hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) (L.I + (size_t) f * n),
@@ -3025,10 +3028,7 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
             double error = 1000;
             const size_t ub = n1 * sizeof(typename Pix<T>::v2);
             const int batch = sor_pick_batch(ctx, n1, sizeof(typename Pix<T>::v2), OFX_BROX_MAX_ITERATIONS);
-            if (L.snap_planes < batch) {
-                OFX_TRY(ofx_alloc(ctx, n1 * batch, &L.Snap));
-                L.snap_planes = batch;
-            }
+            OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, batch, 1));
             auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned, int) -> int {
                 hipLaunchKernelGGL(k_broxt_window<T>, dim3(blocks, nz, sweeps), dim3(sor_window_threads(w.R + 3)), 0,
                                    ctx->stream, L.DU, L.Snap, L.CO, (const T *) L.Dm, (const T *) L.Psis, ctx->d_err, w, nx,
@@ -3043,12 +3043,7 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
             OFX_TRY(sor_window_loop(ctx, 1, (int) n1, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
                                     take, &nsor, &error, nz, &L.sweep_hint));                                       // :430-461
             if (P.verbose) { printf("Iterations: %d\n", nsor); fflush(stdout); }                     // :463-465
-            if (scale < OFX_MAX_SCALES) {
-                if (solve < OFX_MAX_SOLVES) { S.iters[scale][solve] = nsor; S.error[scale][solve] = error; }
-                S.iter_launches[scale] += nsor;
-            }
-            S.work_pix_iters += (double) nsor * n1;
-            solve++;
+            sor_record_solve(&ctx->stats, 1, scale, solve++, &nsor, &error, 0.f, (double) n1);
         }
         hipLaunchKernelGGL(k_brox_add<T>, g1, b1, 0, ctx->stream, L.U, L.DU, (int) n1);                // :469-472
         OFX_LAUNCH_CHECK(ctx);

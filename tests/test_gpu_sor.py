@@ -420,6 +420,38 @@ def test_sor_groups_with_small_batches_and_windows(gpu64, synth):
             assert np.array_equal(got[k], np.stack(wantb[k][:2], axis=-1).astype(np.float32)), (batch, k)
 
 
+def test_sor_work_records_of_groups_and_sequences(gpu64, synth):
+    """What the solvers share in book-keeping: a pair's record out of a group equals the record of its lone solve (sweep
+    table, launches per scale, pixel sweeps), without a stats_out table pair 0's record still ends up in the context, and a
+    temporal solve counts nx ny (frames - 1) pixels per sweep."""
+    import ctypes as C
+    nx, ny, G, ns = 48, 40, 3, 2
+    pairs, d0, d1, flo = _group_inputs(synth, G, nx, ny)
+    ptrs = ([t.data_ptr() for t in d0], [t.data_ptr() for t in d1], [flo[k].data_ptr() for k in range(G)])
+    record = lambda st: (st.iterations().tolist(), [st.iter_launches[s] for s in range(ns)], st.work_pix_iters)
+    hk = dict(alpha=7.0, nscales=ns, zfactor=0.5, warps=3, TOL=1e-4, maxiter=60)
+    bk = dict(alpha=50.0, gamma=10.0, nscales=ns, nu=0.5, TOL=1e-4, inner=2, outer=2)
+    for group, lone, fn, kw in ((gpu64.hs_group_dev, gpu64.hs_pyramidal, gpu64.L.ofx_hs_group_dev, hk),
+                                (gpu64.brox_group_dev, gpu64.brox_spatial, gpu64.L.ofx_brox_group_dev, bk)):
+        st = group(*ptrs, nx, ny, **kw)
+        alone = []
+        for k in range(G):
+            lone(pairs[k][0], pairs[k][1], **kw)
+            alone.append(record(gpu64.stats()))
+            assert record(st[k]) == alone[k], k
+            assert alone[k][2] > 0
+        lone(pairs[1][0], pairs[1][1], **dict(kw, nscales=1))    # the context now holds a record of another shape
+        assert len(gpu64.stats().iterations()) == 1
+        tables = [(C.c_void_p * G)(*p) for p in ptrs]
+        gpu64._ck(fn(gpu64.h, G, *tables, nx, ny, *kw.values(), None))
+        assert record(gpu64.stats()) == alone[0]
+    frames = 4
+    gpu64.brox_temporal(synth.sequence(40, 33, frames), nscales=2, inner=1, outer=2)
+    st = gpu64.stats()
+    want = sum(int(st.iterations()[s].sum()) * st.nx[s] * st.ny[s] * (frames - 1) for s in range(st.nscales))
+    assert want > 0 and st.work_pix_iters == want
+
+
 def test_sor_batch_entry_points(ofx_mod, synth):
     """ofx_hs_batch_dev / ofx_brox_batch_dev: 7 pairs on 2 contexts (groups of 4 + 3), work records per pair"""
     nx, ny, n = 120, 80, 7
