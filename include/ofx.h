@@ -483,6 +483,47 @@ int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const doub
                       double *const *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta, int nscales,
                       double zfactor, int warps, double epsilon);
 
+/* The same solve over a DEVICE-RESIDENT SEQUENCE of frames: the counterparts of the *_group_dev / *_batch_dev entries of the
+ * other solvers, with the sequence as the unit of work.  n_frames frames give n_frames - 2 triples, triple t =
+ * (F[t], F[t + 1], F[t + 2]), and each triple gets what ofx_tvl1occ_multiscale(F[t], F[t + 1], F[t + 2], filtI0 = F[t + 1])
+ * computes on those values -- the front-end's default when no smoothed image is given -- with its own stopping test and
+ * outer-iteration counts.
+ *   dF[k]     n_frames device pointers, nxx * nyy elements of the context's storage precision each (double for OFX_F64, float for
+ *             OFX_F32), aligned to that element.  They are converted exactly to double; arithmetic and internal storage stay
+ *             double, as ofx_tvl1occ_multiscale promises.
+ *   d_flo[t]  n_frames - 2 device pointers: the .flo payload, nxx * nyy interleaved (u1, u2) float32, bit-identical to (float) of
+ *             the lone entry's u1, u2.  Stored as float2 like every payload of the library: 8-byte aligned.
+ *   d_occ[t]  n_frames - 2 device pointers: nxx * nyy bytes, 255 where the thresholded chi is 1, else 0 -- the bytes tvl1occflow
+ *             writes as its occlusion map.  No alignment needed.
+ * What is shared: no normalisation is applied to the images (the reference overwrites it, tvl1occflow.cpp:382-395), so the
+ * presmoothed pyramid of a frame and its centred gradients depend on that frame alone.  A group keeps every frame once per level
+ * and the three roles a frame plays in consecutive triples (I1, then I0 and filtI0, then I_1) are views into that array; the
+ * pyramid, the gradients, the zoom-in of (u1, u2, chi) and the results take one launch per stage for the whole group.
+ * ofx_tvl1occ_sequence_group_dev: one lockstep group, n_frames in 3 .. 18.  stats_out: NULL or n_frames - 2 records (level sizes,
+ * iters[scale][warp], error, work_pix_iters, total_ms as ofx_tvl1occ_multiscale fills them).  Asynchronous on the context's stream
+ * like the other *_group_dev entries: the stopping tests are resolved on return, the results are complete once the stream is
+ * synchronised.
+ * ofx_tvl1occ_sequence_dev: any n_frames >= 3 on one or several contexts of ONE device and one precision.  The triples are cut
+ * into groups of G consecutive triples, group q = frames q G .. q G + cnt + 1 on ctxs[q % n_ctx], a worker thread per context; the
+ * two frames neighbouring groups share are built by both.  G = the smallest of: option "lockstep" of ctxs[0] if positive; 16; what
+ * the memory rule allows; ceil(triples / n_ctx).  The memory rule is ofx_tvl1occ_batch's for this layout, under option
+ * "mem_budget" (default: half of the free device memory), divided by n_ctx: a group of G triples takes, in doubles, G + 2 frames
+ * and 3 G result planes per pyramid level, 2 (G + 2) + 27 G full-size planes and 13 G hyperplane-major ones, plus 5 %; if one
+ * triple does not fit: OFX_ERR_NOMEM.  work_pix_iters: NULL or one double per triple.  Returns when every payload is complete.
+ * Errors, all found before any work (no byte of d_flo / d_occ is written): everything ofx_tvl1occ_multiscale rejects (sizes,
+ * nscales, warps, zfactor, theta, lambda, a coarsest level below 2x2), a pyramid that cannot be built (OFX_ERR_SIGMA: a level too
+ * small for its Gaussian), n_frames < 3, n_frames > 18 for the group entry, a NULL array, a NULL or misaligned pointer at index k,
+ * contexts on different devices or of different precision.
+ * Not provided: device-resident triples that are not consecutive frames of one sequence, and a separate filtI0 -- use the host
+ * entries above for those. */
+int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                                   void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
+                                   double theta, int nscales, double zfactor, int warps, double epsilon,
+                                   ofx_stats *stats_out);
+int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                             void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
+                             int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters);
+
 #ifdef __cplusplus
 }
 #endif

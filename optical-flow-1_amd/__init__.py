@@ -144,6 +144,10 @@ def lib():
         "ofx_solver_wrt_chi": (_i, [_vp] + [_dp] * 14 + [_d] * 6 + [_i, _i, _dp, _dp, _i]),
         "ofx_tvl1occ_multiscale": (_i, [_vp] + [_dp] * 7 + [_i, _i, _d, _d, _d, _d, _i, _d, _i, _d, _i]),
         "ofx_tvl1occ_batch": (_i, [_vp, _i, _i] + [_vp] * 7 + [_i, _i, _d, _d, _d, _d, _i, _d, _i, _d]),
+        "ofx_tvl1occ_sequence_group_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _d, _d, _i, _d,
+                                                _i, _d, C.POINTER(Stats)]),
+        "ofx_tvl1occ_sequence_dev": (_i, [C.POINTER(_vp), _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _d,
+                                          _d, _i, _d, _i, _d, C.POINTER(_d)]),
         "ofx_hs_classic": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _d]),
         "ofx_brox_temporal": (_i, [_vp, _dp, _dp, _dp, _i, _i, _i, _d, _d, _i, _d, _d, _i, _i, _i]),
     }
@@ -228,6 +232,22 @@ def tvl1occ_batch(ctxs, triples, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nsc
     if s:
         raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
     return list(zip(*outs))
+
+
+def tvl1occ_sequence_dev(ctxs, dF, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3, zfactor=0.5, warps=2,
+                         epsilon=0.01):
+    """ofx_tvl1occ_sequence_dev: dF = device pointers (ints) of the frames of a sequence, in the contexts' storage type; d_flo,
+    d_occ = device pointers of the len(dF) - 2 .flo payloads (float32 pairs) and occlusion maps (bytes, 0 | 255), triple t =
+    frames t, t + 1, t + 2.  Lockstep groups of consecutive triples, group q on ctxs[q % len(ctxs)]; returns when every result
+    is complete, with the per-triple work (pixel-iterations)."""
+    n = len(dF)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n - 2, 1))()
+    s = lib().ofx_tvl1occ_sequence_dev(arr([c.h.value for c in ctxs]), len(ctxs), n, arr(dF), arr(d_flo), arr(d_occ), nx, ny, lam,
+                                       alpha, beta, theta, nscales, zfactor, warps, epsilon, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(max(n - 2, 0))]
 
 
 def tvl1_batch_group_size(ctxs, n_pairs, nx, ny, nscales=5, zfactor=0.5):
@@ -615,6 +635,17 @@ class Ofx:
         self._ck(self.L.ofx_tvl1occ_multiscale(self.h, _f64(I_1), _f64(I0), _f64(I1), _f64(filtI0), u1, u2, chi, nx, ny, lam, alpha,
                                                beta, theta, nscales, zfactor, warps, epsilon, verbose))
         return u1, u2, chi
+
+    def tvl1occ_sequence_group_dev(self, dF, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3, zfactor=0.5,
+                                   warps=2, epsilon=0.01):
+        """ofx_tvl1occ_sequence_group_dev: the len(dF) - 2 triples of 3..18 device-resident frames in lockstep on this context
+        (pointer lists as tvl1occ_sequence_dev).  Enqueues on the context's stream; returns the per-triple Stats records."""
+        n = len(dF)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n - 2, 1))()
+        self._ck(self.L.ofx_tvl1occ_sequence_group_dev(self.h, n, arr(dF), arr(d_flo), arr(d_occ), nx, ny, lam, alpha, beta, theta,
+                                                       nscales, zfactor, warps, epsilon, st))
+        return [st[i] for i in range(max(n - 2, 0))]
 
     def occ_solver_u(self, v1, v2, chi, g, theta, beta, p=None, n_iter=10):
         """Solver_wrt_u with the four dual planes as explicit state -> (u1, u2, [p11, p12, p21, p22]); p defaults to zero"""

@@ -1395,11 +1395,11 @@ struct OccParams {
 // work planes of a group of G solves, allocated once at the finest level's size; a level uses them as [G][nx ny] /
 // [G][rof_skew_elems()]
 struct OccWork {
-    double *I1x, *I1y, *I_1x, *I_1y, *I1wx, *I1wy, *I_1wx, *I_1wy, *rho1_c, *rho3_c, *grad1, *grad3, *v1, *v2, *vf1, *vf2, *vb1,
+    double *I1wx, *I1wy, *I_1wx, *I_1wy, *rho1_c, *rho3_c, *grad1, *grad3, *v1, *v2, *vf1, *vf2, *vb1,
         *vb2, *g, *u1p, *u2p, *f1, *f2, *t1, *t2, *divu, *state, *eta, *rof, *part, *chi_alt;
     int alloc(ofx_ctx *ctx, size_t n, size_t nskew, int G)
     {
-        double **planes[] = {&I1x, &I1y, &I_1x, &I_1y, &I1wx, &I1wy, &I_1wx, &I_1wy, &rho1_c, &rho3_c, &grad1, &grad3, &v1,
+        double **planes[] = {&I1wx, &I1wy, &I_1wx, &I_1wy, &rho1_c, &rho3_c, &grad1, &grad3, &v1,
                              &v2, &vf1, &vf2, &vb1, &vb2, &g, &u1p, &u2p, &f1, &f2, &t1, &t2, &divu};
         for (auto p : planes) OFX_TRY(ofx_alloc(ctx, n * G, p));
         OFX_TRY(ofx_alloc(ctx, 4 * nskew * G, &state));      // dual planes of Solver_wrt_u, hyperplane-major
@@ -1410,9 +1410,15 @@ struct OccWork {
     }
 };
 
+// centred gradients of the level's images, [G][nx ny] like the images: the caller computes them (a group of host triples plane by
+// plane, a sequence once per frame).  filtx / filty are only read before the level's first iteration: they may be W.t1 / W.t2.
+struct OccGrad {
+    const double *filtx, *filty, *I1x, *I1y, *I_1x, *I_1y;
+};
+
 // one level of G triples, arrays [G][nx ny] on the device, u1 / u2 / chi in place; the level's dual state is zeroed here.
 // stats[g]: the record of triple g.
-int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I0, const double *I1, const double *filtI0, double *u1,
+int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I0, const double *I1, const OccGrad &D, double *u1,
                          double *u2, double *chi, int nx, int ny, const OccParams &P, const OccWork &W, int scale, ofx_stats *stats)
 {
     const size_t n = (size_t) nx * ny;
@@ -1424,16 +1430,10 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     OFX_HIP(ctx, hipMemsetAsync(W.state, 0, 4 * nsk * G * sizeof(double), st));
     OFX_HIP(ctx, hipMemsetAsync(W.eta, 0, 2 * n * G * sizeof(double), st));
     double *eta1 = W.eta, *eta2 = W.eta + n * G;
-    for (int g = 0; g < G; g++) {                         // once per level: plane by plane
-        const size_t o = g * n;
-        OFX_TRY(op_centered_gradient<double>(ctx, filtI0 + o, W.t1 + o, W.t2 + o, nx, ny));
-        OFX_TRY(op_centered_gradient<double>(ctx, I1 + o, W.I1x + o, W.I1y + o, nx, ny));
-        OFX_TRY(op_centered_gradient<double>(ctx, I_1 + o, W.I_1x + o, W.I_1y + o, nx, ny));
-    }
-    hipLaunchKernelGGL(k_occ_g, dim3(occ_grid1d(n * G)), dim3(256), 0, st, (const double *) W.t1, (const double *) W.t2, W.g, n * G);
+    hipLaunchKernelGGL(k_occ_g, dim3(occ_grid1d(n * G)), dim3(256), 0, st, D.filtx, D.filty, W.g, n * G);
     OFX_HIP(ctx, hipMemcpyAsync(W.u1p, u1, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
     OFX_HIP(ctx, hipMemcpyAsync(W.u2p, u2, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
-    const OccPrep prep = {I0, I1, W.I1x, W.I1y, I_1, W.I_1x, W.I_1y, u1, u2, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.grad1, W.grad3,
+    const OccPrep prep = {I0, I1, D.I1x, D.I1y, I_1, D.I_1x, D.I_1y, u1, u2, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.grad1, W.grad3,
                           W.rho1_c, W.rho3_c};
     const OccV av = {u1, u2, chi, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.rho1_c, W.rho3_c, W.grad1, W.grad3,
                      W.v1, W.v2, W.vf1, W.vf2, W.vb1, W.vb2};
@@ -1520,6 +1520,8 @@ int occ_group_impl(ofx_ctx *ctx, int G, const double *const *I_1, const double *
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { S.nx[s] = nxs[s]; S.ny[s] = nys[s]; }
     }
     const size_t size = (size_t) nxx * nyy;
+    double *gr[4];                                          // centred gradients of I1 and I_1, a level uses them as [G][n_s]
+    for (int k = 0; k < 4; k++) OFX_TRY(ofx_alloc(ctx, size * G, &gr[k]));
     OccWork W;
     OFX_TRY(W.alloc(ctx, size, rof_skew_elems(nxx, nyy), G));
     struct Lv { double *im[4], *u1, *u2, *chi; };           // im: I_1, I0, I1, filtI0; every array [G][n_s]
@@ -1553,8 +1555,14 @@ int occ_group_impl(ofx_ctx *ctx, int G, const double *const *I_1, const double *
     }
     for (int s = nscales - 1; s >= 0; s--) {
         if (P.verbose && G == 1) fprintf(stderr, "Scale %d: %dx%d\n", s, nxs[s], nys[s]);
-        OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].im[0], lv[s].im[1], lv[s].im[2], lv[s].im[3], lv[s].u1, lv[s].u2, lv[s].chi, nxs[s],
-                                     nys[s], P, W, s, stats));
+        for (int g = 0; g < G; g++) {                       // once per level: plane by plane
+            const size_t o = (size_t) g * nxs[s] * nys[s];
+            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[3] + o, W.t1 + o, W.t2 + o, nxs[s], nys[s]));
+            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[2] + o, gr[0] + o, gr[1] + o, nxs[s], nys[s]));
+            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[0] + o, gr[2] + o, gr[3] + o, nxs[s], nys[s]));
+        }
+        OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].im[0], lv[s].im[1], lv[s].im[2], OccGrad{W.t1, W.t2, gr[0], gr[1], gr[2], gr[3]},
+                                     lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P, W, s, stats));
         if (s) {
             const double fx = (double) nxs[s - 1] / nxs[s], fy = (double) nys[s - 1] / nys[s];
             const size_t n = (size_t) nxs[s - 1] * nys[s - 1], nc = (size_t) nxs[s] * nys[s];
@@ -1622,7 +1630,7 @@ extern "C" int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples,
         OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
     }
     // group size: option "lockstep" of ctxs[0], else as many as fit.  Per triple: 7 planes per pyramid level (occ_group: 4 images,
-    // u1, u2, chi) + OccWork's 31 full-size row-major and 13 hyperplane-major planes + 2 of Gaussian / zoom scratch
+    // u1, u2, chi) + 31 full-size row-major (OccWork's 27, 4 of gradients) and 13 hyperplane-major planes + 2 of Gaussian / zoom scratch
     int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
     if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
     {
@@ -1659,6 +1667,243 @@ extern "C" int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples,
                 ctx->stats = st[0];
             }
             if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : th) t.join();
+    return status.load();
+}
+
+// ==== the same solve over a device-resident sequence (ofx_tvl1occ_sequence_group_dev / _dev) =====================================
+// Triple t of F frames is (F[t], F[t + 1], F[t + 2]) with filtI0 = F[t + 1].  No normalisation is applied (above), so the
+// presmoothed pyramid of a frame and its centred gradients depend on that frame alone: a level keeps the G + 2 frames of a
+// group of G consecutive triples ONCE, [G + 2][n_s], and their gradients likewise; the arrays of the triples are views at an
+// offset -- I_1 = base, I0 = filtI0 = base + n_s, I1 = base + 2 n_s, each again [G][n_s] with stride n_s, which is how the
+// iteration kernels address a group.  Every stage outside the level solver is one launch for all frames / triples.
+struct OccSeqIn {
+    const void *f[OCC_MAX_GROUP + 2];
+};
+struct OccSeqOut {
+    float2 *flo[OCC_MAX_GROUP];
+    unsigned char *occ[OCC_MAX_GROUP];
+};
+// the caller's frames, in their storage type, into the finest level (exact: float -> double); blockIdx.z = frame
+template <typename TIN> __global__ void k_occ_seq_in(OccSeqIn in, double *__restrict__ dst, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dst[(size_t) blockIdx.z * n + i] = ldw(static_cast<const TIN *>(in.f[blockIdx.z]) + i);
+}
+// Results of triple g = blockIdx.z: the .flo payload (float) u1, (float) u2 interleaved, and the map 255 (chi > THR_CHI) as
+// bytes.  A block serves 1024 pixels under two lane mappings.  Payload: pixel = 256 k + lane, k = 0 .. 3 -- a float2 per lane,
+// 512 contiguous bytes per wave and store.  Map: a lane owns one ALIGNED 32-bit word of the destination, i.e. the pixels
+// 4 w - a .. 4 w - a + 3 where a = address of the map mod 4 (the map needs no alignment); a word that lies wholly inside the
+// map is one store, the up to two words across its ends (n + a not a multiple of 4, a != 0) go out byte by byte.
+__global__ __launch_bounds__(256) void k_occ_seq_out(const double *__restrict__ u1, const double *__restrict__ u2,
+                                                     const double *__restrict__ chi, OccSeqOut out, int n)
+{
+    const size_t o = (size_t) blockIdx.z * n;
+    float2 *__restrict__ flo = out.flo[blockIdx.z];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i = (int) ((blockIdx.x * 4 + k) * 256 + threadIdx.x);
+        if (i < n) flo[i] = make_float2((float) u1[o + i], (float) u2[o + i]);
+    }
+    unsigned char *__restrict__ occ = out.occ[blockIdx.z];
+    const int a = (int) (reinterpret_cast<uintptr_t>(occ) & 3u);
+    const int i0 = 4 * (int) (blockIdx.x * 256 + threadIdx.x) - a;
+    if (i0 >= n) return;
+    unsigned char b[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i = i0 + k;
+        b[k] = (i >= 0 && i < n && chi[o + i] > OCC_THR_CHI) ? 255 : 0;
+    }
+    if (i0 >= 0 && i0 + 3 < n) {
+        *reinterpret_cast<unsigned *>(occ + i0) = (unsigned) b[0] | ((unsigned) b[1] << 8) | ((unsigned) b[2] << 16) | ((unsigned) b[3] << 24);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (i0 + k >= 0 && i0 + k < n) occ[i0 + k] = b[k];
+    }
+}
+
+namespace {
+
+// what must hold before any work: the pyramid's sizes, its coarsest level, and room for both Gaussians on the levels they
+// smooth (op_gaussian's rule, which the host entries meet while they build the pyramid)
+int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor, std::vector<int> &nxs, std::vector<int> &nys)
+{
+    OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+    if (nxs[nscales - 1] < 2 || nys[nscales - 1] < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: coarsest level %dx%d", nxs[nscales - 1], nys[nscales - 1]);
+    for (int s = 0; s < nscales; s++) {
+        const double sigma = s ? 0.6 * sqrt(1.0 / (zfactor * zfactor) - 1.0) : OCC_PRESMOOTHING_SIGMA;     // smooths level s - 1 | 0
+        const int nx = nxs[s ? s - 1 : 0], ny = nys[s ? s - 1 : 0];
+        GaussTaps taps;
+        if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+            return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
+        if (taps.size >= nx || taps.size >= ny)
+            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    }
+    return OFX_OK;
+}
+
+// pointer arrays of a sequence of n_frames frames: no NULL, the frames aligned to their element, the payloads to a float2
+// (they are stored as such, like every .flo payload of the library); the maps need no alignment
+int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo, void *const *d_occ)
+{
+    if (!dF || !d_flo || !d_occ) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: NULL pointer");
+    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    for (int k = 0; k < n_frames; k++)
+        if (!dF[k] || reinterpret_cast<uintptr_t>(dF[k]) % el) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: frame %d NULL or misaligned", k);
+    for (int t = 0; t < n_frames - 2; t++)
+        if (!d_flo[t] || !d_occ[t] || reinterpret_cast<uintptr_t>(d_flo[t]) % sizeof(float2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: result pointer of triple %d NULL or misaligned", t);
+    return OFX_OK;
+}
+
+// G = n_frames - 2 triples in lockstep; sizes checked by the caller
+template <typename TIN>
+int occ_seq_group_impl(ofx_ctx *ctx, int G, const void *const *dF, void *const *d_flo, void *const *d_occ, const OccParams &P,
+                       int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys, ofx_stats *stats)
+{
+    const int F = G + 2, nxx = nxs[0], nyy = nys[0];
+    for (int g = 0; g < G; g++) {
+        ofx_stats &S = stats[g];
+        S = ofx_stats{};
+        S.nscales = nscales;
+        S.nsolves = P.warps;
+        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { S.nx[s] = nxs[s]; S.ny[s] = nys[s]; }
+    }
+    const size_t size = (size_t) nxx * nyy;
+    OccWork W;
+    OFX_TRY(W.alloc(ctx, size, rof_skew_elems(nxx, nyy), G));
+    double *gx, *gy;                                        // centred gradients of the level's frames, [F][n_s]; before the first
+    OFX_TRY(ofx_alloc(ctx, size * F, &gx));                 // level is solved: the scratch of the Gaussian and the zoom-out
+    OFX_TRY(ofx_alloc(ctx, size * F, &gy));
+    struct Lv { double *fr, *u1, *u2, *chi; };              // fr: [F][n_s], the others [G][n_s]
+    std::vector<Lv> lv(nscales);
+    for (int s = 0; s < nscales; s++) {
+        const size_t n = (size_t) nxs[s] * nys[s];
+        OFX_TRY(ofx_alloc(ctx, n * F, &lv[s].fr));
+        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u1));
+        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u2));
+        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].chi));
+    }
+    hipStream_t st = ctx->stream;
+    OccSeqIn in = {};
+    for (int k = 0; k < F; k++) in.f[k] = dF[k];
+    hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, F), dim3(256), 0, st, in, lv[0].fr, (int) size);
+    OFX_LAUNCH_CHECK(ctx);
+    OFX_TRY(op_gaussian_planes<double>(ctx, F, F, lv[0].fr, nullptr, size, gx, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
+    for (int s = 1; s < nscales; s++)
+        OFX_TRY(op_zoom_out_channels_planes<double>(ctx, F, F, lv[s - 1].fr, nullptr, lv[s].fr, nullptr, gx, gy, nxs[s - 1], nys[s - 1], 1, zfactor));
+    {
+        const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1] * G;
+        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u1, 0, n * sizeof(double), st));
+        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u2, 0, n * sizeof(double), st));
+        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].chi, 0, n * sizeof(double), st));
+    }
+    for (int s = nscales - 1; s >= 0; s--) {
+        const size_t n = (size_t) nxs[s] * nys[s];
+        OFX_TRY(op_centered_gradient_planes<double>(ctx, F, lv[s].fr, gx, gy, nxs[s], nys[s]));
+        const OccGrad D = {gx + n, gy + n, gx + 2 * n, gy + 2 * n, gx, gy};
+        OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr + n, lv[s].fr + 2 * n, D, lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P,
+                                     W, s, stats));
+        if (s)
+            OFX_TRY(op_zoom_in_planes3<double>(ctx, G, lv[s].u1, lv[s].u2, lv[s].chi, lv[s - 1].u1, lv[s - 1].u2, lv[s - 1].chi, nxs[s], nys[s],
+                                               nxs[s - 1], nys[s - 1], (double) 1.0 / zfactor));
+    }
+    OccSeqOut out = {};
+    for (int g = 0; g < G; g++) { out.flo[g] = static_cast<float2 *>(d_flo[g]); out.occ[g] = static_cast<unsigned char *>(d_occ[g]); }
+    hipLaunchKernelGGL(k_occ_seq_out, dim3(ofx_cdiv(ofx_cdiv((int) size + 3, 4), 256), 1, G), dim3(256), 0, st, (const double *) lv[0].u1,
+                       (const double *) lv[0].u2, (const double *) lv[0].chi, out, (int) size);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+}   // namespace
+
+extern "C" int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                                              void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
+                                              double theta, int nscales, double zfactor, int warps, double epsilon,
+                                              ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (n_frames < 3 || n_frames > OCC_MAX_GROUP + 2)
+        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: a lockstep group holds 3..%d frames (got %d)", OCC_MAX_GROUP + 2, n_frames);
+    OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
+    OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+    const int G = n_frames - 2;
+    const double t0 = ofx_now_ms();
+    std::vector<ofx_stats> local(stats_out ? 0 : G);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
+    const int s = ctx->precision == OFX_F64 ? occ_seq_group_impl<double>(ctx, G, dF, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
+                                            : occ_seq_group_impl<float>(ctx, G, dF, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
+    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < G; g++) st[g].total_ms = ms;
+    ctx->stats = st[0];
+    return s;
+}
+
+// Any number of frames: groups of G consecutive triples, group q = frames q G .. q G + cnt + 1 on context q mod n_ctx, a host
+// thread per context.  G: option "lockstep" of ctxs[0], at most 16, what the memory budget holds, and no more than evens the
+// groups out over the contexts.  Memory of a group, ofx_tvl1occ_batch's rule for this layout: per level G + 2 frames and 3 G of
+// (u1, u2, chi); full size 2 (G + 2) of gradients / scratch and OccWork's 27 G; 13 G hyperplane-major planes.
+extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                                        void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
+                                        double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
+{
+    if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
+    for (int w = 0; w < n_ctx; w++)
+        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision) return OFX_ERR_ARG;
+    int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
+    if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
+    {
+        ofx_ctx *ctx = ctxs[0];
+        OFX_ENTER(ctx);
+        if (n_frames < 3) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: %d frames (at least 3)", n_frames);
+        OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
+        OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
+        std::vector<int> nxs, nys;
+        OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+        size_t free_b = 0, total_b = 0;
+        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+        const double budget = (ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b) / n_ctx;
+        double level_px = 0.0;
+        for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
+        const double full = (double) nxx * nyy, skew = (double) rof_skew_elems(nxx, nyy), unit = 8.0 * 1.05;
+        const double fixed = unit * (2.0 * level_px + 4.0 * full), per = unit * (4.0 * level_px + 29.0 * full + 13.0 * skew);
+        const int fit = budget > fixed ? (int) fmin((budget - fixed) / per, (double) OCC_MAX_GROUP) : 0;
+        if (fit < 1)
+            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ sequence: %.2f GB for one triple, %.2f GB per context available", (fixed + per) / 1e9, budget / 1e9);
+        if (G > fit) G = fit;
+    }
+    const int n_triples = n_frames - 2;
+    const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
+    if (G > per_ctx) G = per_ctx;
+    const int n_groups = (n_triples + G - 1) / G;
+    std::atomic<int> status(OFX_OK);
+    auto worker = [&](int w) {
+        std::vector<ofx_stats> st(G);
+        for (int q = w; q < n_groups; q += n_ctx) {
+            if (status.load() != OFX_OK) return;
+            const int first = q * G, cnt = (n_triples - first < G) ? n_triples - first : G;
+            int s = ofx_tvl1occ_sequence_group_dev(ctxs[w], cnt + 2, dF + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta,
+                                                   theta, nscales, zfactor, warps, epsilon, st.data());
+            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
+            if (work_pix_iters)
+                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
+        }
+        if (hipStreamSynchronize(ctxs[w]->stream) != hipSuccess) {
+            int expected = OFX_OK;
+            status.compare_exchange_strong(expected, ofx_fail(ctxs[w], OFX_ERR_HIP, "hipStreamSynchronize failed"));
         }
     };
     std::vector<std::thread> th;

@@ -48,19 +48,31 @@ template <typename T> int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA
 // tmpA, tmpB are nx*ny*nz scratch images; OFX_ERR_SIGMA under zoom_out's rule, before anything is launched
 template <typename T> int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz,
                                                double factor);
-// the same for the 2 G images of a lockstep group, one launch per stage: A / B = the G first / second images back to back
-// (nx*ny*nz elements each), oA / oB the results likewise, tmpA / tmpB scratch for 2 G images
+// the same for `count` images (at most 2 * OFX_MAX_GROUP), one launch per stage: images 0 .. split - 1 back to back at A (nx*ny*nz
+// elements each), the others at B, the results likewise at oA / oB, tmpA / tmpB scratch for count images
+template <typename T> int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, const T *B, T *oA, T *oB,
+                                                      T *tmpA, T *tmpB, int nx, int ny, int nz, double factor);
+// ... for the 2 G images of a lockstep group of pairs: A / B = the G first / second images
 template <typename T> int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB,
                                                      int nx, int ny, int nz, double factor);
-// op_gaussian on the first nx*ny elements of 2 G images, one launch per pass: image g of A / B lies `stride` elements after
-// image g - 1, tmp holds 2 G planes of nx*ny
+// op_gaussian on the first nx*ny elements of `count` images, one launch per pass: images 0 .. split - 1 start at A, the others at
+// B, each `stride` elements after the one before; tmp holds count planes of nx*ny
+template <typename T> int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny,
+                                             double sigma, int dirichlet = 0);
+// ... for the 2 G images of a lockstep group of pairs
 template <typename T> int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma,
                                             int dirichlet = 0);
+// zoom_in (op_resample with per-axis factors) of the G planes of u1, u2 and c in one launch, u1 and u2 then `*= scale`
+// (src/tvl1occflow.cpp:466-475): planes back to back, nx*ny in, nxx*nyy out
+template <typename T> int op_zoom_in_planes3(ofx_ctx *ctx, int G, const T *u1, const T *u2, const T *c, T *u1o, T *u2o, T *co, int nx,
+                                             int ny, int nxx, int nyy, double scale);
 
 // planar operators for the operator-level API
 template <typename T> int op_divergence(ofx_ctx *ctx, const T *v1, const T *v2, T *div, int nx, int ny);
 template <typename T> int op_forward_gradient(ofx_ctx *ctx, const T *f, T *fx, T *fy, int nx, int ny);
 template <typename T> int op_centered_gradient(ofx_ctx *ctx, const T *f, T *dx, T *dy, int nx, int ny);
+// ... of `count` planes back to back (f, dx, dy alike) in one launch
+template <typename T> int op_centered_gradient_planes(ofx_ctx *ctx, int count, const T *f, T *dx, T *dy, int nx, int ny);
 template <typename T> int op_second_derivative(ofx_ctx *ctx, const T *f, T *out, int nx, int ny, int which);
 template <typename T> int op_bicubic_warp(ofx_ctx *ctx, const T *in, const T *u, const T *v, T *out, int nx,
                                           int ny, int border_out);

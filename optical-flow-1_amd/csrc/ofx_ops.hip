@@ -470,13 +470,14 @@ template <typename T> int op_gaussian(ofx_ctx *ctx, T *I, T *tmp, int nx, int ny
     return OFX_OK;
 }
 
-// op_gaussian on the first nx * ny elements of the 2 G images of a lockstep group, one launch per pass (blockIdx.z = image):
-// image g of A / B starts `stride` elements after image g - 1; tmp holds 2 G planes of nx * ny.  Per pixel k_gauss_pass.
+// op_gaussian on the first nx * ny elements of `count` images, one launch per pass (blockIdx.z = image): images 0 .. split - 1
+// start at A, the others at B, each `stride` elements after the one before; tmp holds count planes of nx * ny.  Per pixel
+// k_gauss_pass.
 template <typename T>
-int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
+int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
 {
     GaussTaps taps;
-    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: group of %d", G);
+    if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: %d planes (%d first)", count, split);
     if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
         return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
     taps.dirichlet = dirichlet != 0;
@@ -484,14 +485,21 @@ int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, in
         return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
     const size_t n = (size_t) nx * ny;
     dim3 g = grid2d(nx, ny);
-    g.z = 2 * G;
-    hipLaunchKernelGGL((k_gauss_pass_g<T, true>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, G, stride},
-                       OfxPlanes2<T>{tmp, tmp + (size_t) G * n, G, n}, nx, ny, taps);
+    g.z = count;
+    hipLaunchKernelGGL((k_gauss_pass_g<T, true>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, split, stride},
+                       OfxPlanes2<T>{tmp, tmp + (size_t) split * n, split, n}, nx, ny, taps);
     OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmp, tmp + (size_t) G * n, G, n},
-                       OfxPlanes2<T>{A, B, G, stride}, nx, ny, taps);
+    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmp, tmp + (size_t) split * n, split, n},
+                       OfxPlanes2<T>{A, B, split, stride}, nx, ny, taps);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
+}
+// the 2 G images of a lockstep group of pairs: A / B = the G first / second images
+template <typename T>
+int op_gaussian_group(ofx_ctx *ctx, int G, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
+{
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: group of %d", G);
+    return op_gaussian_planes<T>(ctx, 2 * G, G, A, B, stride, tmp, nx, ny, sigma, dirichlet);
 }
 
 // ---- bicubic resampling: zoom_out / zoom_in (src/zoom.cpp:41-78,132-155) ---------------------------
@@ -546,6 +554,29 @@ __global__ void k_zoom_in_flow(const typename Pix<T>::v2 *__restrict__ U, typena
     stn2(Uout + (size_t) i1 * nxx + j1, r);
 }
 
+// zoom_in of the G planes of each of three arrays in one launch (blockIdx.z = array x plane), the first two arrays -- a flow --
+// multiplied by `scale` afterwards: per plane resample_px, then the product the separate `*= scale` pass would store
+template <typename T> struct OfxPlanes3 {
+    T *p[3];
+};
+template <typename T>
+__global__ void k_zoom_in_planes3(OfxPlanes3<const T> in, OfxPlanes3<T> out, int G, int nx, int ny, int nxx, int nyy, double fx,
+                                  double fy, double scale)
+{
+    const int j1 = blockIdx.x * BX + threadIdx.x;
+    const int i1 = blockIdx.y * BY + threadIdx.y;
+    if (j1 >= nxx || i1 >= nyy) return;
+    const int a = blockIdx.z / G, g = blockIdx.z - a * G;
+    const T *__restrict__ src = in.p[a] + (size_t) g * nx * ny;
+    T *__restrict__ dst = out.p[a] + (size_t) g * nxx * nyy;
+    const double i2 = i1 / fy, j2 = j1 / fx;
+    const BicubicTaps t = bicubic_taps(j2, i2, nx, ny);
+    double v = bicubic_sample(src, t, nx);
+    if (sizeof(T) == sizeof(float)) v = (double) (float) v;         // the value the resample pass stores
+    if (a < 2) v *= scale;
+    stn(dst + (size_t) i1 * nxx + j1, v);
+}
+
 template <typename T>
 int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx, int ny, int nxx, int nyy, double fx, double fy)
 {
@@ -562,6 +593,20 @@ int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, typename Pix<T>:
     dim3 g = grid2d(nxx, nyy);
     g.z = G;
     hipLaunchKernelGGL(k_zoom_in_flow<T>, g, block2d(), 0, ctx->stream, U, Uout, nx, ny, nxx, nyy, fx, fy, scale);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+template <typename T>
+int op_zoom_in_planes3(ofx_ctx *ctx, int G, const T *u1, const T *u2, const T *c, T *u1o, T *u2o, T *co, int nx, int ny, int nxx,
+                       int nyy, double scale)
+{
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_in: group of %d", G);
+    const double fx = ((double) nxx / nx), fy = ((double) nyy / ny);     // zoom.cpp:141-142
+    dim3 g = grid2d(nxx, nyy);
+    g.z = 3 * G;
+    hipLaunchKernelGGL(k_zoom_in_planes3<T>, g, block2d(), 0, ctx->stream, OfxPlanes3<const T>{{u1, u2, c}}, OfxPlanes3<T>{{u1o, u2o, co}},
+                       G, nx, ny, nxx, nyy, fx, fy, scale);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -662,19 +707,20 @@ int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, in
     return OFX_OK;
 }
 
-// op_zoom_out_channels for the 2 G images of a lockstep group, one launch per stage (blockIdx.z = image; the counterpart of
-// op_build_pyramid_group for interleaved channels): A / B hold the G first / second images back to back, nx * ny * nz elements
-// each, oA / oB the zoomed ones likewise; tmpA, tmpB are scratch for 2 G images of nx * ny * nz.  Every image is computed by
-// the single-image path's per-pixel code.
+// op_zoom_out_channels for `count` images, one launch per stage (blockIdx.z = image; the counterpart of op_build_pyramid_group
+// for interleaved channels): images 0 .. split - 1 lie back to back at A, the others at B, nx * ny * nz elements each, the
+// zoomed ones likewise at oA / oB; tmpA, tmpB are scratch for count images of nx * ny * nz.  Every image is computed by the
+// single-image path's per-pixel code.
 template <typename T>
-int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB, int nx, int ny, int nz,
-                               double factor)
+int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB, int nx,
+                                int ny, int nz, double factor)
 {
     int nxx, nyy;
     ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
     const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.h:21,66
     GaussTaps taps;
-    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: group of %d", G);
+    if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count)
+        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %d images (%d first)", count, split);
     if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
     if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
         return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
@@ -682,19 +728,27 @@ int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *o
         return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
     const size_t st = (size_t) nx * ny * nz, sto = (size_t) nxx * nyy * nz;
     dim3 g = grid2d(nx * nz, ny);
-    g.z = 2 * G;
-    hipLaunchKernelGGL(k_gauss_row_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, G, st},
-                       OfxPlanes2<T>{tmpA, tmpA + (size_t) G * st, G, st}, nx, ny, nz, taps);
+    g.z = count;
+    hipLaunchKernelGGL(k_gauss_row_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{A, B, split, st},
+                       OfxPlanes2<T>{tmpA, tmpA + (size_t) split * st, split, st}, nx, ny, nz, taps);
     OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpA, tmpA + (size_t) G * st, G, st},
-                       OfxPlanes2<T>{tmpB, tmpB + (size_t) G * st, G, st}, nx * nz, ny, taps);
+    hipLaunchKernelGGL((k_gauss_pass_g<T, false>), g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpA, tmpA + (size_t) split * st, split, st},
+                       OfxPlanes2<T>{tmpB, tmpB + (size_t) split * st, split, st}, nx * nz, ny, taps);
     OFX_LAUNCH_CHECK(ctx);
     g = grid2d(nxx, nyy);
-    g.z = 2 * G;
-    hipLaunchKernelGGL(k_resample_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpB, tmpB + (size_t) G * st, G, st},
-                       OfxPlanes2<T>{oA, oB, G, sto}, nx, ny, nz, nxx, nyy, factor);
+    g.z = count;
+    hipLaunchKernelGGL(k_resample_ch_g<T>, g, block2d(), 0, ctx->stream, OfxPlanes2<const T>{tmpB, tmpB + (size_t) split * st, split, st},
+                       OfxPlanes2<T>{oA, oB, split, sto}, nx, ny, nz, nxx, nyy, factor);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
+}
+// the 2 G images of a lockstep group of pairs: A / B = the G first / second images
+template <typename T>
+int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB, int nx, int ny, int nz,
+                               double factor)
+{
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: group of %d", G);
+    return op_zoom_out_channels_planes<T>(ctx, 2 * G, G, A, B, oA, oB, tmpA, tmpB, nx, ny, nz, factor);
 }
 
 // ---- planar stencil operators (operator-level API) --------------------------------------------------
@@ -726,7 +780,7 @@ __global__ void k_forward_gradient(const T *__restrict__ f, T *__restrict__ fx, 
 
 // src/operators.cpp:335-406 (nz = 1): the missing neighbour at a border is the pixel itself, factor 1/2 kept
 template <typename T>
-__global__ void k_centered_gradient(const T *__restrict__ f, T *__restrict__ dx, T *__restrict__ dy, int nx, int ny)
+OFX_DEV void centered_gradient_px(const T *__restrict__ f, T *__restrict__ dx, T *__restrict__ dy, int nx, int ny)
 {
     const int j = blockIdx.x * BX + threadIdx.x;
     const int i = blockIdx.y * BY + threadIdx.y;
@@ -736,6 +790,18 @@ __global__ void k_centered_gradient(const T *__restrict__ f, T *__restrict__ dx,
     const size_t p = (size_t) i * nx + j;
     stn(dx + p, 0.5 * (ldw(f + (size_t) i * nx + jr) - ldw(f + (size_t) i * nx + jl)));
     stn(dy + p, 0.5 * (ldw(f + (size_t) id * nx + j) - ldw(f + (size_t) iu * nx + j)));
+}
+template <typename T>
+__global__ void k_centered_gradient(const T *__restrict__ f, T *__restrict__ dx, T *__restrict__ dy, int nx, int ny)
+{
+    centered_gradient_px<T>(f, dx, dy, nx, ny);
+}
+// planes back to back in all three arrays (blockIdx.z = plane)
+template <typename T>
+__global__ void k_centered_gradient_g(const T *__restrict__ f, T *__restrict__ dx, T *__restrict__ dy, int nx, int ny)
+{
+    const size_t o = (size_t) blockIdx.z * nx * ny;
+    centered_gradient_px<T>(f + o, dx + o, dy + o, nx, ny);
 }
 
 // Dxx / Dyy / Dxy = mask3x3 (src/operators.cpp:132-328) specialised to the three fixed masks.  Taps
@@ -847,6 +913,15 @@ template <typename T> int op_forward_gradient(ofx_ctx *ctx, const T *f, T *fx, T
 template <typename T> int op_centered_gradient(ofx_ctx *ctx, const T *f, T *dx, T *dy, int nx, int ny)
 {
     hipLaunchKernelGGL(k_centered_gradient<T>, grid2d(nx, ny), block2d(), 0, ctx->stream, f, dx, dy, nx, ny);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+template <typename T> int op_centered_gradient_planes(ofx_ctx *ctx, int count, const T *f, T *dx, T *dy, int nx, int ny)
+{
+    if (count < 1 || count > 2 * OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "centered_gradient: %d planes", count);
+    dim3 g = grid2d(nx, ny);
+    g.z = count;
+    hipLaunchKernelGGL(k_centered_gradient_g<T>, g, block2d(), 0, ctx->stream, f, dx, dy, nx, ny);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -1108,6 +1183,10 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
     template int op_resample<T>(ofx_ctx *, const T *, T *, int, int, int, int, double, double);                       \
     template int op_zoom_in_flow<T>(ofx_ctx *, const Pix<T>::v2 *, Pix<T>::v2 *, int, int, int, int, double, int);    \
     template int op_gaussian_group<T>(ofx_ctx *, int, T *, T *, size_t, T *, int, int, double, int);                   \
+    template int op_gaussian_planes<T>(ofx_ctx *, int, int, T *, T *, size_t, T *, int, int, double, int);             \
+    template int op_zoom_out_channels_planes<T>(ofx_ctx *, int, int, const T *, const T *, T *, T *, T *, T *, int, int, int, double); \
+    template int op_zoom_in_planes3<T>(ofx_ctx *, int, const T *, const T *, const T *, T *, T *, T *, int, int, int, int, double); \
+    template int op_centered_gradient_planes<T>(ofx_ctx *, int, const T *, T *, T *, int, int);                        \
     template int op_zoom_out_channels_group<T>(ofx_ctx *, int, const T *, const T *, T *, T *, T *, T *, int, int, int, double); \
     template int op_zoom_out<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, double);                               \
     template int op_zoom_out_channels<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, int, double);                 \

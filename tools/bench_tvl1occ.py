@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """TV-L1 with occlusions, whole solve: GPU (ofx_tvl1occ_multiscale) against the CPU reference / oracle on one triple.
-    python tools/bench_tvl1occ.py [--size 640x480] [--cpu ref|oracle|none] [--check]
-One JSON line per size.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
+    python tools/bench_tvl1occ.py [--size 640x480] [--cpu ref|oracle|none] [--check] [--batch CTX:TRIPLES] [--sequence CTX:FRAMES]
+One JSON line per size.  --sequence: the frames of synth.sequence on the device through ofx_tvl1occ_sequence_dev against
+ofx_tvl1occ_batch on the same triples from host planes, in one process, both warmed, median of three.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
 import argparse
 import importlib
 import json
@@ -22,8 +23,12 @@ ap.add_argument("--cpu", default="ref")
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--warps", type=int, default=2)
 ap.add_argument("--batch", default="", help="contexts:triples, e.g. 4:8 -- also time a batch of independent triples")
+ap.add_argument("--sequence", default="", help="contexts:frames, e.g. 3:50 -- time the device-resident sequence entry against the host batch")
 ap.add_argument("--opt", action="append", default=[], help="name=value for every context (e.g. rof_pipe=0)")
 a = ap.parse_args()
+if a.sequence:
+    import torch                # torch brings its own HIP runtime and has to see the device before libofx.so does
+    torch.cuda.init()
 ctx = ofx.Ofx(0, ofx.F64)
 for o in a.opt:
     ctx.set_option(o.split("=")[0], float(o.split("=")[1]))
@@ -69,4 +74,43 @@ for size in a.size or ["320x240"]:
         ofx.tvl1occ_batch(ctxs, triples, out=res_b, **kw)
         bt = time.perf_counter() - t
         rec["batch"] = {"contexts": n_ctx, "triples": n_tr, "seconds": round(bt, 4), "s_per_triple": round(bt / n_tr, 4)}
+    if a.sequence:
+        n_ctx, n_fr = (int(v) for v in a.sequence.split(":"))
+        ctxs = [ofx.Ofx(0, ofx.F64) for _ in range(n_ctx)]
+        for c_ in ctxs:
+            for o in a.opt:
+                c_.set_option(o.split("=")[0], float(o.split("=")[1]))
+        frames = synth.sequence(nx, ny, n_fr, 1)
+        n_tr = n_fr - 2
+        dF = torch.from_numpy(frames).cuda()
+        d_flo = torch.zeros((n_tr, ny, nx, 2), dtype=torch.float32, device="cuda")
+        d_occ = torch.zeros((n_tr, ny, nx), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ptr = lambda t: [t[k].data_ptr() for k in range(t.shape[0])]
+        triples = [(frames[t], frames[t + 1], frames[t + 2]) for t in range(n_tr)]
+        run_seq = lambda: ofx.tvl1occ_sequence_dev(ctxs, ptr(dF), ptr(d_flo), ptr(d_occ), nx, ny, **kw)
+        run_seq()                                                                               # warm both paths on every context
+        res_b = ofx.tvl1occ_batch(ctxs, triples, **kw)
+        t_seq, t_host = [], []
+        for _ in range(3):                                                                      # interleaved
+            t = time.perf_counter()
+            run_seq()
+            t_seq.append(time.perf_counter() - t)
+            t = time.perf_counter()
+            ofx.tvl1occ_batch(ctxs, triples, out=res_b, **kw)
+            t_host.append(time.perf_counter() - t)
+        s_seq, s_host = sorted(t_seq)[1] / n_tr, sorted(t_host)[1] / n_tr
+        rec["sequence"] = {"contexts": n_ctx, "frames": n_fr, "triples": n_tr,
+                           "sequence_s_per_triple": round(s_seq, 5), "host_batch_s_per_triple": round(s_host, 5),
+                           "host_over_sequence": round(s_host / s_seq, 3),
+                           "sequence_s_repetitions": [round(x, 4) for x in t_seq], "host_batch_s_repetitions": [round(x, 4) for x in t_host]}
+        if a.check:
+            flo, occ = d_flo.cpu().numpy(), d_occ.cpu().numpy()
+            worst = 0.0
+            for t_ in (0, n_tr // 2, n_tr - 1):
+                u_, v_, c_ = ctx.tvl1occ_multiscale(*triples[t_], **kw)
+                worst = max(worst, float(np.abs(flo[t_, ..., 0] - u_.astype(np.float32)).max()),
+                            float(np.abs(flo[t_, ..., 1] - v_.astype(np.float32)).max()),
+                            float(np.abs(occ[t_].astype(np.float64) - 255 * c_).max()))
+            rec["sequence"]["max_abs_diff_vs_lone"] = worst
     print(json.dumps(rec), flush=True)
