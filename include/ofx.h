@@ -417,6 +417,37 @@ int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, double *v, int n
                       double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter,
                       int outer_iter, int verbose);
 
+/* The same solve on a device-resident sequence.  dF[k], k < frames: frame k, nxx * nyy elements of the context's storage type
+ * (double for OFX_F64, float for OFX_F32), aligned to the element; the frames need not be contiguous nor distinct (a still
+ * frame may be passed twice).  d_flo[f], f < frames - 1: the .flo payload of the flow from frame f to f + 1, nxx * nyy
+ * interleaved (u, v) float32 pairs, 8-byte aligned (stored as float2): bit for bit (float) of what ofx_brox_temporal returns on
+ * the same values.  3 <= frames <= OFX_BROXT_MAX_FRAMES (the frames reach the kernels through a by-value pointer table).
+ * Asynchronous on the context's stream: the stopping tests are resolved on return, the payloads are complete once the stream
+ * is synchronised.  ofx_get_stats is filled as by ofx_brox_temporal.
+ * Every error is found before any work and no byte of d_flo is written: what ofx_brox_temporal rejects (frames <= 2, images
+ * or a level below 3x3, negative iteration counts, OFX_ERR_SIGMA when a Gaussian of the pyramid does not fit its level), more
+ * than OFX_BROXT_MAX_FRAMES frames, a NULL array, a NULL or misaligned pointer (its index is in ofx_last_error). */
+#define OFX_BROXT_MAX_FRAMES 32
+int ofx_brox_temporal_dev(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy, double alpha,
+                          double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter);
+
+/* n_seq independent sequences of `frames` frames each: dF holds n_seq * frames pointers (sequence q at dF + q * frames), d_flo
+ * n_seq * (frames - 1) (sequence q at d_flo + q * (frames - 1)).  Sequence q is solved by ofx_brox_temporal_dev on
+ * ctxs[q % n_ctx], one worker thread and stream per context; the solves are independent (no lockstep).  All contexts on ONE
+ * device and of one precision; option "concurrency" of the contexts is raised to the number at work for the call.  Returns when
+ * every payload is complete, with the first failing status.  work_pix_iters: NULL or one double per sequence
+ * (ofx_stats.work_pix_iters of its solve).
+ * Memory: one sequence takes, in elements of the storage type per pixel of a pyramid level, `frames` (the level's images) +
+ * 27 (frames - 1) (the level's twelve work arrays: 3 scalar, 6 pair and 3 quadruple planes per flow field) + 2 B (frames - 1)
+ * (B snapshot planes of pairs, B = option "sor_batch" or 64), and 2 * frames full-size planes of pyramid scratch; plus 5 %.
+ * Under option "mem_budget" of ctxs[0] (default: half of the free device memory) only as many contexts work at once as
+ * sequences fit, sequence q then on ctxs[q % that number]; if not even one fits: OFX_ERR_NOMEM before any work.
+ * Errors as ofx_brox_temporal_dev, found for every sequence before any work, and: n_seq < 1, n_ctx < 1, a NULL context,
+ * contexts on different devices or of different precision. */
+int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int n_seq, int frames, const void *const *dF,
+                                void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
+                                double TOL, int inner_iter, int outer_iter, double *work_pix_iters);
+
 /* ---- colour operators (replace src/bicubic_interpolation.h:66-75, src/utils.h:39-96) -----------------*/
 /* bicubic_interpolation_warp_color: nz interleaved channels, every sample through bicubic_interpolation_at_color */
 int ofx_bicubic_warp_color(ofx_ctx *ctx, const double *input, const double *u, const double *v, double *output,

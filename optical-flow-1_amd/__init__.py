@@ -150,6 +150,9 @@ def lib():
                                           _d, _i, _d, _i, _d, C.POINTER(_d)]),
         "ofx_hs_classic": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _d]),
         "ofx_brox_temporal": (_i, [_vp, _dp, _dp, _dp, _i, _i, _i, _d, _d, _i, _d, _d, _i, _i, _i]),
+        "ofx_brox_temporal_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d, _i, _i]),
+        "ofx_brox_temporal_batch_dev": (_i, [C.POINTER(_vp), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d,
+                                             _i, _i, C.POINTER(_d)]),
     }
     L.ofx_missing = []
     for name, (res, args) in sig.items():
@@ -248,6 +251,21 @@ def tvl1occ_sequence_dev(ctxs, dF, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, b
     if s:
         raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
     return [work[i] for i in range(max(n - 2, 0))]
+
+
+def brox_temporal_batch_dev(ctxs, dF, d_flo, nx, ny, frames, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15):
+    """ofx_brox_temporal_batch_dev: dF = device pointers (ints) of the frames of len(dF) // frames independent sequences, one
+    after the other, in the contexts' storage type; d_flo = device pointers of their frames - 1 .flo payloads each (float32
+    pairs).  Sequence q is solved on ctxs[q % len(ctxs)]; returns when every payload is complete, with the per-sequence work
+    (pixel-sweeps)."""
+    n_seq = len(dF) // frames if frames > 0 else 0
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n_seq, 1))()
+    s = lib().ofx_brox_temporal_batch_dev(arr([c.h.value for c in ctxs]), len(ctxs), n_seq, frames, arr(dF), arr(d_flo), nx, ny,
+                                          alpha, gamma, nscales, nu, TOL, inner, outer, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(n_seq)]
 
 
 def tvl1_batch_group_size(ctxs, n_pairs, nx, ny, nscales=5, zfactor=0.5):
@@ -519,6 +537,14 @@ class Ofx:
         self._ck(self.L.ofx_brox_temporal(self.h, _f64(I), u, v, nx, ny, frames, alpha, gamma, nscales, nu, TOL, inner,
                                           outer, verbose))
         return u, v
+
+    def brox_temporal_dev(self, dF, d_flo, nx, ny, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15):
+        """ofx_brox_temporal_dev: dF = device pointers (ints) of the 3..32 frames of a sequence in the context's storage type,
+        d_flo = device pointers of the len(dF) - 1 .flo payloads (float32 pairs).  Enqueues on the context's stream; stats() is
+        brox_temporal's."""
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_brox_temporal_dev(self.h, len(dF), arr(dF), arr(d_flo), nx, ny, alpha, gamma, nscales, nu, TOL, inner,
+                                              outer))
 
     # ---- colour / sequence variants of the operator surface --------------------------------------------------
     def centered_gradient3(self, f):

@@ -3006,16 +3006,11 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
     const dim3 g = g2d(nx, ny), b = b2d(), g3(g.x, g.y, nz);
     const dim3 g1((unsigned) ((n1 + 255) / 256)), b1(256);
     int solve = 0;
-    for (int f = 0; f < nz; f++) {                                                                   // :346-355
-        hipLaunchKernelGGL(k_brox_prepare<T>, g, b, 0, ctx->stream, (const T *) (L.I + (size_t) f * n),
-                           (const T *) (L.I + (size_t) (f + 1) * n), L.G1 + (size_t) f * n, L.PA + (size_t) f * n,
-                           L.PB + (size_t) f * n, nx, ny);
-    }
+    // :346-355 for all flow fields at once (blockIdx.z = f): I1 = frame f, I2 = frame f + 1 of the frame-major level
+    hipLaunchKernelGGL(k_brox_prepare<T>, g3, b, 0, ctx->stream, (const T *) L.I, (const T *) (L.I + n), L.G1, L.PA, L.PB, nx, ny);
     OFX_LAUNCH_CHECK(ctx);
     for (int no = 0; no < P.outer_iter; no++) {                                                      // :358
-        for (int f = 0; f < nz; f++)                                                                 // :360-367
-            hipLaunchKernelGGL(k_brox_warp<T>, g, b, 0, ctx->stream, L.PA + (size_t) f * n, L.PB + (size_t) f * n,
-                               L.U + (size_t) f * n, L.WA + (size_t) f * n, L.WB + (size_t) f * n, nx, ny);
+        hipLaunchKernelGGL(k_brox_warp<T>, g3, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny);   // :360-367
         hipLaunchKernelGGL(k_broxt_psis<T>, g3, b, 0, ctx->stream, L.U, L.Psis, nx, ny, nz);          // :370-374
         hipLaunchKernelGGL(k_broxt_div<T>, g3, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, nz,
                            P.alpha);                                                                 // :377-390
@@ -3051,48 +3046,178 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
     return OFX_OK;
 }
 
-// src/brox_optic_flow_temporal.cpp:520-627
+// ---- the driver, src/brox_optic_flow_temporal.cpp:520-627, on a device-resident sequence ------------------------------------
+// Every stage outside the level solver is one launch for all frames / flow fields (the frame or field in blockIdx.z or .y) with
+// the single-image path's per-pixel code.  The caller's frames reach the head through a by-value pointer table of
+// OFX_BROXT_MAX_FRAMES entries; a longer sequence (the host entry takes any length) goes through in chunks of that many.
+struct BroxtFrames { const void *f[OFX_BROXT_MAX_FRAMES]; };
+struct BroxtFlos { float2 *flo[OFX_BROXT_MAX_FRAMES]; };
+#define BROXT_MM_BLOCKS 32                                        // partial minima / maxima per frame
+
+// getminmax over the frames of a chunk (exact, so the order is free): block (x, y) covers a stride of frame y and writes its
+// minimum / maximum to lo[y * BROXT_MM_BLOCKS + x] / hi[...]
 template <typename T>
-static int broxt_host(ofx_ctx *ctx, const double *I, double *u, double *v, int nx, int ny, int frames, const BroxParams &P,
-                      int nscales, double nu)
+__global__ __launch_bounds__(256) void k_broxt_mm_partial(BroxtFrames in, int n, double *__restrict__ lo_out, double *__restrict__ hi_out)
 {
+    const T *__restrict__ I = static_cast<const T *>(in.f[blockIdx.y]);
+    double lo = ldw(I), hi = lo;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += BROXT_MM_BLOCKS * 256) {
+        const double a = ldw(I + i);
+        lo = a < lo ? a : lo; hi = a > hi ? a : hi;
+    }
+    lo = wave_allreduce_min(lo);
+    hi = wave_allreduce_max(hi);
+    __shared__ double slo[4], shi[4];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
+        lo_out[blockIdx.y * BROXT_MM_BLOCKS + blockIdx.x] = lo;
+        hi_out[blockIdx.y * BROXT_MM_BLOCKS + blockIdx.x] = hi;
+    }
+}
+// one block: the `count` partial minima / maxima -> mm[0] = min, mm[1] = max
+__global__ __launch_bounds__(256) void k_broxt_mm_final(const double *__restrict__ lo_in, const double *__restrict__ hi_in, int count,
+                                                        double *__restrict__ mm)
+{
+    double lo = lo_in[0], hi = hi_in[0];
+    for (int i = threadIdx.x; i < count; i += 256) {
+        lo = lo_in[i] < lo ? lo_in[i] : lo;
+        hi = hi_in[i] > hi ? hi_in[i] : hi;
+    }
+    lo = wave_allreduce_min(lo);
+    hi = wave_allreduce_max(hi);
+    __shared__ double slo[4], shi[4];
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
+        mm[0] = lo;
+        mm[1] = hi;
+    }
+}
+// image_normalization_1 (src/utils.cpp): 255 (I - min) / den, a copy when den = 0 -- normalize2_px's arithmetic; frame
+// blockIdx.z of the chunk into the frame-major level
+template <typename T> __global__ void k_broxt_norm(BroxtFrames in, T *__restrict__ out, int n, const double *__restrict__ mm)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double lo = mm[0], den = mm[1] - mm[0];
+    const double a = ldw(static_cast<const T *>(in.f[blockIdx.z]) + i);
+    T *o = out + (size_t) blockIdx.z * n + i;
+    if (den > 0) stn(o, 255.0 * (a - lo) / den);
+    else stn(o, a);
+}
+// the .flo payloads of flow fields blockIdx.z of a chunk: (float) u, (float) v interleaved, as k_to_flo
+template <typename T> __global__ void k_broxt_out(const typename Pix<T>::v2 *__restrict__ U, BroxtFlos out, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double2 v = ldw2(U + (size_t) blockIdx.z * n + i);
+    out.flo[blockIdx.z][i] = make_float2((float) v.x, (float) v.y);
+}
+
+// What every temporal entry checks before any work, in the order in which the solve would meet it: the pyramid's sizes, the
+// presmoothing Gaussian on level 0 and the zoom Gaussian on every level that is zoomed out (op_gaussian's rule), the 3x3
+// minimum of the level solver and the index range.
+static int broxt_check(ofx_ctx *ctx, int frames, int nxx, int nyy, int nscales, double nu, int inner_iter, int outer_iter,
+                       std::vector<int> &nxs, std::vector<int> &nys)
+{
+    if (frames <= 2) return ofx_fail(ctx, OFX_ERR_ARG, "The method needs more than two frames");     // :537-541
+    if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: negative iteration count");
+    if (nxx < 3 || nyy < 3) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: images smaller than 3x3");
+    OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, nu, nxs, nys));
+    for (int pass = 0; pass < (nscales > 1 ? 2 : 1); pass++) {     // presmoothing: level 0; zoom-out: every level but the coarsest
+        const double sigma = pass ? 0.6 * sqrt(1.0 / (nu * nu) - 1.0) : BROX_SIGMA;
+        GaussTaps taps;
+        if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+            return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
+        for (int s = 0; s < (pass ? nscales - 1 : 1); s++)
+            if (taps.size >= nxs[s] || taps.size >= nys[s])
+                return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, scale %d is %dx%d)", taps.size, s,
+                                nxs[s], nys[s]);
+    }
+    for (int s = 0; s < nscales; s++)
+        if (nxs[s] < 3 || nys[s] < 3)
+            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: level %dx%d has no interior", nxs[s], nys[s]);
+    if ((long long) nxx * nyy * frames >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: sequence larger than 2^31 pixels");
+    return OFX_OK;
+}
+
+// The solve: dF = the frames on the device in storage type T; nxs, nys from broxt_check.  On success lv[0].U holds the
+// frames - 1 flows of the finest level and ctx->stats the record.
+template <typename T>
+static int broxt_sequence_dev(ofx_ctx *ctx, int frames, const void *const *dF, const BroxParams &P, int nscales, double nu,
+                              const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxtLevel<T>> &lv)
+{
+    const int nx = nxs[0], ny = nys[0], MF = OFX_BROXT_MAX_FRAMES;
     const size_t n = (size_t) nx * ny;
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, nu, nxs, nys));
     sor_stats_begin(ctx, nscales, P.inner_iter * P.outer_iter);
-    T *dI, *dummy, *tmpA, *tmpB;
-    double *scr;
-    OFX_TRY(upload_plane<T>(ctx, I, n * frames, &dI));
-    OFX_TRY(ofx_alloc(ctx, n * frames, &dummy));
-    OFX_TRY(ofx_alloc(ctx, n, &tmpA));
-    OFX_TRY(ofx_alloc(ctx, n, &tmpB));
-    OFX_TRY(ofx_alloc(ctx, op_pyramid_scratch_doubles(), &scr));
-    std::vector<BroxtLevel<T>> lv(nscales);
+    T *tmpA, *tmpB = nullptr;
+    double *mm;                                                  // [frames * BROXT_MM_BLOCKS] minima, the maxima, {min, max}
+    const int parts = frames * BROXT_MM_BLOCKS;
+    OFX_TRY(ofx_alloc(ctx, n * frames, &tmpA));
+    if (nscales > 1) OFX_TRY(ofx_alloc(ctx, n * frames, &tmpB));
+    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * parts + 2, &mm));
+    lv.resize(nscales);
     for (int s = 0; s < nscales; s++) {
         OFX_TRY(broxt_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], frames));
         if (s < OFX_MAX_SCALES) { ctx->stats.nx[s] = nxs[s]; ctx->stats.ny[s] = nys[s]; }
     }
-    // image_normalization_1 over the whole sequence (:548): the joint-min/max kernel of normalization_2 fed the
-    // sequence twice computes the same 255 (I - min) / den
-    OFX_TRY(op_normalize2<T>(ctx, dI, dI, lv[0].I, dummy, (int) (n * frames), scr));
-    for (int f = 0; f < frames; f++) OFX_TRY(op_gaussian<T>(ctx, lv[0].I + f * n, tmpA, nx, ny, BROX_SIGMA));     // :551-553
+    // image_normalization_1 over the whole sequence (:548)
+    for (int f0 = 0; f0 < frames; f0 += MF) {
+        const int cnt = frames - f0 < MF ? frames - f0 : MF;
+        BroxtFrames in = {};
+        for (int k = 0; k < cnt; k++) in.f[k] = dF[f0 + k];
+        hipLaunchKernelGGL(k_broxt_mm_partial<T>, dim3(BROXT_MM_BLOCKS, cnt), dim3(256), 0, ctx->stream, in, (int) n,
+                           mm + (size_t) f0 * BROXT_MM_BLOCKS, mm + parts + (size_t) f0 * BROXT_MM_BLOCKS);
+    }
+    hipLaunchKernelGGL(k_broxt_mm_final, dim3(1), dim3(256), 0, ctx->stream, (const double *) mm, (const double *) (mm + parts), parts,
+                       mm + 2 * parts);
+    OFX_LAUNCH_CHECK(ctx);
+    for (int f0 = 0; f0 < frames; f0 += MF) {
+        const int cnt = frames - f0 < MF ? frames - f0 : MF;
+        BroxtFrames in = {};
+        for (int k = 0; k < cnt; k++) in.f[k] = dF[f0 + k];
+        hipLaunchKernelGGL(k_broxt_norm<T>, dim3((unsigned) ((n + 255) / 256), 1, cnt), dim3(256), 0, ctx->stream, in, lv[0].I + f0 * n,
+                           (int) n, (const double *) (mm + 2 * parts));
+        OFX_LAUNCH_CHECK(ctx);
+        OFX_TRY(op_gaussian_planes<T>(ctx, cnt, cnt, lv[0].I + f0 * n, nullptr, n, tmpA, nx, ny, BROX_SIGMA));          // :551-553
+    }
     for (int s = 1; s < nscales; s++) {                                                              // :561-575
         const size_t np = (size_t) nxs[s - 1] * nys[s - 1], nc = (size_t) nxs[s] * nys[s];
-        for (int f = 0; f < frames; f++)
-            OFX_TRY(op_zoom_out<T>(ctx, lv[s - 1].I + f * np, lv[s].I + f * nc, tmpA, tmpB, nxs[s - 1], nys[s - 1], nu));
+        for (int f0 = 0; f0 < frames; f0 += MF) {
+            const int cnt = frames - f0 < MF ? frames - f0 : MF;
+            OFX_TRY(op_zoom_out_channels_planes<T>(ctx, cnt, cnt, lv[s - 1].I + f0 * np, nullptr, lv[s].I + f0 * nc, nullptr, tmpA, tmpB,
+                                                   nxs[s - 1], nys[s - 1], 1, nu));
+        }
     }
     BroxtLevel<T> &C = lv[nscales - 1];
     OFX_TRY(op_fill2<T>(ctx, C.U, (size_t) C.nx * C.ny * (frames - 1)));                             // :578-580
     for (int s = nscales - 1; s >= 0; s--) {                                                        // :587
         if (P.verbose) { printf("Scale: %d\n", s); fflush(stdout); }
         OFX_TRY(broxt_single_scale_dev<T>(ctx, lv[s], P, frames, s));
-        if (s) {
-            const size_t nc = (size_t) lv[s].nx * lv[s].ny, nf = (size_t) lv[s - 1].nx * lv[s - 1].ny;
-            for (int f = 0; f < frames - 1; f++)
-                OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U + f * nc, lv[s - 1].U + f * nf, lv[s].nx, lv[s].ny, lv[s - 1].nx,
-                                           lv[s - 1].ny, 1.0 / nu));                                 // :600-612
-        }
+        if (s)
+            OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U, lv[s - 1].U, lv[s].nx, lv[s].ny, lv[s - 1].nx, lv[s - 1].ny, 1.0 / nu,
+                                       frames - 1));                                                 // :600-612
     }
+    return OFX_OK;
+}
+
+// host planes: upload the frames in the storage type, the driver, download
+template <typename T>
+static int broxt_host(ofx_ctx *ctx, const double *I, double *u, double *v, int frames, const BroxParams &P, int nscales, double nu,
+                      const std::vector<int> &nxs, const std::vector<int> &nys)
+{
+    const size_t n = (size_t) nxs[0] * nys[0];
+    T *dI;
+    OFX_TRY(upload_plane<T>(ctx, I, n * frames, &dI));
+    std::vector<const void *> dF(frames);
+    for (int k = 0; k < frames; k++) dF[k] = dI + k * n;
+    std::vector<BroxtLevel<T>> lv;
+    OFX_TRY(broxt_sequence_dev<T>(ctx, frames, dF.data(), P, nscales, nu, nxs, nys, lv));
     return download_flow<T>(ctx, lv[0].U, u, v, n * (frames - 1));
 }
 
@@ -3102,15 +3227,111 @@ extern "C" int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, doubl
 {
     OFX_ENTER(ctx);
     if (!I || !u || !v) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: NULL pointer");
-    if (frames <= 2) return ofx_fail(ctx, OFX_ERR_ARG, "The method needs more than two frames");     // :537-541
-    if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: negative iteration count");
-    if (nxx < 3 || nyy < 3) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: images smaller than 3x3");
+    std::vector<int> nxs, nys;
+    OFX_TRY(broxt_check(ctx, frames, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
     const double t0 = ofx_now_ms();
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, verbose};
-    int s = ctx->precision == OFX_F64 ? broxt_host<double>(ctx, I, u, v, nxx, nyy, frames, P, nscales, nu)
-                                      : broxt_host<float>(ctx, I, u, v, nxx, nyy, frames, P, nscales, nu);
+    int s = ctx->precision == OFX_F64 ? broxt_host<double>(ctx, I, u, v, frames, P, nscales, nu, nxs, nys)
+                                      : broxt_host<float>(ctx, I, u, v, frames, P, nscales, nu, nxs, nys);
     ctx->stats.total_ms = ofx_now_ms() - t0;
     return s;
+}
+
+// the pointer tables of n_seq sequences: no NULL, the frames aligned to their element, the payloads to a float2
+static int broxt_check_ptrs(ofx_ctx *ctx, int n_seq, int frames, const void *const *dF, void *const *d_flo)
+{
+    if (!dF || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: NULL pointer array");
+    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    for (int k = 0; k < n_seq * frames; k++)
+        if (!dF[k] || reinterpret_cast<uintptr_t>(dF[k]) % el)
+            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: frame %d (sequence %d) NULL or misaligned", k % frames, k / frames);
+    for (int k = 0; k < n_seq * (frames - 1); k++)
+        if (!d_flo[k] || reinterpret_cast<uintptr_t>(d_flo[k]) % sizeof(float2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: payload pointer %d (sequence %d) NULL or misaligned", k % (frames - 1),
+                            k / (frames - 1));
+    return OFX_OK;
+}
+// everything the device entries refuse, for n_seq sequences
+static int broxt_dev_check(ofx_ctx *ctx, int n_seq, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy,
+                           int nscales, double nu, int inner_iter, int outer_iter, std::vector<int> &nxs, std::vector<int> &nys)
+{
+    OFX_TRY(broxt_check(ctx, frames, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
+    if (frames > OFX_BROXT_MAX_FRAMES)
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: %d frames (a device-resident sequence holds at most %d)", frames, OFX_BROXT_MAX_FRAMES);
+    return broxt_check_ptrs(ctx, n_seq, frames, dF, d_flo);
+}
+
+template <typename T>
+static int broxt_devapi(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, const BroxParams &P, int nscales, double nu,
+                        const std::vector<int> &nxs, const std::vector<int> &nys)
+{
+    std::vector<BroxtLevel<T>> lv;
+    OFX_TRY(broxt_sequence_dev<T>(ctx, frames, dF, P, nscales, nu, nxs, nys, lv));
+    const size_t n = (size_t) nxs[0] * nys[0];
+    BroxtFlos out = {};
+    for (int f = 0; f < frames - 1; f++) out.flo[f] = static_cast<float2 *>(d_flo[f]);
+    hipLaunchKernelGGL(k_broxt_out<T>, dim3((unsigned) ((n + 255) / 256), 1, frames - 1), dim3(256), 0, ctx->stream, lv[0].U, out, (int) n);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+static int broxt_dev_run(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, double alpha, double gamma, int nscales,
+                         double nu, double TOL, int inner_iter, int outer_iter, const std::vector<int> &nxs, const std::vector<int> &nys)
+{
+    const double t0 = ofx_now_ms();
+    const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
+    int s = ctx->precision == OFX_F64 ? broxt_devapi<double>(ctx, frames, dF, d_flo, P, nscales, nu, nxs, nys)
+                                      : broxt_devapi<float>(ctx, frames, dF, d_flo, P, nscales, nu, nxs, nys);
+    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // nothing in flight when the arena is reset
+    ctx->stats.total_ms = ofx_now_ms() - t0;
+    return s;
+}
+
+// ofx_brox_temporal on a device-resident sequence (include/ofx.h)
+extern "C" int ofx_brox_temporal_dev(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy,
+                                     double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter)
+{
+    OFX_ENTER(ctx);
+    std::vector<int> nxs, nys;
+    OFX_TRY(broxt_dev_check(ctx, 1, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
+    return broxt_dev_run(ctx, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys);
+}
+
+// n_seq independent sequences, sequence q on context q mod (contexts at work): sor_batch_run with groups of one (include/ofx.h)
+extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int n_seq, int frames, const void *const *dF,
+                                           void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
+                                           double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
+{
+    if (!ctxs || n_ctx < 1 || !ctxs[0]) return OFX_ERR_ARG;
+    ofx_ctx *ctx = ctxs[0];
+    OFX_ENTER(ctx);
+    for (int w = 0; w < n_ctx; w++)
+        if (!ctxs[w] || ctxs[w]->device != ctx->device || ctxs[w]->precision != ctx->precision)
+            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: context %d NULL, on another device or of another precision", w);
+    if (n_seq < 1) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: %d sequences", n_seq);
+    std::vector<int> nxs, nys;
+    OFX_TRY(broxt_dev_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
+    int n_use = n_ctx < n_seq ? n_ctx : n_seq;
+    {
+        size_t free_b = 0, total_b = 0;
+        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+        const double budget = ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b;
+        const double el = ctx->precision == OFX_F64 ? 8.0 : 4.0, B = ctx->sor_batch > 0 ? ctx->sor_batch : 64;
+        double level_px = 0.0;
+        for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
+        const double per = 1.05 * el * (level_px * (frames + (27.0 + 2.0 * B) * (frames - 1)) + 2.0 * frames * (double) nxx * nyy);
+        const double fit = budget / per;
+        if (fit < 1.0)
+            return ofx_fail(ctx, OFX_ERR_NOMEM, "brox temporal batch: %.3f GB for one sequence, %.3f GB available", per / 1e9, budget / 1e9);
+        if (fit < n_use) n_use = (int) fit;
+    }
+    return sor_batch_run(ctxs, n_use, n_seq, 1, work_pix_iters, [&](ofx_ctx *c, int q, int, ofx_stats *st) {
+        OFX_ENTER(c);
+        const int s = broxt_dev_run(c, frames, dF + (size_t) q * frames, d_flo + (size_t) q * (frames - 1), alpha, gamma, nscales, nu, TOL,
+                                    inner_iter, outer_iter, nxs, nys);
+        st[0] = c->stats;
+        return s;
+    });
 }
 
 
