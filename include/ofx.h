@@ -106,11 +106,19 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *                         everywhere: 1.3e-4).  Lone solves 5-10x faster than exact, lockstep groups supported.  On inputs where
  *                         the solves run into maxiter unconverged (the discontinuous pair P1 at 1080p) ANY re-ordering moves the
  *                         flow by as much as the reference's own OpenMP threads do (AEPE 2.5e-2) -- use the exact mode there.
- *   "sor_fuse"       sor_exact = 0: sweeps per launch of the tile kernels, K = 1..4 (0 = default: Horn-Schunck 2 in lockstep groups of >= 4 pairs, else 4; Brox's red-black
+ *                         Temporal Brox (all three entries), 0: 3-D red-black sweeps over the frames - 1 flow fields of a level,
+ *                         every voxel with (row + column + field) even, then every voxel with it odd; the update, omega and the
+ *                         stopping test are the reference's.  AEPE 6.7e-6 against the reference's order on 640x480 x 5 frames
+ *                         (2086 sweeps against 2123), lone solve 7.7x faster than exact
+ *                         (profiles/r11_brox_temporal_tolerance_640x480.json).  1 and 2 both run the windowed exact schedule.
+ *   "sor_fuse"      sor_exact = 0: sweeps per launch of the tile kernels, K = 1..4 (0 = default: Horn-Schunck 2 in lockstep groups of >= 4 pairs, else 4; Brox's red-black
  *                         levels 4); 9 = Brox's red-black levels through k_brox_sor, two launches per sweep (A/B); -1 = the round-1
  *                         kernels, one launch per colour and sweep (single pairs only; Brox: red-black on every level).  Results
- *                         do not depend on K.
- *   "sor_tile"       sor_exact = 0, Horn-Schunck: tile geometry 1 = 128 x 32 pixels on 16 waves, 2 = on 8 waves (default),
+ *                         do not depend on K.  Temporal Brox: K = 1, 2, 4 (3 = 2; 0 = default: 2) sweeps per launch on LDS tiles
+ *                         that hold every flow field, for sequences of up to 5 frames (4 flow fields); 9 or -1, and every value
+ *                         for longer sequences: one launch per colour and sweep from global memory.  The order alone decides
+ *                         the result: the same bits for every value.
+ *   "sor_tile"      sor_exact = 0, Horn-Schunck: tile geometry 1 = 128 x 32 pixels on 16 waves, 2 = on 8 waves (default),
  *                         3 = 128 x 48 on 12 waves.  Results do not depend on it.
  *   "sor_wave_levels"  sor_exact = 0, Brox: pyramid levels 0 .. n - 1 use the checkerboard-of-tiles sweeps (default 1: the
  *                         finest), the coarser ones red-black.  PART OF THE RESULT (as is "sor_tile_w").
@@ -412,7 +420,9 @@ int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, const double *I
 /* ---- Brox temporal (replace src/brox_optic_flow.h:41-55) ---------------------------*/
 /* I: `frames` images of nx*ny, frame-major; u, v: frames - 1 flow fields (u[f] takes frame f to frame f + 1).
  * frames <= 2 is an error ("The method needs more than two frames", brox_optic_flow_temporal.cpp:537-541: the
- * reference prints that and returns).  SOR sweeps run in the reference's order (windowed exact schedule). */
+ * reference prints that and returns).  SOR sweeps run in the reference's order (windowed exact schedule) by default; option
+ * sor_exact = 0 sweeps in the 3-D red-black order described there (AEPE < 1e-4 against the reference's order, several times
+ * faster), sor_fuse picks its kernel.  Levels below 3x3 are OFX_ERR_ARG in every mode. */
 int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, double *v, int nxx, int nyy, int frames,
                       double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter,
                       int outer_iter, int verbose);
@@ -421,7 +431,7 @@ int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, double *v, int n
  * (double for OFX_F64, float for OFX_F32), aligned to the element; the frames need not be contiguous nor distinct (a still
  * frame may be passed twice).  d_flo[f], f < frames - 1: the .flo payload of the flow from frame f to f + 1, nxx * nyy
  * interleaved (u, v) float32 pairs, 8-byte aligned (stored as float2): bit for bit (float) of what ofx_brox_temporal returns on
- * the same values.  3 <= frames <= OFX_BROXT_MAX_FRAMES (the frames reach the kernels through a by-value pointer table).
+ * the same values under equal options (sor_exact, sor_fuse: the entries share the level solver).  3 <= frames <= OFX_BROXT_MAX_FRAMES (the frames reach the kernels through a by-value pointer table).
  * Asynchronous on the context's stream: the stopping tests are resolved on return, the payloads are complete once the stream
  * is synchronised.  ofx_get_stats is filled as by ofx_brox_temporal.
  * Every error is found before any work and no byte of d_flo is written: what ofx_brox_temporal rejects (frames <= 2, images
@@ -433,7 +443,8 @@ int ofx_brox_temporal_dev(ofx_ctx *ctx, int frames, const void *const *dF, void 
 
 /* n_seq independent sequences of `frames` frames each: dF holds n_seq * frames pointers (sequence q at dF + q * frames), d_flo
  * n_seq * (frames - 1) (sequence q at d_flo + q * (frames - 1)).  Sequence q is solved by ofx_brox_temporal_dev on
- * ctxs[q % n_ctx], one worker thread and stream per context; the solves are independent (no lockstep).  All contexts on ONE
+ * ctxs[q % n_ctx], one worker thread and stream per context; the solves are independent (no lockstep).  Each context solves
+ * under its OWN options: the payloads are bit for bit the host entry's when sor_exact / sor_fuse are equal on every context.  All contexts on ONE
  * device and of one precision; option "concurrency" of the contexts is raised to the number at work for the call.  Returns when
  * every payload is complete, with the first failing status.  work_pix_iters: NULL or one double per sequence
  * (ofx_stats.work_pix_iters of its solve).

@@ -531,7 +531,12 @@ class Ofx:
         return u, v
 
     def brox_temporal(self, I, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15, verbose=0):
-        """I: (frames, ny, nx) -> u, v of shape (frames - 1, ny, nx)"""
+        """I: (frames, ny, nx) -> u, v of shape (frames - 1, ny, nx).  By default the SOR sweeps run in the reference's order (the
+        reference bit for bit in f64 storage).  set_option("sor_exact", 0) selects the tolerance mode: 3-D red-black sweeps over the
+        frames - 1 flow fields (every voxel with row + column + field even, then the odd ones), average end-point error below 1e-4
+        against the reference's order and several times faster; "sor_fuse" = 1, 2, 4 sweeps per launch on LDS tiles (0 = default),
+        9 = one launch per colour -- the result is the same for every value.  brox_temporal_dev and brox_temporal_batch_dev follow
+        the same options."""
         frames, ny, nx = I.shape
         u, v = np.zeros((max(frames - 1, 0), ny, nx)), np.zeros((max(frames - 1, 0), ny, nx))
         self._ck(self.L.ofx_brox_temporal(self.h, _f64(I), u, v, nx, ny, frames, alpha, gamma, nscales, nu, TOL, inner,

@@ -25,7 +25,8 @@ static ofx_ctx *cli_context(void)
     }
     if (getenv("OFX_STATS")) ofx_set_option(ctx, "profile", 1);       /* HIP-event times of the iteration launches per scale */
     if (getenv("OFX_TOLERANCE")) ofx_set_option(ctx, "relaxed_dual", atoi(getenv("OFX_TOLERANCE")) != 0);
-    /* OFX_SOR_TOLERANCE=1: Horn-Schunck / Brox with re-ordered sweeps inside the AEPE < 1e-4 bar (option sor_exact = 0) */
+    /* OFX_SOR_TOLERANCE=1: Horn-Schunck / Brox, spatial and temporal (brox_temporal: 3-D red-black), with re-ordered
+     * sweeps inside the AEPE < 1e-4 bar (option sor_exact = 0) */
     if (getenv("OFX_SOR_TOLERANCE")) ofx_set_option(ctx, "sor_exact", atoi(getenv("OFX_SOR_TOLERANCE")) != 0 ? 0 : 1);
     return ctx;
 }

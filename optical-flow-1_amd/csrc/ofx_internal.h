@@ -104,7 +104,8 @@ struct ofx_ctx {
     int fixed_work;
     int sor_exact;      // 1: reference sweep order, windowed launches; 2: same, one launch per time step; 0: colour order
     int sor_fuse;       // sor_exact = 0: K sweeps per launch on LDS tiles (ofx_sor_tile.hip): 0 = automatic (default), 1..4 = K,
-                        // -1 = one launch per colour and sweep (k_hs_sor / k_brox_sor; single pairs only)
+                        // -1 = one launch per colour and sweep (k_hs_sor / k_brox_sor; single pairs only); temporal Brox: -1 and
+                        // 9 = k_broxt_rb
     int sor_tile;       // tile geometry of the sor_exact = 0 sweeps (0 = default; ofx_sor_tile.hip)
     int sor_tile_w;     // Brox, sor_exact = 0: columns per tile of the checkerboard sweeps (0 = 128, the maximum)
     int sor_wave_p;     // ... anti-diagonals of operand prefetch in k_brox_wave (0 = 4)

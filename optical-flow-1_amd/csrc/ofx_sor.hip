@@ -2804,7 +2804,8 @@ extern "C" double ofx_ctx_expo_host_ms(const ofx_ctx *ctx) { return ctx ? ctx->e
 // per-frame kernels of the spatial method (prepare, warp, coefficient assembly) are reused unchanged.  New: the
 // smoothness weight with the temporal flow derivative, psi5 / psi6 and their divergence terms, the 7-point SOR
 // update, and the frame dimension in the exact schedule (a sweep visits frames 1 .. nz-2, then 0, then nz-1,
-// :439-459; every frame in the spatial method's pixel order).
+// :439-459; every frame in the spatial method's pixel order).  Option sor_exact = 0 sweeps in a 3-D red-black order
+// instead (ofx_broxt_tile_solve, ofx_sor_tile.hip); everything outside the sweeps is the same code.
 
 struct Psi6 { double p1, p2, p3, p4, p5, p6; };
 // src/brox_temporal_mask.cpp:18-132 at one pixel: psi1..4 within the frame, psi5 / psi6 = half-sums with the previous /
@@ -3021,6 +3022,16 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
             OFX_LAUNCH_CHECK(ctx);
             int nsor = 0;
             double error = 1000;
+            if (ctx->sor_exact == 0) {
+                // tolerance mode: 3-D red-black sweeps (ofx_sor_tile.hip).  No snapshots; ONE plane of them is the second buffer
+                // of the tile kernel's ping-pong, so the memory rule of the exact mode bounds this one too.
+                OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, 1, 1));
+                OFX_TRY(ofx_broxt_tile_solve<T>(ctx, L.DU, L.Snap, L.CO, (const T *) L.Dm, (const T *) L.Psis, nx, ny, nz, P.alpha, P.TOL,
+                                                OFX_BROX_MAX_ITERATIONS, ctx->sor_fuse, &nsor, &error, nullptr));
+                if (P.verbose) { printf("Iterations: %d\n", nsor); fflush(stdout); }                 // :463-465
+                sor_record_solve(&ctx->stats, 1, scale, solve++, &nsor, &error, 0.f, (double) n1);
+                continue;
+            }
             const size_t ub = n1 * sizeof(typename Pix<T>::v2);
             const int batch = sor_pick_batch(ctx, n1, sizeof(typename Pix<T>::v2), OFX_BROX_MAX_ITERATIONS);
             OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, batch, 1));

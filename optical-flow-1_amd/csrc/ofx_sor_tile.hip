@@ -1067,3 +1067,263 @@ template int ofx_brox_tile_solve<double>(ofx_ctx *, int, double2 *, double2 *, c
                                          double, double, int, int, int *, double *, float *);
 template int ofx_brox_tile_solve<float>(ofx_ctx *, int, float2 *, float2 *, const float4 *, const float *, const float *, int, int, double,
                                         double, int, int, int *, double *, float *);
+
+// ============================================================================================
+// Temporal Brox (src/brox_optic_flow_temporal.cpp:120-170, 430-461): 3-D red-black sweeps
+// ============================================================================================
+// One sweep over the nz = frames - 1 flow fields of a level: every voxel with (i + j + f) even, then every voxel with (i + j + f)
+// odd.  The 7-point stencil of a voxel only holds voxels of the other colour, so a colour step is a parallel map and the result
+// depends on nothing but this order: not on the tiling, the sweeps per launch or the launch geometry.  The update is broxt_point's
+// (ofx_sor.hip), expression for expression: psi1..6 are half-sums of psi_s with the neighbour, a missing neighbour (row, column or
+// frame) is the voxel itself with psi = 0, dv takes the NEW du, tile_rnd<T> rounds both new values to the storage type, the
+// divisions are plain IEEE divisions.  tests/broxt_colour_ref.c (order 1) is the CPU statement of the same order.
+//
+// k_broxt_rb: one colour of one sweep per launch straight from global memory, in place, for any nz (the counterpart of k_brox_sor).
+// k_broxt_tile: K sweeps per launch on an LDS tile of BXT_TW x BXT_TH voxels x ALL nz fields -- no halo in f; sequences of more
+// than BXT_NF fields go to k_broxt_rb.  A sweep's dependency cone is 2 voxels in x and y (black sees red sees black), so K sweeps
+// recompute a halo of 2 K; sweep s only updates rows / columns [2 s + 1, size - 2 - 2 s] of the tile.  The tile origin is even in x
+// and y, so a voxel's colour in the tile is its colour in the volume.
+#define BXT_SOR_W 1.9                // BROX_SOR_W of ofx_sor.hip
+#define BXT_TW 64                    // tile columns
+#define BXT_TH 24                    // tile rows
+#define BXT_NF 4                     // fields a tile can hold: 64 x 24 x 4 voxels x 24 B (unknowns + psi_s) = 144 KiB of the CU's 160
+#define BXT_NT (BXT_TW / 2 * BXT_TH) // one thread per pair of columns and row; it serves that pair in every field
+#define BXT_DEFAULT_K 2              // sweeps per launch of option sor_fuse = 0.  Measured (640x480 x 5 frames, 2086 sweeps, device
+                                     // entry): 100.2 ms (k_broxt_rb) / 87.3 / 64.7 / 71.3 ms for K = 1 / 2 / 4; exact mode 497 ms
+
+// the new (du, dv) of a voxel from its own value c, the six neighbours and psi1..6; e = its squared update
+template <typename T>
+OFX_DEV double2 bxt_update(double2 c, double2 dn, double2 up, double2 rt, double2 lf, double2 pv, double2 nxt, double p1, double p2,
+                           double p3, double p4, double p5, double p6, double4 co, double D, double alpha, double &e)
+{
+    const double w = BXT_SOR_W;
+    const double div_du = p1 * dn.x + p2 * up.x + p3 * rt.x + p4 * lf.x + p5 * pv.x + p6 * nxt.x;      // :157-159
+    const double div_dv = p1 * dn.y + p2 * up.y + p3 * rt.y + p4 * lf.y + p5 * pv.y + p6 * nxt.y;      // :160-162
+    const double duk = c.x, dvk = c.y;
+    const double dun = tile_rnd<T>((1. - w) * duk + w * (co.x - D * dvk + alpha * div_du) / co.z);     // :167
+    const double dvn = tile_rnd<T>((1. - w) * dvk + w * (co.y - D * dun + alpha * div_dv) / co.w);     // :168
+    e = (dun - duk) * (dun - duk) + (dvn - dvk) * (dvn - dvk);                                          // :171
+    return make_double2(dun, dvn);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_broxt_rb(typename Pix<T>::v2 *DU, const typename Pix<T>::v4 *__restrict__ CO,
+                                                  const T *__restrict__ Dm, const T *__restrict__ Ps, double *__restrict__ err, int k,
+                                                  int nx, int ny, int nz, int colour, double alpha, double tol)
+{
+    const double prev = loop_fetch_prev(err, k);
+    const int f = blockIdx.z;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    const int j = 2 * (blockIdx.x * 64 + threadIdx.x) + ((i + f + colour) & 1);
+    const int gw = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + threadIdx.y;
+    if (!loop_continues(prev, k, nx * ny * nz, tol, OFX_CRIT_SQRT_MEAN)) return;
+    double e = 0.0;
+    if (j < nx && i < ny) {
+        const size_t df = (size_t) nx * ny, p = f * df + (size_t) i * nx + j;
+        const size_t pdn = (i < ny - 1) ? p + nx : p, pup = (i > 0) ? p - nx : p;
+        const size_t prt = (j < nx - 1) ? p + 1 : p, plf = (j > 0) ? p - 1 : p;
+        const size_t ppv = (f > 0) ? p - df : p, pnx = (f < nz - 1) ? p + df : p;
+        const double pc = ldw(Ps + p);
+        const double p1 = (i < ny - 1) ? 0.5 * (ldw(Ps + pdn) + pc) : 0.0, p2 = (i > 0) ? 0.5 * (ldw(Ps + pup) + pc) : 0.0;
+        const double p3 = (j < nx - 1) ? 0.5 * (ldw(Ps + prt) + pc) : 0.0, p4 = (j > 0) ? 0.5 * (ldw(Ps + plf) + pc) : 0.0;
+        const double p5 = (f > 0) ? 0.5 * (ldw(Ps + ppv) + pc) : 0.0, p6 = (f < nz - 1) ? 0.5 * (ldw(Ps + pnx) + pc) : 0.0;
+        const double2 un = bxt_update<T>(ldw2(DU + p), ldw2(DU + pdn), ldw2(DU + pup), ldw2(DU + prt), ldw2(DU + plf), ldw2(DU + ppv),
+                                         ldw2(DU + pnx), p1, p2, p3, p4, p5, p6, ldw4(CO + p), ldw(Dm + p), alpha, e);
+        stn2(DU + p, un);
+    }
+    loop_accumulate(err, k, e, gw);
+}
+
+// LDS index of voxel (field f, tile row li, tile column lj): the even columns of a row first, then the odd ones, so that the lanes
+// of a colour step (every second column) touch consecutive 16-byte slots
+OFX_DEV int bxt_at(int f, int li, int lj) { return (f * BXT_TH + li) * BXT_TW + ((lj & 1) * (BXT_TW / 2) + (lj >> 1)); }
+
+// one colour of sweep s for the thread's voxels of every field; co, dm: the constant operands of its voxel of that colour per field
+template <typename T>
+OFX_DEV double bxt_colour_step(double2 *s_u, const double *s_ps, const double4 (&co)[BXT_NF], const double (&dm)[BXT_NF], int colour, int s,
+                               int li, int jh, int ii, int x0, int nx, int ny, int nz, int halo, double alpha)
+{
+    double e = 0.0;
+    const bool rowok = ii >= 0 && ii < ny && (unsigned) (li - (2 * s + 1)) <= (unsigned) (BXT_TH - 3 - 4 * s);
+    const bool rowown = li >= halo && li < BXT_TH - halo;
+#pragma unroll
+    for (int f = 0; f < BXT_NF; f++) {
+        if (f >= nz) break;
+        const int lj = 2 * jh + ((li + f + colour) & 1), jj = x0 + lj;
+        const bool active = rowok && jj >= 0 && jj < nx && (unsigned) (lj - (2 * s + 1)) <= (unsigned) (BXT_TW - 3 - 4 * s);
+        if (!active) continue;
+        // (an active voxel is at least one row and column inside the tile: its in-tile neighbours exist)
+        const bool top = ii == 0, bot = ii == ny - 1, lef = jj == 0, rig = jj == nx - 1, fst = f == 0, lst = f == nz - 1;
+        const int a = bxt_at(f, li, lj);
+        const int adn = bxt_at(f, bot ? li : li + 1, lj), aup = bxt_at(f, top ? li : li - 1, lj);
+        const int art = bxt_at(f, li, rig ? lj : lj + 1), alf = bxt_at(f, li, lef ? lj : lj - 1);
+        const int apv = bxt_at(fst ? f : f - 1, li, lj), anx = bxt_at(lst ? f : f + 1, li, lj);
+        const double pc = s_ps[a];
+        const double p1 = bot ? 0.0 : 0.5 * (s_ps[adn] + pc), p2 = top ? 0.0 : 0.5 * (s_ps[aup] + pc);
+        const double p3 = rig ? 0.0 : 0.5 * (s_ps[art] + pc), p4 = lef ? 0.0 : 0.5 * (s_ps[alf] + pc);
+        const double p5 = fst ? 0.0 : 0.5 * (s_ps[apv] + pc), p6 = lst ? 0.0 : 0.5 * (s_ps[anx] + pc);
+        double e1;
+        const double2 un = bxt_update<T>(s_u[a], s_u[adn], s_u[aup], s_u[art], s_u[alf], s_u[apv], s_u[anx], p1, p2, p3, p4, p5, p6, co[f],
+                                         dm[f], alpha, e1);
+        s_u[a] = un;
+        e += (rowown && lj >= halo && lj < BXT_TW - halo) ? e1 : 0.0;     // only owners add to the error
+    }
+    return e;
+}
+
+template <typename T, int K>
+__global__ __launch_bounds__(BXT_NT) void k_broxt_tile(const typename Pix<T>::v2 *__restrict__ Uin, typename Pix<T>::v2 *__restrict__ Uout,
+                                                       const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                                                       const T *__restrict__ Ps, double *__restrict__ err, int k0, int check, int slot0,
+                                                       int niter, int nx, int ny, int nz, int tiles_x, double alpha, double tol)
+{
+    static_assert(K >= 1 && BXT_TW - 4 * K > 0 && BXT_TH - 4 * K > 0 && BXT_NT % 64 == 0 && BXT_NT <= 1024, "tile geometry");
+    constexpr int H = 2 * K, OW = BXT_TW - 2 * H, OH = BXT_TH - 2 * H;
+    extern __shared__ double2 s_u[];                        // nz x BXT_TH x BXT_TW unknowns, then as many psi_s (bxt_at)
+    double *s_ps = reinterpret_cast<double *>(s_u + nz * BXT_TH * BXT_TW);
+    const int jh = threadIdx.x & 31, li = threadIdx.x >> 5, wave = threadIdx.x >> 6;
+    double prev[K];
+#pragma unroll
+    for (int q = 0; q < K; q++) prev[q] = (check && k0 - q > 0) ? loop_fetch_prev(err, k0 - q) : 0.0;
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int x0 = tx * OW - H, y0 = ty * OH - H;           // both even: tile parity = volume parity
+    const int ii = y0 + li, ic = ii < 0 ? 0 : (ii > ny - 1 ? ny - 1 : ii);
+    const size_t df = (size_t) nx * ny;
+    double4 co[2][BXT_NF];                                  // [colour][field]: the thread's voxel of that colour in the field
+    double dm[2][BXT_NF];
+#pragma unroll
+    for (int f = 0; f < BXT_NF; f++) {
+#pragma unroll
+        for (int col = 0; col < 2; col++) {
+            const int lj = 2 * jh + ((li + f + col) & 1), jj = x0 + lj, jc = jj < 0 ? 0 : (jj > nx - 1 ? nx - 1 : jj);
+            const size_t p = (f < nz ? f : 0) * df + (size_t) ic * nx + jc;          // clamped into the volume
+            co[col][f] = ldw4(CO + p);
+            dm[col][f] = ldw(Dm + p);
+            if (f < nz) {                                   // (a launch that turns out to be a no-op below only wrote its own LDS)
+                s_u[bxt_at(f, li, lj)] = ldw2(Uin + p);
+                s_ps[bxt_at(f, li, lj)] = ldw(Ps + p);
+            }
+        }
+    }
+    if (check) {                                            // :433 -- the same decision in every wave, before the first barrier
+#pragma unroll
+        for (int q = 0; q < K; q++)
+            if (k0 - q > 0 && !(loop_error_from_sum(wave_allreduce_sum(prev[q]), nx * ny * nz, OFX_CRIT_SQRT_MEAN) > tol)) return;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < niter; s++) {
+        double e = bxt_colour_step<T>(s_u, s_ps, co[0], dm[0], 0, s, li, jh, ii, x0, nx, ny, nz, H, alpha);
+        __syncthreads();
+        e += bxt_colour_step<T>(s_u, s_ps, co[1], dm[1], 1, s, li, jh, ii, x0, nx, ny, nz, H, alpha);
+        __syncthreads();
+        loop_accumulate(err, slot0 + (check ? s : 0), e, blockIdx.x * (BXT_NT / 64) + wave);
+    }
+    if (ii < 0 || ii >= ny || li < H || li >= BXT_TH - H) return;
+#pragma unroll
+    for (int f = 0; f < BXT_NF; f++) {
+        if (f >= nz) break;
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const int lj = 2 * jh + c, jj = x0 + lj;
+            if (jj >= 0 && jj < nx && lj >= H && lj < BXT_TW - H) stn2(Uout + (f * df + (size_t) ii * nx + jj), s_u[bxt_at(f, li, lj)]);
+        }
+    }
+}
+
+template <typename T, int K>
+static int broxt_tile_launch(ofx_ctx *ctx, const typename Pix<T>::v2 *Uin, typename Pix<T>::v2 *Uout, const typename Pix<T>::v4 *CO,
+                             const T *Dm, const T *Ps, int k0, int check, int slot0, int niter, int nx, int ny, int nz, double alpha,
+                             double thr)
+{
+    constexpr int OW = BXT_TW - 4 * K, OH = BXT_TH - 4 * K;
+    const int tiles_x = ofx_cdiv(nx, OW), tiles_y = ofx_cdiv(ny, OH);
+    const size_t lds = (size_t) nz * BXT_TH * BXT_TW * (sizeof(double2) + sizeof(double));
+    if (lds > 64 * 1024)
+        OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_broxt_tile<T, K>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int) lds));
+    hipLaunchKernelGGL((k_broxt_tile<T, K>), dim3((unsigned) (tiles_x * tiles_y)), dim3(BXT_NT), lds, ctx->stream, Uin, Uout, CO, Dm, Ps,
+                       ctx->d_err, k0, check, slot0, niter, nx, ny, nz, tiles_x, alpha, thr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "brox temporal tile launch failed: %s", hipGetErrorString(e));
+    return OFX_OK;
+}
+
+// One solve (:430-461): DU0 holds the incoming (du, dv) of the nz fields and the result; DU1 is the second buffer of the tile
+// kernel's ping-pong (k_broxt_rb works in place and never touches it).
+template <typename T>
+int ofx_broxt_tile_solve(ofx_ctx *ctx, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO, const T *Dm,
+                         const T *Ps, int nx, int ny, int nz, double alpha, double TOL, int maxiter, int K, int *niter, double *error,
+                         float *ms)
+{
+    using v2 = typename Pix<T>::v2;
+    *niter = 0;
+    *error = 1000;                                                                                   // :430
+    if (nz < 1 || (double) nx * ny * nz >= 2147483648.0) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: %dx%dx%d voxels", nx, ny, nz);
+    if (maxiter <= 0 || !(1000.0 > TOL)) return OFX_OK;
+    const bool rb = K < 0 || K == 9 || nz > BXT_NF;
+    if (K <= 0) K = BXT_DEFAULT_K;
+    if (K > 4) K = 4;
+    if (K == 3) K = 2;                                      // instantiated: 1, 2, 4
+    if (rb) K = 1;
+    LoopSpec S;
+    S.max_iter = maxiter;
+    S.size = nx * ny * nz;
+    S.thr = TOL;
+    S.crit = OFX_CRIT_SQRT_MEAN;
+    S.fixed = ctx->fixed_work != 0;
+    S.pairs = K == 2;
+    S.fuse = K > 2 ? K : 0;
+    S.afac = 0.0;
+    if (ctx->chunk > 0) S.chunk = ctx->chunk;
+    else if (rb) {
+        const double est_us = fmax(8.0, (double) S.size * 100.0 / 2.0e6);                            // sor_pick_chunk's estimate, 2 launches
+        const int c = (int) (60.0 / est_us);
+        S.chunk = c < 2 ? 2 : (c > 32 ? 32 : c);
+    } else {
+        const double tiles = (double) ofx_cdiv(nx, BXT_TW - 4 * K) * ofx_cdiv(ny, BXT_TH - 4 * K);
+        const double est_us = 4.0 + 4.0 * K * (tiles < 256.0 ? 1.0 : tiles / 256.0);
+        int units = (int) (80.0 / est_us);
+        units = units < 1 ? 1 : (units > 8 ? 8 : units);
+        S.chunk = units * K;
+    }
+    if (rb) {
+        const dim3 g(ofx_cdiv(ofx_cdiv(nx, 2) + 1, 64), ofx_cdiv(ny, 4), nz), b(64, 4);
+        auto launch = [&](int k, int, double thr) -> int {
+            for (int col = 0; col < 2; col++)
+                hipLaunchKernelGGL(k_broxt_rb<T>, g, b, 0, ctx->stream, DU0, CO, Dm, Ps, ctx->d_err, k, nx, ny, nz, col, alpha, thr);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "brox temporal sweep launch failed: %s", hipGetErrorString(e));
+            return OFX_OK;
+        };
+        return ofx_run_loop_group(ctx, S, 1, launch, [](const int *) { return OFX_OK; }, niter, error, ms);
+    }
+    auto go = [&](int k0, int check, int slot0, int cnt, double thr, bool from1) -> int {
+        const v2 *in = from1 ? DU1 : DU0;
+        v2 *out = from1 ? DU0 : DU1;
+        switch (K) {
+        case 1: return broxt_tile_launch<T, 1>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
+        case 2: return broxt_tile_launch<T, 2>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
+        default: return broxt_tile_launch<T, 4>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
+        }
+    };
+    // unit j = sweeps j K .. j K + K - 1 reads DU0 when j is even
+    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, cnt, thr, ((k / K) & 1) != 0); };
+    auto redo = [&](const int *k_of) -> int {
+        if (k_of[0] < 0) return OFX_OK;
+        const int n = k_of[0] + 1, j = (n - 1) / K;
+        return go(0, 0, S.max_iter, n - j * K, -1.0, (j & 1) != 0);
+    };
+    OFX_TRY(ofx_run_loop_group(ctx, S, 1, launch, redo, niter, error, ms));
+    if (((*niter + K - 1) / K) & 1) {
+        const size_t n1 = (size_t) nx * ny * nz;
+        hipLaunchKernelGGL((k_copy_pairs<v2>), dim3((unsigned) ((n1 + 255) / 256), 1), dim3(256), 0, ctx->stream, (const v2 *) DU1, DU0, n1, 1u);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "copy launch failed: %s", hipGetErrorString(e));
+    }
+    return OFX_OK;
+}
+template int ofx_broxt_tile_solve<double>(ofx_ctx *, double2 *, double2 *, const double4 *, const double *, const double *, int, int, int,
+                                          double, double, int, int, int *, double *, float *);
+template int ofx_broxt_tile_solve<float>(ofx_ctx *, float2 *, float2 *, const float4 *, const float *, const float *, int, int, int, double,
+                                         double, int, int, int *, double *, float *);

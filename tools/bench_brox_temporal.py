@@ -4,7 +4,9 @@
     python tools/bench_brox_temporal.py [--size 640x480] [--frames 5] [--check] [--batch CTX:SEQUENCES] [--reps 5]
 One JSON line.  Every figure is wall time of a warmed call, the median of --reps timed runs; the host and the device entry are
 timed in turn.  --check: the payloads of the device entry and of the batch against the host entry (array_equal), and the host
-entry against the compiled reference on one thread (test infrastructure, oracle/; the port when the reference is not built).
+entry against the compiled reference on one thread (test infrastructure, oracle/; the port when the reference is not built):
+largest difference, average end-point error (the figure that matters under --opt sor_exact=0, which sweeps in another order) and
+the reference order's sweep count next to "sweeps".
 A library without the device entries (OFX_LIB_PATH: an A/B against an older build) is timed on the host entry alone."""
 import argparse
 import importlib
@@ -118,5 +120,11 @@ if a.check:
     t = time.perf_counter()
     r = cpu.brox_temporal(I, **kw)
     rec["cpu_reference"] = {"kind": cpu.kind, "seconds_1_thread": round(time.perf_counter() - t, 3),
-                            "host_entry_max_abs_diff": float(max(np.abs(u - r[0]).max(), np.abs(v - r[1]).max()))}
+                            "host_entry_max_abs_diff": float(max(np.abs(u - r[0]).max(), np.abs(v - r[1]).max())),
+                            "host_entry_aepe": float(np.mean(np.hypot(u - r[0], v - r[1])))}
+    if len(r) < 3:                                         # the compiled reference does not report its sweeps: the port's table
+        port = oracle.Oracle()
+        port.set_num_threads(1)
+        r = port.brox_temporal(I, **kw)
+    rec["cpu_reference"]["sweeps_reference"] = int(r[2].sum())
 print(json.dumps(rec), flush=True)
