@@ -92,7 +92,7 @@ template <typename T> int gaussian_t(ofx_ctx *ctx, double *I, int nx, int ny, do
     T *a, *tmp;
     OFX_TRY(h.in(I, &a, n));
     OFX_TRY(h.out_alloc(&tmp, n));
-    OFX_TRY(op_gaussian<T>(ctx, a, tmp, nx, ny, sigma));
+    OFX_TRY(op_gaussian_planes<T>(ctx, 1, 1, a, nullptr, n, tmp, nx, ny, sigma));
     OFX_TRY(h.out(a, I, n));
     return h.sync();
 }
@@ -142,7 +142,7 @@ template <typename T> int zoom_out_t(ofx_ctx *ctx, const double *I, double *Iout
     OFX_TRY(h.out_alloc(&o, (size_t) nxx * nyy));
     OFX_TRY(h.out_alloc(&t1, n));
     OFX_TRY(h.out_alloc(&t2, n));
-    OFX_TRY(op_zoom_out<T>(ctx, a, o, t1, t2, nx, ny, factor));
+    OFX_TRY(op_zoom_out_channels_planes<T>(ctx, 1, 1, a, nullptr, o, nullptr, t1, t2, nx, ny, 1, factor));
     OFX_TRY(h.out(o, Iout, (size_t) nxx * nyy));
     return h.sync();
 }
@@ -154,12 +154,15 @@ template <typename T> int zoom_out_channels_t(ofx_ctx *ctx, const double *I, dou
     int nxx, nyy;
     ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
     if (nxx < 1 || nyy < 1) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: empty output");
+    GaussTaps taps;                                              // this entry names the factor, not zoom_out's sigma
+    if (ofx_gauss_taps(0.6 * sqrt(1.0 / (factor * factor) - 1.0), &taps) != OFX_OK)
+        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
     T *a, *o, *t1, *t2;
     OFX_TRY(h.in(I, &a, n));
     OFX_TRY(h.out_alloc(&o, (size_t) nxx * nyy * nz));
     OFX_TRY(h.out_alloc(&t1, n));
     OFX_TRY(h.out_alloc(&t2, n));
-    OFX_TRY(op_zoom_out_channels<T>(ctx, a, o, t1, t2, nx, ny, nz, factor));
+    OFX_TRY(op_zoom_out_channels_planes<T>(ctx, 1, 1, a, nullptr, o, nullptr, t1, t2, nx, ny, nz, factor));
     OFX_TRY(h.out(o, Iout, (size_t) nxx * nyy * nz));
     return h.sync();
 }
@@ -184,8 +187,8 @@ template <typename T> int norm_t(ofx_ctx *ctx, const double *I1, const double *I
     OFX_TRY(h.in(I2, &b, (size_t) size));
     OFX_TRY(h.out_alloc(&x, (size_t) size));
     OFX_TRY(h.out_alloc(&y, (size_t) size));
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * 1024 + 2, &scr));
-    OFX_TRY(op_normalize2<T>(ctx, a, b, x, y, size, scr));
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, (size_t) size, 1), &scr));
+    OFX_TRY((op_normalize_sets<T, T>(ctx, OfxSrcPtrs{{a, b}}, OfxDstPtrs{{x, y}}, 1, 2, (size_t) size, 1, scr)));
     OFX_TRY(h.out(x, o1, (size_t) size));
     OFX_TRY(h.out(y, o2, (size_t) size));
     return h.sync();
@@ -220,7 +223,7 @@ int gradient3_t(ofx_ctx *ctx, const double *f, double *gx, double *gy, double *g
     OFX_TRY(h.out_alloc(&ox, n));
     OFX_TRY(h.out_alloc(&oy, n));
     OFX_TRY(h.out_alloc(&oz, n));
-    for (int k = 0; k < nz; k++) OFX_TRY(op_centered_gradient<T>(ctx, a + k * df, ox + k * df, oy + k * df, nx, ny));
+    OFX_TRY(op_centered_gradient_planes<T>(ctx, nz, a, ox, oy, nx, ny));          // all frames in one launch
     OFX_TRY(op_gradient_dz<T>(ctx, a, oz, nx, ny, nz));
     OFX_TRY(h.out(ox, gx, n));
     OFX_TRY(h.out(oy, gy, n));
@@ -231,13 +234,12 @@ int gradient3_t(ofx_ctx *ctx, const double *f, double *gx, double *gy, double *g
 template <typename T> int norm1_t(ofx_ctx *ctx, const double *I, double *o, int size)
 {
     HostOp<T> h{ctx};
-    T *a, *x, *dummy;
+    T *a, *x;
     double *scr;
     OFX_TRY(h.in(I, &a, (size_t) size));
     OFX_TRY(h.out_alloc(&x, (size_t) size));
-    OFX_TRY(h.out_alloc(&dummy, (size_t) size));
-    OFX_TRY(ofx_alloc(ctx, op_pyramid_scratch_doubles(), &scr));
-    OFX_TRY(op_normalize2<T>(ctx, a, a, x, dummy, size, scr));      // joint min / max of (I, I) = min / max of I
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, (size_t) size, 1), &scr));
+    OFX_TRY((op_normalize_sets<T, T>(ctx, OfxSrcPtrs{{a}}, OfxDstPtrs{{x}}, 1, 1, (size_t) size, 1, scr)));
     OFX_TRY(h.out(x, o, (size_t) size));
     return h.sync();
 }
@@ -248,9 +250,10 @@ template <typename T> int minmax_t(ofx_ctx *ctx, const double *x, int size, doub
     T *a;
     double *scr, mm[2];
     OFX_TRY(h.in(x, &a, (size_t) size));
-    OFX_TRY(ofx_alloc(ctx, op_pyramid_scratch_doubles(), &scr));
-    OFX_TRY(op_minmax<T>(ctx, a, size, scr));
-    OFX_HIP(ctx, hipMemcpyAsync(mm, scr + 2 * 1024, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, (size_t) size, 1), &scr));
+    OFX_TRY(op_minmax_partial<T>(ctx, OfxSrcPtrs{{a}}, 1, 1, (size_t) size, 1, scr));
+    OFX_TRY(op_minmax_final(ctx, 1, (size_t) size, 1, scr));
+    OFX_HIP(ctx, hipMemcpyAsync(mm, op_minmax_result(scr), 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     OFX_TRY(h.sync());
     *mn = mm[0];
     *mx = mm[1];

@@ -13,7 +13,6 @@
 
 #define OCC_IS_ZERO 1E-10      // src/tvl1occflow_constants.h:31
 #define OCC_THR_CHI 0.75       // src/tvl1occflow_constants.h:32
-#define OCC_MM_BLOCKS 256
 #define OFX_MEDIAN_MAX_W 9     // largest window side of ofx_me_median_filtering
 
 static inline int occ_grid1d(size_t n) { return (int) ((n + 255) / 256); }
@@ -101,70 +100,7 @@ extern "C" int ofx_bicubic_warp_color(ofx_ctx *ctx, const double *input, const d
     return d.sync();
 }
 
-// ---- min / max of strided element sets (exact: order-independent) -------------------------------------------------------
-// part[b] / part[OCC_MM_BLOCKS + b] = min / max over elements first + t * stride (t = 0 .. count - 1) of up to two arrays
-__global__ void k_mm_partial(const double *__restrict__ a, const double *__restrict__ b, size_t first, size_t stride,
-                             size_t count, double *__restrict__ part)
-{
-    double lo = a[first], hi = lo;
-    for (size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t) gridDim.x * blockDim.x) {
-        const double x = a[first + t * stride];
-        lo = x < lo ? x : lo; hi = x > hi ? x : hi;
-        if (b) {
-            const double y = b[first + t * stride];
-            lo = y < lo ? y : lo; hi = y > hi ? y : hi;
-        }
-    }
-    lo = wave_allreduce_min(lo);
-    hi = wave_allreduce_max(hi);
-    __shared__ double slo[4], shi[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
-        part[blockIdx.x] = lo;
-        part[OCC_MM_BLOCKS + blockIdx.x] = hi;
-    }
-}
-// mm[0] = min, mm[1] = max over the partials; `acc` != 0 merges with what mm already holds
-__global__ void k_mm_final(const double *__restrict__ part, int nblocks, double *__restrict__ mm, int acc)
-{
-    if (threadIdx.x != 0) return;
-    double lo = part[0], hi = part[OCC_MM_BLOCKS];
-    for (int i = 1; i < nblocks; i++) {
-        lo = part[i] < lo ? part[i] : lo;
-        hi = part[OCC_MM_BLOCKS + i] > hi ? part[OCC_MM_BLOCKS + i] : hi;
-    }
-    if (acc) { lo = mm[0] < lo ? mm[0] : lo; hi = mm[1] > hi ? mm[1] : hi; }
-    mm[0] = lo;
-    mm[1] = hi;
-}
-static int occ_minmax(ofx_ctx *ctx, const double *a, const double *b, size_t first, size_t stride, size_t count, double *part,
-                      double *mm, int acc)
-{
-    int nb = occ_grid1d(count);
-    nb = nb < 1 ? 1 : (nb > OCC_MM_BLOCKS ? OCC_MM_BLOCKS : nb);
-    hipLaunchKernelGGL(k_mm_partial, dim3(nb), dim3(256), 0, ctx->stream, a, b, first, stride, count, part);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mm_final, dim3(1), dim3(64), 0, ctx->stream, (const double *) part, nb, mm, acc);
-    OFX_LAUNCH_CHECK(ctx);
-    return OFX_OK;
-}
-
-// 255 (x - min) / den per element, or a copy when `guard` and den <= 0 (image_normalization_2_color / _4); channel c of
-// an nz-interleaved array uses mm[2 c], mm[2 c + 1]
-__global__ void k_norm_map(const double *__restrict__ in, double *__restrict__ out, size_t n, int nz,
-                           const double *__restrict__ mm, int guard)
-{
-    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int c = (int) (e % nz);
-    const double lo = mm[2 * c], den = mm[2 * c + 1] - lo;
-    const double x = in[e];
-    out[e] = (!guard || den > 0) ? 255.0 * (x - lo) / den : x;
-}
-
+// ---- image_normalization_2_color / _3 / _4 (src/utils.cpp:333-501): op_normalize_sets on uploaded doubles --------------
 extern "C" int ofx_image_normalization_2_color(ofx_ctx *ctx, const double *I1, const double *I2, double *I1n, double *I2n,
                                                int size, int nz)
 {
@@ -174,19 +110,13 @@ extern "C" int ofx_image_normalization_2_color(ofx_ctx *ctx, const double *I1, c
     // the arrays there
     if (nz < 1 || size < nz || size % nz) return ofx_fail(ctx, OFX_ERR_ARG, "image_normalization_2_color: size %d, nz %d", size, nz);
     Dev d{ctx};
-    double *a, *b, *oa, *ob, *part, *mm;
+    double *a, *b, *oa, *ob, *scr;
     OFX_TRY(d.in(I1, &a, size));
     OFX_TRY(d.in(I2, &b, size));
     OFX_TRY(ofx_alloc(ctx, (size_t) size, &oa));
     OFX_TRY(ofx_alloc(ctx, (size_t) size, &ob));
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * OCC_MM_BLOCKS, &part));
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * nz, &mm));
-    for (int c = 0; c < nz; c++) OFX_TRY(occ_minmax(ctx, a, b, (size_t) c, (size_t) nz, (size_t) size / nz, part, mm + 2 * c, 0));
-    hipLaunchKernelGGL(k_norm_map, dim3(occ_grid1d(size)), dim3(256), 0, ctx->stream, (const double *) a, oa, (size_t) size, nz,
-                       (const double *) mm, 1);
-    hipLaunchKernelGGL(k_norm_map, dim3(occ_grid1d(size)), dim3(256), 0, ctx->stream, (const double *) b, ob, (size_t) size, nz,
-                       (const double *) mm, 1);
-    OFX_LAUNCH_CHECK(ctx);
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, (size_t) size / nz, nz), &scr));
+    OFX_TRY((op_normalize_sets<double, double>(ctx, OfxSrcPtrs{{a, b}}, OfxDstPtrs{{oa, ob}}, 1, 2, (size_t) size / nz, nz, scr)));
     OFX_TRY(d.out(oa, I1n, size));
     OFX_TRY(d.out(ob, I2n, size));
     return d.sync();
@@ -196,19 +126,18 @@ extern "C" int ofx_image_normalization_2_color(ofx_ctx *ctx, const double *I1, c
 static int occ_normalize_joint(ofx_ctx *ctx, int k, const double *const *in, double *const *out, int size, int guard)
 {
     Dev d{ctx};
-    double *dv[4], *ov[4], *part, *mm;
+    double *dv, *scr;
+    OfxSrcPtrs src = {};
+    OfxDstPtrs dst = {};
     for (int q = 0; q < k; q++) {
-        OFX_TRY(d.in(in[q], &dv[q], size));
-        OFX_TRY(ofx_alloc(ctx, (size_t) size, &ov[q]));
+        OFX_TRY(d.in(in[q], &dv, size));
+        src.p[q] = dv;
+        OFX_TRY(ofx_alloc(ctx, (size_t) size, &dv));
+        dst.p[q] = dv;
     }
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * OCC_MM_BLOCKS, &part));
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2, &mm));
-    for (int q = 0; q < k; q++) OFX_TRY(occ_minmax(ctx, dv[q], nullptr, 0, 1, (size_t) size, part, mm, q > 0));
-    for (int q = 0; q < k; q++)
-        hipLaunchKernelGGL(k_norm_map, dim3(occ_grid1d(size)), dim3(256), 0, ctx->stream, (const double *) dv[q], ov[q],
-                           (size_t) size, 1, (const double *) mm, guard);
-    OFX_LAUNCH_CHECK(ctx);
-    for (int q = 0; q < k; q++) OFX_TRY(d.out(ov[q], out[q], size));
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, (size_t) size, 1), &scr));
+    OFX_TRY((op_normalize_sets<double, double>(ctx, src, dst, 1, k, (size_t) size, 1, scr, guard)));
+    for (int q = 0; q < k; q++) OFX_TRY(d.out((const double *) dst.p[q], out[q], size));
     return d.sync();
 }
 
@@ -1539,13 +1468,14 @@ int occ_group_impl(ofx_ctx *ctx, int G, const double *const *I_1, const double *
     for (int g = 0; g < G; g++)
         for (int k = 0; k < 4; k++) {
             OFX_HIP(ctx, hipMemcpyAsync(lv[0].im[k] + g * size, host[k][g], size * sizeof(double), hipMemcpyHostToDevice, st));
-            OFX_TRY(op_gaussian<double>(ctx, lv[0].im[k] + g * size, W.t1, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
+            OFX_TRY(op_gaussian_planes<double>(ctx, 1, 1, lv[0].im[k] + g * size, nullptr, size, W.t1, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
         }
     for (int s = 1; s < nscales; s++) {
         const size_t np = (size_t) nxs[s - 1] * nys[s - 1], n = (size_t) nxs[s] * nys[s];
         for (int g = 0; g < G; g++)
             for (int k = 0; k < 4; k++)
-                OFX_TRY(op_zoom_out<double>(ctx, lv[s - 1].im[k] + g * np, lv[s].im[k] + g * n, W.t1, W.t2, nxs[s - 1], nys[s - 1], zfactor));
+                OFX_TRY(op_zoom_out_channels_planes<double>(ctx, 1, 1, lv[s - 1].im[k] + g * np, nullptr, lv[s].im[k] + g * n, nullptr, W.t1,
+                                                            W.t2, nxs[s - 1], nys[s - 1], 1, zfactor));
     }
     {
         const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1] * G;
@@ -1733,7 +1663,7 @@ __global__ __launch_bounds__(256) void k_occ_seq_out(const double *__restrict__ 
 namespace {
 
 // what must hold before any work: the pyramid's sizes, its coarsest level, and room for both Gaussians on the levels they
-// smooth (op_gaussian's rule, which the host entries meet while they build the pyramid)
+// smooth (op_gaussian_planes' rule, which the host entries meet while they build the pyramid)
 int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor, std::vector<int> &nxs, std::vector<int> &nys)
 {
     OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));

@@ -26,12 +26,34 @@ template <typename T> int op_deinterleave2(ofx_ctx *ctx, const typename Pix<T>::
 template <typename T> int op_to_flo(ofx_ctx *ctx, const typename Pix<T>::v2 *src, float2 *dst, size_t n);
 template <typename T> int op_fill2(ofx_ctx *ctx, typename Pix<T>::v2 *dst, size_t n);   // zero
 
-// image_normalization_2 (src/utils.cpp:283-326); scratch: 4 * 1024 T-sized... see .hip (own alloc)
-template <typename T> int op_normalize2(ofx_ctx *ctx, const T *I1, const T *I2, T *o1, T *o2, int size,
-                                        double *d_scratch /* >= 2*2048+2 doubles */);
-
-// gaussian (src/operators.cpp:506-624): I updated in place, tmp is an nx*ny scratch image
-template <typename T> int op_gaussian(ofx_ctx *ctx, T *I, T *tmp, int nx, int ny, double sigma, int dirichlet = 0);
+// ---- joint min / max and the normalisation map (getminmax, image_normalization_1 / _2 / _2_color / _3 / _4, src/utils.cpp) ----
+// The sources of one launch reach the kernels through a by-value table of OFX_MM_MAX_SRC (== 2 * OFX_MAX_GROUP ==
+// OFX_BROXT_MAX_FRAMES) pointers of type S (double, or the storage type; converted exactly to double).  `per` consecutive
+// sources form a SET that shares {min, max}; with nz interleaved channels, channel c of a set has its own {min, max} over
+// elements t * nz + c (t < npix) of the set's sources.  One set may come in several CHUNKS (launches): chunk k of `chunks`
+// adds its partial results behind those of the chunks before, op_minmax_final reduces them all.  min / max are exact, so the
+// reduction order is free.
+#define OFX_MM_MAX_SRC 32
+static_assert(OFX_MM_MAX_SRC >= 2 * OFX_MAX_GROUP && OFX_MM_MAX_SRC >= OFX_BROXT_MAX_FRAMES, "the table holds a group's pairs and a sequence's frames");
+struct OfxSrcPtrs { const void *p[OFX_MM_MAX_SRC]; };
+struct OfxDstPtrs { void *p[OFX_MM_MAX_SRC]; };
+// doubles of scratch for `nsets` sets of sources of npix * nz elements; the layout is private to ofx_ops.hip
+size_t op_minmax_scratch_doubles(int nsets, size_t npix, int nz, int chunks = 1);
+template <typename S>
+int op_minmax_partial(ofx_ctx *ctx, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr, int chunk = 0,
+                      int chunks = 1);
+int op_minmax_final(ofx_ctx *ctx, int nsets, size_t npix, int nz, double *scr, int chunks = 1);
+// after op_minmax_final: {min, max} of channel c of set s on the device at op_minmax_result(scr)[2 * (s * nz + c)]
+const double *op_minmax_result(const double *scr);
+// dst[q][e] = 255 (src[q][e] - min) / (max - min) for the npix * nz elements e of every source q, {min, max} those of q's set and
+// e's channel; guard != 0: a copy where max - min <= 0 (image_normalization_3 alone divides regardless, as the reference does)
+template <typename T, typename S>
+int op_normalize_map(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                     const double *scr, int guard = 1);
+// the three steps for sets that come in one chunk; scr: op_minmax_scratch_doubles(nsets, npix, nz) doubles
+template <typename T, typename S>
+int op_normalize_sets(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz, double *scr,
+                      int guard = 1);
 
 // generic bicubic resampling out(i1,j1) = bicubic(in, j1/fx, i1/fy, border_out=false)
 // (zoom_out: fx=fy=factor, src/zoom.cpp:67-75; zoom_in: per-axis factors, src/zoom.cpp:142-154)
@@ -41,22 +63,18 @@ template <typename T> int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx,
 // G > 1: the G flow fields of a lockstep group, back to back in U and Uout, in one launch
 template <typename T> int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, typename Pix<T>::v2 *Uout,
                                           int nx, int ny, int nxx, int nyy, double scale, int G = 1);
-// zoom_out (src/zoom.cpp:41-78): tmpA, tmpB are nx*ny scratch images
-template <typename T> int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny,
-                                      double factor);
-// zoom_out of nz interleaved channels, each channel as zoom_out (the IPOL original of robust_expo_methods, zoom.h:45-85):
-// tmpA, tmpB are nx*ny*nz scratch images; OFX_ERR_SIGMA under zoom_out's rule, before anything is launched
-template <typename T> int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz,
-                                               double factor);
-// the same for `count` images (at most 2 * OFX_MAX_GROUP), one launch per stage: images 0 .. split - 1 back to back at A (nx*ny*nz
-// elements each), the others at B, the results likewise at oA / oB, tmpA / tmpB scratch for count images
+// zoom_out (src/zoom.cpp:41-78) of `count` images (at most 2 * OFX_MAX_GROUP) of nz interleaved channels, each channel as zoom_out
+// (the IPOL original of robust_expo_methods, zoom.h:45-85), one launch per stage: images 0 .. split - 1 back to back at A (nx*ny*nz
+// elements each), the others at B, the results likewise at oA / oB, tmpA / tmpB scratch for count images; OFX_ERR_SIGMA under
+// zoom_out's rule, before anything is launched.  A single image is count = split = 1, a plane nz = 1.
 template <typename T> int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, const T *B, T *oA, T *oB,
                                                       T *tmpA, T *tmpB, int nx, int ny, int nz, double factor);
 // ... for the 2 G images of a lockstep group of pairs: A / B = the G first / second images
 template <typename T> int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB,
                                                      int nx, int ny, int nz, double factor);
-// op_gaussian on the first nx*ny elements of `count` images, one launch per pass: images 0 .. split - 1 start at A, the others at
-// B, each `stride` elements after the one before; tmp holds count planes of nx*ny
+// gaussian (src/operators.cpp:506-624) in place on the first nx*ny elements of `count` images, one launch per pass: images
+// 0 .. split - 1 start at A, the others at B, each `stride` elements after the one before; tmp holds count planes of nx*ny.  A
+// single image is count = split = 1
 template <typename T> int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny,
                                              double sigma, int dirichlet = 0);
 // ... for the 2 G images of a lockstep group of pairs
@@ -71,7 +89,7 @@ template <typename T> int op_zoom_in_planes3(ofx_ctx *ctx, int G, const T *u1, c
 template <typename T> int op_divergence(ofx_ctx *ctx, const T *v1, const T *v2, T *div, int nx, int ny);
 template <typename T> int op_forward_gradient(ofx_ctx *ctx, const T *f, T *fx, T *fy, int nx, int ny);
 template <typename T> int op_centered_gradient(ofx_ctx *ctx, const T *f, T *dx, T *dy, int nx, int ny);
-// ... of `count` planes back to back (f, dx, dy alike) in one launch
+// ... of `count` planes (at most 65535) back to back (f, dx, dy alike) in one launch
 template <typename T> int op_centered_gradient_planes(ofx_ctx *ctx, int count, const T *f, T *dx, T *dy, int nx, int ny);
 template <typename T> int op_second_derivative(ofx_ctx *ctx, const T *f, T *out, int nx, int ny, int which);
 template <typename T> int op_bicubic_warp(ofx_ctx *ctx, const T *in, const T *u, const T *v, T *out, int nx,
@@ -83,29 +101,16 @@ template <typename T> int op_bicubic_at(ofx_ctx *ctx, const T *in, const double 
 template <typename T> int op_bicubic_at_color(ofx_ctx *ctx, const T *in, const double *uu, const double *vv, double *out,
                                               int n, int nx, int ny, int nz, int ch, int border_out);
 template <typename T> int op_gradient_dz(ofx_ctx *ctx, const T *in, T *dz, int nx, int ny, int nz);
-// scr >= op_pyramid_scratch_doubles(); result: scr[2 * 1024] = min, scr[2 * 1024 + 1] = max
-template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *scr);
 
 // pa = (f, centred dx) pairs, pb = centred dy: one pair gather + one scalar gather per bicubic tap serve the
 // three warps of (f, fx, fy) (see bicubic_sample3 in ofx_device.h for why not one padded 4-vector)
 template <typename T> int op_grad_pack(ofx_ctx *ctx, const T *f, typename Pix<T>::v2 *pa, T *pb, int nx, int ny, int G = 1);
 
 // Shared pyramid prologue (src/tvl1flow.cpp:236-280 == horn_schunck_pyramidal.cpp:279-323 ==
-// brox_optic_flow_spatial.cpp:467-509): joint normalisation, presmoothing, zoom_out chain.
-template <typename T> struct ImgLevel {
-    int nx, ny;
-    T *A, *B;
-};
-template <typename T>
-int op_build_pyramid(ofx_ctx *ctx, const T *dA, const T *dB, int nx, int ny, int nscales, double zfactor,
-                     double presmooth_sigma, std::vector<ImgLevel<T>> &lv);
-
-// the same in pieces, for callers that lay several pyramids out in their own arrays (TV-L1 lockstep groups)
+// brox_optic_flow_spatial.cpp:467-509): joint normalisation, presmoothing, zoom_out chain -- op_build_pyramid_group below, on
+// levels that the caller lays out (op_pyramid_sizes) with op_pyramid_scratch_doubles() doubles of scratch per pair.
 int op_pyramid_sizes(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor, std::vector<int> &nxs, std::vector<int> &nys);
 size_t op_pyramid_scratch_doubles();
-template <typename T>
-int op_build_pyramid_into(ofx_ctx *ctx, const T *dA, const T *dB, int nscales, double zfactor, double presmooth_sigma,
-                          const std::vector<ImgLevel<T>> &lv, T *tmpA, T *tmpB, double *scr);
 
 // device pointers of the caller's G image pairs, passed to kernels by value
 struct OfxGroupPtrs {

@@ -101,20 +101,17 @@ template <typename T> int op_fill2(ofx_ctx *ctx, typename Pix<T>::v2 *dst, size_
     return OFX_OK;
 }
 
-// ---- image_normalization_2 (src/utils.cpp:283-326, getminmax :509-525) -----------------------------
-// min/max are exact (order-independent); two-stage reduction: per-block partials, then one block.
+// ---- joint min / max of sets of images and the normalisation map (src/utils.cpp:283-501, getminmax :509-525) --------
+// min / max are exact (order-independent): per-block partials, then one block per set and channel.  Scratch of nslots =
+// nsets * nz {min, max} results whose partials come in `count` = chunks * blocks-per-chunk pieces each:
+//   scr[2 * slot], scr[2 * slot + 1]            {min, max} of slot = set * nz + channel
+//   scr[2 * nslots + slot * count + k]          partial minima of the slot
+//   scr[2 * nslots + (nslots + slot) * count + k]   partial maxima
 #define MM_BLOCKS 1024
-#define MM_SCR (2 * MM_BLOCKS + 2)      // doubles of scratch per (pair of) image(s): partial minima, partial maxima, {min, max}
-template <typename T>
-OFX_DEV void minmax_partial_block(const T *__restrict__ I1, const T *__restrict__ I2, int size, double *__restrict__ part)
+static inline int mm_blocks(size_t npix) { return npix > (size_t) MM_BLOCKS * 256 ? MM_BLOCKS : (int) ((npix + 255) / 256); }
+
+OFX_DEV void minmax_block_reduce(double lo, double hi, double *__restrict__ plo, double *__restrict__ phi)
 {
-    double lo = ldw(I1), hi = lo;
-    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < (size_t) size;
-         i += (size_t) gridDim.x * blockDim.x) {
-        const double a = ldw(I1 + i), b = ldw(I2 + i);
-        lo = a < lo ? a : lo; hi = a > hi ? a : hi;
-        lo = b < lo ? b : lo; hi = b > hi ? b : hi;
-    }
     lo = wave_allreduce_min(lo);
     hi = wave_allreduce_max(hi);
     __shared__ double slo[4], shi[4];
@@ -123,96 +120,107 @@ OFX_DEV void minmax_partial_block(const T *__restrict__ I1, const T *__restrict_
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
-        part[blockIdx.x] = lo;
-        part[MM_BLOCKS + blockIdx.x] = hi;
+        *plo = lo;
+        *phi = hi;
     }
 }
-OFX_DEV void minmax_final_block(const double *__restrict__ part, int nblocks, double *__restrict__ mm)
+// block (c * nb + b, set): a stride of channel c of all `per` sources of the set, two sources at a time (their pointers fetched
+// once, two loads in flight per lane; an odd last source is read twice); first = this chunk's place among the pieces
+template <typename S>
+__global__ __launch_bounds__(256) void k_minmax_partial(OfxSrcPtrs src, int per, size_t npix, int nz, int nb, int first, int count,
+                                                        double *__restrict__ scr)
 {
-    double lo = part[0], hi = part[MM_BLOCKS];
-    for (int i = threadIdx.x; i < nblocks; i += blockDim.x) {
-        lo = part[i] < lo ? part[i] : lo;
-        hi = part[MM_BLOCKS + i] > hi ? part[MM_BLOCKS + i] : hi;
+    const int c = blockIdx.x / nb, b = blockIdx.x - c * nb, set = blockIdx.y;
+    const int nslots = gridDim.y * nz, slot = set * nz + c;
+    double lo = ldw((const S *) src.p[set * per] + c), hi = lo;
+    for (int k = 0; k < per; k += 2) {
+        const S *__restrict__ I1 = (const S *) src.p[set * per + k] + c;
+        const S *__restrict__ I2 = (const S *) src.p[set * per + (k + 1 < per ? k + 1 : k)] + c;
+        for (size_t t = (size_t) b * 256 + threadIdx.x; t < npix; t += (size_t) nb * 256) {
+            const double x = ldw(I1 + t * nz), y = ldw(I2 + t * nz);
+            lo = x < lo ? x : lo; hi = x > hi ? x : hi;
+            lo = y < lo ? y : lo; hi = y > hi ? y : hi;
+        }
     }
-    lo = wave_allreduce_min(lo);
-    hi = wave_allreduce_max(hi);
-    __shared__ double slo[4], shi[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
-        mm[0] = lo;
-        mm[1] = hi;
-    }
+    double *part = scr + 2 * (size_t) nslots + (size_t) slot * count + first + b;
+    minmax_block_reduce(lo, hi, part, part + (size_t) nslots * count);
 }
-template <typename T>
-OFX_DEV void normalize2_px(const T *__restrict__ I1, const T *__restrict__ I2, T *__restrict__ o1, T *__restrict__ o2, int size,
-                           const double *__restrict__ mm)
+// block = slot
+__global__ __launch_bounds__(256) void k_minmax_final(double *__restrict__ scr, int count)
 {
-    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t) size) return;
-    const double lo = mm[0], den = mm[1] - mm[0];
-    const double a = ldw(I1 + i), b = ldw(I2 + i);
-    if (den > 0) {
-        stn(o1 + i, 255.0 * (a - lo) / den);
-        stn(o2 + i, 255.0 * (b - lo) / den);
-    } else {
-        stn(o1 + i, a);
-        stn(o2 + i, b);
+    const int nslots = gridDim.x, slot = blockIdx.x;
+    const double *plo = scr + 2 * (size_t) nslots + (size_t) slot * count, *phi = plo + (size_t) nslots * count;
+    double lo = plo[0], hi = phi[0];
+    for (int i = threadIdx.x; i < count; i += 256) {
+        lo = plo[i] < lo ? plo[i] : lo;
+        hi = phi[i] > hi ? phi[i] : hi;
+    }
+    minmax_block_reduce(lo, hi, scr + 2 * slot, scr + 2 * slot + 1);
+}
+// thread = element e of every source of set blockIdx.y
+template <typename T, typename S>
+__global__ void k_normalize_map(OfxSrcPtrs src, OfxDstPtrs dst, int per, size_t n, int nz, const double *__restrict__ mm, int guard)
+{
+    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int set = blockIdx.y, slot = set * nz + (nz == 1 ? 0 : (int) ((unsigned) e % (unsigned) nz));      // n < 2^31
+    const double lo = mm[2 * slot], den = mm[2 * slot + 1] - mm[2 * slot];
+    const bool map = !guard || den > 0;
+    for (int k = 0; k < per; k += 2) {                           // two sources at a time: both loads before the stores
+        const bool two = k + 1 < per;
+        const double x = ldw((const S *) src.p[set * per + k] + e), y = two ? ldw((const S *) src.p[set * per + k + 1] + e) : 0.0;
+        stn((T *) dst.p[set * per + k] + e, map ? 255.0 * (x - lo) / den : x);
+        if (two) stn((T *) dst.p[set * per + k + 1] + e, map ? 255.0 * (y - lo) / den : y);
     }
 }
 
-template <typename T>
-__global__ void k_minmax_partial(const T *__restrict__ I1, const T *__restrict__ I2, int size,
-                                 double *__restrict__ part /* [2][MM_BLOCKS] */)
+size_t op_minmax_scratch_doubles(int nsets, size_t npix, int nz, int chunks)
 {
-    minmax_partial_block<T>(I1, I2, size, part);
+    return (size_t) nsets * nz * (2 + 2 * (size_t) chunks * mm_blocks(npix));
 }
-__global__ void k_minmax_final(const double *__restrict__ part, int nblocks, double *__restrict__ mm)
-{
-    minmax_final_block(part, nblocks, mm);
-}
-template <typename T>
-__global__ void k_normalize2(const T *__restrict__ I1, const T *__restrict__ I2, T *__restrict__ o1,
-                             T *__restrict__ o2, int size, const double *__restrict__ mm)
-{
-    normalize2_px<T>(I1, I2, o1, o2, size, mm);
-}
-// the same three kernels for the G pairs of a lockstep group in one launch each (blockIdx.y = pair); the inputs are the
-// caller's separate device images, the outputs level arrays that hold the pairs back to back
-template <typename T> __global__ void k_minmax_partial_g(OfxGroupPtrs P, int size, double *__restrict__ scr)
-{
-    const int g = blockIdx.y;
-    minmax_partial_block<T>((const T *) P.a[g], (const T *) P.b[g], size, scr + (size_t) g * MM_SCR);
-}
-__global__ void k_minmax_final_g(double *__restrict__ scr, int nblocks)
-{
-    double *s = scr + (size_t) blockIdx.x * MM_SCR;
-    minmax_final_block(s, nblocks, s + 2 * MM_BLOCKS);
-}
-template <typename T>
-__global__ void k_normalize2_g(OfxGroupPtrs P, T *__restrict__ o1, T *__restrict__ o2, int size, const double *__restrict__ scr)
-{
-    const int g = blockIdx.y;
-    normalize2_px<T>((const T *) P.a[g], (const T *) P.b[g], o1 + (size_t) g * size, o2 + (size_t) g * size, size,
-                     scr + (size_t) g * MM_SCR + 2 * MM_BLOCKS);
-}
+size_t op_pyramid_scratch_doubles() { return 2 + 2 * MM_BLOCKS; }      // a pair: one set, one channel, one chunk
+const double *op_minmax_result(const double *scr) { return scr; }
 
-template <typename T>
-int op_normalize2(ofx_ctx *ctx, const T *I1, const T *I2, T *o1, T *o2, int size, double *scr)
+static int minmax_check(ofx_ctx *ctx, int nsets, int per, size_t npix, int nz)
 {
-    int nb = grid1d((size_t) size);
-    if (nb > MM_BLOCKS) nb = MM_BLOCKS;
-    double *part = scr, *mm = scr + 2 * MM_BLOCKS;
-    hipLaunchKernelGGL(k_minmax_partial<T>, dim3(nb), dim3(256), 0, ctx->stream, I1, I2, size, part);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(256), 0, ctx->stream, part, nb, mm);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_normalize2<T>, dim3(grid1d((size_t) size)), dim3(256), 0, ctx->stream, I1, I2, o1, o2,
-                       size, mm);
+    if (nsets < 1 || per < 1 || nsets * per > OFX_MM_MAX_SRC || nz < 1 || npix < 1 || npix * nz > 0x7fffffffULL)
+        return ofx_fail(ctx, OFX_ERR_ARG, "minmax: %d sets of %d sources, %zu x %d elements", nsets, per, npix, nz);
+    return OFX_OK;
+}
+template <typename S>
+int op_minmax_partial(ofx_ctx *ctx, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr, int chunk, int chunks)
+{
+    OFX_TRY(minmax_check(ctx, nsets, per, npix, nz));
+    const int nb = mm_blocks(npix);
+    hipLaunchKernelGGL(k_minmax_partial<S>, dim3(nb * nz, nsets), dim3(256), 0, ctx->stream, src, per, npix, nz, nb, chunk * nb,
+                       chunks * nb, scr);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
+}
+int op_minmax_final(ofx_ctx *ctx, int nsets, size_t npix, int nz, double *scr, int chunks)
+{
+    OFX_TRY(minmax_check(ctx, nsets, 1, npix, nz));
+    hipLaunchKernelGGL(k_minmax_final, dim3(nsets * nz), dim3(256), 0, ctx->stream, scr, chunks * mm_blocks(npix));
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+template <typename T, typename S>
+int op_normalize_map(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                     const double *scr, int guard)
+{
+    OFX_TRY(minmax_check(ctx, nsets, per, npix, nz));
+    hipLaunchKernelGGL((k_normalize_map<T, S>), dim3(grid1d(npix * nz), nsets), dim3(256), 0, ctx->stream, src, dst, per, npix * nz, nz,
+                       scr, guard);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+template <typename T, typename S>
+int op_normalize_sets(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz, double *scr,
+                      int guard)
+{
+    OFX_TRY(op_minmax_partial<S>(ctx, src, nsets, per, npix, nz, scr));
+    OFX_TRY(op_minmax_final(ctx, nsets, npix, nz, scr));
+    return op_normalize_map<T, S>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
 }
 
 // ---- gaussian (src/operators.cpp:506-624) -----------------------------------------------------------
@@ -277,11 +285,6 @@ OFX_DEV void gauss_pass_px(const T *__restrict__ in, T *__restrict__ out, int nx
     stn(out + p, sum);
 }
 template <typename T, bool ALONG_X>
-__global__ void k_gauss_pass(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, GaussTaps taps)
-{
-    gauss_pass_px<T, ALONG_X>(in, out, nx, ny, taps);
-}
-template <typename T, bool ALONG_X>
 __global__ void k_gauss_pass_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, GaussTaps taps)
 {
     gauss_pass_px<T, ALONG_X>(in.at(blockIdx.z), out.at(blockIdx.z), nx, ny, taps);
@@ -290,7 +293,7 @@ __global__ void k_gauss_pass_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx
 // Both passes in one launch for the pyramids of a lockstep group: a block brings a (GXY_TH + 2 r) x (64 + 2 r) region of the
 // input into LDS (reflected indices resolved while loading), runs the row pass on all of its rows, then the column pass on the
 // GXY_TH inner ones -- the intermediate image never touches memory (the two-pass form writes and re-reads it: 4 plane moves
-// instead of 2).  Per pixel the same sums in the same order as k_gauss_pass, the intermediate rounded to the storage type as
+// instead of 2).  Per pixel the same sums in the same order as k_gauss_pass_g, the intermediate rounded to the storage type as
 // the two-pass form stores it.  in != out (neighbouring blocks read what a block would overwrite).  Radius <= GXY_RMAX.
 #define GXY_TH 32
 #define GXY_RMAX 8
@@ -450,39 +453,27 @@ static void gauss_xy_launch(ofx_ctx *ctx, dim3 grid, OfxPlanes2<const T> in, Ofx
 #undef OFX_GXY
 }
 
-template <typename T> int op_gaussian(ofx_ctx *ctx, T *I, T *tmp, int nx, int ny, double sigma, int dirichlet)
+// The taps of a Gaussian on an nx x ny image, or the error.  The reference throws when size > xdim (:520-522) and reads out of
+// bounds when size == xdim or size >= ydim -- all three are reported as OFX_ERR_SIGMA here.  (Dirichlet: no check, the padded
+// line always has room.)
+static int gauss_taps_checked(ofx_ctx *ctx, double sigma, int nx, int ny, int dirichlet, GaussTaps *taps)
 {
-    GaussTaps taps;
-    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
+    if (ofx_gauss_taps(sigma, taps) != OFX_OK)
         return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
-    taps.dirichlet = dirichlet != 0;
-    // reference: throws when size > xdim (:520-522); reads out of bounds when size == xdim or
-    // size >= ydim -- all three are reported as OFX_ERR_SIGMA here.  (Dirichlet: no check, the padded line always has room.)
-    if (!dirichlet && (taps.size >= nx || taps.size >= ny))
-        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)",
-                        taps.size, nx, ny);
-    hipLaunchKernelGGL((k_gauss_pass<T, true>), grid2d(nx, ny), block2d(), 0, ctx->stream, (const T *) I, tmp,
-                       nx, ny, taps);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_gauss_pass<T, false>), grid2d(nx, ny), block2d(), 0, ctx->stream, (const T *) tmp, I,
-                       nx, ny, taps);
-    OFX_LAUNCH_CHECK(ctx);
+    taps->dirichlet = dirichlet != 0;
+    if (!dirichlet && (taps->size >= nx || taps->size >= ny))
+        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps->size, nx, ny);
     return OFX_OK;
 }
 
-// op_gaussian on the first nx * ny elements of `count` images, one launch per pass (blockIdx.z = image): images 0 .. split - 1
-// start at A, the others at B, each `stride` elements after the one before; tmp holds count planes of nx * ny.  Per pixel
-// k_gauss_pass.
+// gaussian in place on the first nx * ny elements of `count` images, one launch per pass (blockIdx.z = image): images
+// 0 .. split - 1 start at A, the others at B, each `stride` elements after the one before; tmp holds count planes of nx * ny.
 template <typename T>
 int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
 {
     GaussTaps taps;
     if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: %d planes (%d first)", count, split);
-    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
-        return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sigma, OFX_GAUSS_MAX_TAPS);
-    taps.dirichlet = dirichlet != 0;
-    if (!dirichlet && (taps.size >= nx || taps.size >= ny))           // op_gaussian's rule
-        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    OFX_TRY(gauss_taps_checked(ctx, sigma, nx, ny, dirichlet, &taps));
     const size_t n = (size_t) nx * ny;
     dim3 g = grid2d(nx, ny);
     g.z = count;
@@ -512,12 +503,6 @@ OFX_DEV void resample_px(const T *__restrict__ in, T *__restrict__ out, int nx, 
     const double i2 = i1 / fy, j2 = j1 / fx;
     const BicubicTaps t = bicubic_taps(j2, i2, nx, ny);
     stn(out + (size_t) i1 * nxx + j1, bicubic_sample(in, t, nx));
-}
-template <typename T>
-__global__ void k_resample(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nxx, int nyy,
-                           double fx, double fy)
-{
-    resample_px<T>(in, out, nx, ny, nxx, nyy, fx, fy);
 }
 template <typename T>
 __global__ void k_resample_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, int nxx, int nyy, double fx, double fy)
@@ -580,7 +565,8 @@ __global__ void k_zoom_in_planes3(OfxPlanes3<const T> in, OfxPlanes3<T> out, int
 template <typename T>
 int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx, int ny, int nxx, int nyy, double fx, double fy)
 {
-    hipLaunchKernelGGL(k_resample<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, in, out, nx, ny, nxx, nyy, fx, fy);
+    hipLaunchKernelGGL(k_resample_g<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, OfxPlanes2<const T>{in, nullptr, 1, 0},
+                       OfxPlanes2<T>{out, nullptr, 1, 0}, nx, ny, nxx, nyy, fx, fy);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -611,22 +597,13 @@ int op_zoom_in_planes3(ofx_ctx *ctx, int G, const T *u1, const T *u2, const T *c
     return OFX_OK;
 }
 
-template <typename T>
-int op_zoom_out(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, double factor)
-{
-    int nxx, nyy;
-    ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
-    const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.cpp:15,60
-    OFX_HIP(ctx, hipMemcpyAsync(tmpA, I, (size_t) nx * ny * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-    OFX_TRY(op_gaussian<T>(ctx, tmpA, tmpB, nx, ny, sigma));
-    return op_resample<T>(ctx, tmpA, Iout, nx, ny, nxx, nyy, factor, factor);
-}
-
-// ---- zoom_out of nz interleaved channels (IPOL original of robust_expo_methods, zoom.h:45-85 with gaussian.h:23-168) ----
-// Channel k of the result is zoom_out of channel k: per pixel the sums and the cubics of k_gauss_pass / bicubic_sample in the
-// same order, on the interleaved image itself.
+// ---- zoom_out (src/zoom.cpp:41-78), of nz interleaved channels (IPOL original of robust_expo_methods, zoom.h:45-85 with
+// gaussian.h:23-168) ----
+// Channel k of the result is zoom_out of channel k: per pixel the sums and the cubics of gauss_pass_px / bicubic_sample in the
+// same order, on the interleaved image itself; with nz = 1 the row pass is gauss_pass_px<T, true>'s reflecting branch and the
+// sample stage resample_px, term for term.
 // Row pass: a row is nx * nz contiguous elements, one lane per ELEMENT (a wave loads 64 consecutive elements per tap); the
-// taps are nz elements apart and the reflection is taken on the pixel index.  The column pass is k_gauss_pass<T, false> on an
+// taps are nz elements apart and the reflection is taken on the pixel index.  The column pass is k_gauss_pass_g<T, false> on an
 // image of nx * nz columns: the channels of a column are independent columns there.
 template <typename T>
 OFX_DEV void gauss_row_ch_px(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, const GaussTaps &taps)
@@ -640,11 +617,6 @@ OFX_DEV void gauss_row_ch_px(const T *__restrict__ in, T *__restrict__ out, int 
     for (int t = 1; t < taps.size; t++)
         sum += taps.B[t] * (ldw(row + (size_t) gauss_reflect(j - t, nx) * nz) + ldw(row + (size_t) gauss_reflect(j + t, nx) * nz));
     stn(out + (size_t) i * nx * nz + e, sum);
-}
-template <typename T>
-__global__ void k_gauss_row_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, GaussTaps taps)
-{
-    gauss_row_ch_px<T>(in, out, nx, ny, nz, taps);
 }
 template <typename T>
 __global__ void k_gauss_row_ch_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, int nz, GaussTaps taps)
@@ -676,41 +648,14 @@ OFX_DEV void resample_ch_px(const T *__restrict__ in, T *__restrict__ out, int n
     }
 }
 template <typename T>
-__global__ void k_resample_ch(const T *__restrict__ in, T *__restrict__ out, int nx, int ny, int nz, int nxx, int nyy, double factor)
-{
-    resample_ch_px<T>(in, out, nx, ny, nz, nxx, nyy, factor);
-}
-template <typename T>
 __global__ void k_resample_ch_g(OfxPlanes2<const T> in, OfxPlanes2<T> out, int nx, int ny, int nz, int nxx, int nyy, double factor)
 {
     resample_ch_px<T>(in.at(blockIdx.z), out.at(blockIdx.z), nx, ny, nz, nxx, nyy, factor);
 }
 
-template <typename T>
-int op_zoom_out_channels(ofx_ctx *ctx, const T *I, T *Iout, T *tmpA, T *tmpB, int nx, int ny, int nz, double factor)
-{
-    int nxx, nyy;
-    ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
-    const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.h:21,66
-    GaussTaps taps;
-    if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
-    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
-        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
-    if (taps.size >= nx || taps.size >= ny)                               // op_gaussian's rule
-        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
-    hipLaunchKernelGGL(k_gauss_row_ch<T>, grid2d(nx * nz, ny), block2d(), 0, ctx->stream, I, tmpA, nx, ny, nz, taps);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_gauss_pass<T, false>), grid2d(nx * nz, ny), block2d(), 0, ctx->stream, (const T *) tmpA, tmpB, nx * nz, ny, taps);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_resample_ch<T>, grid2d(nxx, nyy), block2d(), 0, ctx->stream, (const T *) tmpB, Iout, nx, ny, nz, nxx, nyy, factor);
-    OFX_LAUNCH_CHECK(ctx);
-    return OFX_OK;
-}
-
-// op_zoom_out_channels for `count` images, one launch per stage (blockIdx.z = image; the counterpart of op_build_pyramid_group
-// for interleaved channels): images 0 .. split - 1 lie back to back at A, the others at B, nx * ny * nz elements each, the
-// zoomed ones likewise at oA / oB; tmpA, tmpB are scratch for count images of nx * ny * nz.  Every image is computed by the
-// single-image path's per-pixel code.
+// `count` images, one launch per stage (blockIdx.z = image; the counterpart of op_build_pyramid_group for interleaved
+// channels): images 0 .. split - 1 lie back to back at A, the others at B, nx * ny * nz elements each, the zoomed ones
+// likewise at oA / oB; tmpA, tmpB are scratch for count images of nx * ny * nz.
 template <typename T>
 int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, const T *B, T *oA, T *oB, T *tmpA, T *tmpB, int nx,
                                 int ny, int nz, double factor)
@@ -722,10 +667,7 @@ int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, 
     if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count)
         return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %d images (%d first)", count, split);
     if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
-    if (ofx_gauss_taps(sigma, &taps) != OFX_OK)
-        return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: factor %g needs more than %d taps", factor, OFX_GAUSS_MAX_TAPS);
-    if (taps.size >= nx || taps.size >= ny)                               // op_gaussian's rule
-        return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+    OFX_TRY(gauss_taps_checked(ctx, sigma, nx, ny, 0, &taps));
     const size_t st = (size_t) nx * ny * nz, sto = (size_t) nxx * nyy * nz;
     dim3 g = grid2d(nx * nz, ny);
     g.z = count;
@@ -790,11 +732,6 @@ OFX_DEV void centered_gradient_px(const T *__restrict__ f, T *__restrict__ dx, T
     const size_t p = (size_t) i * nx + j;
     stn(dx + p, 0.5 * (ldw(f + (size_t) i * nx + jr) - ldw(f + (size_t) i * nx + jl)));
     stn(dy + p, 0.5 * (ldw(f + (size_t) id * nx + j) - ldw(f + (size_t) iu * nx + j)));
-}
-template <typename T>
-__global__ void k_centered_gradient(const T *__restrict__ f, T *__restrict__ dx, T *__restrict__ dy, int nx, int ny)
-{
-    centered_gradient_px<T>(f, dx, dy, nx, ny);
 }
 // planes back to back in all three arrays (blockIdx.z = plane)
 template <typename T>
@@ -912,13 +849,11 @@ template <typename T> int op_forward_gradient(ofx_ctx *ctx, const T *f, T *fx, T
 }
 template <typename T> int op_centered_gradient(ofx_ctx *ctx, const T *f, T *dx, T *dy, int nx, int ny)
 {
-    hipLaunchKernelGGL(k_centered_gradient<T>, grid2d(nx, ny), block2d(), 0, ctx->stream, f, dx, dy, nx, ny);
-    OFX_LAUNCH_CHECK(ctx);
-    return OFX_OK;
+    return op_centered_gradient_planes<T>(ctx, 1, f, dx, dy, nx, ny);
 }
 template <typename T> int op_centered_gradient_planes(ofx_ctx *ctx, int count, const T *f, T *dx, T *dy, int nx, int ny)
 {
-    if (count < 1 || count > 2 * OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "centered_gradient: %d planes", count);
+    if (count < 1 || count > 65535) return ofx_fail(ctx, OFX_ERR_ARG, "centered_gradient: %d planes", count);     // gridDim.z
     dim3 g = grid2d(nx, ny);
     g.z = count;
     hipLaunchKernelGGL(k_centered_gradient_g<T>, g, block2d(), 0, ctx->stream, f, dx, dy, nx, ny);
@@ -998,29 +933,10 @@ int op_pyramid_sizes(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor
     return OFX_OK;
 }
 
-size_t op_pyramid_scratch_doubles() { return (size_t) MM_SCR; }
-
-// lv[s] = sizes and DESTINATION arrays of every level (caller-allocated); tmpA / tmpB: full-size scratch
-// images, scr: op_pyramid_scratch_doubles() doubles.
-template <typename T>
-int op_build_pyramid_into(ofx_ctx *ctx, const T *dA, const T *dB, int nscales, double zfactor, double sigma,
-                          const std::vector<ImgLevel<T>> &lv, T *tmpA, T *tmpB, double *scr)
-{
-    const int nxx = lv[0].nx, nyy = lv[0].ny;
-    OFX_TRY(op_normalize2<T>(ctx, dA, dB, lv[0].A, lv[0].B, nxx * nyy, scr));
-    OFX_TRY(op_gaussian<T>(ctx, lv[0].A, tmpA, nxx, nyy, sigma));
-    OFX_TRY(op_gaussian<T>(ctx, lv[0].B, tmpA, nxx, nyy, sigma));
-    for (int s = 1; s < nscales; s++) {
-        OFX_TRY(op_zoom_out<T>(ctx, lv[s - 1].A, lv[s].A, tmpA, tmpB, lv[s - 1].nx, lv[s - 1].ny, zfactor));
-        OFX_TRY(op_zoom_out<T>(ctx, lv[s - 1].B, lv[s].B, tmpA, tmpB, lv[s - 1].nx, lv[s - 1].ny, zfactor));
-    }
-    return OFX_OK;
-}
-
-// The same prologue for the G pairs of a lockstep group with ONE launch per step for all 2 G images (per pair it is 39
-// launches, most of them tiny): lvA[s] / lvB[s] = level arrays holding the G images back to back, tmpA / tmpB = scratch
-// for 2 G full-size images each, scr = G * op_pyramid_scratch_doubles() doubles.  Same per-pixel arithmetic as
-// op_build_pyramid_into; zoom_out's scratch copy (zoom.cpp:54-57) is not made -- the first Gaussian pass reads the level itself.
+// The pyramid prologue for the G pairs of a lockstep group with ONE launch per step for all 2 G images (per pair it would be
+// 39 launches, most of them tiny): lvA[s] / lvB[s] = level arrays holding the G images back to back, tmpA / tmpB = scratch
+// for 2 G full-size images each, scr = G * op_pyramid_scratch_doubles() doubles.  Per pixel image_normalization_2, gaussian
+// and zoom_out; zoom_out's scratch copy (zoom.cpp:54-57) is not made -- the first Gaussian pass reads the level itself.
 template <typename T>
 int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const void *const *dB, int nscales, double zfactor,
                            double sigma, const int *nxs, const int *nys, T *const *lvA, T *const *lvB, T *tmpA, T *tmpB,
@@ -1028,14 +944,6 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "pyramid group of %d", G);
     const int nxx = nxs[0], nyy = nys[0], size = nxx * nyy;
-    OfxGroupPtrs P;
-    for (int g = 0; g < OFX_MAX_GROUP; g++) { P.a[g] = g < G ? dA[g] : nullptr; P.b[g] = g < G ? dB[g] : nullptr; }
-    int nb = grid1d((size_t) size);
-    if (nb > MM_BLOCKS) nb = MM_BLOCKS;
-    hipLaunchKernelGGL(k_minmax_partial_g<T>, dim3(nb, G), dim3(256), 0, ctx->stream, P, size, scr);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_minmax_final_g, dim3(G), dim3(256), 0, ctx->stream, scr, nb);
-    OFX_LAUNCH_CHECK(ctx);
     // fused row + column pass (k_gauss_xy_g) when the radius allows: it cannot work in place, so the normalised images go to
     // the scratch array and the presmoothing writes the level
     GaussTaps t0;
@@ -1043,15 +951,18 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
     bool fused = ctx->gauss_fused != 0 && ofx_gauss_taps(sigma, &t0) == OFX_OK && t0.size - 1 <= GXY_RMAX;
     if (fused && nscales > 1) fused = ofx_gauss_taps(zsigma, &t0) == OFX_OK && t0.size - 1 <= GXY_RMAX;
     T *n0 = fused ? tmpA : lvA[0], *n1 = fused ? tmpA + (size_t) G * size : lvB[0];
-    hipLaunchKernelGGL(k_normalize2_g<T>, dim3(grid1d((size_t) size), G), dim3(256), 0, ctx->stream, P, n0, n1, size,
-                       (const double *) scr);
-    OFX_LAUNCH_CHECK(ctx);
+    OfxSrcPtrs src = {};
+    OfxDstPtrs dst = {};
+    for (int g = 0; g < G; g++) {                                               // set g = pair g
+        src.p[2 * g] = dA[g];
+        src.p[2 * g + 1] = dB[g];
+        dst.p[2 * g] = n0 + (size_t) g * size;
+        dst.p[2 * g + 1] = n1 + (size_t) g * size;
+    }
+    OFX_TRY((op_normalize_sets<T, T>(ctx, src, dst, G, 2, (size_t) size, 1, scr)));
     auto gauss_xy = [&](const T *ia, const T *ib, T *oa, T *ob, int nx, int ny, double sg) -> int {
         GaussTaps taps;
-        if (ofx_gauss_taps(sg, &taps) != OFX_OK)
-            return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sg, OFX_GAUSS_MAX_TAPS);
-        if (taps.size >= nx || taps.size >= ny)
-            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+        OFX_TRY(gauss_taps_checked(ctx, sg, nx, ny, 0, &taps));
         const size_t st = (size_t) nx * ny;
         if (ctx->gauss_fused == 2)                         // the generic-radius kernel (A/B and tests)
             hipLaunchKernelGGL(k_gauss_xy_g<T>, dim3(ofx_cdiv(nx, 64), ofx_cdiv(ny, GXY_TH), 2 * G), dim3(64, 4), 0, ctx->stream,
@@ -1088,10 +999,7 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
     }
     auto gauss = [&](const T *ia, const T *ib, T *oa, T *ob, T *ta, T *tb, int nx, int ny, double sg) -> int {
         GaussTaps taps;
-        if (ofx_gauss_taps(sg, &taps) != OFX_OK)
-            return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: sigma %g needs more than %d taps", sg, OFX_GAUSS_MAX_TAPS);
-        if (taps.size >= nx || taps.size >= ny)
-            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+        OFX_TRY(gauss_taps_checked(ctx, sg, nx, ny, 0, &taps));
         const size_t st = (size_t) nx * ny;
         dim3 g = grid2d(nx, ny);
         g.z = 2 * G;
@@ -1120,27 +1028,6 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
 }
 
 template <typename T>
-int op_build_pyramid(ofx_ctx *ctx, const T *dA, const T *dB, int nxx, int nyy, int nscales, double zfactor,
-                     double sigma, std::vector<ImgLevel<T>> &lv)
-{
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    lv.resize(nscales);
-    for (int s = 0; s < nscales; s++) {
-        lv[s].nx = nxs[s];
-        lv[s].ny = nys[s];
-        OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s], &lv[s].A));
-        OFX_TRY(ofx_alloc(ctx, (size_t) nxs[s] * nys[s], &lv[s].B));
-    }
-    T *tmpA, *tmpB;
-    double *scr;
-    OFX_TRY(ofx_alloc(ctx, (size_t) nxx * nyy, &tmpA));
-    OFX_TRY(ofx_alloc(ctx, (size_t) nxx * nyy, &tmpB));
-    OFX_TRY(ofx_alloc(ctx, op_pyramid_scratch_doubles(), &scr));
-    return op_build_pyramid_into<T>(ctx, dA, dB, nscales, zfactor, sigma, lv, tmpA, tmpB, scr);
-}
-
-template <typename T>
 int op_bicubic_at_color(ofx_ctx *ctx, const T *in, const double *uu, const double *vv, double *out, int n, int nx, int ny,
                         int nz, int ch, int border_out)
 {
@@ -1158,18 +1045,6 @@ template <typename T> int op_gradient_dz(ofx_ctx *ctx, const T *in, T *dz, int n
     return OFX_OK;
 }
 
-// getminmax (src/utils.cpp:509-525) of one array: mm[0] = min, mm[1] = max on the device
-template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *scr)
-{
-    int nb = grid1d((size_t) size);
-    if (nb > MM_BLOCKS) nb = MM_BLOCKS;
-    hipLaunchKernelGGL(k_minmax_partial<T>, dim3(nb), dim3(256), 0, ctx->stream, x, x, size, scr);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(256), 0, ctx->stream, scr, nb, scr + 2 * MM_BLOCKS);
-    OFX_LAUNCH_CHECK(ctx);
-    return OFX_OK;
-}
-
 // ---- explicit instantiations -----------------------------------------------------------------------
 #define OFX_INSTANTIATE(T)                                                                                           \
     template int op_convert_in<T>(ofx_ctx *, const double *, T *, size_t);                                            \
@@ -1178,8 +1053,6 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
     template int op_deinterleave2<T>(ofx_ctx *, const Pix<T>::v2 *, double *, double *, size_t);                      \
     template int op_to_flo<T>(ofx_ctx *, const Pix<T>::v2 *, float2 *, size_t);                                       \
     template int op_fill2<T>(ofx_ctx *, Pix<T>::v2 *, size_t);                                                        \
-    template int op_normalize2<T>(ofx_ctx *, const T *, const T *, T *, T *, int, double *);                          \
-    template int op_gaussian<T>(ofx_ctx *, T *, T *, int, int, double, int);                                          \
     template int op_resample<T>(ofx_ctx *, const T *, T *, int, int, int, int, double, double);                       \
     template int op_zoom_in_flow<T>(ofx_ctx *, const Pix<T>::v2 *, Pix<T>::v2 *, int, int, int, int, double, int);    \
     template int op_gaussian_group<T>(ofx_ctx *, int, T *, T *, size_t, T *, int, int, double, int);                   \
@@ -1188,8 +1061,6 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
     template int op_zoom_in_planes3<T>(ofx_ctx *, int, const T *, const T *, const T *, T *, T *, T *, int, int, int, int, double); \
     template int op_centered_gradient_planes<T>(ofx_ctx *, int, const T *, T *, T *, int, int);                        \
     template int op_zoom_out_channels_group<T>(ofx_ctx *, int, const T *, const T *, T *, T *, T *, T *, int, int, int, double); \
-    template int op_zoom_out<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, double);                               \
-    template int op_zoom_out_channels<T>(ofx_ctx *, const T *, T *, T *, T *, int, int, int, double);                 \
     template int op_divergence<T>(ofx_ctx *, const T *, const T *, T *, int, int);                                    \
     template int op_forward_gradient<T>(ofx_ctx *, const T *, T *, T *, int, int);                                    \
     template int op_centered_gradient<T>(ofx_ctx *, const T *, T *, T *, int, int);                                   \
@@ -1201,11 +1072,11 @@ template <typename T> int op_minmax(ofx_ctx *ctx, const T *x, int size, double *
                                            const int *, const int *, T *const *, T *const *, T *, T *, double *);              \
     template int op_bicubic_at_color<T>(ofx_ctx *, const T *, const double *, const double *, double *, int, int, int, int, int, int); \
     template int op_gradient_dz<T>(ofx_ctx *, const T *, T *, int, int, int);                                                   \
-    template int op_minmax<T>(ofx_ctx *, const T *, int, double *);                                                             \
-    template int op_build_pyramid<T>(ofx_ctx *, const T *, const T *, int, int, int, double, double,                   \
-                                     std::vector<ImgLevel<T>> &);                                                      \
-    template int op_build_pyramid_into<T>(ofx_ctx *, const T *, const T *, int, double, double,                        \
-                                          const std::vector<ImgLevel<T>> &, T *, T *, double *);
+    template int op_minmax_partial<T>(ofx_ctx *, const OfxSrcPtrs &, int, int, size_t, int, double *, int, int);             \
+    template int op_normalize_map<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, const double *, int); \
+    template int op_normalize_sets<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int);
 
 OFX_INSTANTIATE(double)
 OFX_INSTANTIATE(float)
+// float storage fed with the doubles of a host image (the robust_expo host path rounds after the normalisation)
+template int op_normalize_sets<float, double>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int);

@@ -1983,57 +1983,6 @@ __global__ void k_rexpo_coeff_c(const T *__restrict__ I1, const typename Pix<T>:
     stn(Dm + i, psid * DI_Data + g * DI_Gradient);
 }
 
-// image_normalization_2_color (src/utils.cpp:334-406) on device data: per pair and channel the joint minimum / maximum of
-// both images (exact, order-independent), then 255 (x - min) / den, or a copy when den <= 0.  S = the type the images come in
-// (double: host images uploaded as they are; the storage type: the device images of a group), converted exactly to double;
-// blockIdx.z / blockIdx.y of the two kernels = pair.
-#define RX_MM_BLOCKS 64
-template <typename S>
-__global__ __launch_bounds__(256) void k_rexpo_mm_partial(OfxGroupPtrs P, size_t npix, int nz,
-                                                          double *__restrict__ part /* [G][nz][2][RX_MM_BLOCKS] */)
-{
-    const int c = blockIdx.y, pair = blockIdx.z;
-    const S *__restrict__ a = (const S *) P.a[pair], *__restrict__ b = (const S *) P.b[pair];
-    double lo = (double) a[c], hi = lo;
-    for (size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x; t < npix; t += (size_t) gridDim.x * blockDim.x) {
-        const double x = (double) a[t * nz + c], y = (double) b[t * nz + c];
-        lo = x < lo ? x : lo; hi = x > hi ? x : hi;
-        lo = y < lo ? y : lo; hi = y > hi ? y : hi;
-    }
-    __shared__ double slo[256], shi[256];
-    slo[threadIdx.x] = lo;
-    shi[threadIdx.x] = hi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int) threadIdx.x < s) {
-            const double l2 = slo[threadIdx.x + s], h2 = shi[threadIdx.x + s];
-            if (l2 < slo[threadIdx.x]) slo[threadIdx.x] = l2;
-            if (h2 > shi[threadIdx.x]) shi[threadIdx.x] = h2;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[(((size_t) pair * nz + c) * 2 + 0) * RX_MM_BLOCKS + blockIdx.x] = slo[0];
-        part[(((size_t) pair * nz + c) * 2 + 1) * RX_MM_BLOCKS + blockIdx.x] = shi[0];
-    }
-}
-// n = elements of ONE image; the images of pair g go to oa + g * n, ob + g * n
-template <typename T, typename S>
-__global__ void k_rexpo_norm_map(OfxGroupPtrs P, T *__restrict__ oa, T *__restrict__ ob, size_t n, int nz,
-                                 const double *__restrict__ part, int nblocks)
-{
-    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int c = (int) (e % nz), pair = blockIdx.y;
-    const double *pl = part + (((size_t) pair * nz + c) * 2 + 0) * RX_MM_BLOCKS, *ph = pl + RX_MM_BLOCKS;
-    double lo = pl[0], hi = ph[0];
-    for (int k = 1; k < nblocks; k++) { lo = pl[k] < lo ? pl[k] : lo; hi = ph[k] > hi ? ph[k] : hi; }
-    const double den = hi - lo;
-    const double a = (double) ((const S *) P.a[pair])[e], b = (double) ((const S *) P.b[pair])[e];
-    stn(oa + (size_t) pair * n + e, den > 0 ? 255.0 * (a - lo) / den : a);
-    stn(ob + (size_t) pair * n + e, den > 0 ? 255.0 * (b - lo) / den : b);
-}
-
 // One level of a lockstep group: every array holds G pairs back to back (pair g at element g * nx * ny).
 template <typename T> struct BroxLevel {
     using v2 = typename Pix<T>::v2;
@@ -2414,17 +2363,21 @@ template <typename T, typename S>
 static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nx, int ny, int nz, T *A, T *B)
 {
     const size_t n = (size_t) nx * ny, nc = n * nz;
-    double *part;
+    double *scr;
     T *tmp;
-    OFX_TRY(ofx_alloc(ctx, (size_t) G * nz * 2 * RX_MM_BLOCKS, &part));
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(G, n, nz), &scr));
     OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * n, &tmp));
-    int nb = (int) ((n + 255) / 256);
-    if (nb > RX_MM_BLOCKS) nb = RX_MM_BLOCKS;
-    hipLaunchKernelGGL(k_rexpo_mm_partial<S>, dim3(nb, nz, G), dim3(256), 0, ctx->stream, src, n, nz, part);
-    OFX_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_rexpo_norm_map<T, S>), dim3((unsigned) ((nc + 255) / 256), G), dim3(256), 0, ctx->stream, src, A, B, nc, nz,
-                       (const double *) part, nb);
-    OFX_LAUNCH_CHECK(ctx);
+    // image_normalization_2_color (src/utils.cpp:334-406): per pair and channel the joint minimum / maximum of both images,
+    // then 255 (x - min) / den, or a copy when den <= 0
+    OfxSrcPtrs in = {};
+    OfxDstPtrs out = {};
+    for (int g = 0; g < G; g++) {
+        in.p[2 * g] = src.a[g];
+        in.p[2 * g + 1] = src.b[g];
+        out.p[2 * g] = A + g * nc;
+        out.p[2 * g + 1] = B + g * nc;
+    }
+    OFX_TRY((op_normalize_sets<T, S>(ctx, in, out, G, 2, n, nz, scr)));
     // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
     // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
     // so only the first nx * ny elements of each interleaved image are smoothed (across pixels and channels alike)
@@ -2458,7 +2411,7 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
 }
 
 // The multiscale overload (src/robust_expo_methods.cpp:482-566) on nz interleaved channels at any number of scales, with ONE
-// call replaced: the levels come from op_zoom_out_channels -- the zoom_out of the IPOL original, each channel as zoom_out --
+// call replaced: the levels come from op_zoom_out_channels_group -- the zoom_out of the IPOL original, each channel as zoom_out --
 // where the reference's zoom_out_color reads beyond its scratch copy (zoom.cpp:96-118).  Everything else is the reference's
 // driver: the head above, a zero flow at the coarsest level, brox_single_scale_dev and op_zoom_in_flow per level.  Every
 // robust_expo entry but the single-scale one runs it.
@@ -3059,68 +3012,9 @@ static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxPara
 
 // ---- the driver, src/brox_optic_flow_temporal.cpp:520-627, on a device-resident sequence ------------------------------------
 // Every stage outside the level solver is one launch for all frames / flow fields (the frame or field in blockIdx.z or .y) with
-// the single-image path's per-pixel code.  The caller's frames reach the head through a by-value pointer table of
-// OFX_BROXT_MAX_FRAMES entries; a longer sequence (the host entry takes any length) goes through in chunks of that many.
-struct BroxtFrames { const void *f[OFX_BROXT_MAX_FRAMES]; };
+// the operators' per-pixel code.  The caller's frames reach the head through the by-value pointer table of ofx_ops.h
+// (OFX_BROXT_MAX_FRAMES entries); a longer sequence (the host entry takes any length) goes through in chunks of that many.
 struct BroxtFlos { float2 *flo[OFX_BROXT_MAX_FRAMES]; };
-#define BROXT_MM_BLOCKS 32                                        // partial minima / maxima per frame
-
-// getminmax over the frames of a chunk (exact, so the order is free): block (x, y) covers a stride of frame y and writes its
-// minimum / maximum to lo[y * BROXT_MM_BLOCKS + x] / hi[...]
-template <typename T>
-__global__ __launch_bounds__(256) void k_broxt_mm_partial(BroxtFrames in, int n, double *__restrict__ lo_out, double *__restrict__ hi_out)
-{
-    const T *__restrict__ I = static_cast<const T *>(in.f[blockIdx.y]);
-    double lo = ldw(I), hi = lo;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += BROXT_MM_BLOCKS * 256) {
-        const double a = ldw(I + i);
-        lo = a < lo ? a : lo; hi = a > hi ? a : hi;
-    }
-    lo = wave_allreduce_min(lo);
-    hi = wave_allreduce_max(hi);
-    __shared__ double slo[4], shi[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
-        lo_out[blockIdx.y * BROXT_MM_BLOCKS + blockIdx.x] = lo;
-        hi_out[blockIdx.y * BROXT_MM_BLOCKS + blockIdx.x] = hi;
-    }
-}
-// one block: the `count` partial minima / maxima -> mm[0] = min, mm[1] = max
-__global__ __launch_bounds__(256) void k_broxt_mm_final(const double *__restrict__ lo_in, const double *__restrict__ hi_in, int count,
-                                                        double *__restrict__ mm)
-{
-    double lo = lo_in[0], hi = hi_in[0];
-    for (int i = threadIdx.x; i < count; i += 256) {
-        lo = lo_in[i] < lo ? lo_in[i] : lo;
-        hi = hi_in[i] > hi ? hi_in[i] : hi;
-    }
-    lo = wave_allreduce_min(lo);
-    hi = wave_allreduce_max(hi);
-    __shared__ double slo[4], shi[4];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { slo[w] = lo; shi[w] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) { lo = slo[k] < lo ? slo[k] : lo; hi = shi[k] > hi ? shi[k] : hi; }
-        mm[0] = lo;
-        mm[1] = hi;
-    }
-}
-// image_normalization_1 (src/utils.cpp): 255 (I - min) / den, a copy when den = 0 -- normalize2_px's arithmetic; frame
-// blockIdx.z of the chunk into the frame-major level
-template <typename T> __global__ void k_broxt_norm(BroxtFrames in, T *__restrict__ out, int n, const double *__restrict__ mm)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double lo = mm[0], den = mm[1] - mm[0];
-    const double a = ldw(static_cast<const T *>(in.f[blockIdx.z]) + i);
-    T *o = out + (size_t) blockIdx.z * n + i;
-    if (den > 0) stn(o, 255.0 * (a - lo) / den);
-    else stn(o, a);
-}
 // the .flo payloads of flow fields blockIdx.z of a chunk: (float) u, (float) v interleaved, as k_to_flo
 template <typename T> __global__ void k_broxt_out(const typename Pix<T>::v2 *__restrict__ U, BroxtFlos out, int n)
 {
@@ -3131,7 +3025,7 @@ template <typename T> __global__ void k_broxt_out(const typename Pix<T>::v2 *__r
 }
 
 // What every temporal entry checks before any work, in the order in which the solve would meet it: the pyramid's sizes, the
-// presmoothing Gaussian on level 0 and the zoom Gaussian on every level that is zoomed out (op_gaussian's rule), the 3x3
+// presmoothing Gaussian on level 0 and the zoom Gaussian on every level that is zoomed out (op_gaussian_planes' rule), the 3x3
 // minimum of the level solver and the index range.
 static int broxt_check(ofx_ctx *ctx, int frames, int nxx, int nyy, int nscales, double nu, int inner_iter, int outer_iter,
                        std::vector<int> &nxs, std::vector<int> &nys)
@@ -3167,34 +3061,30 @@ static int broxt_sequence_dev(ofx_ctx *ctx, int frames, const void *const *dF, c
     const size_t n = (size_t) nx * ny;
     sor_stats_begin(ctx, nscales, P.inner_iter * P.outer_iter);
     T *tmpA, *tmpB = nullptr;
-    double *mm;                                                  // [frames * BROXT_MM_BLOCKS] minima, the maxima, {min, max}
-    const int parts = frames * BROXT_MM_BLOCKS;
+    double *mm;
+    const int chunks = (frames + MF - 1) / MF;
     OFX_TRY(ofx_alloc(ctx, n * frames, &tmpA));
     if (nscales > 1) OFX_TRY(ofx_alloc(ctx, n * frames, &tmpB));
-    OFX_TRY(ofx_alloc(ctx, (size_t) 2 * parts + 2, &mm));
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, n, 1, chunks), &mm));
     lv.resize(nscales);
     for (int s = 0; s < nscales; s++) {
         OFX_TRY(broxt_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], frames));
         if (s < OFX_MAX_SCALES) { ctx->stats.nx[s] = nxs[s]; ctx->stats.ny[s] = nys[s]; }
     }
-    // image_normalization_1 over the whole sequence (:548)
+    // image_normalization_1 over the whole sequence (:548): one set of all frames, a chunk of the table's size per launch
     for (int f0 = 0; f0 < frames; f0 += MF) {
         const int cnt = frames - f0 < MF ? frames - f0 : MF;
-        BroxtFrames in = {};
-        for (int k = 0; k < cnt; k++) in.f[k] = dF[f0 + k];
-        hipLaunchKernelGGL(k_broxt_mm_partial<T>, dim3(BROXT_MM_BLOCKS, cnt), dim3(256), 0, ctx->stream, in, (int) n,
-                           mm + (size_t) f0 * BROXT_MM_BLOCKS, mm + parts + (size_t) f0 * BROXT_MM_BLOCKS);
+        OfxSrcPtrs in = {};
+        for (int k = 0; k < cnt; k++) in.p[k] = dF[f0 + k];
+        OFX_TRY(op_minmax_partial<T>(ctx, in, 1, cnt, n, 1, mm, f0 / MF, chunks));
     }
-    hipLaunchKernelGGL(k_broxt_mm_final, dim3(1), dim3(256), 0, ctx->stream, (const double *) mm, (const double *) (mm + parts), parts,
-                       mm + 2 * parts);
-    OFX_LAUNCH_CHECK(ctx);
+    OFX_TRY(op_minmax_final(ctx, 1, n, 1, mm, chunks));
     for (int f0 = 0; f0 < frames; f0 += MF) {
         const int cnt = frames - f0 < MF ? frames - f0 : MF;
-        BroxtFrames in = {};
-        for (int k = 0; k < cnt; k++) in.f[k] = dF[f0 + k];
-        hipLaunchKernelGGL(k_broxt_norm<T>, dim3((unsigned) ((n + 255) / 256), 1, cnt), dim3(256), 0, ctx->stream, in, lv[0].I + f0 * n,
-                           (int) n, (const double *) (mm + 2 * parts));
-        OFX_LAUNCH_CHECK(ctx);
+        OfxSrcPtrs in = {};
+        OfxDstPtrs out = {};
+        for (int k = 0; k < cnt; k++) { in.p[k] = dF[f0 + k]; out.p[k] = lv[0].I + (f0 + k) * n; }
+        OFX_TRY((op_normalize_map<T, T>(ctx, in, out, 1, cnt, n, 1, mm)));
         OFX_TRY(op_gaussian_planes<T>(ctx, cnt, cnt, lv[0].I + f0 * n, nullptr, n, tmpA, nx, ny, BROX_SIGMA));          // :551-553
     }
     for (int s = 1; s < nscales; s++) {                                                              // :561-575

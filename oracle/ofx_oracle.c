@@ -203,7 +203,7 @@ static inline int gauss_reflect(int t, int n)
     return t < 0 ? -t : (t >= n ? 2 * n - 1 - t : t);
 }
 
-/* store_f32: the HIP path's float storage (op_gaussian<float>, csrc/ofx_ops.hip) -- the row pass is stored into a float
+/* store_f32: the HIP path's float storage (op_gaussian_planes<float>, csrc/ofx_ops.hip) -- the row pass is stored into a float
  * plane before the column pass reads it, and the result is stored as float */
 static int gaussian(double *I, int nx, int ny, double sigma, int store_f32)
 {
@@ -319,8 +319,8 @@ void orc_zoom_size(int nx, int ny, int *nxx, int *nyy, double factor)
     *nyy = (int) (ny * factor + 0.5);
 }
 
-/* src/zoom.cpp:41-78.  store_f32: op_zoom_out<float> (csrc/ofx_ops.hip) -- float input, the smoothed image as
- * op_gaussian<float> stores it, the output stored as float. */
+/* src/zoom.cpp:41-78.  store_f32: op_zoom_out_channels_planes<float> (csrc/ofx_ops.hip) -- float input, the smoothed image as
+ * op_gaussian_planes<float> stores it, the output stored as float. */
 static int zoom_out(const double *I, double *Iout, int nx, int ny, double factor, int store_f32)
 {
     double *Is = dalloc((size_t) nx * ny);

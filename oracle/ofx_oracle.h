@@ -79,7 +79,7 @@ void orc_tvl1_single_scale_mode(const double *I0, const double *I1, double *u1, 
 int  orc_tvl1_multiscale_mode(const double *I0, const double *I1, double *u1, double *u2, int nx, int ny,
                               double tau, double lambda, double theta, int nscales, double zfactor,
                               int warps, double epsilon, int verbose, int *iters, double *errs, int relaxed);
-/* store_f32 = 1: op_gaussian<float> / op_zoom_out<float> -- input, intermediate of the two passes, smoothed image and
+/* store_f32 = 1: op_gaussian_planes<float> / op_zoom_out_channels_planes<float> -- input, intermediate of the two passes, smoothed image and
  * output rounded to float where the GPU stores them */
 int  orc_gaussian_mode(double *I, int nx, int ny, double sigma, int store_f32);
 int  orc_zoom_out_mode(const double *I, double *Iout, int nx, int ny, double factor, int store_f32);

@@ -5,7 +5,7 @@ contract is bit for bit: payload f == float32 of (u[f], v[f]) of the host entry 
 sweep tables.  Every comparison is np.array_equal.  The frames are integers (synth.sequence floors), exact in float32 too.
 
 Two shapes of the issue's list, 3x3 and 67x5, are not solvable by EITHER entry: the presmoothing Gaussian (sigma 0.8, radius
-(int) (5 sigma) + 1 = 5) must be smaller than both image sides (op_gaussian's rule: the reference throws or reads out of bounds
+(int) (5 sigma) + 1 = 5) must be smaller than both image sides (op_gaussian_planes' rule: the reference throws or reads out of bounds
 there), so ofx_brox_temporal returns OFX_ERR_SIGMA on them, and did before the device entries existed.  "Equal to the host entry"
 is therefore asserted uniformly for every shape as: the same status, and on success the same payload and sweep table; on an
 error the sentinel-filled payloads are untouched.  The smallest shapes that do solve, 6x6 (the one-sided temporal differences
