@@ -434,6 +434,9 @@ int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, double *v, int n
  * the same values under equal options (sor_exact, sor_fuse: the entries share the level solver).  3 <= frames <= OFX_BROXT_MAX_FRAMES (the frames reach the kernels through a by-value pointer table).
  * Asynchronous on the context's stream: the stopping tests are resolved on return, the payloads are complete once the stream
  * is synchronised.  ofx_get_stats is filled as by ofx_brox_temporal.
+ * The stopping values of the exact mode (ofx_stats.error, for this entry and ofx_brox_temporal alike) are the same in every run while
+ * (frames - 1) * row blocks of 64 rows * waves per block <= 64 on every level: each then adds into a shard of its own; on larger
+ * levels several workgroups add atomically into one shard and the last bits may depend on the order in which they arrive.
  * Every error is found before any work and no byte of d_flo is written: what ofx_brox_temporal rejects (frames <= 2, images
  * or a level below 3x3, negative iteration counts, OFX_ERR_SIGMA when a Gaussian of the pyramid does not fit its level), more
  * than OFX_BROXT_MAX_FRAMES frames, a NULL array, a NULL or misaligned pointer (its index is in ofx_last_error). */
@@ -441,8 +444,39 @@ int ofx_brox_temporal(ofx_ctx *ctx, const double *I, double *u, double *v, int n
 int ofx_brox_temporal_dev(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy, double alpha,
                           double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter);
 
+/* A LOCKSTEP GROUP of n_seq (1 .. 16) sequences of `frames` frames each through the same kernel launches on one context: dF holds
+ * n_seq * frames pointers (sequence q at dF + q * frames), d_flo n_seq * (frames - 1) (sequence q at d_flo + q * (frames - 1)),
+ * frames and payloads as for ofx_brox_temporal_dev; frames may be shared between sequences or repeated within one.  Every
+ * sequence keeps its own normalisation (image_normalization_1 over that sequence alone), stopping test, sweep counts, snapshots
+ * and, under sor_exact = 0, ping-pong phase: sequence q's payload is bit for bit what ofx_brox_temporal_dev writes for it
+ * alone on a context with the same options (sor_exact = 1, 2 or 0, every sor_fuse, both storage types), and its sweep table
+ * [scale][solve] is the lone solve's.  In the exact mode its stopping values are the lone solve's too: a group keeps the lone
+ * entry's window geometry (8 steps per launch, 64 rows per block; options sor_window / sor_rows override both entries alike)
+ * and its windows cut every sweep by the sweep's number in the solve, so the stopping sum is associated as alone.  (Every
+ * frame, row block and wave of a sweep adds into a shard of its own while (frames - 1) * row blocks * waves per block <= 64;
+ * on larger levels several workgroups add atomically into one shard, for the lone entry as for a group, and the last bits of
+ * a stopping value may then depend on the order in which they arrive.)
+ * What a group shares is every launch: normalisation, presmoothing and the pyramid over all n_seq * frames planes (as many
+ * per launch as the by-value pointer tables hold), the per-level kernels and the SOR windows / tile sweeps with the sequence in
+ * the grid.  A sequence that has stopped drops out of the windows that follow.
+ * stats_out: NULL or n_seq records, each filled as ofx_brox_temporal_dev fills the context's; ofx_get_stats holds sequence 0's
+ * afterwards.  Asynchronous on the context's stream like ofx_brox_temporal_dev.  Memory: n_seq times the per-sequence figure
+ * given for the batch entry below.
+ * Every error is found before any work and no byte of any payload is written: what ofx_brox_temporal_dev rejects, checked for
+ * every sequence (sequence and frame index in ofx_last_error), n_seq outside 1 .. 16, and a group of 2^31 voxels (nxx * nyy *
+ * frames * n_seq) or more. */
+int ofx_brox_temporal_group_dev(ofx_ctx *ctx, int n_seq, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy,
+                                double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
+                                ofx_stats *stats_out);
+
 /* n_seq independent sequences of `frames` frames each: dF holds n_seq * frames pointers (sequence q at dF + q * frames), d_flo
- * n_seq * (frames - 1) (sequence q at d_flo + q * (frames - 1)).  Sequence q is solved by ofx_brox_temporal_dev on
+ * n_seq * (frames - 1) (sequence q at d_flo + q * (frames - 1)).
+ * Option "lockstep" of ctxs[0] = L >= 2 (opt-in): lockstep groups of L consecutive sequences (a last, smaller group is normal),
+ * group q through ofx_brox_temporal_group_dev on ctxs[q % contexts at work], EVERY context under ctxs[0]'s sor_exact / sor_fuse
+ * for the call (also when the memory rule or n_seq leaves groups of one); the payloads are bit for bit the lone entry's under those options.  The memory rule below then counts the
+ * group size times one sequence per context: L is reduced first until contexts at work x L sequences fit the budget, then the
+ * number of contexts; OFX_ERR_NOMEM before any work if one sequence does not fit.
+ * Option "lockstep" of ctxs[0] = 0 or 1 (default): sequence q is solved by ofx_brox_temporal_dev on
  * ctxs[q % n_ctx], one worker thread and stream per context; the solves are independent (no lockstep).  Each context solves
  * under its OWN options: the payloads are bit for bit the host entry's when sor_exact / sor_fuse are equal on every context.  All contexts on ONE
  * device and of one precision; option "concurrency" of the contexts is raised to the number at work for the call.  Returns when

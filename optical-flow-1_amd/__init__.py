@@ -153,6 +153,8 @@ def lib():
         "ofx_brox_temporal_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d, _i, _i]),
         "ofx_brox_temporal_batch_dev": (_i, [C.POINTER(_vp), _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d,
                                              _i, _i, C.POINTER(_d)]),
+        "ofx_brox_temporal_group_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d, _i, _i,
+                                             C.POINTER(Stats)]),
     }
     L.ofx_missing = []
     for name, (res, args) in sig.items():
@@ -550,6 +552,19 @@ class Ofx:
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_brox_temporal_dev(self.h, len(dF), arr(dF), arr(d_flo), nx, ny, alpha, gamma, nscales, nu, TOL, inner,
                                               outer))
+
+    def brox_temporal_group_dev(self, dF, d_flo, nx, ny, frames, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1,
+                                outer=15):
+        """ofx_brox_temporal_group_dev: dF = device pointers (ints) of the frames of len(dF) // frames sequences (at most 16), one
+        sequence after the other, d_flo = those of their (frames - 1) payloads each.  All sequences share every launch on this
+        context; each gets the payload, sweep table and (exact mode) stopping values of brox_temporal_dev on it alone.  Enqueues on
+        the context's stream; returns the per-sequence Stats records (stats() holds sequence 0's)."""
+        n_seq = len(dF) // frames
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n_seq, 1))()
+        self._ck(self.L.ofx_brox_temporal_group_dev(self.h, n_seq, frames, arr(dF), arr(d_flo), nx, ny, alpha, gamma, nscales, nu,
+                                                    TOL, inner, outer, st))
+        return [st[i] for i in range(n_seq)]
 
     # ---- colour / sequence variants of the operator surface --------------------------------------------------
     def centered_gradient3(self, f):

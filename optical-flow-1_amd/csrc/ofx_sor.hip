@@ -607,7 +607,12 @@ static int sor_window_loop(ofx_ctx *ctx, int G, int size, int ny, double TOL, in
         OFX_TRY(ofx_loop_clear(ctx, (size_t) G * per));
         const long tail = (long) w.lag_b * (B - 1) + (long) w.lag_f * (nz - 1);   // the last unit of a sweep ends this much later
         const long total = (long) qmax + 1 + tail + (long) w.lag_s * (ns - 1);
-        for (long tau0 = 0; tau0 < total; tau0 += w.K) {
+        // Temporal Brox promises a sequence of a lockstep group the stopping VALUES of its lone solve, while a group sizes its
+        // batches from the largest hint of its members.  Which steps of a sweep share a launch -- the association of its stopping
+        // sum -- depends on (lag_s * s) mod K for its number s within the batch, so a later batch starts its windows up to K - 1
+        // steps early: the windows then cut every sweep where the sweep's number in the SOLVE puts them, whatever the batch sizes.
+        const long t_first = nz > 1 ? -(((long) w.lag_s * niter) % w.K) : 0;
+        for (long tau0 = t_first; tau0 < total; tau0 += w.K) {
             long s_lo = (tau0 - qmax - tail + w.lag_s - 1) / w.lag_s;   // smallest s still inside the image
             if (tau0 - qmax - tail < 0) s_lo = 0;
             long s_hi = (tau0 + w.K - 1) / w.lag_s;              // largest s that has started
@@ -1249,6 +1254,15 @@ template <typename T> OFX_DEV double d2xy(const T *f, int i, int j, int nx, int 
 
 // src/brox_optic_flow_spatial.cpp:235-241: gradient of I1; I2 with its first and second derivatives
 template <typename T>
+OFX_DEV void brox_prepare_px(const T *__restrict__ I1, const T *__restrict__ I2, typename Pix<T>::v2 *__restrict__ G1,
+                             typename Pix<T>::v4 *__restrict__ PA, typename Pix<T>::v2 *__restrict__ PB, int i, int j, int nx, int ny)
+{
+    const size_t p = (size_t) i * nx + j;
+    stn2(G1 + p, make_double2(cdx(I1, i, j, nx, ny), cdy(I1, i, j, nx, ny)));
+    stn4(PA + p, make_double4(ldw(I2 + p), cdx(I2, i, j, nx, ny), cdy(I2, i, j, nx, ny), d2xx(I2, i, j, nx, ny)));
+    stn2(PB + p, make_double2(d2xy(I2, i, j, nx, ny), d2yy(I2, i, j, nx, ny)));
+}
+template <typename T>
 __global__ void k_brox_prepare(const T *__restrict__ I1, const T *__restrict__ I2, typename Pix<T>::v2 *__restrict__ G1,
                                typename Pix<T>::v4 *__restrict__ PA, typename Pix<T>::v2 *__restrict__ PB, int nx, int ny)
 {
@@ -1256,11 +1270,19 @@ __global__ void k_brox_prepare(const T *__restrict__ I1, const T *__restrict__ I
     const int i = blockIdx.y * 4 + threadIdx.y;
     if (j >= nx || i >= ny) return;
     const size_t go = (size_t) blockIdx.z * nx * ny;             // pair of a lockstep group
-    I1 += go; I2 += go; G1 += go; PA += go; PB += go;
-    const size_t p = (size_t) i * nx + j;
-    stn2(G1 + p, make_double2(cdx(I1, i, j, nx, ny), cdy(I1, i, j, nx, ny)));
-    stn4(PA + p, make_double4(ldw(I2 + p), cdx(I2, i, j, nx, ny), cdy(I2, i, j, nx, ny), d2xx(I2, i, j, nx, ny)));
-    stn2(PB + p, make_double2(d2xy(I2, i, j, nx, ny), d2yy(I2, i, j, nx, ny)));
+    brox_prepare_px<T>(I1 + go, I2 + go, G1 + go, PA + go, PB + go, i, j, nx, ny);
+}
+// ... for a lockstep group of temporal Brox: blockIdx.z = flow field of sequences of `fields` fields back to back, whose images
+// are sequences of fields + 1 frames back to back -- field z is frame z + z / fields (I1) and the one after it (I2)
+template <typename T>
+__global__ void k_broxt_prepare_group(const T *__restrict__ I, typename Pix<T>::v2 *__restrict__ G1, typename Pix<T>::v4 *__restrict__ PA,
+                                      typename Pix<T>::v2 *__restrict__ PB, int nx, int ny, int fields)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int i = blockIdx.y * 4 + threadIdx.y;
+    if (j >= nx || i >= ny) return;
+    const size_t n = (size_t) nx * ny, go = blockIdx.z * n, gi = (blockIdx.z + blockIdx.z / fields) * n;
+    brox_prepare_px<T>(I + gi, I + gi + n, G1 + go, PA + go, PB + go, i, j, nx, ny);
 }
 
 // the six fields (I2, I2x, I2y, I2xx | I2xy, I2yy) of one image or channel at a pixel's bicubic taps; 0 when the taps lie outside
@@ -1431,16 +1453,13 @@ __global__ void k_brox_div(const typename Pix<T>::v2 *__restrict__ U, const T *_
 }
 
 // psi_data, psi_gradient and the constant parts of the scheme, :279-309 (+ :33-92)
+// element i of the level's arrays; i1 = its value of the first image
 template <typename T>
-__global__ void k_brox_coeff(const T *__restrict__ I1, const typename Pix<T>::v2 *__restrict__ G1,
-                             const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
-                             const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
-                             const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n,
-                             double alpha, double gamma)
+OFX_DEV void brox_coeff_px(double i1, const typename Pix<T>::v2 *__restrict__ G1, const typename Pix<T>::v4 *__restrict__ WA,
+                           const typename Pix<T>::v2 *__restrict__ WB, const typename Pix<T>::v2 *__restrict__ DU,
+                           const typename Pix<T>::v2 *__restrict__ DV, const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO,
+                           T *__restrict__ Dm, size_t i, double alpha, double gamma)
 {
-    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t) n) return;
-    const double i1 = ldw(I1 + i);
     const double2 g1 = ldw2(G1 + i);
     const double4 wa = ldw4(WA + i);
     const double2 wb = ldw2(WB + i);
@@ -1472,6 +1491,31 @@ __global__ void k_brox_coeff(const T *__restrict__ I1, const typename Pix<T>::v2
     const double dd = ldw(Dd + i);
     stn4(CO + i, make_double4(BNu + GNu + alpha * dv.x, BNv + GNv + alpha * dv.y, BDu + GDu + dd, BDv + GDv + dd));
     stn(Dm + i, Duv);
+}
+template <typename T>
+__global__ void k_brox_coeff(const T *__restrict__ I1, const typename Pix<T>::v2 *__restrict__ G1,
+                             const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
+                             const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
+                             const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n,
+                             double alpha, double gamma)
+{
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t) n) return;
+    brox_coeff_px<T>(ldw(I1 + i), G1, WA, WB, DU, DV, Dd, CO, Dm, i, alpha, gamma);
+}
+// ... for a lockstep group of temporal Brox: sequences of seq_elems field elements back to back; the images of each hold one frame
+// of `plane` elements more, so sequence q's frames start q planes further on (n < 2^31)
+template <typename T>
+__global__ void k_broxt_coeff_group(const T *__restrict__ I, const typename Pix<T>::v2 *__restrict__ G1,
+                                    const typename Pix<T>::v4 *__restrict__ WA, const typename Pix<T>::v2 *__restrict__ WB,
+                                    const typename Pix<T>::v2 *__restrict__ DU, const typename Pix<T>::v2 *__restrict__ DV,
+                                    const T *__restrict__ Dd, typename Pix<T>::v4 *__restrict__ CO, T *__restrict__ Dm, int n,
+                                    double alpha, double gamma, int seq_elems, int plane)
+{
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t) n) return;
+    const double i1 = ldw(I + i + (size_t) ((unsigned) i / (unsigned) seq_elems) * (size_t) plane);
+    brox_coeff_px<T>(i1, G1, WA, WB, DU, DV, Dd, CO, Dm, i, alpha, gamma);
 }
 
 // SOR update of one pixel, src/brox_optic_flow_spatial.cpp:129-172, in two halves (operands first, see HsOps);
@@ -2778,14 +2822,19 @@ template <typename T> OFX_DEV Psi6 broxt_psi6(const T *Psis, int f, int i, int j
 
 // psi_smooth (:94-118) of centered_gradient3 (src/operators.cpp:413-499): the in-frame centred gradient plus the
 // temporal centred difference (one-sided, still x 0.5, in the first / last frame)
-template <typename T>
+// GRP (a lockstep group): blockIdx.z = g * nz + f, the temporal taps take the field f WITHIN its sequence g and never leave it
+template <typename T, bool GRP>
 __global__ void k_broxt_psis(const typename Pix<T>::v2 *__restrict__ U, T *__restrict__ Psis, int nx, int ny, int nz)
 {
     const int j = blockIdx.x * 64 + threadIdx.x;
     const int i = blockIdx.y * 4 + threadIdx.y;
-    const int f = blockIdx.z;
+    const int f = GRP ? blockIdx.z % nz : blockIdx.z;
     if (j >= nx || i >= ny) return;
     const size_t df = (size_t) nx * ny;
+    if (GRP) {
+        const size_t so = (size_t) (blockIdx.z - f) * df;        // the sequence's first field
+        U += so; Psis += so;
+    }
     const typename Pix<T>::v2 *Uf = U + f * df;
     const int jl = j > 0 ? j - 1 : 0, jr = j < nx - 1 ? j + 1 : nx - 1;
     const int iu = i > 0 ? i - 1 : 0, id = i < ny - 1 ? i + 1 : ny - 1;
@@ -2803,16 +2852,20 @@ __global__ void k_broxt_psis(const typename Pix<T>::v2 *__restrict__ U, T *__res
 
 // div_u, div_v (src/brox_temporal_mask.cpp:140-239: the in-frame sum, then `+=` the temporal terms as ONE added
 // expression), div_d = alpha (psi1 + ... + psi6) and du = dv = 0 (:383-390)
-template <typename T>
+template <typename T, bool GRP>
 __global__ void k_broxt_div(const typename Pix<T>::v2 *__restrict__ U, const T *__restrict__ Psis,
                             typename Pix<T>::v2 *__restrict__ DV, T *__restrict__ Dd, typename Pix<T>::v2 *__restrict__ DU,
                             int nx, int ny, int nz, double alpha)
 {
     const int j = blockIdx.x * 64 + threadIdx.x;
     const int i = blockIdx.y * 4 + threadIdx.y;
-    const int f = blockIdx.z;
+    const int f = GRP ? blockIdx.z % nz : blockIdx.z;            // as k_broxt_psis
     if (j >= nx || i >= ny) return;
     const size_t df = (size_t) nx * ny;
+    if (GRP) {
+        const size_t so = (size_t) (blockIdx.z - f) * df;
+        U += so; Psis += so; DV += so; Dd += so; DU += so;
+    }
     const size_t k = f * df + (size_t) i * nx + j;
     const Psi6 s = broxt_psi6(Psis, f, i, j, nx, ny, nz);
     const double2 c = ldw2(U + k);
@@ -2881,20 +2934,19 @@ OFX_DEV double broxt_point(typename Pix<T>::v2 *DU, typename Pix<T>::v2 *snap, c
     return (dun - duk) * (dun - duk) + (dvn - dvk) * (dvn - dvk);                                  // :171
 }
 
-// Windowed exact schedule (k_brox_window) with the frame dimension: one workgroup per (sweep, frame, row block).
-// blockIdx.y = position o of the frame in the sweep's visiting order: frames 1 .. nz-2, then 0, then nz-1 (:439-459).
+// Windowed exact schedule (k_brox_window) with the frame dimension: one workgroup per (sequence, sweep, frame, row block).
+// broxt_window_unit is the K steps of one such unit on the sequence's own arrays, snapshot plane and error slots; o = the position
+// of the frame in the sweep's visiting order: frames 1 .. nz-2, then 0, then nz-1 (:439-459).  In a lockstep group
+// (k_broxt_window_group) blockIdx.y = g * nz + o for sequence g (SorGrp: npix = the nz fields of one sequence).  A sequence whose
+// solve has stopped and an idle unit leave before the first barrier; both tests are uniform over the workgroup.
 template <typename T>
-__global__ __launch_bounds__(1024) void k_broxt_window(typename Pix<T>::v2 *DU, typename Pix<T>::v2 *snap,
-                                                       const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
-                                                       const T *__restrict__ Psis, double *__restrict__ err, SorWin w,
-                                                       int nx, int ny, int nz, double alpha)
+OFX_DEV void broxt_window_unit(typename Pix<T>::v2 *DU, typename Pix<T>::v2 *mysnap, const typename Pix<T>::v4 *__restrict__ CO,
+                               const T *__restrict__ Dm, const T *__restrict__ Psis, double *__restrict__ err, const SorWin &w, int o,
+                               int s, int q_first, int nx, int ny, int nz, double alpha)
 {
-    const int b = blockIdx.x, o = blockIdx.y, s = w.s_first + blockIdx.z;
+    const int b = blockIdx.x;
     const int f = (o < nz - 2) ? o + 1 : (o == nz - 2 ? 0 : nz - 1);
     const int qmax = ny + nx - 2;
-    const int q_first = w.tau0 - w.lag_s * s - w.lag_f * o - w.lag_b * b;
-    if (sor_unit_idle(w, b, q_first, w.K, 1, nx, ny)) return;
-    typename Pix<T>::v2 *mysnap = snap + (size_t) s * nz * nx * ny;
     const int r = sor_window_item(w, b, threadIdx.x, ny);
     double e = 0.0;
     for (int q = q_first; q < q_first + w.K; q++) {
@@ -2911,26 +2963,59 @@ __global__ __launch_bounds__(1024) void k_broxt_window(typename Pix<T>::v2 *DU, 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    loop_accumulate(err, s, e, (o * 8 + b) * 4 + (threadIdx.x >> 6));
+    // One shard per (frame, row block, wave) while nz * row blocks * waves <= OFX_NSHARD (640x480 x 5 frames: 4 * 8 * 2): every
+    // shard then receives ONE add per launch, in stream order, and the stopping sum is associated the same way in every run, alone
+    // or in a group.  (The former (o * 8 + b) * 4 + wave wrapped at o = 2, so frames o and o + 2 raced for a shard.)  Larger
+    // levels wrap and add atomically into shared shards.
+    loop_accumulate(err, s, e, (o * (int) gridDim.x + b) * (int) (blockDim.x >> 6) + (threadIdx.x >> 6));
+}
+// a lone sequence: blockIdx.y = o.  The exact mode of a lone solve is bound by the host's launch rate, so this kernel keeps the
+// short argument list and the group has a kernel of its own.
+template <typename T>
+__global__ __launch_bounds__(1024) void k_broxt_window(typename Pix<T>::v2 *DU, typename Pix<T>::v2 *snap,
+                                                       const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                                                       const T *__restrict__ Psis, double *__restrict__ err, SorWin w,
+                                                       int nx, int ny, int nz, double alpha)
+{
+    const int o = blockIdx.y, s = w.s_first + blockIdx.z;
+    const int q_first = w.tau0 - w.lag_s * s - w.lag_f * o - w.lag_b * (int) blockIdx.x;
+    if (sor_unit_idle(w, blockIdx.x, q_first, w.K, 1, nx, ny)) return;
+    broxt_window_unit<T>(DU, snap + (size_t) s * nz * nx * ny, CO, Dm, Psis, err, w, o, s, q_first, nx, ny, nz, alpha);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void k_broxt_window_group(typename Pix<T>::v2 *DU, typename Pix<T>::v2 *snap,
+                                                             const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                                                             const T *__restrict__ Psis, double *__restrict__ err, SorWin w, SorGrp grp,
+                                                             int nx, int ny, int nz, double alpha)
+{
+    const int g = blockIdx.y / nz;
+    if (!((grp.runmask >> g) & 1u)) return;                      // this sequence's solve has already stopped
+    const int o = blockIdx.y - g * nz, s = w.s_first + blockIdx.z;
+    const int q_first = w.tau0 - w.lag_s * s - w.lag_f * o - w.lag_b * (int) blockIdx.x;
+    if (sor_unit_idle(w, blockIdx.x, q_first, w.K, 1, nx, ny)) return;
+    broxt_window_unit<T>(DU + g * grp.npix, snap + g * grp.snap_stride + (size_t) s * grp.npix, CO + g * grp.npix, Dm + g * grp.npix,
+                         Psis + g * grp.npix, err + (size_t) g * grp.err_stride, w, o, s, q_first, nx, ny, nz, alpha);
 }
 
+// One level of G sequences in lockstep: sequence g's frames at frame g * frames of I, its flow fields at field g * nz of
+// every other array -- a sequence is nz planes back to back, a group G sequences back to back.
 template <typename T> struct BroxtLevel {
     using v2 = typename Pix<T>::v2;
     using v4 = typename Pix<T>::v4;
     int nx, ny;
-    T *I;                       // frames * n
-    T *Psis, *Dd, *Dm;          // nz * n each
+    T *I;                       // G * frames * n
+    T *Psis, *Dd, *Dm;          // G * nz * n each
     v2 *G1, *PB, *WB, *U, *DV, *DU, *Snap;
     v4 *PA, *WA, *CO;
     int snap_planes, sweep_hint;
 };
 
-template <typename T> static int broxt_level_alloc(ofx_ctx *ctx, BroxtLevel<T> &L, int nx, int ny, int frames)
+template <typename T> static int broxt_level_alloc(ofx_ctx *ctx, BroxtLevel<T> &L, int nx, int ny, int frames, int G)
 {
-    const size_t n1 = (size_t) nx * ny * (frames - 1);
+    const size_t n1 = (size_t) nx * ny * (frames - 1) * G;
     L.nx = nx;
     L.ny = ny;
-    OFX_TRY(ofx_alloc(ctx, (size_t) nx * ny * frames, &L.I));
+    OFX_TRY(ofx_alloc(ctx, (size_t) nx * ny * frames * G, &L.I));
     OFX_TRY(ofx_alloc(ctx, n1, &L.Psis));
     OFX_TRY(ofx_alloc(ctx, n1, &L.Dd));
     OFX_TRY(ofx_alloc(ctx, n1, &L.Dm));
@@ -2951,60 +3036,84 @@ template <typename T> static int broxt_level_alloc(ofx_ctx *ctx, BroxtLevel<T> &
 
 // src/brox_optic_flow_temporal.cpp:282-512 on device data
 template <typename T>
-static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxParams &P, int frames, int scale)
+static int broxt_single_scale_dev(ofx_ctx *ctx, BroxtLevel<T> &L, const BroxParams &P, int frames, int scale, int G, ofx_stats *stats)
 {
     const int nx = L.nx, ny = L.ny, nz = frames - 1, n = nx * ny;
-    const size_t n1 = (size_t) n * nz;
-    if ((long long) n1 >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: sequence larger than 2^31 pixels");
+    const size_t n1 = (size_t) n * nz, nG = n1 * G;              // the fields of one sequence, of the group
+    if ((long long) n * frames * G >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: group larger than 2^31 pixels");
     if (nx < 3 || ny < 3) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: level %dx%d has no interior", nx, ny);
-    const dim3 g = g2d(nx, ny), b = b2d(), g3(g.x, g.y, nz);
-    const dim3 g1((unsigned) ((n1 + 255) / 256)), b1(256);
+    const dim3 g = g2d(nx, ny), b = b2d(), g3(g.x, g.y, G * nz);
+    const dim3 g1((unsigned) ((nG + 255) / 256)), b1(256);
     int solve = 0;
-    // :346-355 for all flow fields at once (blockIdx.z = f): I1 = frame f, I2 = frame f + 1 of the frame-major level
-    hipLaunchKernelGGL(k_brox_prepare<T>, g3, b, 0, ctx->stream, (const T *) L.I, (const T *) (L.I + n), L.G1, L.PA, L.PB, nx, ny);
+    // :346-355 for all flow fields of all sequences at once (blockIdx.z = g * nz + f): I1 = frame f, I2 = frame f + 1 of
+    // sequence g of the frame-major level
+    // (a lone sequence launches the lone kernels with their short argument lists throughout: it is bound by the host's launch rate)
+    if (G == 1) hipLaunchKernelGGL(k_brox_prepare<T>, g3, b, 0, ctx->stream, (const T *) L.I, (const T *) (L.I + n), L.G1, L.PA, L.PB, nx, ny);
+    else hipLaunchKernelGGL(k_broxt_prepare_group<T>, g3, b, 0, ctx->stream, (const T *) L.I, L.G1, L.PA, L.PB, nx, ny, nz);
     OFX_LAUNCH_CHECK(ctx);
     for (int no = 0; no < P.outer_iter; no++) {                                                      // :358
         hipLaunchKernelGGL(k_brox_warp<T>, g3, b, 0, ctx->stream, L.PA, L.PB, L.U, L.WA, L.WB, nx, ny);   // :360-367
-        hipLaunchKernelGGL(k_broxt_psis<T>, g3, b, 0, ctx->stream, L.U, L.Psis, nx, ny, nz);          // :370-374
-        hipLaunchKernelGGL(k_broxt_div<T>, g3, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, nz,
-                           P.alpha);                                                                 // :377-390
+        if (G == 1) {
+            hipLaunchKernelGGL((k_broxt_psis<T, false>), g3, b, 0, ctx->stream, L.U, L.Psis, nx, ny, nz);      // :370-374
+            hipLaunchKernelGGL((k_broxt_div<T, false>), g3, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, nz,
+                               P.alpha);                                                             // :377-390
+        } else {
+            hipLaunchKernelGGL((k_broxt_psis<T, true>), g3, b, 0, ctx->stream, L.U, L.Psis, nx, ny, nz);
+            hipLaunchKernelGGL((k_broxt_div<T, true>), g3, b, 0, ctx->stream, L.U, (const T *) L.Psis, L.DV, L.Dd, L.DU, nx, ny, nz,
+                               P.alpha);
+        }
         OFX_LAUNCH_CHECK(ctx);
         for (int ni = 0; ni < P.inner_iter; ni++) {                                                  // :394
-            hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I, L.G1, L.WA, L.WB, L.DU, L.DV,
-                               (const T *) L.Dd, L.CO, L.Dm, (int) n1, P.alpha, P.gamma);            // :396-427
+            if (G == 1)
+                hipLaunchKernelGGL(k_brox_coeff<T>, g1, b1, 0, ctx->stream, (const T *) L.I, L.G1, L.WA, L.WB, L.DU, L.DV,
+                                   (const T *) L.Dd, L.CO, L.Dm, (int) nG, P.alpha, P.gamma);        // :396-427
+            else
+                hipLaunchKernelGGL(k_broxt_coeff_group<T>, g1, b1, 0, ctx->stream, (const T *) L.I, L.G1, L.WA, L.WB, L.DU, L.DV,
+                                   (const T *) L.Dd, L.CO, L.Dm, (int) nG, P.alpha, P.gamma, (int) n1, n);
             OFX_LAUNCH_CHECK(ctx);
-            int nsor = 0;
-            double error = 1000;
+            int nsor[OFX_MAX_GROUP] = {0};
+            double error[OFX_MAX_GROUP];
+            for (int q = 0; q < G; q++) error[q] = 1000;
             if (ctx->sor_exact == 0) {
-                // tolerance mode: 3-D red-black sweeps (ofx_sor_tile.hip).  No snapshots; ONE plane of them is the second buffer
-                // of the tile kernel's ping-pong, so the memory rule of the exact mode bounds this one too.
-                OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, 1, 1));
-                OFX_TRY(ofx_broxt_tile_solve<T>(ctx, L.DU, L.Snap, L.CO, (const T *) L.Dm, (const T *) L.Psis, nx, ny, nz, P.alpha, P.TOL,
-                                                OFX_BROX_MAX_ITERATIONS, ctx->sor_fuse, &nsor, &error, nullptr));
-                if (P.verbose) { printf("Iterations: %d\n", nsor); fflush(stdout); }                 // :463-465
-                sor_record_solve(&ctx->stats, 1, scale, solve++, &nsor, &error, 0.f, (double) n1);
+                // tolerance mode: 3-D red-black sweeps (ofx_sor_tile.hip).  No snapshots; ONE plane of them per sequence is the
+                // second buffer of the tile kernel's ping-pong, so the memory rule of the exact mode bounds this one too.
+                OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, 1, G));
+                OFX_TRY(ofx_broxt_tile_solve<T>(ctx, G, L.DU, L.Snap, L.CO, (const T *) L.Dm, (const T *) L.Psis, nx, ny, nz, P.alpha,
+                                                P.TOL, OFX_BROX_MAX_ITERATIONS, ctx->sor_fuse, nsor, error, nullptr));
+                if (P.verbose && G == 1) { printf("Iterations: %d\n", nsor[0]); fflush(stdout); }    // :463-465
+                sor_record_solve(stats, G, scale, solve++, nsor, error, 0.f, (double) n1);
                 continue;
             }
+            // Every sequence of a group gets the stopping VALUES of its lone solve, and the association of the stopping sum
+            // follows the window geometry (a thread's K steps, then the shard of its frame, row block and wave): groups keep the lone
+            // geometry, 8 steps and 64 rows, as the robust_expo groups do.  Options sor_window / sor_rows override both alike.
             const size_t ub = n1 * sizeof(typename Pix<T>::v2);
-            const int batch = sor_pick_batch(ctx, n1, sizeof(typename Pix<T>::v2), OFX_BROX_MAX_ITERATIONS);
-            OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, batch, 1));
-            auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned, int) -> int {
-                hipLaunchKernelGGL(k_broxt_window<T>, dim3(blocks, nz, sweeps), dim3(sor_window_threads(w.R + 3)), 0,
-                                   ctx->stream, L.DU, L.Snap, L.CO, (const T *) L.Dm, (const T *) L.Psis, ctx->d_err, w, nx,
-                                   ny, nz, P.alpha);
+            const int batch = sor_pick_batch(ctx, n1, sizeof(typename Pix<T>::v2), OFX_BROX_MAX_ITERATIONS, G);
+            OFX_TRY(sor_snap_reserve(ctx, &L.Snap, &L.snap_planes, n1, batch, G));
+            const size_t snap_stride = n1 * L.snap_planes;
+            auto window = [&](const SorWin &w, int blocks, int sweeps, unsigned runmask, int err_stride) -> int {
+                const SorGrp grp = {runmask, err_stride, n1, snap_stride};
+                const dim3 grid(blocks, G * nz, sweeps), blk(sor_window_threads(w.R + 3));
+                if (G == 1)
+                    hipLaunchKernelGGL(k_broxt_window<T>, grid, blk, 0, ctx->stream, L.DU, L.Snap, L.CO, (const T *) L.Dm,
+                                       (const T *) L.Psis, ctx->d_err, w, nx, ny, nz, P.alpha);
+                else
+                    hipLaunchKernelGGL(k_broxt_window_group<T>, grid, blk, 0, ctx->stream, L.DU, L.Snap, L.CO, (const T *) L.Dm,
+                                       (const T *) L.Psis, ctx->d_err, w, grp, nx, ny, nz, P.alpha);
                 OFX_LAUNCH_CHECK(ctx);
                 return OFX_OK;
             };
-            auto take = [&](int, int k) -> int {
-                OFX_HIP(ctx, hipMemcpyAsync(L.DU, L.Snap + (size_t) (k - 1) * n1, ub, hipMemcpyDeviceToDevice, ctx->stream));
+            auto take = [&](int q, int k) -> int {
+                OFX_HIP(ctx, hipMemcpyAsync(L.DU + q * n1, L.Snap + q * snap_stride + (size_t) (k - 1) * n1, ub,
+                                            hipMemcpyDeviceToDevice, ctx->stream));
                 return OFX_OK;
             };
-            OFX_TRY(sor_window_loop(ctx, 1, (int) n1, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
-                                    take, &nsor, &error, nz, &L.sweep_hint));                                       // :430-461
-            if (P.verbose) { printf("Iterations: %d\n", nsor); fflush(stdout); }                     // :463-465
-            sor_record_solve(&ctx->stats, 1, scale, solve++, &nsor, &error, 0.f, (double) n1);
+            OFX_TRY(sor_window_loop(ctx, G, (int) n1, ny, P.TOL, OFX_BROX_MAX_ITERATIONS, ny + nx - 2, BROX_PLANE_C, batch, window,
+                                    take, nsor, error, nz, &L.sweep_hint, 8, 64));                                  // :430-461
+            if (P.verbose && G == 1) { printf("Iterations: %d\n", nsor[0]); fflush(stdout); }        // :463-465
+            sor_record_solve(stats, G, scale, solve++, nsor, error, 0.f, (double) n1);
         }
-        hipLaunchKernelGGL(k_brox_add<T>, g1, b1, 0, ctx->stream, L.U, L.DU, (int) n1);                // :469-472
+        hipLaunchKernelGGL(k_brox_add<T>, g1, b1, 0, ctx->stream, L.U, L.DU, (int) nG);                // :469-472
         OFX_LAUNCH_CHECK(ctx);
     }
     return OFX_OK;
@@ -3051,58 +3160,76 @@ static int broxt_check(ofx_ctx *ctx, int frames, int nxx, int nyy, int nscales, 
     return OFX_OK;
 }
 
-// The solve: dF = the frames on the device in storage type T; nxs, nys from broxt_check.  On success lv[0].U holds the
-// frames - 1 flows of the finest level and ctx->stats the record.
+// The solve of G sequences in lockstep: dF = their frames on the device in storage type T, sequence g's at dF + g * frames; nxs,
+// nys from broxt_check.  On success lv[0].U holds the G * (frames - 1) flows of the finest level and stats[g] the record of
+// sequence g.  Every launch of the head serves as many planes of the group as the by-value tables hold.
 template <typename T>
-static int broxt_sequence_dev(ofx_ctx *ctx, int frames, const void *const *dF, const BroxParams &P, int nscales, double nu,
-                              const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxtLevel<T>> &lv)
+static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const *dF, const BroxParams &P, int nscales, double nu,
+                              const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxtLevel<T>> &lv, ofx_stats *stats)
 {
     const int nx = nxs[0], ny = nys[0], MF = OFX_BROXT_MAX_FRAMES;
     const size_t n = (size_t) nx * ny;
-    sor_stats_begin(ctx, nscales, P.inner_iter * P.outer_iter);
+    if (G < 1 || G > OFX_MAX_GROUP || (G > 1 && frames > MF)) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: group of %d sequences", G);
+    const int planes = G * frames, tmp_planes = planes < MF ? planes : MF;
+    for (int g = 0; g < G; g++) sor_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
     T *tmpA, *tmpB = nullptr;
     double *mm;
-    const int chunks = (frames + MF - 1) / MF;
-    OFX_TRY(ofx_alloc(ctx, n * frames, &tmpA));
-    if (nscales > 1) OFX_TRY(ofx_alloc(ctx, n * frames, &tmpB));
-    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(1, n, 1, chunks), &mm));
+    // image_normalization_1 (:548) has one {min, max} set per SEQUENCE.  A table holds the frames of `per_launch` whole sequences
+    // (sets of one chunk); a sequence longer than the table (host entry, G = 1) is one set in `chunks` chunks.
+    const int chunks = (frames + MF - 1) / MF, per_launch = frames <= MF ? MF / frames : 1;
+    const size_t mm_doubles = op_minmax_scratch_doubles(per_launch, n, 1, chunks);
+    OFX_TRY(ofx_alloc(ctx, n * tmp_planes, &tmpA));
+    if (nscales > 1) OFX_TRY(ofx_alloc(ctx, n * tmp_planes, &tmpB));
+    OFX_TRY(ofx_alloc(ctx, mm_doubles * ((G + per_launch - 1) / per_launch), &mm));
     lv.resize(nscales);
     for (int s = 0; s < nscales; s++) {
-        OFX_TRY(broxt_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], frames));
-        if (s < OFX_MAX_SCALES) { ctx->stats.nx[s] = nxs[s]; ctx->stats.ny[s] = nys[s]; }
+        OFX_TRY(broxt_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], frames, G));
+        for (int g = 0; g < G && s < OFX_MAX_SCALES; g++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
-    // image_normalization_1 over the whole sequence (:548): one set of all frames, a chunk of the table's size per launch
-    for (int f0 = 0; f0 < frames; f0 += MF) {
-        const int cnt = frames - f0 < MF ? frames - f0 : MF;
-        OfxSrcPtrs in = {};
-        for (int k = 0; k < cnt; k++) in.p[k] = dF[f0 + k];
-        OFX_TRY(op_minmax_partial<T>(ctx, in, 1, cnt, n, 1, mm, f0 / MF, chunks));
+    if (chunks > 1) {                                            // one long sequence: a chunk of the table's size per launch
+        for (int f0 = 0; f0 < frames; f0 += MF) {
+            const int cnt = frames - f0 < MF ? frames - f0 : MF;
+            OfxSrcPtrs in = {};
+            for (int k = 0; k < cnt; k++) in.p[k] = dF[f0 + k];
+            OFX_TRY(op_minmax_partial<T>(ctx, in, 1, cnt, n, 1, mm, f0 / MF, chunks));
+        }
+        OFX_TRY(op_minmax_final(ctx, 1, n, 1, mm, chunks));
+        for (int f0 = 0; f0 < frames; f0 += MF) {
+            const int cnt = frames - f0 < MF ? frames - f0 : MF;
+            OfxSrcPtrs in = {};
+            OfxDstPtrs out = {};
+            for (int k = 0; k < cnt; k++) { in.p[k] = dF[f0 + k]; out.p[k] = lv[0].I + (f0 + k) * n; }
+            OFX_TRY((op_normalize_map<T, T>(ctx, in, out, 1, cnt, n, 1, mm)));
+        }
+    } else {
+        for (int g0 = 0; g0 < G; g0 += per_launch) {
+            const int sets = G - g0 < per_launch ? G - g0 : per_launch;
+            OfxSrcPtrs in = {};
+            OfxDstPtrs out = {};
+            for (int k = 0; k < sets * frames; k++) { in.p[k] = dF[g0 * frames + k]; out.p[k] = lv[0].I + (size_t) (g0 * frames + k) * n; }
+            OFX_TRY((op_normalize_sets<T, T>(ctx, in, out, sets, frames, n, 1, mm + (g0 / per_launch) * mm_doubles)));
+        }
     }
-    OFX_TRY(op_minmax_final(ctx, 1, n, 1, mm, chunks));
-    for (int f0 = 0; f0 < frames; f0 += MF) {
-        const int cnt = frames - f0 < MF ? frames - f0 : MF;
-        OfxSrcPtrs in = {};
-        OfxDstPtrs out = {};
-        for (int k = 0; k < cnt; k++) { in.p[k] = dF[f0 + k]; out.p[k] = lv[0].I + (f0 + k) * n; }
-        OFX_TRY((op_normalize_map<T, T>(ctx, in, out, 1, cnt, n, 1, mm)));
-        OFX_TRY(op_gaussian_planes<T>(ctx, cnt, cnt, lv[0].I + f0 * n, nullptr, n, tmpA, nx, ny, BROX_SIGMA));          // :551-553
+    for (int f0 = 0; f0 < planes; f0 += MF) {                                                        // :551-553
+        const int cnt = planes - f0 < MF ? planes - f0 : MF;
+        OFX_TRY(op_gaussian_planes<T>(ctx, cnt, cnt, lv[0].I + f0 * n, nullptr, n, tmpA, nx, ny, BROX_SIGMA));
     }
     for (int s = 1; s < nscales; s++) {                                                              // :561-575
         const size_t np = (size_t) nxs[s - 1] * nys[s - 1], nc = (size_t) nxs[s] * nys[s];
-        for (int f0 = 0; f0 < frames; f0 += MF) {
-            const int cnt = frames - f0 < MF ? frames - f0 : MF;
+        for (int f0 = 0; f0 < planes; f0 += MF) {
+            const int cnt = planes - f0 < MF ? planes - f0 : MF;
             OFX_TRY(op_zoom_out_channels_planes<T>(ctx, cnt, cnt, lv[s - 1].I + f0 * np, nullptr, lv[s].I + f0 * nc, nullptr, tmpA, tmpB,
                                                    nxs[s - 1], nys[s - 1], 1, nu));
         }
     }
     BroxtLevel<T> &C = lv[nscales - 1];
-    OFX_TRY(op_fill2<T>(ctx, C.U, (size_t) C.nx * C.ny * (frames - 1)));                             // :578-580
+    OFX_TRY(op_fill2<T>(ctx, C.U, (size_t) C.nx * C.ny * (frames - 1) * G));                         // :578-580
     for (int s = nscales - 1; s >= 0; s--) {                                                        // :587
-        if (P.verbose) { printf("Scale: %d\n", s); fflush(stdout); }
-        OFX_TRY(broxt_single_scale_dev<T>(ctx, lv[s], P, frames, s));
+        if (P.verbose && G == 1) { printf("Scale: %d\n", s); fflush(stdout); }
+        OFX_TRY(broxt_single_scale_dev<T>(ctx, lv[s], P, frames, s, G, stats));
         if (s)
             OFX_TRY(op_zoom_in_flow<T>(ctx, lv[s].U, lv[s - 1].U, lv[s].nx, lv[s].ny, lv[s - 1].nx, lv[s - 1].ny, 1.0 / nu,
-                                       frames - 1));                                                 // :600-612
+                                       (frames - 1) * G));                                           // :600-612
     }
     return OFX_OK;
 }
@@ -3118,7 +3245,7 @@ static int broxt_host(ofx_ctx *ctx, const double *I, double *u, double *v, int f
     std::vector<const void *> dF(frames);
     for (int k = 0; k < frames; k++) dF[k] = dI + k * n;
     std::vector<BroxtLevel<T>> lv;
-    OFX_TRY(broxt_sequence_dev<T>(ctx, frames, dF.data(), P, nscales, nu, nxs, nys, lv));
+    OFX_TRY(broxt_sequence_dev<T>(ctx, 1, frames, dF.data(), P, nscales, nu, nxs, nys, lv, &ctx->stats));
     return download_flow<T>(ctx, lv[0].U, u, v, n * (frames - 1));
 }
 
@@ -3162,29 +3289,38 @@ static int broxt_dev_check(ofx_ctx *ctx, int n_seq, int frames, const void *cons
     return broxt_check_ptrs(ctx, n_seq, frames, dF, d_flo);
 }
 
+// G sequences in lockstep and their payloads: the table of k_broxt_out holds OFX_BROXT_MAX_FRAMES fields per launch
 template <typename T>
-static int broxt_devapi(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, const BroxParams &P, int nscales, double nu,
-                        const std::vector<int> &nxs, const std::vector<int> &nys)
+static int broxt_devapi(ofx_ctx *ctx, int G, int frames, const void *const *dF, void *const *d_flo, const BroxParams &P, int nscales,
+                        double nu, const std::vector<int> &nxs, const std::vector<int> &nys, ofx_stats *stats)
 {
     std::vector<BroxtLevel<T>> lv;
-    OFX_TRY(broxt_sequence_dev<T>(ctx, frames, dF, P, nscales, nu, nxs, nys, lv));
+    OFX_TRY(broxt_sequence_dev<T>(ctx, G, frames, dF, P, nscales, nu, nxs, nys, lv, stats));
     const size_t n = (size_t) nxs[0] * nys[0];
-    BroxtFlos out = {};
-    for (int f = 0; f < frames - 1; f++) out.flo[f] = static_cast<float2 *>(d_flo[f]);
-    hipLaunchKernelGGL(k_broxt_out<T>, dim3((unsigned) ((n + 255) / 256), 1, frames - 1), dim3(256), 0, ctx->stream, lv[0].U, out, (int) n);
-    OFX_LAUNCH_CHECK(ctx);
+    const int fields = G * (frames - 1);
+    for (int f0 = 0; f0 < fields; f0 += OFX_BROXT_MAX_FRAMES) {
+        const int cnt = fields - f0 < OFX_BROXT_MAX_FRAMES ? fields - f0 : OFX_BROXT_MAX_FRAMES;
+        BroxtFlos out = {};
+        for (int f = 0; f < cnt; f++) out.flo[f] = static_cast<float2 *>(d_flo[f0 + f]);
+        hipLaunchKernelGGL(k_broxt_out<T>, dim3((unsigned) ((n + 255) / 256), 1, cnt), dim3(256), 0, ctx->stream, lv[0].U + f0 * n, out,
+                           (int) n);
+        OFX_LAUNCH_CHECK(ctx);
+    }
     return OFX_OK;
 }
 
-static int broxt_dev_run(ofx_ctx *ctx, int frames, const void *const *dF, void *const *d_flo, double alpha, double gamma, int nscales,
-                         double nu, double TOL, int inner_iter, int outer_iter, const std::vector<int> &nxs, const std::vector<int> &nys)
+// the checked solve of G sequences; stats: G records
+static int broxt_dev_run(ofx_ctx *ctx, int G, int frames, const void *const *dF, void *const *d_flo, double alpha, double gamma,
+                         int nscales, double nu, double TOL, int inner_iter, int outer_iter, const std::vector<int> &nxs,
+                         const std::vector<int> &nys, ofx_stats *stats)
 {
     const double t0 = ofx_now_ms();
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
-    int s = ctx->precision == OFX_F64 ? broxt_devapi<double>(ctx, frames, dF, d_flo, P, nscales, nu, nxs, nys)
-                                      : broxt_devapi<float>(ctx, frames, dF, d_flo, P, nscales, nu, nxs, nys);
+    int s = ctx->precision == OFX_F64 ? broxt_devapi<double>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, stats)
+                                      : broxt_devapi<float>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, stats);
     if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // nothing in flight when the arena is reset
-    ctx->stats.total_ms = ofx_now_ms() - t0;
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < G; g++) stats[g].total_ms = ms;
     return s;
 }
 
@@ -3195,10 +3331,40 @@ extern "C" int ofx_brox_temporal_dev(ofx_ctx *ctx, int frames, const void *const
     OFX_ENTER(ctx);
     std::vector<int> nxs, nys;
     OFX_TRY(broxt_dev_check(ctx, 1, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
-    return broxt_dev_run(ctx, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys);
+    return broxt_dev_run(ctx, 1, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, &ctx->stats);
 }
 
-// n_seq independent sequences, sequence q on context q mod (contexts at work): sor_batch_run with groups of one (include/ofx.h)
+// what a group adds to broxt_dev_check: its size, and the index range over all its sequences
+static int broxt_group_check(ofx_ctx *ctx, int n_seq, int frames, const void *const *dF, void *const *d_flo, int nxx, int nyy,
+                             int nscales, double nu, int inner_iter, int outer_iter, std::vector<int> &nxs, std::vector<int> &nys)
+{
+    if (n_seq < 1 || n_seq > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: a lockstep group holds 1..%d sequences (got %d)", OFX_MAX_GROUP, n_seq);
+    OFX_TRY(broxt_dev_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
+    if ((long long) nxx * nyy * frames * n_seq >= (1LL << 31))
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: group of %d sequences larger than 2^31 voxels", n_seq);
+    return OFX_OK;
+}
+
+// n_seq sequences through the same launches, each with its own normalisation, stopping test and snapshots (include/ofx.h)
+extern "C" int ofx_brox_temporal_group_dev(ofx_ctx *ctx, int n_seq, int frames, const void *const *dF, void *const *d_flo, int nxx,
+                                           int nyy, double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter,
+                                           int outer_iter, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    std::vector<int> nxs, nys;
+    OFX_TRY(broxt_group_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
+    std::vector<ofx_stats> local(stats_out ? 0 : n_seq);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    const int s = broxt_dev_run(ctx, n_seq, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, st);
+    ctx->stats = st[0];                                          // as the other *_group_dev entries: sequence 0's record
+    return s;
+}
+
+// n_seq independent sequences over the contexts (include/ofx.h).  Option "lockstep" of ctxs[0] = 0 or 1: sequence q alone on
+// context q mod (contexts at work), each context under its own options.  L >= 2: lockstep groups of L consecutive sequences
+// (ofx_brox_temporal_group_dev), group q on context q mod (contexts at work), every context under ctxs[0]'s sor_exact / sor_fuse
+// -- also when the memory rule or n_seq leaves groups of one.
 extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int n_seq, int frames, const void *const *dF,
                                            void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
                                            double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
@@ -3212,7 +3378,10 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
     if (n_seq < 1) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: %d sequences", n_seq);
     std::vector<int> nxs, nys;
     OFX_TRY(broxt_dev_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
-    int n_use = n_ctx < n_seq ? n_ctx : n_seq;
+    int L = ctx->lockstep < 2 ? 1 : (ctx->lockstep > OFX_MAX_GROUP ? OFX_MAX_GROUP : ctx->lockstep);
+    if (L > n_seq) L = n_seq;
+    while (L > 1 && (long long) nxx * nyy * frames * L >= (1LL << 31)) L--;
+    int n_use = 1;
     {
         size_t free_b = 0, total_b = 0;
         OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -3221,16 +3390,37 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
         double level_px = 0.0;
         for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
         const double per = 1.05 * el * (level_px * (frames + (27.0 + 2.0 * B) * (frames - 1)) + 2.0 * frames * (double) nxx * nyy);
-        const double fit = budget / per;
+        const double fit = budget / per;                         // sequences that fit: the per-sequence rule times the group size
         if (fit < 1.0)
             return ofx_fail(ctx, OFX_ERR_NOMEM, "brox temporal batch: %.3f GB for one sequence, %.3f GB available", per / 1e9, budget / 1e9);
-        if (fit < n_use) n_use = (int) fit;
+        const int n_groups = (n_seq + L - 1) / L;
+        n_use = n_ctx < n_groups ? n_ctx : n_groups;
+        while (L > 1 && fit < (double) n_use * L) {              // the group size first ...
+            L--;
+            const int ng = (n_seq + L - 1) / L;
+            n_use = n_ctx < ng ? n_ctx : ng;
+        }
+        if (fit < n_use) n_use = (int) fit;                      // ... then the contexts
     }
-    return sor_batch_run(ctxs, n_use, n_seq, 1, work_pix_iters, [&](ofx_ctx *c, int q, int, ofx_stats *st) {
+    if (ctx->lockstep < 2)
+        return sor_batch_run(ctxs, n_use, n_seq, 1, work_pix_iters, [&](ofx_ctx *c, int q, int, ofx_stats *st) {
+            OFX_ENTER(c);
+            const int s = broxt_dev_run(c, 1, frames, dF + (size_t) q * frames, d_flo + (size_t) q * (frames - 1), alpha, gamma, nscales,
+                                        nu, TOL, inner_iter, outer_iter, nxs, nys, &c->stats);
+            st[0] = c->stats;
+            return s;
+        });
+    const int exact = ctx->sor_exact, fuse = ctx->sor_fuse;
+    return sor_batch_run(ctxs, n_use, n_seq, L, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
         OFX_ENTER(c);
-        const int s = broxt_dev_run(c, frames, dF + (size_t) q * frames, d_flo + (size_t) q * (frames - 1), alpha, gamma, nscales, nu, TOL,
-                                    inner_iter, outer_iter, nxs, nys);
-        st[0] = c->stats;
+        const int exact_c = c->sor_exact, fuse_c = c->sor_fuse;
+        c->sor_exact = exact;
+        c->sor_fuse = fuse;
+        const int s = broxt_dev_run(c, cnt, frames, dF + (size_t) first * frames, d_flo + (size_t) first * (frames - 1), alpha, gamma,
+                                    nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, st);
+        c->stats = st[0];
+        c->sor_exact = exact_c;
+        c->sor_fuse = fuse_c;
         return s;
     });
 }

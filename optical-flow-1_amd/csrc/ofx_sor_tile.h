@@ -31,13 +31,15 @@ int ofx_brox_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename 
                         const T *Dm, const T *Ps, int nx, int ny, double alpha, double TOL, int maxiter, int K, int *niter, double *error,
                         float *ms);
 
-// Temporal Brox (src/brox_optic_flow_temporal.cpp:430-461), ONE solve over the nz = frames - 1 flow fields of a level (frame-major
-// arrays, nx * ny * nz elements): 3-D red-black sweeps, every voxel with (i + j + f) even, then every voxel with (i + j + f) odd, the
-// order of tests/broxt_colour_ref.c (order 1).  The result depends on nothing but that order.  K = 1, 2, 4 (3 -> 2): sweeps per launch
+// Temporal Brox (src/brox_optic_flow_temporal.cpp:430-461), ONE solve over the nz = frames - 1 flow fields of a level for each of
+// the G sequences of a lockstep group (frame-major arrays, nx * ny * nz elements per sequence, the sequences back to back): 3-D
+// red-black sweeps, every voxel with (i + j + f) even, then every voxel with (i + j + f) odd, the order of
+// tests/broxt_colour_ref.c (order 1).  The result depends on nothing but that order.  K = 1, 2, 4 (3 -> 2): sweeps per launch
 // on LDS tiles that hold all nz fields (k_broxt_tile), for nz <= 4; 0 = the default K; K = 9 or -1, and EVERY K when nz > 4: one
 // launch per colour and sweep straight from global memory, in place (k_broxt_rb).  Both paths give the same bits.  DU0 holds
-// (du, dv) on entry and on return; DU1 (nx * ny * nz elements) is the second buffer of the tile kernel's ping-pong.
+// (du, dv) on entry and on return; DU1 (as large) is the second buffer of the tile kernel's ping-pong.  Every sequence keeps its
+// own error slots, stopping test and ping-pong phase: niter[g], error[g] are those of its solve alone.
 template <typename T>
-int ofx_broxt_tile_solve(ofx_ctx *ctx, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO, const T *Dm,
-                         const T *Ps, int nx, int ny, int nz, double alpha, double TOL, int maxiter, int K, int *niter, double *error,
-                         float *ms);
+int ofx_broxt_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO,
+                         const T *Dm, const T *Ps, int nx, int ny, int nz, double alpha, double TOL, int maxiter, int K, int *niter,
+                         double *error, float *ms);

@@ -1106,16 +1106,16 @@ OFX_DEV double2 bxt_update(double2 c, double2 dn, double2 up, double2 rt, double
     return make_double2(dun, dvn);
 }
 
+// field f of ONE sequence (its nz fields at DU, CO, Dm, Ps; its error slots at err)
 template <typename T>
-__global__ __launch_bounds__(256) void k_broxt_rb(typename Pix<T>::v2 *DU, const typename Pix<T>::v4 *__restrict__ CO,
-                                                  const T *__restrict__ Dm, const T *__restrict__ Ps, double *__restrict__ err, int k,
-                                                  int nx, int ny, int nz, int colour, double alpha, double tol)
+OFX_DEV void broxt_rb_unit(typename Pix<T>::v2 *DU, const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                           const T *__restrict__ Ps, double *__restrict__ err, int k, int f, int nx, int ny, int nz, int colour,
+                           double alpha, double tol)
 {
     const double prev = loop_fetch_prev(err, k);
-    const int f = blockIdx.z;
     const int i = blockIdx.y * 4 + threadIdx.y;
     const int j = 2 * (blockIdx.x * 64 + threadIdx.x) + ((i + f + colour) & 1);
-    const int gw = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + threadIdx.y;
+    const int gw = ((f * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + threadIdx.y;
     if (!loop_continues(prev, k, nx * ny * nz, tol, OFX_CRIT_SQRT_MEAN)) return;
     double e = 0.0;
     if (j < nx && i < ny) {
@@ -1132,6 +1132,26 @@ __global__ __launch_bounds__(256) void k_broxt_rb(typename Pix<T>::v2 *DU, const
         stn2(DU + p, un);
     }
     loop_accumulate(err, k, e, gw);
+}
+// a lone sequence: blockIdx.z = f.  A lone solve is bound by the host's launch rate, so its kernels keep their short argument lists
+// and a lockstep group has kernels of its own over the same device functions.
+template <typename T>
+__global__ __launch_bounds__(256) void k_broxt_rb(typename Pix<T>::v2 *DU, const typename Pix<T>::v4 *__restrict__ CO,
+                                                  const T *__restrict__ Dm, const T *__restrict__ Ps, double *__restrict__ err, int k,
+                                                  int nx, int ny, int nz, int colour, double alpha, double tol)
+{
+    broxt_rb_unit<T>(DU, CO, Dm, Ps, err, k, blockIdx.z, nx, ny, nz, colour, alpha, tol);
+}
+// blockIdx.z = g * nz + f: field f of sequence g of a lockstep group, which has its own error slots and stopping test
+template <typename T>
+__global__ __launch_bounds__(256) void k_broxt_rb_group(typename Pix<T>::v2 *DU, const typename Pix<T>::v4 *__restrict__ CO,
+                                                        const T *__restrict__ Dm, const T *__restrict__ Ps, double *__restrict__ err,
+                                                        int k, int nx, int ny, int nz, int colour, double alpha, double tol,
+                                                        int err_stride)
+{
+    const int g = blockIdx.z / nz, f = blockIdx.z - g * nz;
+    const size_t seq = (size_t) nx * ny * nz * g;
+    broxt_rb_unit<T>(DU + seq, CO + seq, Dm + seq, Ps + seq, err + (size_t) g * err_stride, k, f, nx, ny, nz, colour, alpha, tol);
 }
 
 // LDS index of voxel (field f, tile row li, tile column lj): the even columns of a row first, then the odd ones, so that the lanes
@@ -1171,11 +1191,12 @@ OFX_DEV double bxt_colour_step(double2 *s_u, const double *s_ps, const double4 (
     return e;
 }
 
+// K sweeps of ONE sequence on the tile blockIdx.x: from Uin to Uout
 template <typename T, int K>
-__global__ __launch_bounds__(BXT_NT) void k_broxt_tile(const typename Pix<T>::v2 *__restrict__ Uin, typename Pix<T>::v2 *__restrict__ Uout,
-                                                       const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
-                                                       const T *__restrict__ Ps, double *__restrict__ err, int k0, int check, int slot0,
-                                                       int niter, int nx, int ny, int nz, int tiles_x, double alpha, double tol)
+OFX_DEV void broxt_tile_unit(const typename Pix<T>::v2 *__restrict__ Uin, typename Pix<T>::v2 *__restrict__ Uout,
+                             const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm, const T *__restrict__ Ps,
+                             double *__restrict__ err, int k0, int check, int slot0, int niter, int nx, int ny, int nz, int tiles_x,
+                             double alpha, double tol)
 {
     static_assert(K >= 1 && BXT_TW - 4 * K > 0 && BXT_TH - 4 * K > 0 && BXT_NT % 64 == 0 && BXT_NT <= 1024, "tile geometry");
     constexpr int H = 2 * K, OW = BXT_TW - 2 * H, OH = BXT_TH - 2 * H;
@@ -1232,34 +1253,79 @@ __global__ __launch_bounds__(BXT_NT) void k_broxt_tile(const typename Pix<T>::v2
 }
 
 template <typename T, int K>
-static int broxt_tile_launch(ofx_ctx *ctx, const typename Pix<T>::v2 *Uin, typename Pix<T>::v2 *Uout, const typename Pix<T>::v4 *CO,
-                             const T *Dm, const T *Ps, int k0, int check, int slot0, int niter, int nx, int ny, int nz, double alpha,
-                             double thr)
+__global__ __launch_bounds__(BXT_NT) void k_broxt_tile(const typename Pix<T>::v2 *__restrict__ Uin, typename Pix<T>::v2 *__restrict__ Uout,
+                                                       const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                                                       const T *__restrict__ Ps, double *__restrict__ err, int k0, int check, int slot0,
+                                                       int niter, int nx, int ny, int nz, int tiles_x, double alpha, double tol)
+{
+    broxt_tile_unit<T, K>(Uin, Uout, CO, Dm, Ps, err, k0, check, slot0, niter, nx, ny, nz, tiles_x, alpha, tol);
+}
+// What a lockstep group adds to a launch (as k_brox_tile): blockIdx.y = sequence g; bit g of runmask = it takes part in this launch,
+// bit g of incode = its flow is in DU1, bits 4 g .. 4 g + 3 of nit = its sweeps in this launch
+struct BxtGrp {
+    unsigned incode, runmask;
+    unsigned long long nit;
+    int err_stride;
+};
+template <typename T, int K>
+__global__ __launch_bounds__(BXT_NT) void k_broxt_tile_group(typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1,
+                                                             const typename Pix<T>::v4 *__restrict__ CO, const T *__restrict__ Dm,
+                                                             const T *__restrict__ Ps, double *__restrict__ err, int k0, int check,
+                                                             int slot0, BxtGrp grp, int nx, int ny, int nz, int tiles_x, double alpha,
+                                                             double tol)
+{
+    const int g = blockIdx.y;
+    if (!((grp.runmask >> g) & 1u)) return;
+    const size_t seq = (size_t) nx * ny * nz * g;
+    const bool from1 = (grp.incode >> g) & 1u;
+    broxt_tile_unit<T, K>((from1 ? DU1 : DU0) + seq, (from1 ? DU0 : DU1) + seq, CO + seq, Dm + seq, Ps + seq,
+                          err + (size_t) g * grp.err_stride, k0, check, slot0, (int) ((grp.nit >> (4 * g)) & 15ull), nx, ny, nz, tiles_x,
+                          alpha, tol);
+}
+
+template <typename T, int K>
+static int broxt_tile_launch(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO,
+                             const T *Dm, const T *Ps, int k0, int check, int slot0, int nx, int ny, int nz, double alpha, double thr,
+                             unsigned incode, unsigned runmask, unsigned long long nit, int err_stride)
 {
     constexpr int OW = BXT_TW - 4 * K, OH = BXT_TH - 4 * K;
     const int tiles_x = ofx_cdiv(nx, OW), tiles_y = ofx_cdiv(ny, OH);
     const size_t lds = (size_t) nz * BXT_TH * BXT_TW * (sizeof(double2) + sizeof(double));
-    if (lds > 64 * 1024)
-        OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_broxt_tile<T, K>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int) lds));
-    hipLaunchKernelGGL((k_broxt_tile<T, K>), dim3((unsigned) (tiles_x * tiles_y)), dim3(BXT_NT), lds, ctx->stream, Uin, Uout, CO, Dm, Ps,
-                       ctx->d_err, k0, check, slot0, niter, nx, ny, nz, tiles_x, alpha, thr);
+    if (G == 1) {                                           // the lone kernel: the buffers are chosen here
+        using v2 = typename Pix<T>::v2;
+        const bool from1 = incode & 1u;
+        const v2 *in = from1 ? DU1 : DU0;
+        v2 *out = from1 ? DU0 : DU1;
+        if (lds > 64 * 1024)
+            OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_broxt_tile<T, K>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int) lds));
+        hipLaunchKernelGGL((k_broxt_tile<T, K>), dim3((unsigned) (tiles_x * tiles_y)), dim3(BXT_NT), lds, ctx->stream, in, out, CO, Dm, Ps,
+                           ctx->d_err, k0, check, slot0, (int) (nit & 15ull), nx, ny, nz, tiles_x, alpha, thr);
+    } else {
+        if (lds > 64 * 1024)
+            OFX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_broxt_tile_group<T, K>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        hipLaunchKernelGGL((k_broxt_tile_group<T, K>), dim3((unsigned) (tiles_x * tiles_y), G), dim3(BXT_NT), lds, ctx->stream, DU0, DU1, CO,
+                           Dm, Ps, ctx->d_err, k0, check, slot0, BxtGrp{incode, runmask, nit, err_stride}, nx, ny, nz, tiles_x, alpha, thr);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "brox temporal tile launch failed: %s", hipGetErrorString(e));
     return OFX_OK;
 }
 
-// One solve (:430-461): DU0 holds the incoming (du, dv) of the nz fields and the result; DU1 is the second buffer of the tile
-// kernel's ping-pong (k_broxt_rb works in place and never touches it).
+// One solve (:430-461) of each of G sequences: DU0 holds the incoming (du, dv) of their nz fields each and the result; DU1 is the
+// second buffer of the tile kernel's ping-pong (k_broxt_rb works in place and never touches it).  On return the result is in DU0
+// again for every sequence (k_copy_pairs for those whose last launch wrote DU1).
 template <typename T>
-int ofx_broxt_tile_solve(ofx_ctx *ctx, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO, const T *Dm,
-                         const T *Ps, int nx, int ny, int nz, double alpha, double TOL, int maxiter, int K, int *niter, double *error,
-                         float *ms)
+int ofx_broxt_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename Pix<T>::v2 *DU1, const typename Pix<T>::v4 *CO,
+                         const T *Dm, const T *Ps, int nx, int ny, int nz, double alpha, double TOL, int maxiter, int K, int *niter,
+                         double *error, float *ms)
 {
     using v2 = typename Pix<T>::v2;
-    *niter = 0;
-    *error = 1000;                                                                                   // :430
-    if (nz < 1 || (double) nx * ny * nz >= 2147483648.0) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: %dx%dx%d voxels", nx, ny, nz);
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: group of %d sequences", G);
+    for (int g = 0; g < G; g++) { niter[g] = 0; error[g] = 1000; }                                   // :430
+    if (nz < 1 || (double) nx * ny * nz * G >= 2147483648.0)
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: %d x %dx%dx%d voxels", G, nx, ny, nz);
     if (maxiter <= 0 || !(1000.0 > TOL)) return OFX_OK;
     const bool rb = K < 0 || K == 9 || nz > BXT_NF;
     if (K <= 0) K = BXT_DEFAULT_K;
@@ -1277,53 +1343,72 @@ int ofx_broxt_tile_solve(ofx_ctx *ctx, typename Pix<T>::v2 *DU0, typename Pix<T>
     S.afac = 0.0;
     if (ctx->chunk > 0) S.chunk = ctx->chunk;
     else if (rb) {
-        const double est_us = fmax(8.0, (double) S.size * 100.0 / 2.0e6);                            // sor_pick_chunk's estimate, 2 launches
+        const double est_us = fmax(8.0, (double) S.size * G * 100.0 / 2.0e6);                        // sor_pick_chunk's estimate, 2 launches
         const int c = (int) (60.0 / est_us);
         S.chunk = c < 2 ? 2 : (c > 32 ? 32 : c);
     } else {
-        const double tiles = (double) ofx_cdiv(nx, BXT_TW - 4 * K) * ofx_cdiv(ny, BXT_TH - 4 * K);
+        const double tiles = (double) ofx_cdiv(nx, BXT_TW - 4 * K) * ofx_cdiv(ny, BXT_TH - 4 * K) * G;
         const double est_us = 4.0 + 4.0 * K * (tiles < 256.0 ? 1.0 : tiles / 256.0);
         int units = (int) (80.0 / est_us);
         units = units < 1 ? 1 : (units > 8 ? 8 : units);
         S.chunk = units * K;
     }
+    const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
     if (rb) {
-        const dim3 g(ofx_cdiv(ofx_cdiv(nx, 2) + 1, 64), ofx_cdiv(ny, 4), nz), b(64, 4);
+        const dim3 g(ofx_cdiv(ofx_cdiv(nx, 2) + 1, 64), ofx_cdiv(ny, 4), G * nz), b(64, 4);
         auto launch = [&](int k, int, double thr) -> int {
             for (int col = 0; col < 2; col++)
-                hipLaunchKernelGGL(k_broxt_rb<T>, g, b, 0, ctx->stream, DU0, CO, Dm, Ps, ctx->d_err, k, nx, ny, nz, col, alpha, thr);
+                if (G == 1)
+                    hipLaunchKernelGGL(k_broxt_rb<T>, g, b, 0, ctx->stream, DU0, CO, Dm, Ps, ctx->d_err, k, nx, ny, nz, col, alpha, thr);
+                else
+                    hipLaunchKernelGGL(k_broxt_rb_group<T>, g, b, 0, ctx->stream, DU0, CO, Dm, Ps, ctx->d_err, k, nx, ny, nz, col, alpha,
+                                       thr, err_stride);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "brox temporal sweep launch failed: %s", hipGetErrorString(e));
             return OFX_OK;
         };
-        return ofx_run_loop_group(ctx, S, 1, launch, [](const int *) { return OFX_OK; }, niter, error, ms);
+        return ofx_run_loop_group(ctx, S, G, launch, [](const int *) { return OFX_OK; }, niter, error, ms);
     }
-    auto go = [&](int k0, int check, int slot0, int cnt, double thr, bool from1) -> int {
-        const v2 *in = from1 ? DU1 : DU0;
-        v2 *out = from1 ? DU0 : DU1;
+    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
+    auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit) -> int {
         switch (K) {
-        case 1: return broxt_tile_launch<T, 1>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
-        case 2: return broxt_tile_launch<T, 2>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
-        default: return broxt_tile_launch<T, 4>(ctx, in, out, CO, Dm, Ps, k0, check, slot0, cnt, nx, ny, nz, alpha, thr);
+        case 1: return broxt_tile_launch<T, 1>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, nz, alpha, thr, incode, runmask, nit, err_stride);
+        case 2: return broxt_tile_launch<T, 2>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, nz, alpha, thr, incode, runmask, nit, err_stride);
+        default: return broxt_tile_launch<T, 4>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, nz, alpha, thr, incode, runmask, nit, err_stride);
         }
     };
-    // unit j = sweeps j K .. j K + K - 1 reads DU0 when j is even
-    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, cnt, thr, ((k / K) & 1) != 0); };
-    auto redo = [&](const int *k_of) -> int {
-        if (k_of[0] < 0) return OFX_OK;
-        const int n = k_of[0] + 1, j = (n - 1) / K;
-        return go(0, 0, S.max_iter, n - j * K, -1.0, (j & 1) != 0);
+    // unit j = sweeps j K .. j K + K - 1 reads DU0 when j is even (every sequence starts in DU0; one that has stopped leaves at
+    // the kernel's own test, before it writes)
+    auto launch = [&](int k, int cnt, double thr) -> int {
+        unsigned long long nit = 0;
+        for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
+        return go(k, 1, k, thr, ((k / K) & 1) ? all : 0u, all, nit);
     };
-    OFX_TRY(ofx_run_loop_group(ctx, S, 1, launch, redo, niter, error, ms));
-    if (((*niter + K - 1) / K) & 1) {
+    // the sequences that stopped inside a launch unit: its first sweeps again from the unit's input, each in its own phase
+    auto redo = [&](const int *k_of) -> int {
+        unsigned incode = 0, runmask = 0;
+        unsigned long long nit = 0;
+        for (int g = 0; g < G; g++) {
+            if (k_of[g] < 0) continue;
+            const int n = k_of[g] + 1, j = (n - 1) / K;
+            runmask |= 1u << g;
+            incode |= ((unsigned) j & 1u) << g;
+            nit |= (unsigned long long) (n - j * K) << (4 * g);
+        }
+        return go(0, 0, S.max_iter, -1.0, incode, runmask, nit);
+    };
+    OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, niter, error, ms));
+    unsigned in1 = 0;
+    for (int g = 0; g < G; g++) in1 |= ((unsigned) ((niter[g] + K - 1) / K) & 1u) << g;
+    if (in1) {
         const size_t n1 = (size_t) nx * ny * nz;
-        hipLaunchKernelGGL((k_copy_pairs<v2>), dim3((unsigned) ((n1 + 255) / 256), 1), dim3(256), 0, ctx->stream, (const v2 *) DU1, DU0, n1, 1u);
+        hipLaunchKernelGGL((k_copy_pairs<v2>), dim3((unsigned) ((n1 + 255) / 256), G), dim3(256), 0, ctx->stream, (const v2 *) DU1, DU0, n1, in1);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "copy launch failed: %s", hipGetErrorString(e));
     }
     return OFX_OK;
 }
-template int ofx_broxt_tile_solve<double>(ofx_ctx *, double2 *, double2 *, const double4 *, const double *, const double *, int, int, int,
+template int ofx_broxt_tile_solve<double>(ofx_ctx *, int, double2 *, double2 *, const double4 *, const double *, const double *, int, int, int,
                                           double, double, int, int, int *, double *, float *);
-template int ofx_broxt_tile_solve<float>(ofx_ctx *, float2 *, float2 *, const float4 *, const float *, const float *, int, int, int, double,
+template int ofx_broxt_tile_solve<float>(ofx_ctx *, int, float2 *, float2 *, const float4 *, const float *, const float *, int, int, int, double,
                                          double, int, int, int *, double *, float *);

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""Temporal Brox, whole solve, three ways in one process: the host entry (ofx_brox_temporal), the device entry on the same frames
-(ofx_brox_temporal_dev) and a batch of independent sequences (ofx_brox_temporal_batch_dev).
-    python tools/bench_brox_temporal.py [--size 640x480] [--frames 5] [--check] [--batch CTX:SEQUENCES] [--reps 5]
+"""Temporal Brox, whole solve, four ways in one process: the host entry (ofx_brox_temporal), the device entry on the same frames
+(ofx_brox_temporal_dev), a lockstep group of sequences (ofx_brox_temporal_group_dev) against the same sequences one after the
+other through the device entry, and a batch of independent sequences (ofx_brox_temporal_batch_dev; --opt lockstep=L makes it
+run lockstep groups of L).
+    python tools/bench_brox_temporal.py [--size 640x480] [--frames 5] [--check] [--group G] [--batch CTX:SEQUENCES] [--reps 5]
 One JSON line.  Every figure is wall time of a warmed call, the median of --reps timed runs; the host and the device entry are
 timed in turn.  --check: the payloads of the device entry and of the batch against the host entry (array_equal), and the host
 entry against the compiled reference on one thread (test infrastructure, oracle/; the port when the reference is not built):
 largest difference, average end-point error (the figure that matters under --opt sor_exact=0, which sweeps in another order) and
-the reference order's sweep count next to "sweeps".
+the reference order's sweep count next to "sweeps" (--no-cpu leaves the CPU run out).  The payloads of a group, and of a batch
+under --opt lockstep=L, are compared one by one with the lone device entry's under the same options.
 A library without the device entries (OFX_LIB_PATH: an A/B against an older build) is timed on the host entry alone."""
 import argparse
 import importlib
@@ -34,6 +37,8 @@ ap.add_argument("--outer", type=int, default=15)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--batch", default="", help="contexts:sequences, e.g. 3:12 -- also time a batch of independent sequences")
+ap.add_argument("--group", type=int, default=0, help="also time one lockstep group of this many sequences against as many lone solves")
+ap.add_argument("--no-cpu", action="store_true", help="with --check: compare the entries with each other only")
 ap.add_argument("--opt", action="append", default=[], help="name=value for every context")
 a = ap.parse_args()
 
@@ -82,17 +87,72 @@ rec = {"config": "brox_temporal %dx%d x %d frames, %s" % (nx, ny, a.frames, kw),
        "flow_crc": int(np.frombuffer(payload(u, v).tobytes(), dtype=np.uint32).sum(dtype=np.uint64)),
        "host_entry": {"seconds": round(statistics.median(t_host), 4), "runs": [round(x, 4) for x in t_host],
                       "mpix_sweeps_per_s": round(work / statistics.median(t_host) / 1e6, 1)},
-       "device_entry": None, "batch": None}
+       "device_entry": None, "group": None, "batch": None}
 if have_dev:
     rec["device_entry"] = {"seconds": round(statistics.median(t_dev), 4), "runs": [round(x, 4) for x in t_dev],
                            "device_over_host": round(statistics.median(t_dev) / statistics.median(t_host), 3)}
     if a.check:
         rec["device_entry"]["payloads_equal_host_entry"] = bool(np.array_equal(d_flo.cpu().numpy(), payload(u, v)))
+have_group = "ofx_brox_temporal_group_dev" not in ofx.lib().ofx_missing
+_clips, _lone = {}, {}
+
+
+def clip(k):
+    if k not in _clips:
+        _clips[k] = torch.from_numpy(synth.sequence(nx, ny, a.frames, k)).cuda()
+    return _clips[k]
+
+
+def lone_payload(k):
+    """sequence k through the lone device entry under the options of `ctx`"""
+    if k not in _lone:
+        flo = torch.zeros((a.frames - 1, ny, nx, 2), dtype=torch.float32, device="cuda")
+        ctx.brox_temporal_dev(ptrs(clip(k)), ptrs(flo), nx, ny, **kw)
+        ctx.synchronize()
+        _lone[k] = flo.cpu().numpy()
+    return _lone[k]
+
+
+if a.group and have_group:
+    G = a.group
+    g_dF = [p for k in range(G) for p in ptrs(clip(k))]
+    g_flo = torch.zeros((G * (a.frames - 1), ny, nx, 2), dtype=torch.float32, device="cuda")
+    l_flo = torch.zeros((a.frames - 1, ny, nx, 2), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+
+    def run_group():
+        st = ctx.brox_temporal_group_dev(g_dF, ptrs(g_flo), nx, ny, a.frames, **kw)
+        ctx.synchronize()
+        return st
+
+    def run_lone():
+        for k in range(G):
+            ctx.brox_temporal_dev(ptrs(clip(k)), ptrs(l_flo), nx, ny, **kw)
+        ctx.synchronize()
+
+    run_group()                                            # warm: the arena grows to the group's size
+    run_lone()
+    t_g, t_l = [], []
+    for _ in range(max(a.reps // 2, 3)):                   # in turn
+        t = time.perf_counter()
+        st = run_group()
+        t_g.append(time.perf_counter() - t)
+        t = time.perf_counter()
+        run_lone()
+        t_l.append(time.perf_counter() - t)
+    gt, lt = statistics.median(t_g), statistics.median(t_l)
+    rec["group"] = {"sequences": G, "seconds": round(gt, 4), "runs": [round(x, 4) for x in t_g], "s_per_sequence": round(gt / G, 4),
+                    "lone_seconds": round(lt, 4), "lone_runs": [round(x, 4) for x in t_l], "lone_s_per_sequence": round(lt / G, 4),
+                    "lone_over_group": round(lt / gt, 3), "sweeps": [int(x.iterations().sum()) for x in st],
+                    "mpix_sweeps_per_s": round(sum(x.work_pix_iters for x in st) / gt / 1e6, 1)}
+    if a.check:
+        got = g_flo.cpu().numpy().reshape(G, a.frames - 1, ny, nx, 2)
+        rec["group"]["payloads_equal_lone_entry"] = all(bool(np.array_equal(got[k], lone_payload(k))) for k in range(G))
 if a.batch and have_dev:
     n_ctx, n_seq = (int(x) for x in a.batch.split(":"))
     ctxs = [context() for _ in range(n_ctx)]
     seqs = [synth.sequence(nx, ny, a.frames, k) for k in range(n_seq)]
-    clips = [torch.from_numpy(s).cuda() for s in seqs]
+    clips = [clip(k) for k in range(n_seq)]
     b_flo = torch.zeros((n_seq * (a.frames - 1), ny, nx, 2), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
     b_dF = [p for c in clips for p in ptrs(c)]
@@ -113,7 +173,8 @@ if a.batch and have_dev:
         for q in sorted({0, n_seq // 2, n_seq - 1}):
             equal = equal and bool(np.array_equal(got[q], payload(*ctx.brox_temporal(seqs[q], **kw))))
         rec["batch"]["payloads_equal_host_entry"] = equal
-if a.check:
+        rec["batch"]["payloads_equal_lone_entry"] = all(bool(np.array_equal(got[q], lone_payload(q))) for q in range(n_seq))
+if a.check and not a.no_cpu:
     import oracle
     cpu = oracle.Ref() if oracle.have_ref() else oracle.Oracle()
     cpu.set_num_threads(1)
