@@ -590,8 +590,8 @@ int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const doub
  * nscales, warps, zfactor, theta, lambda, a coarsest level below 2x2), a pyramid that cannot be built (OFX_ERR_SIGMA: a level too
  * small for its Gaussian), n_frames < 3, n_frames > 18 for the group entry, a NULL array, a NULL or misaligned pointer at index k,
  * contexts on different devices or of different precision.
- * Not provided: device-resident triples that are not consecutive frames of one sequence, and a separate filtI0 -- use the host
- * entries above for those. */
+ * Device-resident triples that are not consecutive frames of one sequence, and a separate filtI0, go through
+ * ofx_tvl1occ_triples_group_dev / ofx_tvl1occ_triples_dev below. */
 int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo,
                                    void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
                                    double theta, int nscales, double zfactor, int warps, double epsilon,
@@ -599,6 +599,53 @@ int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const
 int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
                              void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
                              int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters);
+
+/* The same solve over INDEXED TRIPLES of a table of device-resident planes: the backward triple (F[t + 1], F[t], F[t - 1]), strided
+ * triples (F[t - s], F[t], F[t + s]), a g-image of the caller's own (the I0_Smoothed argument of tvl1occflow) -- any combination
+ * of planes.  Triple k gets what ofx_tvl1occ_multiscale(dF[prev], dF[cur], dF[next], filtI0 = dF[filt]) computes on those values,
+ * bit for bit, with its own stopping test and outer-iteration counts.
+ *   dF[i]     the frame table, n_frames >= 1 device pointers as above (nxx * nyy elements of the context's storage precision,
+ *             aligned to the element, converted exactly to double).  A g-image of the caller's own is simply another plane of the
+ *             table.  Only planes that some triple references are dereferenced: unreferenced entries may be NULL.
+ *   tr[k]     n_triples records of indices into the table; filt = -1 means cur.  Planes are told apart by INDEX, not by pointer:
+ *             two indices with the same pointer are two planes.
+ *   d_flo[k], d_occ[k]  n_triples payloads and maps as above (8-byte aligned | no alignment).
+ * What is shared: as above, a plane's presmoothed pyramid and centred gradients depend on that plane alone, whatever role it plays
+ * in whichever triple.  A group keeps each distinct referenced plane once per level and the roles of a triple are indices into
+ * that array (a by-value table of 4 x 16 bytes, read by the two kernels that read images); every other stage is the sequence
+ * entry's.
+ * ofx_tvl1occ_triples_group_dev: one lockstep group, n_triples in 1 .. 16, hence at most 64 distinct planes: a group never fails
+ * for having "too many frames".  stats_out: NULL or n_triples records, filled as the sequence group entry fills them.
+ * Asynchronous on the context's stream in the same sense.
+ * ofx_tvl1occ_triples_dev: any n_triples >= 1 (0: OFX_OK, nothing done) on one or several contexts of ONE device and one
+ * precision.  Groups are G consecutive triples IN THE CALLER'S ORDER, group q on ctxs[q % n_ctx], a worker thread per context;
+ * a plane that two groups share is built by both, so order the triples so that neighbours share frames (forward and backward
+ * triple of one centre next to each other, centres in sequence order).  G = the smallest of: option "lockstep" of ctxs[0] if
+ * positive; 16; ceil(n_triples / n_ctx); the largest G for which every group fits the memory rule under option "mem_budget"
+ * (default: half of the free device memory) divided by n_ctx.  The memory rule is the sequence entry's with D, the group's own
+ * count of distinct planes, in place of G + 2: in doubles, D + 3 G planes per pyramid level, 2 D + 27 G full-size planes and 13 G
+ * hyperplane-major ones, plus 5 %; if one triple does not fit: OFX_ERR_NOMEM.  work_pix_iters: NULL or one double per triple.
+ * Returns when every payload is complete.
+ * ofx_tvl1occ_triples_frames: the decision both entries build their tables with, pure host code (no context, no device).  Returns
+ * D, the number of distinct referenced indices, or -OFX_ERR_ARG (n_frames < 1, an index outside 0 .. n_frames - 1 other than
+ * filt = -1).  frames_out (NULL or room for 4 * n_triples): the indices in order of first appearance, scanning the triples in
+ * order and the roles prev, cur, next, filt.  roles_out (NULL or [n_triples][4] bytes, n_triples <= 64): the position in
+ * frames_out of role r of triple k, filt = -1 resolved to cur's position.
+ * Errors, all found before any work (no byte of d_flo / d_occ is written): everything ofx_tvl1occ_sequence_group_dev rejects
+ * (sizes, nscales, warps, zfactor, theta, lambda, a coarsest level below 2x2, OFX_ERR_SIGMA for a level too small for its
+ * Gaussian), n_triples outside 1 .. 16 for the group entry, a NULL array, an index outside the table (ofx_last_error names the
+ * triple and the role), a referenced plane that is NULL or misaligned, a NULL or misaligned result pointer, contexts on different
+ * devices or of different precision. */
+typedef struct ofx_occ_triple { int prev, cur, next, filt; } ofx_occ_triple;
+int ofx_tvl1occ_triples_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_triples, const ofx_occ_triple *tr,
+                                  void *const *d_flo, void *const *d_occ, int nxx, int nyy, double lambda, double alpha,
+                                  double beta, double theta, int nscales, double zfactor, int warps, double epsilon,
+                                  ofx_stats *stats_out);
+int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, int n_triples,
+                            const ofx_occ_triple *tr, void *const *d_flo, void *const *d_occ, int nxx, int nyy, double lambda,
+                            double alpha, double beta, double theta, int nscales, double zfactor, int warps, double epsilon,
+                            double *work_pix_iters);
+int ofx_tvl1occ_triples_frames(int n_frames, int n_triples, const ofx_occ_triple *tr, int *frames_out, unsigned char *roles_out);
 
 #ifdef __cplusplus
 }

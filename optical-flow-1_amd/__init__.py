@@ -51,6 +51,11 @@ class Stats(C.Structure):
                          for s in range(self.nscales)])
 
 
+class OccTriple(C.Structure):
+    """ofx_occ_triple: indices into a frame table; filt = -1 means cur"""
+    _fields_ = [("prev", C.c_int), ("cur", C.c_int), ("next", C.c_int), ("filt", C.c_int)]
+
+
 def build(verbose=False):
     """Compile libofx.so for gfx950 (hipcc cross-compiles without a GPU)."""
     out = subprocess.run(["make", "-C", os.path.join(HERE, "csrc"), "-j4"], capture_output=True, text=True)
@@ -148,6 +153,11 @@ def lib():
                                                 _i, _d, C.POINTER(Stats)]),
         "ofx_tvl1occ_sequence_dev": (_i, [C.POINTER(_vp), _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _d,
                                           _d, _i, _d, _i, _d, C.POINTER(_d)]),
+        "ofx_tvl1occ_triples_group_dev": (_i, [_vp, _i, C.POINTER(_vp), _i, C.POINTER(OccTriple), C.POINTER(_vp), C.POINTER(_vp), _i, _i,
+                                               _d, _d, _d, _d, _i, _d, _i, _d, C.POINTER(Stats)]),
+        "ofx_tvl1occ_triples_dev": (_i, [C.POINTER(_vp), _i, _i, C.POINTER(_vp), _i, C.POINTER(OccTriple), C.POINTER(_vp), C.POINTER(_vp),
+                                         _i, _i, _d, _d, _d, _d, _i, _d, _i, _d, C.POINTER(_d)]),
+        "ofx_tvl1occ_triples_frames": (_i, [_i, _i, C.POINTER(OccTriple), C.POINTER(_i), C.POINTER(C.c_ubyte)]),
         "ofx_hs_classic": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _d]),
         "ofx_brox_temporal": (_i, [_vp, _dp, _dp, _dp, _i, _i, _i, _d, _d, _i, _d, _d, _i, _i, _i]),
         "ofx_brox_temporal_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _d, _d, _i, _i]),
@@ -253,6 +263,42 @@ def tvl1occ_sequence_dev(ctxs, dF, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, b
     if s:
         raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
     return [work[i] for i in range(max(n - 2, 0))]
+
+
+def _occ_triples(triples):
+    """(prev, cur, next) or (prev, cur, next, filt) index tuples -> an ofx_occ_triple array (never of length 0)"""
+    arr = (OccTriple * max(len(triples), 1))()
+    for k, t in enumerate(triples):
+        arr[k] = OccTriple(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else -1)
+    return arr
+
+
+def tvl1occ_triples_frames(n_frames, triples):
+    """ofx_tvl1occ_triples_frames: (frames, roles) -- the distinct referenced indices of the triples in order of first appearance
+    and, per triple, the positions of its roles (prev, cur, next, filt) among them.  Raises OfxError on an index outside the table."""
+    n = len(triples)
+    frames = (_i * max(4 * n, 1))()
+    roles = (C.c_ubyte * max(4 * n, 1))()
+    D = lib().ofx_tvl1occ_triples_frames(n_frames, n, _occ_triples(triples), frames, roles)
+    if D < 0:
+        raise OfxError(-D, "tvl1occ triples: index outside the frame table")
+    return [frames[d] for d in range(D)], [tuple(roles[4 * k + r] for r in range(4)) for k in range(n)]
+
+
+def tvl1occ_triples_dev(ctxs, dF, triples, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3, zfactor=0.5,
+                        warps=2, epsilon=0.01):
+    """ofx_tvl1occ_triples_dev: dF = table of device pointers (ints; None where no triple refers to the entry) of planes in the
+    contexts' storage type, triples = (prev, cur, next[, filt]) indices into it; d_flo, d_occ = device pointers of the len(triples)
+    payloads and maps.  Lockstep groups of consecutive triples in the given order, group q on ctxs[q % len(ctxs)] -- order the
+    triples so that neighbours share frames.  Returns when every result is complete, with the per-triple work."""
+    n = len(triples)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n, 1))()
+    s = lib().ofx_tvl1occ_triples_dev(arr([c.h.value for c in ctxs]), len(ctxs), len(dF), arr(dF), n, _occ_triples(triples), arr(d_flo),
+                                      arr(d_occ), nx, ny, lam, alpha, beta, theta, nscales, zfactor, warps, epsilon, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(n)]
 
 
 def brox_temporal_batch_dev(ctxs, dF, d_flo, nx, ny, frames, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15):
@@ -692,6 +738,17 @@ class Ofx:
         self._ck(self.L.ofx_tvl1occ_sequence_group_dev(self.h, n, arr(dF), arr(d_flo), arr(d_occ), nx, ny, lam, alpha, beta, theta,
                                                        nscales, zfactor, warps, epsilon, st))
         return [st[i] for i in range(max(n - 2, 0))]
+
+    def tvl1occ_triples_group_dev(self, dF, triples, d_flo, d_occ, nx, ny, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3,
+                                  zfactor=0.5, warps=2, epsilon=0.01):
+        """ofx_tvl1occ_triples_group_dev: 1..16 indexed triples of a table of device-resident planes in lockstep on this context
+        (arguments as tvl1occ_triples_dev).  Enqueues on the context's stream; returns the per-triple Stats records."""
+        n = len(triples)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n, 1))()
+        self._ck(self.L.ofx_tvl1occ_triples_group_dev(self.h, len(dF), arr(dF), n, _occ_triples(triples), arr(d_flo), arr(d_occ), nx, ny,
+                                                      lam, alpha, beta, theta, nscales, zfactor, warps, epsilon, st))
+        return [st[i] for i in range(n)]
 
     def occ_solver_u(self, v1, v2, chi, g, theta, beta, p=None, n_iter=10):
         """Solver_wrt_u with the four dual planes as explicit state -> (u1, u2, [p11, p12, p21, p22]); p defaults to zero"""

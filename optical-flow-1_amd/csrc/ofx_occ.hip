@@ -1174,12 +1174,40 @@ extern "C" int ofx_solver_wrt_u(ofx_ctx *ctx, double *u1, double *u2, const doub
 #define OCC_MAX_GROUP 16           // triples per lockstep group
 
 // g = 1 / (1 + G_FACTOR |grad filtI0|), choosed_g choice 2 (:96-133); Ix, Iy = centred gradient
+OFX_DEV double occ_g_px(double ix, double iy)
+{
+    const double gggrad = sqrt(ix * ix + iy * iy);
+    return 1. / (1. + OCC_G_FACTOR * gggrad);
+}
 __global__ void k_occ_g(const double *__restrict__ Ix, const double *__restrict__ Iy, double *__restrict__ g, size_t size)
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= size) return;
-    const double gggrad = sqrt(Ix[i] * Ix[i] + Iy[i] * Iy[i]);
-    g[i] = 1. / (1. + OCC_G_FACTOR * gggrad);
+    g[i] = occ_g_px(Ix[i], Iy[i]);
+}
+
+// Role table of a group of indexed triples (ofx_tvl1occ_triples_group_dev): the level keeps D distinct planes once, [D][n], and
+// role r of triple g = blockIdx.z is plane idx.r[g] of them.  Passed by value; the index is uniform over a workgroup, so the
+// plane's base is scalar arithmetic on kernel arguments and the loads stay base + lane offset as in the kernels above.
+struct alignas(4) OccIdx {
+    unsigned char prev[OCC_MAX_GROUP], cur[OCC_MAX_GROUP], next[OCC_MAX_GROUP], filt[OCC_MAX_GROUP];
+};
+// element offset of the plane of one role: the aligned word that holds the triple's byte is a scalar load (a byte load from the
+// kernel arguments would go through the vector memory path), the byte a scalar shift
+OFX_DEV size_t occ_plane(const unsigned char (&role)[OCC_MAX_GROUP], size_t n)
+{
+    const unsigned z = blockIdx.z;
+    unsigned w;
+    __builtin_memcpy(&w, static_cast<const unsigned char *>(__builtin_assume_aligned(role, 4)) + (z & ~3u), sizeof w);
+    return (size_t) ((w >> (8 * (z & 3u))) & 0xffu) * n;
+}
+// k_occ_g with Ix, Iy = gx, gy [D][n] at the plane of role filt; g is [G][n], blockIdx.z = triple
+__global__ void k_occ_g_idx(const double *__restrict__ gx, const double *__restrict__ gy, double *__restrict__ g, int n, OccIdx idx)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t f = occ_plane(idx.filt, n);
+    g[(size_t) blockIdx.z * n + i] = occ_g_px(gx[f + i], gy[f + i]);
 }
 
 // the six warps of one warping step and what is derived from them (:214-248), one thread per pixel: I1, I1x, I1y sampled at
@@ -1198,16 +1226,15 @@ OFX_DEV double occ_sample(const double *__restrict__ in, const BicubicTaps &t, i
                           in[(size_t) t.row[2] * nx + t.col[q]], in[(size_t) t.row[3] * nx + t.col[q]], t.fy);
     return cubic_cell(c[0], c[1], c[2], c[3], t.fx);
 }
-__global__ void k_occ_prepare(OccPrep a, int nx, int ny, OccGrp G)
+// pixel (j, i) of the triple whose planes (u1 .. rho3_c) start at element o; its images start at elements oc (I0), of (I1 and its
+// gradients) and ob (I_1 and its gradients) of a's image arrays
+OFX_DEV void occ_prepare_px(const OccPrep &a, size_t oc, size_t of, size_t ob, size_t o, int j, int i, int nx, int ny)
 {
-    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
-    size_t o;
-    if (j >= nx || i >= ny || !occ_grp(G, o)) return;
     const size_t p = o + (size_t) i * nx + j;
-    const double u1 = a.u1[p], u2 = a.u2[p], i0 = a.I0[p];
+    const double u1 = a.u1[p], u2 = a.u2[p], i0 = a.I0[oc + (size_t) i * nx + j];
     {
         const BicubicTaps t = bicubic_taps(j + u1, i + u2, nx, ny);
-        const double w = occ_sample(a.I1 + o, t, nx), wx = occ_sample(a.I1x + o, t, nx), wy = occ_sample(a.I1y + o, t, nx);
+        const double w = occ_sample(a.I1 + of, t, nx), wx = occ_sample(a.I1x + of, t, nx), wy = occ_sample(a.I1y + of, t, nx);
         a.I1wx[p] = wx;
         a.I1wy[p] = wy;
         a.grad1[p] = (wx * wx + wy * wy);
@@ -1215,12 +1242,28 @@ __global__ void k_occ_prepare(OccPrep a, int nx, int ny, OccGrp G)
     }
     {
         const BicubicTaps t = bicubic_taps(j + (-u1), i + (-u2), nx, ny);
-        const double w = occ_sample(a.I_1 + o, t, nx), wx = occ_sample(a.I_1x + o, t, nx), wy = occ_sample(a.I_1y + o, t, nx);
+        const double w = occ_sample(a.I_1 + ob, t, nx), wx = occ_sample(a.I_1x + ob, t, nx), wy = occ_sample(a.I_1y + ob, t, nx);
         a.I_1wx[p] = wx;
         a.I_1wy[p] = wy;
         a.grad3[p] = (wx * wx + wy * wy);
         a.rho3_c[p] = (w + wx * u1 + wy * u2 - i0);
     }
+}
+__global__ void k_occ_prepare(OccPrep a, int nx, int ny, OccGrp G)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    size_t o;
+    if (j >= nx || i >= ny || !occ_grp(G, o)) return;
+    occ_prepare_px(a, o, o, o, o, j, i, nx, ny);
+}
+// ... of indexed triples: a.I0 = a.I1 = a.I_1 = the level's planes [D][n], a.I1x = a.I_1x and a.I1y = a.I_1y their gradients; the
+// triple's images are the planes of its roles
+__global__ void k_occ_prepare_idx(OccPrep a, OccIdx idx, int nx, int ny, OccGrp G)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    size_t o;
+    if (j >= nx || i >= ny || !occ_grp(G, o)) return;
+    occ_prepare_px(a, occ_plane(idx.cur, G.stride), occ_plane(idx.next, G.stride), occ_plane(idx.prev, G.stride), o, j, i, nx, ny);
 }
 
 // 3 x 3 median of both flow components of every triple in one launch (blockIdx.z = 2 triple + component)
@@ -1346,9 +1389,11 @@ struct OccGrad {
 };
 
 // one level of G triples, arrays [G][nx ny] on the device, u1 / u2 / chi in place; the level's dual state is zeroed here.
-// stats[g]: the record of triple g.
+// stats[g]: the record of triple g.  idx != nullptr: indexed triples -- I_1 = I0 = I1 = the level's planes [D][nx ny], D.I1x = D.I_1x
+// = D.filtx and D.I1y = D.I_1y = D.filty their gradients, and the two kernels that read images take the planes of the roles.
 int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I0, const double *I1, const OccGrad &D, double *u1,
-                         double *u2, double *chi, int nx, int ny, const OccParams &P, const OccWork &W, int scale, ofx_stats *stats)
+                         double *u2, double *chi, int nx, int ny, const OccParams &P, const OccWork &W, int scale, ofx_stats *stats,
+                         const OccIdx *idx = nullptr)
 {
     const size_t n = (size_t) nx * ny;
     const dim3 grid(ofx_cdiv(nx, 64), ofx_cdiv(ny, 4), G), block(64, 4);
@@ -1359,7 +1404,8 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     OFX_HIP(ctx, hipMemsetAsync(W.state, 0, 4 * nsk * G * sizeof(double), st));
     OFX_HIP(ctx, hipMemsetAsync(W.eta, 0, 2 * n * G * sizeof(double), st));
     double *eta1 = W.eta, *eta2 = W.eta + n * G;
-    hipLaunchKernelGGL(k_occ_g, dim3(occ_grid1d(n * G)), dim3(256), 0, st, D.filtx, D.filty, W.g, n * G);
+    if (idx) hipLaunchKernelGGL(k_occ_g_idx, g1, dim3(256), 0, st, D.filtx, D.filty, W.g, (int) n, *idx);
+    else hipLaunchKernelGGL(k_occ_g, dim3(occ_grid1d(n * G)), dim3(256), 0, st, D.filtx, D.filty, W.g, n * G);
     OFX_HIP(ctx, hipMemcpyAsync(W.u1p, u1, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
     OFX_HIP(ctx, hipMemcpyAsync(W.u2p, u2, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
     const OccPrep prep = {I0, I1, D.I1x, D.I1y, I_1, D.I_1x, D.I_1y, u1, u2, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.grad1, W.grad3,
@@ -1374,7 +1420,8 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     double *h_err = ctx->h_aux;                                      // pinned, OFX_MAX_GROUP doubles, not the poll ring
     double *d_err = W.part + (size_t) OCC_ERR_BLOCKS * G;
     for (int w = 0; w < P.warps; w++) {
-        hipLaunchKernelGGL(k_occ_prepare, grid, block, 0, st, prep, nx, ny, OccGrp{n, all});
+        if (idx) hipLaunchKernelGGL(k_occ_prepare_idx, grid, block, 0, st, prep, *idx, nx, ny, OccGrp{n, all});
+        else hipLaunchKernelGGL(k_occ_prepare, grid, block, 0, st, prep, nx, ny, OccGrp{n, all});
         OFX_LAUNCH_CHECK(ctx);
         int it[OCC_MAX_GROUP];
         double error[OCC_MAX_GROUP];
@@ -1694,12 +1741,14 @@ int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *
     return OFX_OK;
 }
 
-// G = n_frames - 2 triples in lockstep; sizes checked by the caller
+// G triples over the F planes dF in lockstep; sizes checked by the caller.  idx == nullptr: the consecutive triples of a sequence,
+// F = G + 2, the roles are views at an offset; else F distinct planes (at most 4 G) and the roles of triple g are idx's.
 template <typename TIN>
-int occ_seq_group_impl(ofx_ctx *ctx, int G, const void *const *dF, void *const *d_flo, void *const *d_occ, const OccParams &P,
-                       int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys, ofx_stats *stats)
+int occ_planes_group_impl(ofx_ctx *ctx, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
+                          const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
+                          ofx_stats *stats)
 {
-    const int F = G + 2, nxx = nxs[0], nyy = nys[0];
+    const int nxx = nxs[0], nyy = nys[0];
     for (int g = 0; g < G; g++) {
         ofx_stats &S = stats[g];
         S = ofx_stats{};
@@ -1723,9 +1772,12 @@ int occ_seq_group_impl(ofx_ctx *ctx, int G, const void *const *dF, void *const *
         OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].chi));
     }
     hipStream_t st = ctx->stream;
-    OccSeqIn in = {};
-    for (int k = 0; k < F; k++) in.f[k] = dF[k];
-    hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, F), dim3(256), 0, st, in, lv[0].fr, (int) size);
+    for (int k0 = 0; k0 < F; k0 += OCC_MAX_GROUP + 2) {     // OccSeqIn holds 18 pointers: a sequence's frames are one launch, 64 planes four
+        const int cnt = F - k0 < OCC_MAX_GROUP + 2 ? F - k0 : OCC_MAX_GROUP + 2;
+        OccSeqIn in = {};
+        for (int k = 0; k < cnt; k++) in.f[k] = dF[k0 + k];
+        hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, (int) size);
+    }
     OFX_LAUNCH_CHECK(ctx);
     OFX_TRY(op_gaussian_planes<double>(ctx, F, F, lv[0].fr, nullptr, size, gx, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
     for (int s = 1; s < nscales; s++)
@@ -1739,9 +1791,14 @@ int occ_seq_group_impl(ofx_ctx *ctx, int G, const void *const *dF, void *const *
     for (int s = nscales - 1; s >= 0; s--) {
         const size_t n = (size_t) nxs[s] * nys[s];
         OFX_TRY(op_centered_gradient_planes<double>(ctx, F, lv[s].fr, gx, gy, nxs[s], nys[s]));
-        const OccGrad D = {gx + n, gy + n, gx + 2 * n, gy + 2 * n, gx, gy};
-        OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr + n, lv[s].fr + 2 * n, D, lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P,
-                                     W, s, stats));
+        if (idx) {
+            OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr, lv[s].fr, OccGrad{gx, gy, gx, gy, gx, gy}, lv[s].u1, lv[s].u2, lv[s].chi,
+                                         nxs[s], nys[s], P, W, s, stats, idx));
+        } else {
+            const OccGrad D = {gx + n, gy + n, gx + 2 * n, gy + 2 * n, gx, gy};
+            OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr + n, lv[s].fr + 2 * n, D, lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P,
+                                         W, s, stats));
+        }
         if (s)
             OFX_TRY(op_zoom_in_planes3<double>(ctx, G, lv[s].u1, lv[s].u2, lv[s].chi, lv[s - 1].u1, lv[s - 1].u2, lv[s - 1].chi, nxs[s], nys[s],
                                                nxs[s - 1], nys[s - 1], (double) 1.0 / zfactor));
@@ -1752,6 +1809,75 @@ int occ_seq_group_impl(ofx_ctx *ctx, int G, const void *const *dF, void *const *
                        (const double *) lv[0].u2, (const double *) lv[0].chi, out, (int) size);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
+}
+
+// a checked group on its context: the storage type, the records (stats_out: NULL or G of them), nothing in flight after an error
+int occ_planes_group(ofx_ctx *ctx, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
+                     const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
+                     ofx_stats *stats_out)
+{
+    const double t0 = ofx_now_ms();
+    std::vector<ofx_stats> local(stats_out ? 0 : G);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    const int s = ctx->precision == OFX_F64
+                      ? occ_planes_group_impl<double>(ctx, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
+                      : occ_planes_group_impl<float>(ctx, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
+    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < G; g++) st[g].total_ms = ms;
+    ctx->stats = st[0];
+    return s;
+}
+
+// the contexts of a multi-context entry: one device, one precision
+int occ_dev_check_ctxs(ofx_ctx *const *ctxs, int n_ctx)
+{
+    if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
+    for (int w = 0; w < n_ctx; w++)
+        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision) return OFX_ERR_ARG;
+    return OFX_OK;
+}
+
+// bytes of a lockstep group of G triples over D planes: per level D planes and 3 G of (u1, u2, chi); full size 2 D of gradients /
+// scratch and OccWork's 27 G; 13 G hyperplane-major planes; plus 5 %
+struct OccDevMem {
+    double level_px, full, skew;
+    OccDevMem(const std::vector<int> &nxs, const std::vector<int> &nys) : level_px(0.0)
+    {
+        for (size_t s = 0; s < nxs.size(); s++) level_px += (double) nxs[s] * nys[s];
+        full = (double) nxs[0] * nys[0];
+        skew = (double) rof_skew_elems(nxs[0], nys[0]);
+    }
+    double bytes(int G, int D) const { return 8.0 * 1.05 * ((D + 3.0 * G) * level_px + (2.0 * D + 27.0 * G) * full + 13.0 * G * skew); }
+};
+
+// groups of G consecutive triples, group q on context q mod n_ctx, a host thread per context; group(ctx, first, cnt, records)
+// enqueues triples first .. first + cnt - 1.  Returns when every payload is complete, with the first failing status.
+template <typename GroupFn>
+int occ_dev_run_groups(ofx_ctx *const *ctxs, int n_ctx, int n_triples, int G, double *work_pix_iters, GroupFn group)
+{
+    const int n_groups = (n_triples + G - 1) / G;
+    std::atomic<int> status(OFX_OK);
+    auto worker = [&](int w) {
+        std::vector<ofx_stats> st(G);
+        for (int q = w; q < n_groups; q += n_ctx) {
+            if (status.load() != OFX_OK) return;
+            const int first = q * G, cnt = (n_triples - first < G) ? n_triples - first : G;
+            int s = group(ctxs[w], first, cnt, st.data());
+            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
+            if (work_pix_iters)
+                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
+        }
+        if (hipStreamSynchronize(ctxs[w]->stream) != hipSuccess) {
+            int expected = OFX_OK;
+            status.compare_exchange_strong(expected, ofx_fail(ctxs[w], OFX_ERR_HIP, "hipStreamSynchronize failed"));
+        }
+    };
+    std::vector<std::thread> th;
+    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : th) t.join();
+    return status.load();
 }
 
 }   // namespace
@@ -1768,31 +1894,19 @@ extern "C" int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const 
     OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
     std::vector<int> nxs, nys;
     OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    const int G = n_frames - 2;
-    const double t0 = ofx_now_ms();
-    std::vector<ofx_stats> local(stats_out ? 0 : G);
-    ofx_stats *st = stats_out ? stats_out : local.data();
     const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
-    const int s = ctx->precision == OFX_F64 ? occ_seq_group_impl<double>(ctx, G, dF, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
-                                            : occ_seq_group_impl<float>(ctx, G, dF, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
-    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < G; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    return occ_planes_group(ctx, n_frames - 2, n_frames, dF, nullptr, d_flo, d_occ, P, nscales, zfactor, nxs, nys, stats_out);
 }
 
 // Any number of frames: groups of G consecutive triples, group q = frames q G .. q G + cnt + 1 on context q mod n_ctx, a host
 // thread per context.  G: option "lockstep" of ctxs[0], at most 16, what the memory budget holds, and no more than evens the
-// groups out over the contexts.  Memory of a group, ofx_tvl1occ_batch's rule for this layout: per level G + 2 frames and 3 G of
-// (u1, u2, chi); full size 2 (G + 2) of gradients / scratch and OccWork's 27 G; 13 G hyperplane-major planes.
+// groups out over the contexts.  Memory of a group, ofx_tvl1occ_batch's rule for this layout (OccDevMem with D = G + 2): per level
+// G + 2 frames and 3 G of (u1, u2, chi); full size 2 (G + 2) of gradients / scratch and OccWork's 27 G; 13 G hyperplane-major planes.
 extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
                                         void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
                                         double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
 {
-    if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision) return OFX_ERR_ARG;
+    OFX_TRY(occ_dev_check_ctxs(ctxs, n_ctx));
     int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
     if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
     {
@@ -1806,39 +1920,150 @@ extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_f
         size_t free_b = 0, total_b = 0;
         OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
         const double budget = (ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b) / n_ctx;
-        double level_px = 0.0;
-        for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
-        const double full = (double) nxx * nyy, skew = (double) rof_skew_elems(nxx, nyy), unit = 8.0 * 1.05;
-        const double fixed = unit * (2.0 * level_px + 4.0 * full), per = unit * (4.0 * level_px + 29.0 * full + 13.0 * skew);
-        const int fit = budget > fixed ? (int) fmin((budget - fixed) / per, (double) OCC_MAX_GROUP) : 0;
-        if (fit < 1)
-            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ sequence: %.2f GB for one triple, %.2f GB per context available", (fixed + per) / 1e9, budget / 1e9);
-        if (G > fit) G = fit;
+        const OccDevMem mem(nxs, nys);
+        while (G >= 1 && mem.bytes(G, G + 2) > budget) G--;
+        if (G < 1)
+            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ sequence: %.2f GB for one triple, %.2f GB per context available", mem.bytes(1, 3) / 1e9, budget / 1e9);
     }
     const int n_triples = n_frames - 2;
     const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
     if (G > per_ctx) G = per_ctx;
-    const int n_groups = (n_triples + G - 1) / G;
-    std::atomic<int> status(OFX_OK);
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_triples - first < G) ? n_triples - first : G;
-            int s = ofx_tvl1occ_sequence_group_dev(ctxs[w], cnt + 2, dF + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta,
-                                                   theta, nscales, zfactor, warps, epsilon, st.data());
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-            if (work_pix_iters)
-                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
+    return occ_dev_run_groups(ctxs, n_ctx, n_triples, G, work_pix_iters, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
+        return ofx_tvl1occ_sequence_group_dev(ctx, cnt + 2, dF + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta, theta,
+                                              nscales, zfactor, warps, epsilon, st);
+    });
+}
+
+// ==== ... over indexed triples of a table of device-resident planes (ofx_tvl1occ_triples_group_dev / _dev) =======================
+// Triple k is (dF[prev], dF[cur], dF[next]) with filtI0 = dF[filt] (filt = -1: cur).  A plane's pyramid and gradients depend on
+// that plane alone whatever its role, so a group keeps its D distinct referenced planes once per level, [D][n_s], exactly as a
+// sequence keeps its G + 2 frames; what differs is that a role is "plane idx.role[g]" (OccIdx) instead of a view at an offset,
+// in the two kernels that read images.
+
+// distinct referenced indices in order of first appearance (triples in order, roles prev, cur, next, filt) and the position of
+// every role among them; pure host code
+extern "C" int ofx_tvl1occ_triples_frames(int n_frames, int n_triples, const ofx_occ_triple *tr, int *frames_out,
+                                          unsigned char *roles_out)
+{
+    if (n_frames < 1 || n_triples < 0 || (n_triples > 0 && !tr)) return -OFX_ERR_ARG;
+    std::vector<int> seen;
+    for (int k = 0; k < n_triples; k++) {
+        const int role[4] = {tr[k].prev, tr[k].cur, tr[k].next, tr[k].filt < 0 ? tr[k].cur : tr[k].filt};
+        if (tr[k].filt < -1) return -OFX_ERR_ARG;
+        for (int r = 0; r < 4; r++) {
+            if (role[r] < 0 || role[r] >= n_frames) return -OFX_ERR_ARG;
+            size_t pos = 0;
+            while (pos < seen.size() && seen[pos] != role[r]) pos++;
+            if (pos == seen.size()) seen.push_back(role[r]);
+            if (roles_out) {
+                if (pos > 255) return -OFX_ERR_ARG;             // a position is a byte: at most 64 triples with a role table
+                roles_out[4 * k + r] = (unsigned char) pos;
+            }
         }
-        if (hipStreamSynchronize(ctxs[w]->stream) != hipSuccess) {
-            int expected = OFX_OK;
-            status.compare_exchange_strong(expected, ofx_fail(ctxs[w], OFX_ERR_HIP, "hipStreamSynchronize failed"));
+    }
+    if (frames_out)
+        for (size_t d = 0; d < seen.size(); d++) frames_out[d] = seen[d];
+    return (int) seen.size();
+}
+
+namespace {
+
+// the tables of n_triples indexed triples: no NULL array, every index inside the table (filt may be -1), every referenced plane
+// aligned to its element, the payloads to a float2; the maps need no alignment
+int occ_tri_check(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_triples, const ofx_occ_triple *tr, void *const *d_flo,
+                  void *const *d_occ)
+{
+    static const char *const role_name[4] = {"prev", "cur", "next", "filt"};
+    if (!dF || !tr || !d_flo || !d_occ) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: NULL pointer");
+    if (n_frames < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: a table of %d planes", n_frames);
+    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    for (int k = 0; k < n_triples; k++) {
+        const int role[4] = {tr[k].prev, tr[k].cur, tr[k].next, tr[k].filt};
+        for (int r = 0; r < 4; r++) {
+            if (r == 3 && role[r] == -1) continue;              // cur, checked
+            if (role[r] < 0 || role[r] >= n_frames)
+                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: triple %d role %s: index %d outside 0..%d", k, role_name[r], role[r], n_frames - 1);
+            if (!dF[role[r]] || reinterpret_cast<uintptr_t>(dF[role[r]]) % el)
+                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: triple %d role %s: plane %d NULL or misaligned", k, role_name[r], role[r]);
         }
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    return status.load();
+        if (!d_flo[k] || !d_occ[k] || reinterpret_cast<uintptr_t>(d_flo[k]) % sizeof(float2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: result pointer of triple %d NULL or misaligned", k);
+    }
+    return OFX_OK;
+}
+
+}   // namespace
+
+extern "C" int ofx_tvl1occ_triples_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_triples,
+                                             const ofx_occ_triple *tr, void *const *d_flo, void *const *d_occ, int nxx, int nyy,
+                                             double lambda, double alpha, double beta, double theta, int nscales, double zfactor,
+                                             int warps, double epsilon, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (n_triples < 1 || n_triples > OCC_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: a lockstep group holds 1..%d triples (got %d)", OCC_MAX_GROUP, n_triples);
+    OFX_TRY(occ_tri_check(ctx, n_frames, dF, n_triples, tr, d_flo, d_occ));
+    OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+    int frames[4 * OCC_MAX_GROUP];
+    unsigned char roles[OCC_MAX_GROUP][4];
+    const int D = ofx_tvl1occ_triples_frames(n_frames, n_triples, tr, frames, &roles[0][0]);
+    if (D < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: bad index table");
+    const void *planes[4 * OCC_MAX_GROUP];
+    for (int d = 0; d < D; d++) planes[d] = dF[frames[d]];
+    OccIdx idx = {};
+    for (int g = 0; g < n_triples; g++) {
+        idx.prev[g] = roles[g][0];
+        idx.cur[g] = roles[g][1];
+        idx.next[g] = roles[g][2];
+        idx.filt[g] = roles[g][3];
+    }
+    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
+    return occ_planes_group(ctx, n_triples, D, planes, &idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, stats_out);
+}
+
+// Any number of triples: groups of G consecutive triples in the caller's order, group q on context q mod n_ctx.  G: option
+// "lockstep" of ctxs[0], at most 16, no more than evens the groups out over the contexts, and the largest such G for which every
+// group fits OccDevMem's rule with its own count of distinct planes.  A plane that two groups share is built by both.
+extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, int n_triples,
+                                       const ofx_occ_triple *tr, void *const *d_flo, void *const *d_occ, int nxx, int nyy,
+                                       double lambda, double alpha, double beta, double theta, int nscales, double zfactor, int warps,
+                                       double epsilon, double *work_pix_iters)
+{
+    OFX_TRY(occ_dev_check_ctxs(ctxs, n_ctx));
+    if (n_triples < 0) return OFX_ERR_ARG;
+    if (n_triples == 0) return OFX_OK;
+    int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
+    if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
+    const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
+    if (G > per_ctx) G = per_ctx;
+    {
+        ofx_ctx *ctx = ctxs[0];
+        OFX_ENTER(ctx);
+        OFX_TRY(occ_tri_check(ctx, n_frames, dF, n_triples, tr, d_flo, d_occ));
+        OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
+        std::vector<int> nxs, nys;
+        OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+        size_t free_b = 0, total_b = 0;
+        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+        const double budget = (ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b) / n_ctx;
+        const OccDevMem mem(nxs, nys);
+        double need = 0.0;
+        for (; G >= 1; G--) {                                 // the largest G whose groups all fit
+            need = 0.0;
+            for (int first = 0; first < n_triples; first += G) {
+                const int cnt = n_triples - first < G ? n_triples - first : G;
+                const double b = mem.bytes(cnt, ofx_tvl1occ_triples_frames(n_frames, cnt, tr + first, nullptr, nullptr));
+                if (b > need) need = b;
+            }
+            if (need <= budget) break;
+        }
+        if (G < 1)
+            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ triples: %.2f GB for one triple, %.2f GB per context available", need / 1e9, budget / 1e9);
+    }
+    return occ_dev_run_groups(ctxs, n_ctx, n_triples, G, work_pix_iters, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
+        return ofx_tvl1occ_triples_group_dev(ctx, n_frames, dF, cnt, tr + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta,
+                                             theta, nscales, zfactor, warps, epsilon, st);
+    });
 }

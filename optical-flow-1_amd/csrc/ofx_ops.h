@@ -63,7 +63,10 @@ template <typename T> int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx,
 // G > 1: the G flow fields of a lockstep group, back to back in U and Uout, in one launch
 template <typename T> int op_zoom_in_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, typename Pix<T>::v2 *Uout,
                                           int nx, int ny, int nxx, int nyy, double scale, int G = 1);
-// zoom_out (src/zoom.cpp:41-78) of `count` images (at most 2 * OFX_MAX_GROUP) of nz interleaved channels, each channel as zoom_out
+// planes one launch of op_gaussian_planes / op_zoom_out_channels_planes serves (blockIdx.z): the pairs of a lockstep group, or the
+// distinct planes of a group of indexed triples (TV-L1 with occlusions: up to four per triple)
+#define OFX_MAX_PLANES (4 * OFX_MAX_GROUP)
+// zoom_out (src/zoom.cpp:41-78) of `count` images (at most OFX_MAX_PLANES) of nz interleaved channels, each channel as zoom_out
 // (the IPOL original of robust_expo_methods, zoom.h:45-85), one launch per stage: images 0 .. split - 1 back to back at A (nx*ny*nz
 // elements each), the others at B, the results likewise at oA / oB, tmpA / tmpB scratch for count images; OFX_ERR_SIGMA under
 // zoom_out's rule, before anything is launched.  A single image is count = split = 1, a plane nz = 1.
@@ -74,7 +77,7 @@ template <typename T> int op_zoom_out_channels_group(ofx_ctx *ctx, int G, const 
                                                      int nx, int ny, int nz, double factor);
 // gaussian (src/operators.cpp:506-624) in place on the first nx*ny elements of `count` images, one launch per pass: images
 // 0 .. split - 1 start at A, the others at B, each `stride` elements after the one before; tmp holds count planes of nx*ny.  A
-// single image is count = split = 1
+// single image is count = split = 1; at most OFX_MAX_PLANES
 template <typename T> int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny,
                                              double sigma, int dirichlet = 0);
 // ... for the 2 G images of a lockstep group of pairs

@@ -472,7 +472,7 @@ template <typename T>
 int op_gaussian_planes(ofx_ctx *ctx, int count, int split, T *A, T *B, size_t stride, T *tmp, int nx, int ny, double sigma, int dirichlet)
 {
     GaussTaps taps;
-    if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: %d planes (%d first)", count, split);
+    if (count < 1 || count > OFX_MAX_PLANES || split < 1 || split > count) return ofx_fail(ctx, OFX_ERR_ARG, "gaussian: %d planes (%d first)", count, split);
     OFX_TRY(gauss_taps_checked(ctx, sigma, nx, ny, dirichlet, &taps));
     const size_t n = (size_t) nx * ny;
     dim3 g = grid2d(nx, ny);
@@ -664,7 +664,7 @@ int op_zoom_out_channels_planes(ofx_ctx *ctx, int count, int split, const T *A, 
     ofx_zoom_size(nx, ny, &nxx, &nyy, factor);
     const double sigma = 0.6 * sqrt(1.0 / (factor * factor) - 1.0);      // ZOOM_SIGMA_ZERO, zoom.h:21,66
     GaussTaps taps;
-    if (count < 1 || count > 2 * OFX_MAX_GROUP || split < 1 || split > count)
+    if (count < 1 || count > OFX_MAX_PLANES || split < 1 || split > count)
         return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %d images (%d first)", count, split);
     if (nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "zoom_out_channels: %dx%dx%d", nx, ny, nz);
     OFX_TRY(gauss_taps_checked(ctx, sigma, nx, ny, 0, &taps));

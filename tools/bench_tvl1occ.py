@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """TV-L1 with occlusions, whole solve: GPU (ofx_tvl1occ_multiscale) against the CPU reference / oracle on one triple.
     python tools/bench_tvl1occ.py [--size 640x480] [--cpu ref|oracle|none] [--check] [--batch CTX:TRIPLES] [--sequence CTX:FRAMES]
+                                  [--triples CTX:FRAMES]
 One JSON line per size.  --sequence: the frames of synth.sequence on the device through ofx_tvl1occ_sequence_dev against
-ofx_tvl1occ_batch on the same triples from host planes, in one process, both warmed, median of three.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
+ofx_tvl1occ_batch on the same triples from host planes, in one process, both warmed, median of three.  --triples: for every
+inner frame t the forward triple (t - 1, t, t + 1) followed by the backward triple (t + 1, t, t - 1), 2 (FRAMES - 2) triples,
+through ofx_tvl1occ_triples_dev against ofx_tvl1occ_batch in the same way; with --check every payload and map must equal the
+host batch's.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
 import argparse
 import importlib
 import json
@@ -24,9 +28,10 @@ ap.add_argument("--check", action="store_true")
 ap.add_argument("--warps", type=int, default=2)
 ap.add_argument("--batch", default="", help="contexts:triples, e.g. 4:8 -- also time a batch of independent triples")
 ap.add_argument("--sequence", default="", help="contexts:frames, e.g. 3:50 -- time the device-resident sequence entry against the host batch")
+ap.add_argument("--triples", default="", help="contexts:frames, e.g. 3:48 -- time forward + backward triples through the indexed-triples entry against the host batch")
 ap.add_argument("--opt", action="append", default=[], help="name=value for every context (e.g. rof_pipe=0)")
 a = ap.parse_args()
-if a.sequence:
+if a.sequence or a.triples:
     import torch                # torch brings its own HIP runtime and has to see the device before libofx.so does
     torch.cuda.init()
 ctx = ofx.Ofx(0, ofx.F64)
@@ -113,4 +118,45 @@ for size in a.size or ["320x240"]:
                             float(np.abs(flo[t_, ..., 1] - v_.astype(np.float32)).max()),
                             float(np.abs(occ[t_].astype(np.float64) - 255 * c_).max()))
             rec["sequence"]["max_abs_diff_vs_lone"] = worst
+    if a.triples:
+        n_ctx, n_fr = (int(v) for v in a.triples.split(":"))
+        ctxs = [ofx.Ofx(0, ofx.F64) for _ in range(n_ctx)]
+        for c_ in ctxs:
+            for o in a.opt:
+                c_.set_option(o.split("=")[0], float(o.split("=")[1]))
+        frames = synth.sequence(nx, ny, n_fr, 1)
+        index = [tr for t in range(1, n_fr - 1) for tr in ((t - 1, t, t + 1), (t + 1, t, t - 1))]     # neighbours share frames
+        n_tr = len(index)
+        dF = torch.from_numpy(frames).cuda()
+        d_flo = torch.zeros((n_tr, ny, nx, 2), dtype=torch.float32, device="cuda")
+        d_occ = torch.zeros((n_tr, ny, nx), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ptr = lambda t: [t[k].data_ptr() for k in range(t.shape[0])]
+        host = [(frames[p], frames[c], frames[n]) for p, c, n in index]
+        run_tri = lambda: ofx.tvl1occ_triples_dev(ctxs, ptr(dF), index, ptr(d_flo), ptr(d_occ), nx, ny, **kw)
+        run_tri()                                                                               # warm both paths on every context
+        res_b = ofx.tvl1occ_batch(ctxs, host, **kw)
+        t_tri, t_host = [], []
+        for _ in range(3):                                                                      # interleaved
+            t = time.perf_counter()
+            run_tri()
+            t_tri.append(time.perf_counter() - t)
+            t = time.perf_counter()
+            ofx.tvl1occ_batch(ctxs, host, out=res_b, **kw)
+            t_host.append(time.perf_counter() - t)
+        s_tri, s_host = sorted(t_tri)[1] / n_tr, sorted(t_host)[1] / n_tr
+        rec["triples"] = {"contexts": n_ctx, "frames": n_fr, "triples": n_tr,
+                          "triples_s_per_triple": round(s_tri, 5), "host_batch_s_per_triple": round(s_host, 5),
+                          "host_over_triples": round(s_host / s_tri, 3),
+                          "triples_s_repetitions": [round(x, 4) for x in t_tri], "host_batch_s_repetitions": [round(x, 4) for x in t_host]}
+        if a.check:
+            flo, occ = d_flo.cpu().numpy(), d_occ.cpu().numpy()
+            bad = [k for k, (u_, v_, c_) in enumerate(res_b)
+                   if not (np.array_equal(flo[k, ..., 0], u_.astype(np.float32)) and np.array_equal(flo[k, ..., 1], v_.astype(np.float32))
+                           and np.array_equal(occ[k], (255 * c_).astype(np.uint8)))]
+            rec["triples"]["equal_to_host_batch"] = not bad
+            rec["triples"]["backward_differs"] = bool(not np.array_equal(flo[0], flo[1]))
+            if bad:
+                print(json.dumps(rec), flush=True)
+                sys.exit("triples %s differ from the host batch" % bad)
     print(json.dumps(rec), flush=True)
