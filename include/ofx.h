@@ -166,8 +166,35 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *                         (default 0 = half of the device memory that is free at the time of the call)
  *   "concurrency"    number of contexts that will be solving on the same device at the same time
  *                         (default 1); a scheduling hint for the strip height of the TV-L1 kernels
- *   "rows_per_wave", "rows_per_wave2", "chunk"   tuning of the TV-L1 kernels / launch batching */
+ *   "rows_per_wave", "rows_per_wave2", "chunk"   tuning of the TV-L1 kernels / launch batching
+ *   "input"          element type of the FRAMES that the *_dev entries read (OFX_IN_* below; default OFX_IN_STORAGE); any other
+ *                         value is OFX_ERR_ARG
+ *   "input_vec"      1/0  the byte kinds of "input" through the kernels that load a run of four elements per lane as aligned
+ *                         32-bit words (default 1); 0 = one element per thread (A/B).  Results do not depend on it.
+ *   "input_lut"      1/0  ... and the 8-bit kinds take 255 (x - min) / (max - min) from a per-workgroup table of its 256 possible
+ *                         values (default 1); 0 = one division per element (A/B).  The same expression on the same operands:
+ *                         results do not depend on it. */
 int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
+
+/* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
+ * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
+ * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
+ * _sequence_dev / _triples_group_dev / _triples_dev, and ofx_normalize_frames_dev -- read elements of this kind wherever their
+ * comments say "the context's storage precision"; a frame is aligned to its element (OFX_IN_RGB8: to a byte).  Every sample
+ * converts exactly to double, so payloads, occlusion maps and iteration / sweep tables are BIT-IDENTICAL to the same call under
+ * OFX_IN_STORAGE on planes that hold the same values (stopping values too, up to the order in which the pair solvers' atomics add
+ * them, which no two runs of one call share).  Entries that take host planes ignore the option; entries
+ * that take several contexts want the same value on all of them (OFX_ERR_ARG otherwise, before any work).  Frames are dense:
+ * element (or pixel) e of a frame is at e times the element size, there is no row pitch -- a pitched surface is not supported.
+ * ofx_robust_expo_group_dev / _batch_dev with nzz > 1 keep their channels interleaved (an HWC uint8 image is that layout as it
+ * stands); OFX_IN_RGB8 there is OFX_ERR_ARG unless nzz == 1. */
+#define OFX_IN_STORAGE 0   /* the context's storage precision (double | float): the default                                    */
+#define OFX_IN_U8      1   /* one byte per element                                                                             */
+#define OFX_IN_U16     2   /* one host-order uint16_t per element                                                              */
+#define OFX_IN_F32     3   /* float elements whatever the storage precision                                                    */
+#define OFX_IN_RGB8    4   /* three interleaved bytes per pixel, collapsed to ONE gray sample while loading by the front-ends'
+                              8-bit rule (uint8_t) (.299 R + .587 G + .114 B): the three products and the two sums each rounded
+                              to double, left to right, no contraction, the result truncated                                   */
 
 /* ---- operators (replace src/operators.h:29-134) ---------------------------------------------*/
 int ofx_divergence(ofx_ctx *ctx, const double *v1, const double *v2, double *div, int nx, int ny);
@@ -215,6 +242,15 @@ int ofx_image_normalization_2(ofx_ctx *ctx, const double *I1, const double *I2, 
                               int size);
 int ofx_image_normalization_1(ofx_ctx *ctx, const double *I, double *In, int size);      /* src/utils.h:17-20 */
 int ofx_getminmax(ofx_ctx *ctx, const double *x, int n, double *min, double *max);        /* src/utils.h:119 */
+/* The joint normalisation that opens every *_dev solver, on device-resident frames: dst[q][e] = 255 (src[q][e] - min) / (max - min)
+ * for source q < nsets * per and element e < npix * nz.  src[q]: npix * nz elements of the context's "input" kind (under
+ * OFX_IN_RGB8 npix PIXELS of three bytes, and nz must be 1), dense, aligned to the element; dst[q]: npix * nz elements of the
+ * storage precision.  `per` consecutive sources form a set that shares {min, max}, per channel when nz > 1 interleaved channels;
+ * guard != 0 as image_normalization_2: a copy where max - min <= 0; guard == 0 divides regardless (image_normalization_3).
+ * nsets * per <= 32 and npix * nz < 2^31 (OFX_ERR_ARG otherwise, nothing written).  Asynchronous on the context's stream. */
+/* dst[q][e] = normalisation of src[q][e] (elements of the context's "input" kind) into the storage type: nsets sets of `per`
+ * sources share {min, max} per channel; guard as image_normalization_2 (copy where max - min <= 0); nsets * per <= 32 */
+int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard);
 
 /* ---- TV-L1 (replace src/tvl1flow.h:36-70) ----------------------------------------------------*/
 /* single scale: u1/u2 are read as the initial flow and overwritten with the result */

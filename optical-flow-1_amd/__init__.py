@@ -19,6 +19,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OFX_LIB_PATH") or os.path.join(HERE, "libofx.so")   # override: A/B builds only
 
 F64, F32 = 0, 1
+# option "input": the element kind of the frames that the *_dev entries read (OFX_IN_* of include/ofx.h)
+IN_STORAGE, IN_U8, IN_U16, IN_F32, IN_RGB8 = 0, 1, 2, 3, 4
 MAX_SCALES, MAX_SOLVES = 32, 64
 
 _STATUS = {1: "invalid argument", 2: "GaussianSmooth: sigma too large", 3: "out of memory",
@@ -109,6 +111,7 @@ def lib():
         "ofx_image_normalization_2": (_i, [_vp, _dp, _dp, _dp, _dp, _i]),
         "ofx_image_normalization_1": (_i, [_vp, _dp, _dp, _i]),
         "ofx_getminmax": (_i, [_vp, _dp, _i, C.POINTER(_d), C.POINTER(_d)]),
+        "ofx_normalize_frames_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
         "ofx_centered_gradient3": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_bicubic_at_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i]),
         "ofx_zoom_out_color": (_i, [_vp, _dp, _dp, _i, _i, _i, _d]),
@@ -485,6 +488,17 @@ class Ofx:
         a, b = np.empty(I1.shape), np.empty(I2.shape)
         self._ck(self.L.ofx_image_normalization_2(self.h, _f64(I1), _f64(I2), a, b, I1.size))
         return a, b
+
+    def normalize_frames_dev(self, src, dst, npix, nz=1, per=None, guard=1):
+        """ofx_normalize_frames_dev: src = device pointers (ints) of frames in the context's "input" kind (set_option("input",
+        IN_U8 | IN_U16 | IN_F32 | IN_RGB8); default: the storage type), npix * nz elements each (IN_RGB8: npix pixels of three
+        bytes, nz = 1); dst = those of the results, npix * nz elements of the storage type.  `per` consecutive sources share
+        {min, max} per channel (default: all of them, one set).  Enqueues on the context's stream."""
+        per = len(src) if per is None else per
+        if per < 1 or len(src) % per or len(dst) != len(src):
+            raise ValueError("normalize_frames_dev: %d sources, %d destinations, sets of %d" % (len(src), len(dst), per))
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_normalize_frames_dev(self.h, len(src) // per, per, arr(src), arr(dst), npix, nz, guard))
 
     # ---- TV-L1 ---------------------------------------------------------------------------------
     def tvl1_single_scale(self, I0, I1, u1, u2, tau=0.25, lam=0.15, theta=0.3, warps=5, epsilon=0.01, verbose=0):

@@ -422,6 +422,33 @@ int ofx_getminmax(ofx_ctx *ctx, const double *x, int n, double *min, double *max
     return DISPATCH(ctx, minmax_t, ctx, x, n, min, max);
 }
 
+// the head of the *_dev solvers on its own: sources in the context's "input" kind, results in the storage type (include/ofx.h)
+int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard)
+{
+    OFX_ENTER(ctx);
+    if (!src || !dst) return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: NULL pointer array");
+    if (nsets < 1 || per < 1 || (long long) nsets * per > OFX_MM_MAX_SRC)
+        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: %d sets of %d sources (at most %d sources)", nsets, per, OFX_MM_MAX_SRC);
+    if (npix < 1 || nz < 1 || (long long) npix * nz > 0x7fffffffLL)
+        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: %d x %d elements", npix, nz);
+    const int kind = ofx_src_kind(ctx);
+    if (kind == OFX_SRC_RGB8 && nz != 1)
+        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: OFX_IN_RGB8 sources give one gray channel (nz = %d)", nz);
+    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    OfxSrcPtrs in = {};
+    OfxDstPtrs out = {};
+    for (int q = 0; q < nsets * per; q++) {
+        if (!src[q] || !dst[q] || reinterpret_cast<uintptr_t>(src[q]) % ofx_src_align(kind) || reinterpret_cast<uintptr_t>(dst[q]) % el)
+            return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: source or destination %d NULL or misaligned", q);
+        in.p[q] = src[q];
+        out.p[q] = dst[q];
+    }
+    double *scr;
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(nsets, (size_t) npix, nz), &scr));
+    return ctx->precision == OFX_F64 ? op_normalize_sets_in<double>(ctx, kind, in, out, nsets, per, (size_t) npix, nz, scr, guard)
+                                     : op_normalize_sets_in<float>(ctx, kind, in, out, nsets, per, (size_t) npix, nz, scr, guard);
+}
+
 int ofx_image_normalization_2(ofx_ctx *ctx, const double *I1, const double *I2, double *I1n, double *I2n, int size)
 {
     OFX_ENTER(ctx);

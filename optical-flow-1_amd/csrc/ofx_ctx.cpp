@@ -110,6 +110,9 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->sor_spw = 0;
     ctx->sor_lds = 1;
     ctx->mem_budget = 0;
+    ctx->input = OFX_IN_STORAGE;
+    ctx->input_vec = 1;
+    ctx->input_lut = 1;         // measured faster in both storage precisions
     ctx->poll_seq = 0;
     ctx->errmsg[0] = 0;
     ctx->expo_host_ms = 0.0;
@@ -278,6 +281,14 @@ extern "C" int ofx_set_option(ofx_ctx *ctx, const char *name, double value)
         ctx->mem_budget = value;
         return OFX_OK;
     }
+    if (!strcmp(name, "input")) {
+        if (value != OFX_IN_STORAGE && value != OFX_IN_U8 && value != OFX_IN_U16 && value != OFX_IN_F32 && value != OFX_IN_RGB8)
+            return ofx_fail(ctx, OFX_ERR_ARG, "input must be one of OFX_IN_STORAGE .. OFX_IN_RGB8 (0 .. 4)");
+        ctx->input = (int) value;
+        return OFX_OK;
+    }
+    if (!strcmp(name, "input_vec")) { ctx->input_vec = value != 0; return OFX_OK; }
+    if (!strcmp(name, "input_lut")) { ctx->input_lut = value != 0; return OFX_OK; }
     if (!strcmp(name, "fuse2")) { ctx->fuse2 = value != 0; return OFX_OK; }
     if (!strcmp(name, "store_a")) {
         if (value != 0 && value != 1 && value != 2) return ofx_fail(ctx, OFX_ERR_ARG, "store_a must be 0, 1 or 2");

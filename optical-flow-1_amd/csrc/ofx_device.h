@@ -12,6 +12,14 @@
 // ---- widening loads / narrowing stores --------------------------------------------------------
 OFX_DEV double  ldw(const double *p) { return *p; }
 OFX_DEV double  ldw(const float *p)  { return (double) *p; }
+// ... of the integer kinds a caller's frames may come in (context option "input"): exact in double and in float.  OfxRgb8 is
+// one interleaved 8-bit pixel; its sample is the front-ends' gray rule (cli/ofx_io.c), every product and sum rounded to double
+// (no contraction: the build's -ffp-contract=off), then truncated
+struct OfxRgb8 { unsigned char r, g, b; };
+OFX_DEV unsigned gray8(unsigned r, unsigned g, unsigned b) { return (unsigned) (unsigned char) (.299 * r + .587 * g + .114 * b); }
+OFX_DEV double  ldw(const unsigned char *p)  { return (double) *p; }
+OFX_DEV double  ldw(const unsigned short *p) { return (double) *p; }
+OFX_DEV double  ldw(const OfxRgb8 *p) { return (double) gray8(p->r, p->g, p->b); }
 OFX_DEV double2 ldw2(const double2 *p) { return *p; }
 OFX_DEV double2 ldw2(const float2 *p)  { float2 v = *p; return make_double2((double) v.x, (double) v.y); }
 OFX_DEV double4 ldw4(const double4 *p) { return *p; }

@@ -116,6 +116,9 @@ struct ofx_ctx {
     int sor_lds;        // windowed exact sweeps: 0 = one global round trip per step, 2 = the launch window staged in LDS, 1 (default) = by
                         // measurement: LDS for lone Horn-Schunck solves, global otherwise (sor_use_lds)
     int sor_spw;        // sweeps per workgroup of the windowed exact kernels (0 = automatic: 1 alone, 2 in lockstep groups)
+    int input;          // element kind of the frames the *_dev entries read (OFX_IN_*, include/ofx.h); host-plane entries ignore it
+    int input_vec;      // 1 (default): the byte kinds through the four-elements-per-lane kernels; 0: one element per thread
+    int input_lut;      // ... 1 (default): the 8-bit kinds look the 256 possible results up in a per-workgroup LDS table; 0: divide per element
     double mem_budget;  // bytes all contexts of a batch may use for level arrays (0 = half of the free device memory)
     unsigned long long poll_seq;
 
@@ -161,6 +164,23 @@ template <> struct Pix<double> { using v2 = double2; using v4 = double4; };
 template <> struct Pix<float>  { using v2 = float2;  using v4 = float4;  };
 
 static inline int ofx_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- element kinds of the caller's frames (option "input" resolved against the storage precision) -------------
+enum { OFX_SRC_F64, OFX_SRC_F32, OFX_SRC_U8, OFX_SRC_U16, OFX_SRC_RGB8 };
+static inline int ofx_storage_kind(const ofx_ctx *ctx) { return ctx->precision == OFX_F64 ? OFX_SRC_F64 : OFX_SRC_F32; }
+static inline int ofx_src_kind(const ofx_ctx *ctx)
+{
+    switch (ctx->input) {
+    case OFX_IN_U8:   return OFX_SRC_U8;
+    case OFX_IN_U16:  return OFX_SRC_U16;
+    case OFX_IN_F32:  return OFX_SRC_F32;
+    case OFX_IN_RGB8: return OFX_SRC_RGB8;
+    default:          return ofx_storage_kind(ctx);
+    }
+}
+// bytes of one element (OFX_SRC_RGB8: of one pixel) and the alignment a frame pointer needs
+static inline size_t ofx_src_bytes(int kind) { static const size_t b[5] = {8, 4, 1, 2, 3}; return b[kind]; }
+static inline size_t ofx_src_align(int kind) { static const size_t a[5] = {8, 4, 1, 2, 1}; return a[kind]; }
 
 // ---- API entry boilerplate ---------------------------------------------------------------------
 #define OFX_ENTER(ctx)                                                                           \

@@ -1666,7 +1666,8 @@ struct OccSeqOut {
     float2 *flo[OCC_MAX_GROUP];
     unsigned char *occ[OCC_MAX_GROUP];
 };
-// the caller's frames, in their storage type, into the finest level (exact: float -> double); blockIdx.z = frame
+// the caller's frames, in their storage type, into the finest level (exact: float -> double); blockIdx.z = frame.  Frames of
+// the byte kinds (context option "input") go through op_convert_sources_in instead.
 template <typename TIN> __global__ void k_occ_seq_in(OccSeqIn in, double *__restrict__ dst, int n)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1732,7 +1733,7 @@ int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zf
 int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo, void *const *d_occ)
 {
     if (!dF || !d_flo || !d_occ) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: NULL pointer");
-    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    const size_t el = ofx_src_align(ofx_src_kind(ctx));
     for (int k = 0; k < n_frames; k++)
         if (!dF[k] || reinterpret_cast<uintptr_t>(dF[k]) % el) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: frame %d NULL or misaligned", k);
     for (int t = 0; t < n_frames - 2; t++)
@@ -1744,7 +1745,7 @@ int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *
 // G triples over the F planes dF in lockstep; sizes checked by the caller.  idx == nullptr: the consecutive triples of a sequence,
 // F = G + 2, the roles are views at an offset; else F distinct planes (at most 4 G) and the roles of triple g are idx's.
 template <typename TIN>
-int occ_planes_group_impl(ofx_ctx *ctx, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
+int occ_planes_group_impl(ofx_ctx *ctx, int kind, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
                           const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
                           ofx_stats *stats)
 {
@@ -1774,6 +1775,13 @@ int occ_planes_group_impl(ofx_ctx *ctx, int G, int F, const void *const *dF, con
     hipStream_t st = ctx->stream;
     for (int k0 = 0; k0 < F; k0 += OCC_MAX_GROUP + 2) {     // OccSeqIn holds 18 pointers: a sequence's frames are one launch, 64 planes four
         const int cnt = F - k0 < OCC_MAX_GROUP + 2 ? F - k0 : OCC_MAX_GROUP + 2;
+        if (kind != OFX_SRC_F64 && kind != OFX_SRC_F32) {   // a byte kind
+            OfxSrcPtrs src = {};
+            OfxDstPtrs dst = {};
+            for (int k = 0; k < cnt; k++) { src.p[k] = dF[k0 + k]; dst.p[k] = lv[0].fr + (k0 + k) * size; }
+            OFX_TRY(op_convert_sources_in<double>(ctx, kind, src, dst, cnt, size));
+            continue;
+        }
         OccSeqIn in = {};
         for (int k = 0; k < cnt; k++) in.f[k] = dF[k0 + k];
         hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, (int) size);
@@ -1819,9 +1827,10 @@ int occ_planes_group(ofx_ctx *ctx, int G, int F, const void *const *dF, const Oc
     const double t0 = ofx_now_ms();
     std::vector<ofx_stats> local(stats_out ? 0 : G);
     ofx_stats *st = stats_out ? stats_out : local.data();
-    const int s = ctx->precision == OFX_F64
-                      ? occ_planes_group_impl<double>(ctx, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
-                      : occ_planes_group_impl<float>(ctx, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
+    const int kind = ofx_src_kind(ctx);                     // the frames come in the context's "input" kind
+    const int s = kind == OFX_SRC_F64
+                      ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
+                      : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
     if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
     const double ms = ofx_now_ms() - t0;
     for (int g = 0; g < G; g++) st[g].total_ms = ms;
@@ -1834,7 +1843,9 @@ int occ_dev_check_ctxs(ofx_ctx *const *ctxs, int n_ctx)
 {
     if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
     for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision) return OFX_ERR_ARG;
+        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision ||
+            ctxs[w]->input != ctxs[0]->input)
+            return OFX_ERR_ARG;
     return OFX_OK;
 }
 
@@ -1976,7 +1987,7 @@ int occ_tri_check(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_tripl
     static const char *const role_name[4] = {"prev", "cur", "next", "filt"};
     if (!dF || !tr || !d_flo || !d_occ) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: NULL pointer");
     if (n_frames < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: a table of %d planes", n_frames);
-    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    const size_t el = ofx_src_align(ofx_src_kind(ctx));
     for (int k = 0; k < n_triples; k++) {
         const int role[4] = {tr[k].prev, tr[k].cur, tr[k].next, tr[k].filt};
         for (int r = 0; r < 4; r++) {

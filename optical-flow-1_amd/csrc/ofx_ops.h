@@ -55,6 +55,23 @@ template <typename T, typename S>
 int op_normalize_sets(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz, double *scr,
                       int guard = 1);
 
+// ---- ... with the sources in a kind chosen at run time (OFX_SRC_*, ofx_internal.h: the context's option "input") ----
+// OFX_SRC_F64 / _F32 are the launches above with S = double / float.  The byte kinds (U8, U16, RGB8 -- there an element is a pixel
+// of three bytes and nz must be 1) run the kernels of ofx_ops.hip that load four elements per lane as aligned 32-bit words, or,
+// with the context's input_vec = 0 and for the min / max of nz > 1 channels, the kernels above on S = unsigned char / unsigned
+// short / OfxRgb8.  Same scratch, same results: every sample is exact in double.
+int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr,
+                         int chunk = 0, int chunks = 1);
+template <typename T>
+int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                        const double *scr, int guard = 1);
+template <typename T>
+int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                         double *scr, int guard = 1);
+// dst[q][e] = src[q][e] for e < n and the `count` <= OFX_MM_MAX_SRC sources of a byte kind (no normalisation)
+template <typename T>
+int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, size_t n);
+
 // generic bicubic resampling out(i1,j1) = bicubic(in, j1/fx, i1/fy, border_out=false)
 // (zoom_out: fx=fy=factor, src/zoom.cpp:67-75; zoom_in: per-axis factors, src/zoom.cpp:142-154)
 template <typename T> int op_resample(ofx_ctx *ctx, const T *in, T *out, int nx, int ny, int nxx, int nyy,
@@ -124,7 +141,7 @@ struct OfxGroupPtrs {
 template <typename T>
 int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const void *const *dB, int nscales, double zfactor,
                            double presmooth_sigma, const int *nxs, const int *nys, T *const *lvA, T *const *lvB, T *tmpA,
-                           T *tmpB, double *scr);
+                           T *tmpB, double *scr, int kind = -1);       // kind: OFX_SRC_* of dA / dB; -1 = the storage type
 
 #define OFX_LAUNCH_CHECK(ctx)                                                                    \
     do {                                                                                         \

@@ -223,6 +223,226 @@ int op_normalize_sets(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst
     return op_normalize_map<T, S>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
 }
 
+// ---- the same for sources of the byte kinds (context option "input"): four consecutive elements per lane ----------------
+// A wave that loads 64 single bytes per instruction wastes the memory pipe, so a lane takes a RUN of four consecutive elements
+// as one (U8), two (U16) or three (RGB8: 12 bytes = four pixels) aligned 32-bit words.  A source starts anywhere: its first
+// head() elements, up to its own 32-bit boundary, and the last (n - head) % 4 go one by one through the first threads of the
+// grid.  Every word of a run lies wholly inside the source.  Integer samples: min / max are taken as integers and converted once.
+template <typename S> struct SrcVec;
+template <> struct SrcVec<unsigned char> {
+    static constexpr int BYTES = 1;
+    static OFX_DEV int head(uintptr_t a) { return (int) ((4 - (a & 3)) & 3); }
+    static OFX_DEV unsigned load1(const unsigned char *p) { return *p; }
+    static OFX_DEV void load4(const unsigned char *p, unsigned v[4])
+    {
+        const unsigned w = *reinterpret_cast<const unsigned *>(p);
+        v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
+    }
+};
+template <> struct SrcVec<unsigned short> {
+    static constexpr int BYTES = 2;
+    static OFX_DEV int head(uintptr_t a) { return (int) ((a & 3) >> 1); }
+    static OFX_DEV unsigned load1(const unsigned char *p) { return *reinterpret_cast<const unsigned short *>(p); }
+    static OFX_DEV void load4(const unsigned char *p, unsigned v[4])
+    {
+        const unsigned w0 = reinterpret_cast<const unsigned *>(p)[0], w1 = reinterpret_cast<const unsigned *>(p)[1];
+        v[0] = w0 & 0xffffu; v[1] = w0 >> 16; v[2] = w1 & 0xffffu; v[3] = w1 >> 16;
+    }
+};
+template <> struct SrcVec<OfxRgb8> {
+    static constexpr int BYTES = 3;
+    static OFX_DEV int head(uintptr_t a) { return (int) (a & 3); }          // (a + 3 h) % 4 == 0 <=> h == a (mod 4)
+    static OFX_DEV unsigned load1(const unsigned char *p) { return gray8(p[0], p[1], p[2]); }
+    static OFX_DEV void load4(const unsigned char *p, unsigned v[4])
+    {
+        const unsigned w0 = reinterpret_cast<const unsigned *>(p)[0], w1 = reinterpret_cast<const unsigned *>(p)[1],
+                       w2 = reinterpret_cast<const unsigned *>(p)[2];
+        v[0] = gray8(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
+        v[1] = gray8(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u);
+        v[2] = gray8((w1 >> 16) & 255u, w1 >> 24, w2 & 255u);
+        v[3] = gray8((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24);
+    }
+};
+// four results at d: the widest stores its address allows (a level plane of a group starts at g * size elements, so a double
+// plane is only known to be 8-byte aligned; the alignment of a source's runs is the same for all of them)
+OFX_DEV void store_run4(double *d, const double o[4])
+{
+    if ((reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+        reinterpret_cast<double2 *>(d)[0] = make_double2(o[0], o[1]);
+        reinterpret_cast<double2 *>(d)[1] = make_double2(o[2], o[3]);
+    } else {
+        d[0] = o[0]; d[1] = o[1]; d[2] = o[2]; d[3] = o[3];
+    }
+}
+OFX_DEV void store_run4(float *d, const double o[4])
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d);
+    if ((a & 15) == 0) {
+        *reinterpret_cast<float4 *>(d) = make_float4((float) o[0], (float) o[1], (float) o[2], (float) o[3]);
+    } else if ((a & 7) == 0) {
+        reinterpret_cast<float2 *>(d)[0] = make_float2((float) o[0], (float) o[1]);
+        reinterpret_cast<float2 *>(d)[1] = make_float2((float) o[2], (float) o[3]);
+    } else {
+        d[0] = (float) o[0]; d[1] = (float) o[1]; d[2] = (float) o[2]; d[3] = (float) o[3];
+    }
+}
+// block (b, set), one channel: the runs of every source of the set block-strided like k_minmax_partial's elements; block 0 also
+// takes the heads and tails.  Partials in k_minmax_partial's layout, so k_minmax_final serves both.
+template <typename S>
+__global__ __launch_bounds__(256) void k_minmax_vec(OfxSrcPtrs src, int per, size_t npix, int nb, int first, int count,
+                                                    double *__restrict__ scr)
+{
+    using V = SrcVec<S>;
+    const int b = blockIdx.x, set = blockIdx.y, nslots = gridDim.y;
+    unsigned lo = V::load1(static_cast<const unsigned char *>(src.p[set * per])), hi = lo;
+    for (int k = 0; k < per; k++) {
+        const unsigned char *__restrict__ p = static_cast<const unsigned char *>(src.p[set * per + k]);
+        size_t h = (size_t) V::head(reinterpret_cast<uintptr_t>(p));
+        if (h > npix) h = npix;
+        const size_t runs = (npix - h) / 4, tail0 = h + 4 * runs;
+        for (size_t r = (size_t) b * 256 + threadIdx.x; r < runs; r += (size_t) nb * 256) {
+            unsigned v[4];
+            V::load4(p + (h + 4 * r) * V::BYTES, v);
+#pragma unroll
+            for (int j = 0; j < 4; j++) { lo = v[j] < lo ? v[j] : lo; hi = v[j] > hi ? v[j] : hi; }
+        }
+        if (b == 0) {
+            const size_t t = threadIdx.x;
+            if (t < h) { const unsigned x = V::load1(p + t * V::BYTES); lo = x < lo ? x : lo; hi = x > hi ? x : hi; }
+            if (tail0 + t < npix) { const unsigned x = V::load1(p + (tail0 + t) * V::BYTES); lo = x < lo ? x : lo; hi = x > hi ? x : hi; }
+        }
+    }
+    double *part = scr + 2 * (size_t) nslots + (size_t) set * count + first + b;
+    minmax_block_reduce((double) lo, (double) hi, part, part + (size_t) nslots * count);
+}
+// thread r = run r, head element r and tail element r of every source of set blockIdx.y; n = npix * nz elements, the channel
+// of element e is e % nz.  mm == nullptr: a plain conversion.  The expression is k_normalize_map's.  LUT (8-bit samples, nz <=
+// VEC_LUT_NZ, mm != nullptr): a sample has 256 values, so thread v of a workgroup evaluates that expression on sample v once per
+// channel into LDS and an element looks its result up -- the same expression on the same operands, hence the same bits, one
+// IEEE division per table entry instead of one per element.
+#define VEC_LUT_NZ 4
+template <typename T, typename S, bool LUT>
+__global__ __launch_bounds__(256) void k_normalize_vec(OfxSrcPtrs src, OfxDstPtrs dst, int per, size_t n, int nz,
+                                                       const double *__restrict__ mm, int guard)
+{
+    using V = SrcVec<S>;
+    const size_t r = (size_t) blockIdx.x * 256 + threadIdx.x;
+    const int set = blockIdx.y;
+    auto eval = [&](int c, unsigned v) -> double {
+        const double x = (double) v;
+        if (!mm) return x;
+        const int slot = set * nz + c;
+        const double lo = mm[2 * slot], den = mm[2 * slot + 1] - mm[2 * slot];
+        return (!guard || den > 0) ? 255.0 * (x - lo) / den : x;
+    };
+    __shared__ double tbl[LUT ? VEC_LUT_NZ * 256 : 1];
+    if (LUT) {
+        for (int c = 0; c < nz; c++) tbl[c * 256 + threadIdx.x] = eval(c, threadIdx.x);
+        __syncthreads();
+    }
+    auto norm = [&](size_t e, unsigned v) -> double {
+        const int c = nz == 1 ? 0 : (int) ((unsigned) e % (unsigned) nz);                                      // n < 2^31
+        return LUT ? tbl[c * 256 + v] : eval(c, v);
+    };
+    for (int k = 0; k < per; k++) {
+        const unsigned char *__restrict__ p = static_cast<const unsigned char *>(src.p[set * per + k]);
+        T *__restrict__ d = static_cast<T *>(dst.p[set * per + k]);
+        size_t h = (size_t) V::head(reinterpret_cast<uintptr_t>(p));
+        if (h > n) h = n;
+        const size_t runs = (n - h) / 4, tail0 = h + 4 * runs;
+        if (r < runs) {
+            const size_t e = h + 4 * r;
+            unsigned v[4];
+            V::load4(p + e * V::BYTES, v);
+            const double o[4] = {norm(e, v[0]), norm(e + 1, v[1]), norm(e + 2, v[2]), norm(e + 3, v[3])};
+            store_run4(d + e, o);
+        }
+        if (r < h) stn(d + r, norm(r, V::load1(p + r * V::BYTES)));
+        if (tail0 + r < n) stn(d + tail0 + r, norm(tail0 + r, V::load1(p + (tail0 + r) * V::BYTES)));
+    }
+}
+static inline int vec_grid(size_t n) { return (int) ((n / 4 + 3) / 256 + 1); }       // threads >= runs, heads and tails (at most 3 each)
+
+template <typename S>
+static int minmax_partial_bytes(ofx_ctx *ctx, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr, int chunk,
+                                int chunks)
+{
+    if (!ctx->input_vec || nz > 1) return op_minmax_partial<S>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    OFX_TRY(minmax_check(ctx, nsets, per, npix, nz));
+    const int nb = mm_blocks(npix);
+    hipLaunchKernelGGL(k_minmax_vec<S>, dim3(nb, nsets), dim3(256), 0, ctx->stream, src, per, npix, nb, chunk * nb, chunks * nb, scr);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+template <typename T, typename S>
+static int normalize_map_bytes(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                               const double *scr, int guard)
+{
+    if (!ctx->input_vec) return op_normalize_map<T, S>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    OFX_TRY(minmax_check(ctx, nsets, per, npix, nz));
+    const dim3 grid(vec_grid(npix * nz), nsets);
+    if (ctx->input_lut && sizeof(S) != sizeof(unsigned short) && nz <= VEC_LUT_NZ)
+        hipLaunchKernelGGL((k_normalize_vec<T, S, true>), grid, dim3(256), 0, ctx->stream, src, dst, per, npix * nz, nz, scr, guard);
+    else
+        hipLaunchKernelGGL((k_normalize_vec<T, S, false>), grid, dim3(256), 0, ctx->stream, src, dst, per, npix * nz, nz, scr, guard);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+static int rgb8_check(ofx_ctx *ctx, int kind, int nz)
+{
+    if (kind < OFX_SRC_F64 || kind > OFX_SRC_RGB8) return ofx_fail(ctx, OFX_ERR_ARG, "source kind %d", kind);
+    if (kind == OFX_SRC_RGB8 && nz != 1) return ofx_fail(ctx, OFX_ERR_ARG, "RGB8 sources give one gray channel (nz = %d)", nz);
+    return OFX_OK;
+}
+int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr, int chunk,
+                         int chunks)
+{
+    OFX_TRY(rgb8_check(ctx, kind, nz));
+    switch (kind) {
+    case OFX_SRC_F64: return op_minmax_partial<double>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_F32: return op_minmax_partial<float>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_U8:  return minmax_partial_bytes<unsigned char>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_U16: return minmax_partial_bytes<unsigned short>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    default:          return minmax_partial_bytes<OfxRgb8>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    }
+}
+template <typename T>
+int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                        const double *scr, int guard)
+{
+    OFX_TRY(rgb8_check(ctx, kind, nz));
+    switch (kind) {
+    case OFX_SRC_F64: return op_normalize_map<T, double>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_F32: return op_normalize_map<T, float>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_U8:  return normalize_map_bytes<T, unsigned char>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_U16: return normalize_map_bytes<T, unsigned short>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    default:          return normalize_map_bytes<T, OfxRgb8>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    }
+}
+template <typename T>
+int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
+                         double *scr, int guard)
+{
+    OFX_TRY(op_minmax_partial_in(ctx, kind, src, nsets, per, npix, nz, scr));
+    OFX_TRY(op_minmax_final(ctx, nsets, npix, nz, scr));
+    return op_normalize_map_in<T>(ctx, kind, src, dst, nsets, per, npix, nz, scr, guard);
+}
+template <typename T>
+int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, size_t n)
+{
+    if (kind != OFX_SRC_U8 && kind != OFX_SRC_U16 && kind != OFX_SRC_RGB8) return ofx_fail(ctx, OFX_ERR_ARG, "source kind %d", kind);
+    OFX_TRY(minmax_check(ctx, 1, count, n, 1));
+    const dim3 grid(vec_grid(n), 1);
+    if (kind == OFX_SRC_U8)
+        hipLaunchKernelGGL((k_normalize_vec<T, unsigned char, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+    else if (kind == OFX_SRC_U16)
+        hipLaunchKernelGGL((k_normalize_vec<T, unsigned short, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+    else
+        hipLaunchKernelGGL((k_normalize_vec<T, OfxRgb8, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
 // ---- gaussian (src/operators.cpp:506-624) -----------------------------------------------------------
 int ofx_gauss_taps(double sigma, GaussTaps *t)
 {
@@ -940,7 +1160,7 @@ int op_pyramid_sizes(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor
 template <typename T>
 int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const void *const *dB, int nscales, double zfactor,
                            double sigma, const int *nxs, const int *nys, T *const *lvA, T *const *lvB, T *tmpA, T *tmpB,
-                           double *scr)
+                           double *scr, int kind)
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "pyramid group of %d", G);
     const int nxx = nxs[0], nyy = nys[0], size = nxx * nyy;
@@ -959,7 +1179,8 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
         dst.p[2 * g] = n0 + (size_t) g * size;
         dst.p[2 * g + 1] = n1 + (size_t) g * size;
     }
-    OFX_TRY((op_normalize_sets<T, T>(ctx, src, dst, G, 2, (size_t) size, 1, scr)));
+    if (kind < 0) OFX_TRY((op_normalize_sets<T, T>(ctx, src, dst, G, 2, (size_t) size, 1, scr)));
+    else OFX_TRY(op_normalize_sets_in<T>(ctx, kind, src, dst, G, 2, (size_t) size, 1, scr));
     auto gauss_xy = [&](const T *ia, const T *ib, T *oa, T *ob, int nx, int ny, double sg) -> int {
         GaussTaps taps;
         OFX_TRY(gauss_taps_checked(ctx, sg, nx, ny, 0, &taps));
@@ -1069,12 +1290,15 @@ template <typename T> int op_gradient_dz(ofx_ctx *ctx, const T *in, T *dz, int n
     template int op_bicubic_at<T>(ofx_ctx *, const T *, const double *, const double *, double *, int, int, int, int);           \
     template int op_grad_pack<T>(ofx_ctx *, const T *, Pix<T>::v2 *, T *, int, int, int);                                       \
     template int op_build_pyramid_group<T>(ofx_ctx *, int, const void *const *, const void *const *, int, double, double,       \
-                                           const int *, const int *, T *const *, T *const *, T *, T *, double *);              \
+                                           const int *, const int *, T *const *, T *const *, T *, T *, double *, int);         \
     template int op_bicubic_at_color<T>(ofx_ctx *, const T *, const double *, const double *, double *, int, int, int, int, int, int); \
     template int op_gradient_dz<T>(ofx_ctx *, const T *, T *, int, int, int);                                                   \
     template int op_minmax_partial<T>(ofx_ctx *, const OfxSrcPtrs &, int, int, size_t, int, double *, int, int);             \
     template int op_normalize_map<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, const double *, int); \
-    template int op_normalize_sets<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int);
+    template int op_normalize_sets<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int); \
+    template int op_normalize_map_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, const double *, int); \
+    template int op_normalize_sets_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int); \
+    template int op_convert_sources_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, size_t);
 
 OFX_INSTANTIATE(double)
 OFX_INSTANTIATE(float)

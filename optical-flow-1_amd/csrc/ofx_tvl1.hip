@@ -1651,12 +1651,12 @@ static void stats_begin(ofx_stats *st, int nscales, int nsolves)
     st->nsolves = nsolves;
 }
 
-// src/tvl1flow.cpp:219-328 for G pairs in lockstep.  dI0[g] / dI1[g]: device images of storage type T.  On
-// success lv[0].U[half of lv[0].cur] holds the flows.
+// src/tvl1flow.cpp:219-328 for G pairs in lockstep.  dI0[g] / dI1[g]: device images of storage type T, or with kind >= 0
+// of that element kind (OFX_SRC_*).  On success lv[0].U[half of lv[0].cur] holds the flows.
 template <typename T>
 static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T *const *dI1, int nxx, int nyy,
                                const Tvl1Params &P, int nscales, double zfactor, std::vector<Tvl1Level<T>> &lv,
-                               ofx_stats *stats)
+                               ofx_stats *stats, int kind = -1)
 {
     if (P.warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", P.warps);
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: group of %d pairs", G);
@@ -1678,7 +1678,7 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
         std::vector<T *> lA(nscales), lB(nscales);
         for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I0; lB[s] = lv[s].I1; }
         OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI0, (const void *const *) dI1, nscales, zfactor,
-                                          TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr));
+                                          TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind));
     }
     Tvl1Level<T> &C = lv[nscales - 1];
     OFX_TRY(op_fill2<T>(ctx, C.U[0], C.n() * G));                                                // :278-280
@@ -1815,6 +1815,7 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
                              int nx, int ny, const Tvl1Params &P, int nscales, double zfactor, ofx_stats *stats)
 {
     const size_t n = (size_t) nx * ny;
+    const int kind = ofx_src_kind(ctx);                      // the frames come in the context's "input" kind
     // Images and payloads that do not live on this context's GPU (a batch spread over several GPUs by ofx_tvl1_batch_dev, or
     // host buffers) are staged: in through arena buffers before the solve, out after it, all on the context's stream.
     const void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
@@ -1824,9 +1825,9 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
         const void **dst[2] = {&dI0[g], &dI1[g]};
         for (int k = 0; k < 2; k++) {
             if (ofx_ptr_is_local(ctx, src[k])) { *dst[k] = src[k]; continue; }
-            T *stage;
-            OFX_TRY(ofx_alloc(ctx, n, &stage));
-            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], n * sizeof(T)));
+            char *stage;                                     // sized by the source element
+            OFX_TRY(ofx_alloc(ctx, n * ofx_src_bytes(kind), &stage));
+            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], n * ofx_src_bytes(kind)));
             *dst[k] = stage;
         }
         d_flo[g] = d_flo_in[g];
@@ -1838,7 +1839,7 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
     }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv,
-                                   stats));
+                                   stats, kind));
     OfxGroupPtrs out;
     for (int g = 0; g < OFX_MAX_GROUP; g++) { out.a[g] = g < G ? d_flo[g] : nullptr; out.b[g] = nullptr; }
     hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
@@ -2090,7 +2091,7 @@ extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
     // are not on its context's GPU is staged there and its payloads are copied back into the caller's arrays (tvl1_group_devapi)
     // -- the C caller's multi-GPU path, no launcher and no collective library needed (pairs are independent).
     for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision) return OFX_ERR_ARG;
+        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input) return OFX_ERR_ARG;
     const int G = ofx_tvl1_batch_group_size(ctxs, n_ctx, n_pairs, nx, ny, nscales, zfactor);
     if (G < 1) return G < 0 ? -G : OFX_ERR_ARG;                 // negative = -status of the failing check
     const int n_groups = (n_pairs + G - 1) / G;
