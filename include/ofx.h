@@ -134,6 +134,11 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *   "fuse3", "fuse3_min_px"  TV-L1: three iterations per launch (k_tvl1_iter3): 0 never, 1 on every level of at least
  *                         fuse3_min_px pixels x pairs, 2 (default) by measurement: not in strict mode, only for lockstep groups
  *                         or contexts sharing the device, levels of >= 500 000 pixels x pairs.  Results do not depend on it.
+ *   "fuse4", "fuse4_min_px"  TV-L1: four iterations per launch (k_tvl1_iter4): 0 never, 1 on every level of at least
+ *                         fuse4_min_px pixels x pairs, 2 (default) by measurement: where "fuse3" = 2 takes three and the level
+ *                         has at least 2 000 000 pixels x pairs (fuse4_min_px > 0 replaces that figure).  Results do not depend
+ *                         on it.  "fuse4_afac3": error / threshold ratio below which a unit of that kernel runs three
+ *                         iterations ("fuse3_afac2" / "fuse3_afac1": two / one); 0 (default) = never three.
  *   "store_a"        TV-L1, fused pairs: a loop that stops on the first iteration of a pair needs the state between the
  *                         two iterations; 1 (default) = a launch also stores it when the previous error is within 1.5x
  *                         of the threshold (the host then just switches buffers), 0 = never (the iteration is

@@ -95,6 +95,9 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->fuse3_cursor = 1;
     ctx->fuse3_afac1 = 0;
     ctx->fuse3_afac2 = 0;
+    ctx->fuse4 = 2;
+    ctx->fuse4_min_px = 0.0;
+    ctx->fuse4_afac3 = 0;
     ctx->rows_per_wave3 = 0;
     ctx->rows3_max = 32;
     ctx->fixed_work = 0;
@@ -310,8 +313,21 @@ extern "C" int ofx_set_option(ofx_ctx *ctx, const char *name, double value)
     }
     if (!strcmp(name, "fuse3_min_px")) { ctx->fuse3_min_px = value; return OFX_OK; }
     if (!strcmp(name, "fuse3_cursor")) { ctx->fuse3_cursor = value != 0; return OFX_OK; }
-    if (!strcmp(name, "fuse3_afac1")) { ctx->fuse3_afac1 = value; return value >= 0 ? OFX_OK : ofx_fail(ctx, OFX_ERR_ARG, "fuse3_afac1 < 0"); }
-    if (!strcmp(name, "fuse3_afac2")) { ctx->fuse3_afac2 = value; return value >= 0 ? OFX_OK : ofx_fail(ctx, OFX_ERR_ARG, "fuse3_afac2 < 0"); }
+    if (!strcmp(name, "fuse3_afac1") || !strcmp(name, "fuse3_afac2") || !strcmp(name, "fuse4_afac3")) {
+        if (!(value >= 0)) return ofx_fail(ctx, OFX_ERR_ARG, "%s < 0", name);       // (a NaN fails too) nothing stored on failure
+        (name[10] == '1' ? ctx->fuse3_afac1 : (name[10] == '2' ? ctx->fuse3_afac2 : ctx->fuse4_afac3)) = value;
+        return OFX_OK;
+    }
+    if (!strcmp(name, "fuse4")) {
+        if (value != 0 && value != 1 && value != 2) return ofx_fail(ctx, OFX_ERR_ARG, "fuse4 must be 0, 1 or 2");
+        ctx->fuse4 = (int) value;
+        return OFX_OK;
+    }
+    if (!strcmp(name, "fuse4_min_px")) {
+        if (!(value >= 0)) return ofx_fail(ctx, OFX_ERR_ARG, "fuse4_min_px < 0");
+        ctx->fuse4_min_px = value;
+        return OFX_OK;
+    }
     if (!strcmp(name, "rows_per_wave3")) { ctx->rows_per_wave3 = (int) value; return OFX_OK; }
     if (!strcmp(name, "rows3_max")) { ctx->rows3_max = (int) value; return OFX_OK; }
     if (!strcmp(name, "spin_us")) {

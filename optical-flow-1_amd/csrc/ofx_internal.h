@@ -93,7 +93,11 @@ struct ofx_ctx {
     double fuse3_min_px;
     int fuse3_cursor;   // 1 (default): k_tvl1_iter3 as a cursor loop -- units shrink to 2 / 1 iterations near the end of a loop; 0: fixed units of 3
     double fuse3_afac1, fuse3_afac2;   // ... error / threshold ratios below which a unit runs 1 / 2 iterations (0 = 1.2 / 1.5)
-    int rows_per_wave3; // strip height of k_tvl1_iter3 (0 = tvl1_pick_rows3)
+    int fuse4;          // TV-L1: four iterations per launch (k_tvl1_iter4): 0 never, 1 levels of >= fuse4_min_px pixels x pairs, 2 auto (default):
+                        // where fuse3 = 2 picks three and the level is large enough (0 = the measured threshold)
+    double fuse4_min_px;
+    double fuse4_afac3; // ... ratio below which a unit of the four-iteration kernel runs 3 iterations (0 = never: measured)
+    int rows_per_wave3; // strip height of k_tvl1_iter3 / k_tvl1_iter4 (0 = tvl1_pick_rows3)
     int rows3_max;      // tallest strip tvl1_pick_rows3 considers when contexts share the device
     int chi_fuse;       // Solver_wrt_chi: 1 = CHI_N iterations per launch on LDS tiles (default), 0 = two launches per iteration
     int rof_window;     // steps per launch of the ROF box sweeps: 10 (default, also 0) | 24

@@ -197,8 +197,9 @@ static int ofx_run_loop(ofx_ctx *ctx, const LoopSpec &L, LaunchFn launch, RedoFn
 
 // ---- cursor loops ---------------------------------------------------------------------------------------------------------
 // The launch units of a loop have NO fixed size: every launch reads where its pair stands from device memory (OfxLoopDev), picks
-// its own iteration count (TV-L1: three iterations while the loop is far from its threshold, fewer when the previous error says
-// the stop is near -- fewer iterations computed past the stop, fewer re-runs) and logs where it started.  The host only counts
+// its own iteration count (TV-L1: three or four iterations -- max_unit -- while the loop is far from its threshold, fewer when the
+// previous error says the stop is near -- fewer iterations computed past the stop, fewer re-runs) and logs where it started.  A
+// launch looks max_unit error slots back, so every launch behind the stop is a no-op.  The host only counts
 // launches: launch(L, thr) enqueues launch L for all problems; units_per_chunk launches, then one finalize kernel (which learns
 // the iteration range from the device state), polled one chunk behind as in ofx_run_loop_group.  On return unit_out[g] / k0_out[g] /
 // ucnt_out[g] describe the launch unit that contains iteration n_g - 1; when n_g - k0 < ucnt the loop ended INSIDE that unit and

@@ -612,46 +612,68 @@ __global__ OFX_ITER2_BOUNDS void k_tvl1_iter2(
 #ifndef STRIP3_OUT
 #define STRIP3_OUT 56
 #endif
-#define STRIP3_HALO ((64 - STRIP3_OUT) / 2)      // halo lanes each side: three are needed
+#define STRIP3_HALO ((64 - STRIP3_OUT) / 2)      // halo lanes each side: three are needed by three iterations, all four by four
 // Round 4 (profiles/r04_ab_iter3_alignment.txt, all on the 1080p x 5 launch): memory ceiling 266 us, ALU ceiling 219 us (256 at
-// 2 waves per SIMD -- which rules out a four-iteration kernel of ~205 VGPRs), production 291 us; measured and dropped: loads two
+// 2 waves per SIMD), production 291 us; measured and dropped: loads two
 // rows ahead (production + 7 %, ceiling + 4 %), non-temporal row loads (+ 9 %: the halo re-reads then miss), a workgroup barrier
 // per step to keep adjacent strips on the same row (+ 1 %), strips of 48 / 64 rows (no change).
+//
+// FOUR iterations per launch (k_tvl1_iter4, N = 4 below): two more stages, S7 u_D(y-6) and S8 p_D(y-7), rows y0-3 .. yend+3 loaded,
+// the same 56 output columns (the four halo lanes are all needed now), 30 instead of 40 bytes per pixel and iteration.  With the
+// whole pipeline in registers that is ~205 VGPRs, i.e. 2 waves per SIMD; but the delay lines of (I1wx, I1wy) and rho_c -- written
+// once per step, read unchanged 2, 4 and 6 steps later -- are pure storage, and live in a ring of TVL1_RING_ROWS rows in LDS instead:
+// 24 bytes per lane and row, 12 KB per wave.  A lane only ever reads the cells it wrote itself, in program order: no barrier, no
+// flag, nothing shared between waves.  The rest of the state fits the 168 VGPRs of 3 waves per SIMD.
+#define TVL1_RING_ROWS 8                          // rows y .. y-6 are live; a power of two
+struct Tvl1Ring {
+    double2 a[TVL1_RING_ROWS][64];               // lane-contiguous 16-byte cells: one conflict-free b128 access per wave
+    double  r[TVL1_RING_ROWS][64];               // ... and 8-byte cells
+};
 // Measured and dropped (profiles/r03_q_ab_three_iterations_per_launch.txt): 2 waves per SIMD instead of 3 (same speed: the
 // launch is not bound by resident waves); the pipeline registers in row-indexed rings with a four-step loop body instead of
 // shifting ~50 doubles per step (v_mov_b64 119 -> 57 per step, 210 VGPRs: 1.5 % SLOWER -- VALU issue is not the bound either).
 #ifndef OFX_ITER3_WAVES
 #define OFX_ITER3_WAVES 3
 #endif
-template <typename T, bool NT, bool STRICT, int CNT>
+// The marching loop of a launch unit of CNT iterations in the kernel of up to N (3: k_tvl1_iter3, 4: k_tvl1_iter4; the kernel
+// loads rows y0-(N-1) .. yend+(N-1), and stage j of N starts N - j rows above the strip).  CNT = 4 keeps the delay lines of
+// (I1wx, I1wy) and rho_c in `ring` (this lane's column of it); the shorter units keep them in registers.
+template <typename T, bool NT, bool STRICT, int CNT, int N>
 OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const typename Pix<T>::v2 *__restrict__ P1in,
                               const typename Pix<T>::v2 *__restrict__ P2in, const typename Pix<T>::v2 *__restrict__ A,
                               const T *__restrict__ R, typename Pix<T>::v2 *Uout, typename Pix<T>::v2 *P1out,
                               typename Pix<T>::v2 *P2out, double *__restrict__ err, int slot0, int slot_step, int gw, int nx,
                               int ny, int y0, int yend, int ys, int yl, bool lef, bool rig, bool owner, unsigned off, unsigned so,
-                              double up12, double up22, RowIn<T> cur, double l_t, double theta, double taut)
+                              double up12, double up22, RowIn<T> cur, double l_t, double theta, double taut,
+                              Tvl1Ring *ring = nullptr)
 {
+    static_assert(CNT >= 1 && CNT <= N && (N == 3 || N == 4), "units of up to three or four iterations");
+    constexpr bool RING = CNT == 4;
     const unsigned E2 = 2 * sizeof(T);
     const unsigned row2 = (unsigned) nx * E2;
     const double2 z2 = make_double2(0.0, 0.0);
     const unsigned level_bytes = (unsigned) nx * (unsigned) ny * E2;
     const ofx_rsrc rU = make_rsrc(Uout, level_bytes), rP1 = make_rsrc(P1out, level_bytes), rP2 = make_rsrc(P2out, level_bytes);
-    double accA = 0.0, accB = 0.0, accC = 0.0;
+    double accA = 0.0, accB = 0.0, accC = 0.0, accD = 0.0;
     double2 uA0 = z2, uA1 = z2, uA2 = z2;                    // u_A of rows y, y-1, y-2
-    double2 a1 = z2, a2 = z2, a3 = z2, a4 = z2;              // (I1wx, I1wy) of rows y-1 .. y-4
-    double r1c = 0.0, r2c = 0.0, r3c = 0.0, r4c = 0.0;       // rho_c of rows y-1 .. y-4
+    double2 a1 = z2, a2 = z2, a3 = z2, a4 = z2;              // (I1wx, I1wy) of rows y-1 .. y-4   (RING: in LDS instead)
+    double r1c = 0.0, r2c = 0.0, r3c = 0.0, r4c = 0.0;       // rho_c of rows y-1 .. y-4           (RING: in LDS instead)
     double2 p0a = z2, p0b = z2;                              // p (iteration k-1) of row y-1
     double2 pA1a = z2, pA1b = z2, pA2a = z2, pA2b = z2;      // p_A of rows y-2, y-3
     double2 uB0 = z2, uB1 = z2, uB2 = z2;                    // u_B of rows y-2, y-3, y-4
     double2 pB1a = z2, pB1b = z2, pB2a = z2, pB2b = z2;      // p_B of rows y-4, y-5
-    double2 uC0 = z2, uC1 = z2;                              // u_C of rows y-4, y-5
+    double2 uC0 = z2, uC1 = z2, uC2 = z2;                    // u_C of rows y-4, y-5, y-6
+    double2 pC1a = z2, pC1b = z2, pC2a = z2, pC2b = z2;      // p_C of rows y-6, y-7
+    double2 uD0 = z2, uD1 = z2;                              // u_D of rows y-6, y-7
     const int nyl = ny - 1;
-    const int yB0 = y0 > 0 ? y0 - 1 : 0;                     // first row of the B stages
+    const int yB0 = y0 > N - 2 ? y0 - (N - 2) : 0;           // first row of the B stages
+    const int yC0 = y0 > N - 3 ? y0 - (N - 3) : 0;           // first row of the C stages
     const int ylc = (yend + CNT - 1 < yl) ? yend + CNT - 1 : yl;                    // last row of u_A
     const int hiA = (yend + CNT - 2 < nyl) ? yend + CNT - 2 : nyl;                  // last row of p_A and u_B
-    const int hiB = (yend + CNT - 3 < nyl) ? yend + CNT - 3 : nyl;                  // last row of p_B
-    const int hiC = (yend < nyl) ? yend : nyl;                                      // last row of u_C
+    const int hiB = (yend + CNT - 3 < nyl) ? yend + CNT - 3 : nyl;                  // last row of p_B and u_C
+    const int hiC = (yend + CNT - 4 < nyl) ? yend + CNT - 4 : nyl;                  // last row of p_C and u_D
     const int ylast = yend - 1 + (2 * CNT - 1);
+    unsigned ri = 0;                                         // ring row of image row y: advances once per step
 #ifdef OFX_CEIL_ALU
     const unsigned off0 = off;
 #endif
@@ -687,13 +709,23 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
             pAnb.x = rnd_to<T>(pAnb.x); pAnb.y = rnd_to<T>(pAnb.y);
             if (CNT == 1 && owner && y - 1 >= y0 && y - 1 < yend) { stp = so - row2; sp1 = pAna; sp2 = pAnb; }
         }
+        // the delay lines of a four-iteration unit: row y into the ring (a lane reads back only its own cells, later in this
+        // function: program order is all the ordering there is)
+        [[maybe_unused]] const int lane = threadIdx.x & 63;
+        if constexpr (RING) {
+            ring->a[ri][lane] = cur.a;
+            ring->r[ri][lane] = cur.r;
+        }
         double2 pBna = z2, pBnb = z2;
         if (CNT >= 2) {
             // S3: u_B(y-2)
             if (y - 2 >= yB0 && y - 2 <= hiA) {
+                double2 ad = a2;
+                double rd = r2c;
+                if constexpr (RING) { ad = ring->a[(ri - 2u) % TVL1_RING_ROWS][lane]; rd = ring->r[(ri - 2u) % TVL1_RING_ROWS][lane]; }
                 const double l11 = wave_shift_up(pA1a.x);
                 const double l21 = wave_shift_up(pA1b.x);
-                uB0 = tvl1_primal<T, STRICT>(uA2, a2, r2c, pA1a, pA1b, l11, l21, pA2a.y, pA2b.y, lef, rig, y - 2 == 0, y - 2 == nyl,
+                uB0 = tvl1_primal<T, STRICT>(uA2, ad, rd, pA1a, pA1b, l11, l21, pA2a.y, pA2b.y, lef, rig, y - 2 == 0, y - 2 == nyl,
                                              l_t, theta);
                 const bool mine = owner && y - 2 >= y0 && y - 2 < yend;
                 const double dB = (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
@@ -710,25 +742,60 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
                 if (CNT == 2 && owner && y - 3 >= y0 && y - 3 < yend) { stp = so - 3 * row2; sp1 = pBna; sp2 = pBnb; }
             }
         }
-        if (CNT == 3) {
+        double2 pCna = z2, pCnb = z2;
+        if (CNT >= 3) {
             // S5: u_C(y-4)
-            if (y - 4 >= y0 && y - 4 <= hiC) {
+            if (y - 4 >= yC0 && y - 4 <= hiB) {
+                double2 ad = a4;
+                double rd = r4c;
+                if constexpr (RING) { ad = ring->a[(ri - 4u) % TVL1_RING_ROWS][lane]; rd = ring->r[(ri - 4u) % TVL1_RING_ROWS][lane]; }
                 const double l11 = wave_shift_up(pB1a.x);
                 const double l21 = wave_shift_up(pB1b.x);
-                uC0 = tvl1_primal<T, STRICT>(uB2, a4, r4c, pB1a, pB1b, l11, l21, pB2a.y, pB2b.y, lef, rig, y - 4 == 0, y - 4 == nyl,
+                uC0 = tvl1_primal<T, STRICT>(uB2, ad, rd, pB1a, pB1b, l11, l21, pB2a.y, pB2b.y, lef, rig, y - 4 == 0, y - 4 == nyl,
                                              l_t, theta);
-                const bool mine = owner && y - 4 < yend;
+                const bool mine = owner && y - 4 >= y0 && y - 4 < yend;
                 const double dC = (uC0.x - uB2.x) * (uC0.x - uB2.x) + (uC0.y - uB2.y) * (uC0.y - uB2.y);
                 accC += mine ? dC : 0.0;
-                stu = mine ? so - 4 * row2 : stu;
-                su = uC0;
+                if (CNT == 3) {
+                    stu = mine ? so - 4 * row2 : stu;
+                    su = uC0;
+                }
             }
             // S6: p_C(y-5)
-            if (y - 5 >= y0 && y - 5 < yend) {
+            if (y - 5 >= yC0 && y - 5 <= hiC) {
                 const double n1 = wave_shift_down(uC1.x);
                 const double n2 = wave_shift_down(uC1.y);
-                tvl1_dual<T, STRICT>(pB2a, pB2b, uC1, n1, n2, uC0, rig, y - 5 == nyl, taut, sp1, sp2);
-                if (owner) stp = so - 5 * row2;
+                tvl1_dual<T, STRICT>(pB2a, pB2b, uC1, n1, n2, uC0, rig, y - 5 == nyl, taut, pCna, pCnb);
+                if (CNT == 3) {                              // the unit's last stage: the store rounds
+                    sp1 = pCna; sp2 = pCnb;
+                    if (owner && y - 5 >= y0) stp = so - 5 * row2;
+                } else {
+                    pCna.x = rnd_to<T>(pCna.x); pCna.y = rnd_to<T>(pCna.y);
+                    pCnb.x = rnd_to<T>(pCnb.x); pCnb.y = rnd_to<T>(pCnb.y);
+                }
+            }
+        }
+        if constexpr (CNT == 4) {
+            // S7: u_D(y-6)
+            if (y - 6 >= y0 && y - 6 <= hiC) {
+                const double2 ad = ring->a[(ri - 6u) % TVL1_RING_ROWS][lane];
+                const double rd = ring->r[(ri - 6u) % TVL1_RING_ROWS][lane];
+                const double l11 = wave_shift_up(pC1a.x);
+                const double l21 = wave_shift_up(pC1b.x);
+                uD0 = tvl1_primal<T, STRICT>(uC2, ad, rd, pC1a, pC1b, l11, l21, pC2a.y, pC2b.y, lef, rig, y - 6 == 0, y - 6 == nyl,
+                                             l_t, theta);
+                const bool mine = owner && y - 6 < yend;
+                const double dD = (uD0.x - uC2.x) * (uD0.x - uC2.x) + (uD0.y - uC2.y) * (uD0.y - uC2.y);
+                accD += mine ? dD : 0.0;
+                stu = mine ? so - 6 * row2 : stu;
+                su = uD0;
+            }
+            // S8: p_D(y-7)
+            if (y - 7 >= y0 && y - 7 < yend) {
+                const double n1 = wave_shift_down(uD1.x);
+                const double n2 = wave_shift_down(uD1.y);
+                tvl1_dual<T, STRICT>(pC2a, pC2b, uD1, n1, n2, uD0, rig, y - 7 == nyl, taut, sp1, sp2);
+                if (owner) stp = so - 7 * row2;
             }
         }
         // the stores of this step: always issued, lanes / steps with nothing to write are out of range
@@ -740,14 +807,20 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
         bst2<NT>(rP2, stp, sp2, P2out);
         // advance the pipeline by one row
         uA2 = uA1; uA1 = uA0;
-        a4 = a3; a3 = a2; a2 = a1; a1 = cur.a;
-        r4c = r3c; r3c = r2c; r2c = r1c; r1c = cur.r;
+        if constexpr (RING) {
+            ri = (ri + 1u) % TVL1_RING_ROWS;
+        } else {
+            a4 = a3; a3 = a2; a2 = a1; a1 = cur.a;
+            r4c = r3c; r3c = r2c; r2c = r1c; r1c = cur.r;
+        }
         p0a = cur.p1; p0b = cur.p2;
         up12 = cur.p1.y; up22 = cur.p2.y;
         pA2a = pA1a; pA2b = pA1b; pA1a = pAna; pA1b = pAnb;
         uB2 = uB1; uB1 = uB0;
         pB2a = pB1a; pB2b = pB1b; pB1a = pBna; pB1b = pBnb;
-        uC1 = uC0;
+        uC2 = uC1; uC1 = uC0;
+        pC2a = pC1a; pC2b = pC1b; pC1a = pCna; pC1b = pCnb;
+        uD1 = uD0;
         cur = nxt;
         off += row2;
         so += row2;
@@ -755,23 +828,26 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
     for (int y = ys; y <= ylast; y++) step(y);
     loop_accumulate(err, slot0, accA, gw);
     if (CNT >= 2) loop_accumulate(err, slot0 + slot_step, accB, gw);
-    if (CNT == 3) loop_accumulate(err, slot0 + 2 * slot_step, accC, gw);
+    if (CNT >= 3) loop_accumulate(err, slot0 + 2 * slot_step, accC, gw);
+    if (CNT == 4) loop_accumulate(err, slot0 + 3 * slot_step, accD, gw);
 }
 
-// Launch unit of up to three iterations.  Two ways to say which:
+// Launch unit of up to N = three (k_tvl1_iter3) or four (k_tvl1_iter4) iterations.  Two ways to say which:
 //  * dev == nullptr (the re-run of a stopped unit's first iterations): k0, `check`, slot0 and `nit` (iterations to run, 4 bits per
 //    pair; all errors into slot0 when check == 0) as arguments -- the interface of k_tvl1_tile;
 //  * dev != nullptr, a CURSOR loop (ofx_loop.h): launch number `launch` of the loop; pair g starts at iteration
-//    k0 = dev->cursor[launch & 1][g] and runs 3 iterations -- or 2 when the error of iteration k0 - 1 is within afac2 of the
-//    threshold, 1 within afac1: the loop is about to stop, and everything computed past the stop is wasted and costs a re-run
-//    (the decision is a function of data every wave reads, so all waves of the pair take the same one).  One thread per pair
-//    leaves the next launch's cursor and logs where this one started, also when the launch is a no-op.
-template <typename T, bool NT, bool STRICT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_WAVES, OFX_ITER3_WAVES))) void k_tvl1_iter3(
-    Tri<typename Pix<T>::v2> Ut, Tri<typename Pix<T>::v2> P1t, Tri<typename Pix<T>::v2> P2t,
-    const typename Pix<T>::v2 *__restrict__ Ag, const T *__restrict__ Rg, double *__restrict__ errg, int k0, int check, int slot0,
-    int nx, int ny, int rows, int strips_x, int strips_pad, double l_t, double theta, double taut, double eps2, unsigned incode,
-    unsigned runmask, unsigned long long nit, int err_stride, OfxLoopDev *dev, int launch, double afac1, double afac2, int max_iter)
+//    k0 = dev->cursor[launch & 1][g] and runs N iterations -- or 3 (of four) when the error of iteration k0 - 1 is within afac3 of
+//    the threshold, 2 within afac2, 1 within afac1: the loop is about to stop, and everything computed past the stop is wasted and
+//    costs a re-run (the decision is a function of data every wave reads, so all waves of the pair take the same one).  One thread
+//    per pair leaves the next launch's cursor and logs where this one started, also when the launch is a no-op.
+// The stopping test looks N slots back: the previous unit ran up to N iterations whether or not its first one ended the loop, so
+// every launch behind the stop stays a no-op and the stopping unit's input stays intact for the re-run.
+template <typename T, bool NT, bool STRICT, int N>
+OFX_DEV void tvl1_unit(Tri<typename Pix<T>::v2> Ut, Tri<typename Pix<T>::v2> P1t, Tri<typename Pix<T>::v2> P2t,
+                       const typename Pix<T>::v2 *__restrict__ Ag, const T *__restrict__ Rg, double *__restrict__ errg, int k0,
+                       int check, int slot0, int nx, int ny, int rows, int strips_x, int strips_pad, double l_t, double theta,
+                       double taut, double eps2, unsigned incode, unsigned runmask, unsigned long long nit, int err_stride,
+                       OfxLoopDev *dev, int launch, double afac1, double afac2, double afac3, int max_iter, Tvl1Ring *ring)
 {
     using v2 = typename Pix<T>::v2;
     const int lane = threadIdx.x & 63;
@@ -796,17 +872,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_W
     const v2 *__restrict__ A = Ag + (size_t) g * npix;
     const T *__restrict__ R = Rg + (size_t) g * npix;
     double *__restrict__ err = errg + (size_t) g * err_stride;
-    double prev[3];
+    double prev[N];
 #pragma unroll
-    for (int i = 0; i < 3; i++) prev[i] = (check && k0 - i > 0) ? loop_fetch_prev(err, k0 - i) : 0.0;
+    for (int i = 0; i < N; i++) prev[i] = (check && k0 - i > 0) ? loop_fetch_prev(err, k0 - i) : 0.0;
 
     const int band = gw / strips_pad, strip = gw % strips_pad;
     const int y0 = band * rows;
     const bool idle = (strip >= strips_x) || (y0 >= ny);
     const int yend = (y0 + rows < ny) ? y0 + rows : ny;     // rows [y0, yend) are written by this wave
-    const int ys = y0 > 2 ? y0 - 2 : 0;                      // first row loaded
-    const int yl = (yend + 2 < ny - 1) ? yend + 2 : ny - 1;  // last row loaded
-    const int c = strip * STRIP3_OUT - STRIP3_HALO + lane;  // lanes 0..2 / 61..63 are halo columns
+    const int ys = y0 > N - 1 ? y0 - (N - 1) : 0;            // first row loaded
+    const int yl = (yend + N - 1 < ny - 1) ? yend + N - 1 : ny - 1;   // last row loaded
+    const int c = strip * STRIP3_OUT - STRIP3_HALO + lane;  // lanes 0..3 / 60..63 are halo columns
     const int cc = c < 0 ? 0 : (c > nx - 1 ? nx - 1 : c);
     const bool lef = (c == 0), rig = (c == nx - 1);
     const bool owner = (lane >= STRIP3_HALO) && (lane < STRIP3_OUT + STRIP3_HALO) && (c < nx);
@@ -826,7 +902,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_W
     if (check) {                                            // stopping test of src/tvl1flow.cpp:113 -- the same decision in every wave
         double e1 = 0.0;
 #pragma unroll
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < N; i++) {
             if (k0 - i > 0) {
                 const double e = loop_error_from_sum(wave_allreduce_sum(prev[i]), nx * ny, OFX_CRIT_MEAN);
                 if (!(e > eps2)) return;
@@ -835,21 +911,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_W
         }
         if (dev) {
             niter = (k0 > 0 && e1 <= eps2 * afac1) ? 1 : ((k0 > 0 && e1 <= eps2 * afac2) ? 2 : 3);
+            if (N == 4 && niter == 3 && !(k0 > 0 && e1 <= eps2 * afac3)) niter = 4;
             if (niter > max_iter - k0) niter = max_iter - k0;
             if (scribe) dev->cursor[(launch + 1) & 1][g] = k0 + niter;
         }
     }
     if (idle) return;
     const int step = check ? 1 : 0;                         // a redo's errors all go into its one scratch slot
-    if (niter >= 3)
-        tvl1_iter3_march<T, NT, STRICT, 3>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys, yl,
-                                           lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
+    if (N == 4 && niter >= 4) {
+        if constexpr (N == 4)
+            tvl1_iter3_march<T, NT, STRICT, 4, N>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend,
+                                                  ys, yl, lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut, ring);
+    } else if (niter >= 3)
+        tvl1_iter3_march<T, NT, STRICT, 3, N>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys,
+                                              yl, lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
     else if (niter == 2)
-        tvl1_iter3_march<T, NT, STRICT, 2>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys, yl,
-                                           lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
+        tvl1_iter3_march<T, NT, STRICT, 2, N>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys,
+                                              yl, lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
     else
-        tvl1_iter3_march<T, NT, STRICT, 1>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys, yl,
-                                           lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
+        tvl1_iter3_march<T, NT, STRICT, 1, N>(Uin, P1in, P2in, A, R, hu.out, h1.out, h2.out, err, slot0, step, gw, nx, ny, y0, yend, ys,
+                                              yl, lef, rig, owner, off, so, up12, up22, cur, l_t, theta, taut);
+}
+
+template <typename T, bool NT, bool STRICT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_WAVES, OFX_ITER3_WAVES))) void k_tvl1_iter3(
+    Tri<typename Pix<T>::v2> Ut, Tri<typename Pix<T>::v2> P1t, Tri<typename Pix<T>::v2> P2t,
+    const typename Pix<T>::v2 *__restrict__ Ag, const T *__restrict__ Rg, double *__restrict__ errg, int k0, int check, int slot0,
+    int nx, int ny, int rows, int strips_x, int strips_pad, double l_t, double theta, double taut, double eps2, unsigned incode,
+    unsigned runmask, unsigned long long nit, int err_stride, OfxLoopDev *dev, int launch, double afac1, double afac2, double afac3,
+    int max_iter)
+{
+    tvl1_unit<T, NT, STRICT, 3>(Ut, P1t, P2t, Ag, Rg, errg, k0, check, slot0, nx, ny, rows, strips_x, strips_pad, l_t, theta, taut, eps2,
+                                incode, runmask, nit, err_stride, dev, launch, afac1, afac2, afac3, max_iter, nullptr);
+}
+
+// Four per launch: 3 waves per SIMD as well (12 KB of ring per wave: 12 waves on a CU hold 144 of its 160 KB of LDS).
+template <typename T, bool NT, bool STRICT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_ITER3_WAVES, OFX_ITER3_WAVES))) void k_tvl1_iter4(
+    Tri<typename Pix<T>::v2> Ut, Tri<typename Pix<T>::v2> P1t, Tri<typename Pix<T>::v2> P2t,
+    const typename Pix<T>::v2 *__restrict__ Ag, const T *__restrict__ Rg, double *__restrict__ errg, int k0, int check, int slot0,
+    int nx, int ny, int rows, int strips_x, int strips_pad, double l_t, double theta, double taut, double eps2, unsigned incode,
+    unsigned runmask, unsigned long long nit, int err_stride, OfxLoopDev *dev, int launch, double afac1, double afac2, double afac3,
+    int max_iter)
+{
+    __shared__ Tvl1Ring rings[4];                           // one per wave of the workgroup, private to it
+    tvl1_unit<T, NT, STRICT, 4>(Ut, P1t, P2t, Ag, Rg, errg, k0, check, slot0, nx, ny, rows, strips_x, strips_pad, l_t, theta, taut, eps2,
+                                incode, runmask, nit, err_stride, dev, launch, afac1, afac2, afac3, max_iter, &rings[threadIdx.x >> 6]);
 }
 
 // ---- K iterations per launch on a 2-D tile: the small pyramid levels ---------------------------------------------------
@@ -1256,12 +1363,13 @@ template <typename T>
 static int tvl1_run_iterations_tile(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int K, int *n_out,
                                     double *err_out, float *ms_out, int *alt_out);
 template <typename T>
-static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int *n_out, double *err_out,
+static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int N, int *n_out, double *err_out,
                                    float *ms_out, int *alt_out);
 
-// strip height of the three-iteration kernel: tvl1_pick_rows2's model with r + 7 marching steps per strip
-static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G)
+// strip height of the three- / four-iteration kernel: tvl1_pick_rows2's model with r + 7 / r + 9 marching steps per strip
+static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G, int N = 3)
 {
+    const int depth = 2 * N + 1;                            // marching steps of a strip beyond its rows
     if (ctx->rows_per_wave3 > 0) return ctx->rows_per_wave3;
     {   // A/B knob only: OFX_ROWS3="ny:rows/ny:rows" forces the strip height on the levels of the given heights
         static const char *tab = getenv("OFX_ROWS3");
@@ -1282,7 +1390,7 @@ static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G)
             if (r > ctx->rows3_max) break;
             const long waves = strips_pad * ofx_cdiv(ny, r);
             const long slots = ctx->rows_slots > 0 ? ctx->rows_slots : 1024;
-            const long cost = ((waves + slots - 1) / slots) * (r + 7);
+            const long cost = ((waves + slots - 1) / slots) * (r + depth);
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
         }
         return best;
@@ -1291,7 +1399,7 @@ static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G)
     for (int k = 1; k <= 4; k++) {
         for (int r = 1; r <= rmax; r++) {
             if (strips_pad * ofx_cdiv(ny, r) > k * slots) continue;
-            const long cost = (long) k * (r + 7);
+            const long cost = (long) k * (r + depth);
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
             break;
         }
@@ -1300,6 +1408,12 @@ static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G)
     return best;
 }
 
+// pixels x pairs from which option fuse4 = 2 takes four iterations per launch.  On the job (four contexts, 1080p, groups of 5;
+// profiles/r15_iter4_ab.txt) 1080p x 5 and 960x540 x 5 gain, 480x270 x 5 does not; a launch alone on the device gains from
+// 1080p x 5 up only (profiles/r15_iter4_ceilings.txt).
+#ifndef TVL1_FUSE4_AUTO_PX
+#define TVL1_FUSE4_AUTO_PX 2e6
+#endif
 // The inner loop of one warp (src/tvl1flow.cpp:111-182) for all pairs of the group in lockstep.  On return
 // L.cur points at the halves holding the results; n_out[g] / err_out[g] are what the reference prints.
 template <typename T>
@@ -1344,9 +1458,15 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
         const bool tri = ctx->fuse3 == 1 ? px >= ctx->fuse3_min_px
                                          : (ctx->fuse3 == 2 && !strict_mode && (G >= 2 || ctx->concurrency > 1) &&
                                             px >= (ctx->fuse3_min_px > 0 ? ctx->fuse3_min_px : 5e5));
-        if (pairs && tri) {
-            if (unit_out) *unit_out = 3;
-            return tvl1_run_iterations_tri<T>(ctx, L, P, S, n_out, err_out, ms_out, alt_out);
+        // Four per launch (k_tvl1_iter4; option "fuse4": 0 never, 1 on every level of at least fuse4_min_px pixels x pairs,
+        // 2 = by measurement, the default): where three would run by the rule above and the level has at least
+        // TVL1_FUSE4_AUTO_PX pixels x pairs (the levels measured one by one).
+        const bool quad = ctx->fuse4 == 1 ? px >= ctx->fuse4_min_px
+                                          : (ctx->fuse4 == 2 && tri && ctx->fuse3 == 2 &&
+                                             px >= (ctx->fuse4_min_px > 0 ? ctx->fuse4_min_px : TVL1_FUSE4_AUTO_PX));
+        if (pairs && (tri || quad)) {
+            if (unit_out) *unit_out = quad ? 4 : 3;
+            return tvl1_run_iterations_tri<T>(ctx, L, P, S, quad ? 4 : 3, n_out, err_out, ms_out, alt_out);
         }
     }
     const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
@@ -1491,24 +1611,25 @@ static int tvl1_run_iterations_tile(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Par
     return OFX_OK;
 }
 
-// tvl1_run_iterations through k_tvl1_iter3 as a CURSOR loop (ofx_loop.h): launch L reads buffer (b_g + L) % 3 of the rotation and
-// writes (b_g + L + 1) % 3 and runs three iterations -- two, or one, once the loop is about to stop (k_tvl1_iter3) --, so where a
+// tvl1_run_iterations through k_tvl1_iter3 (N = 3) or k_tvl1_iter4 (N = 4) as a CURSOR loop (ofx_loop.h): launch L reads buffer
+// (b_g + L) % 3 of the rotation and writes (b_g + L + 1) % 3 and runs N iterations -- fewer once the loop is about to stop
+// (tvl1_unit) --, so where a
 // unit starts is device state.  A loop that still ends inside a unit is finished by one more launch that re-runs the unit's first
 // n - k0 iterations from its input (every pair with its own count).  Option "fuse3_cursor" = 0: the round-3 scheme, fixed units of
-// three iterations with the iteration index passed from the host.
+// N iterations with the iteration index passed from the host.
 template <typename T>
-static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int *n_out, double *err_out,
+static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int N, int *n_out, double *err_out,
                                    float *ms_out, int *alt_out)
 {
     const int nx = L.nx, ny = L.ny, G = L.G;
     const double l_t = P.lambda * P.theta, taut = P.tau / P.theta, theta = P.theta;
     const bool strict = sizeof(T) == sizeof(double) && !ctx->relaxed_dual;
-    const int rows = tvl1_pick_rows3(ctx, nx, ny, G);
+    const int rows = tvl1_pick_rows3(ctx, nx, ny, G, N);
     const int strips_x = ofx_cdiv(nx, STRIP3_OUT), strips_pad = ofx_cdiv(strips_x, 4) * 4;
     const dim3 grid((unsigned) (strips_pad / 4) * ofx_cdiv(ny, rows), G), block(256);
     const bool nt_stores = ctx->nt_stores ? ctx->nt_stores == 1 : (double) nx * ny * G * 15.0 * sizeof(T) > 300e6;
     S.pairs = false;
-    S.fuse = 3;
+    S.fuse = N;
     S.afac = 0.0;
     const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
     const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
@@ -1518,15 +1639,21 @@ static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Para
     // the error decays by 6-14 % per iteration near the threshold: within afac2 the loop has a handful of iterations left,
     // within afac1 the next one is the last more often than not (A/B on one box, profiles/r04_ab_cursor_loop.txt: fixed units of three 68.1k, cursor loop 71.2-71.6k Mpix*warp-iters/s whatever the two ratios in 1.08-1.2 / 1.3-2.0; 1.2 leaves the fewest re-runs)
     const double afac2 = ctx->fuse3_afac2 > 0 ? ctx->fuse3_afac2 : 1.5, afac1 = ctx->fuse3_afac1 > 0 ? ctx->fuse3_afac1 : 1.2;
+    // units of four have a third ratio, within which a unit runs three iterations (option "fuse4_afac3").  Measured on the job
+    // (profiles/r05_iter4_ab.txt): 1.6 costs 0.5 %, 2.4 costs 2.5 % against none -- three iterations in the four-iteration kernel
+    // cost as much per iteration as k_tvl1_iter3, and a wasted fourth less than that.  0 (default) = afac2: never three.
+    const double afac3 = ctx->fuse4_afac3 > 0 ? ctx->fuse4_afac3 : afac2;
     auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit, OfxLoopDev *dev,
                   int launch) -> int {
         auto kern = nt_stores ? k_tvl1_iter3<T, true, false> : k_tvl1_iter3<T, false, false>;
+        if (N == 4) kern = nt_stores ? k_tvl1_iter4<T, true, false> : k_tvl1_iter4<T, false, false>;
         if constexpr (sizeof(T) == sizeof(double)) {
             if (strict) kern = nt_stores ? k_tvl1_iter3<T, true, true> : k_tvl1_iter3<T, false, true>;
+            if (strict && N == 4) kern = nt_stores ? k_tvl1_iter4<T, true, true> : k_tvl1_iter4<T, false, true>;
         }
         hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k0, check,
                            slot0, nx, ny, rows, strips_x, strips_pad, l_t, theta, taut, thr, incode, runmask, nit, err_stride, dev, launch,
-                           afac1, afac2, S.max_iter);
+                           afac1, afac2, afac3, S.max_iter);
         OFX_LAUNCH_CHECK(ctx);
         return OFX_OK;
     };
@@ -1553,32 +1680,32 @@ static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Para
             }
             return go(0, 0, S.max_iter, -1.0, incode, runmask, nit, nullptr, 0);    // no stopping test; errors into the scratch slot
         };
-        const int upc = (S.chunk + 2) / 3 < 1 ? 1 : (S.chunk + 2) / 3;
+        const int upc = (S.chunk + N - 1) / N < 1 ? 1 : (S.chunk + N - 1) / N;
         // the cursor loop reserves G * (max_iter + 1) slots itself; make sure the state block it clears is the large one
-        OFX_TRY(ofx_run_loop_cursor(ctx, S, G, upc, 3, launch, redo, n_out, err_out, unit_of, inside, ms_out));
+        OFX_TRY(ofx_run_loop_cursor(ctx, S, G, upc, N, launch, redo, n_out, err_out, unit_of, inside, ms_out));
     } else {
         auto launch = [&](int k, int cnt, double thr) -> int {
             unsigned long long nit = 0;
             for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
-            return go(k, 1, k, thr, code_of_unit((unsigned) (k / 3)), all, nit, nullptr, 0);
+            return go(k, 1, k, thr, code_of_unit((unsigned) (k / N)), all, nit, nullptr, 0);
         };
         auto redo = [&](const int *k_of) -> int {
             unsigned incode = 0, runmask = 0;
             unsigned long long nit = 0;
             for (int g = 0; g < G; g++) {
                 if (k_of[g] < 0) continue;
-                const int n = k_of[g] + 1, j = (n - 1) / 3;
+                const int n = k_of[g] + 1, j = (n - 1) / N;
                 runmask |= 1u << g;
                 incode |= ((b0[g] + (unsigned) j) % 3u) << (2 * g);
-                nit |= (unsigned long long) (n - j * 3) << (4 * g);
+                nit |= (unsigned long long) (n - j * N) << (4 * g);
             }
             return go(0, 0, S.max_iter, -1.0, incode, runmask, nit, nullptr, 0);
         };
         int took_alt[OFX_MAX_GROUP];
         OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out, 0u, took_alt));
         for (int g = 0; g < G; g++) {
-            unit_of[g] = n_out[g] > 0 ? (n_out[g] - 1) / 3 : -1;
-            inside[g] = (n_out[g] % 3 != 0 && n_out[g] != S.max_iter) ? 1 : 0;
+            unit_of[g] = n_out[g] > 0 ? (n_out[g] - 1) / N : -1;
+            inside[g] = (n_out[g] % N != 0 && n_out[g] != S.max_iter) ? 1 : 0;
         }
     }
     unsigned cur = 0;
