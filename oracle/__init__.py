@@ -415,6 +415,48 @@ class Oracle(_Lib):
             raise ValueError("GaussianSmooth: sigma too large")
         return u, v, np.array(list(iters)).reshape(nscales, inner * outer)
 
+    # The SOR solvers in the HIP path's float storage (ofx_oracle.h: what is rounded to float).  store_f32 = 0: the entries above,
+    # bit for bit.  The sweep orders (set_sor_order, set_sor_tile, set_sor_wave_levels) apply as they do there.
+    def hs_single_scale_mode(self, I1, I2, u, v, alpha=7.0, warps=10, TOL=1e-4, maxiter=150, verbose=0, store_f32=0):
+        ny, nx = I1.shape
+        u, v = _f64(u).copy(), _f64(v).copy()
+        iters = (C.c_int * warps)()
+        self._fn("hs_single_scale_mode", None, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                 C.c_double, C.c_int, C.c_int, _ip, C.c_int)(_f64(I1), _f64(I2), u, v, nx, ny, alpha, warps, TOL, maxiter,
+                                                             verbose, iters, int(store_f32))
+        return u, v, list(iters)
+
+    def hs_pyramidal_mode(self, I1, I2, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4, maxiter=150,
+                          verbose=0, store_f32=0):
+        ny, nx = I1.shape
+        u, v = np.zeros((ny, nx)), np.zeros((ny, nx))
+        iters = (C.c_int * (warps * nscales))()
+        rc = self._fn("hs_pyramidal_mode", C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                      C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, _ip, C.c_int)(
+            _f64(I1), _f64(I2), u, v, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter, verbose, iters, int(store_f32))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return u, v, np.array(list(iters)).reshape(nscales, warps)
+
+    def brox_spatial_mode(self, I1, I2, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1, outer=15,
+                          verbose=0, store_f32=0):
+        ny, nx = I1.shape
+        u, v = np.zeros((ny, nx)), np.zeros((ny, nx))
+        iters = (C.c_int * (inner * outer * nscales))()
+        rc = self._fn("brox_spatial_mode", C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double,
+                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _ip, C.c_int)(
+            _f64(I1), _f64(I2), u, v, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer, verbose, iters, int(store_f32))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return u, v, np.array(list(iters)).reshape(nscales, inner * outer)
+
+    def hs_classic_mode(self, a, b, niter, alpha, store_f32=0):
+        h, w = a.shape
+        u, v = np.zeros((h, w)), np.zeros((h, w))
+        self._fn("hs_classic_mode", None, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int)(
+            u, v, _f64(a), _f64(b), w, h, niter, alpha, int(store_f32))
+        return u, v
+
     def robust_expo(self, I1, I2, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4, inner=1, outer=15,
                     verbose=0):
         """robust_expo_methods, one channel -> (u, v, sweep counts [scale][outer * inner])"""

@@ -8,6 +8,13 @@
  * terms differently (divergence first/last column) the exact order is kept.
  *
  * Every function cites the reference lines it follows (paths relative to /root/reference/).
+ *
+ * The *_mode entry points restate the HIP path's non-strict modes and are no reference behaviour; each takes its switches as
+ * arguments and equals its counterpart bit for bit with all of them 0.  store_f32 = 1 is float storage (OFX_F32): double
+ * arithmetic, a value rounded to float exactly where the float instantiation of the kernels holds a float in memory or calls
+ * rnd_to / tile_rnd.  For the SOR solvers (Horn-Schunck single scale / pyramidal / classic, Brox spatial) the rounded
+ * quantities are listed in ofx_oracle.h -- that list is the contract of the mode (tests/test_oracle_sor_f32.py on the CPU,
+ * tests/test_gpu_sor_f32.py against the kernels, bit for bit).
  */
 #include "ofx_oracle.h"
 
@@ -33,6 +40,10 @@
 
 /* (double)(float) x: a value stored in the HIP path's float storage (rnd_to<float>, csrc/ofx_tvl1.hip) */
 static inline double rnd_f32(double x) { return (double) (float) x; }
+static void round_f32(double *x, size_t n)
+{
+    for (size_t i = 0; i < n; i++) x[i] = rnd_f32(x[i]);
+}
 
 static double *dalloc(size_t n)
 {
@@ -613,8 +624,10 @@ typedef struct {
     double **A, **B, **u, **v;
 } pyramid;
 
+/* f32 (op_build_pyramid_group<float>, csrc/ofx_ops.hip): the images are uploaded into float planes; the normalised images
+ * are stored as floats, the Gaussian and the zoom-out are the *_mode operators above */
 static int pyramid_build(pyramid *P, const double *Ia, const double *Ib, double *u, double *v,
-                         int nx, int ny, int nscales, double zfactor, double presmooth)
+                         int nx, int ny, int nscales, double zfactor, double presmooth, int f32)
 {
     P->nscales = nscales;
     P->nx = (int *) malloc(sizeof(int) * nscales);
@@ -628,15 +641,24 @@ static int pyramid_build(pyramid *P, const double *Ia, const double *Ib, double 
     P->B[0] = dalloc((size_t) nx * ny);
     P->u[0] = u; P->v[0] = v;
     int rc = 0;
-    orc_image_normalization_2(Ia, Ib, P->A[0], P->B[0], nx * ny);
-    rc |= orc_gaussian(P->A[0], nx, ny, presmooth);
-    rc |= orc_gaussian(P->B[0], nx, ny, presmooth);
+    if (f32) {
+        const size_t n0 = (size_t) nx * ny;
+        double *a = dalloc(n0), *b = dalloc(n0);
+        for (size_t i = 0; i < n0; i++) { a[i] = rnd_f32(Ia[i]); b[i] = rnd_f32(Ib[i]); }
+        orc_image_normalization_2(a, b, P->A[0], P->B[0], nx * ny);
+        round_f32(P->A[0], n0);
+        round_f32(P->B[0], n0);
+        free(a); free(b);
+    } else
+        orc_image_normalization_2(Ia, Ib, P->A[0], P->B[0], nx * ny);
+    rc |= gaussian(P->A[0], nx, ny, presmooth, f32);
+    rc |= gaussian(P->B[0], nx, ny, presmooth, f32);
     for (int s = 1; s < nscales && !rc; s++) {
         orc_zoom_size(P->nx[s - 1], P->ny[s - 1], &P->nx[s], &P->ny[s], zfactor);
         const size_t n = (size_t) P->nx[s] * P->ny[s];
         P->A[s] = dalloc(n); P->B[s] = dalloc(n); P->u[s] = dalloc(n); P->v[s] = dalloc(n);
-        rc |= orc_zoom_out(P->A[s - 1], P->A[s], P->nx[s - 1], P->ny[s - 1], zfactor);
-        rc |= orc_zoom_out(P->B[s - 1], P->B[s], P->nx[s - 1], P->ny[s - 1], zfactor);
+        rc |= zoom_out(P->A[s - 1], P->A[s], P->nx[s - 1], P->ny[s - 1], zfactor, f32);
+        rc |= zoom_out(P->B[s - 1], P->B[s], P->nx[s - 1], P->ny[s - 1], zfactor, f32);
     }
     if (!rc) {
         const int c = nscales - 1;
@@ -646,7 +668,8 @@ static int pyramid_build(pyramid *P, const double *Ia, const double *Ib, double 
 }
 
 /* zoom the flow to the next finer level and rescale it: tvl1flow.cpp:302-309 */
-static void pyramid_upsample(pyramid *P, int s, double zfactor)
+/* f32 (k_zoom_in_flow<float>, csrc/ofx_ops.hip): the interpolated value is scaled in double and stored once */
+static void pyramid_upsample(pyramid *P, int s, double zfactor, int f32)
 {
     orc_zoom_in(P->u[s], P->u[s - 1], P->nx[s], P->ny[s], P->nx[s - 1], P->ny[s - 1]);
     orc_zoom_in(P->v[s], P->v[s - 1], P->nx[s], P->ny[s], P->nx[s - 1], P->ny[s - 1]);
@@ -655,6 +678,7 @@ static void pyramid_upsample(pyramid *P, int s, double zfactor)
         P->u[s - 1][i] *= 1.0 / zfactor;
         P->v[s - 1][i] *= 1.0 / zfactor;
     }
+    if (f32) { round_f32(P->u[s - 1], (size_t) n); round_f32(P->v[s - 1], (size_t) n); }
 }
 
 static void pyramid_free(pyramid *P)
@@ -672,13 +696,13 @@ static int tvl1_multiscale(const double *I0, const double *I1, double *u1, doubl
                            int warps, double epsilon, int verbose, int *iters, double *errs, int relaxed)
 {
     pyramid P;
-    int rc = pyramid_build(&P, I0, I1, u1, u2, nx, ny, nscales, zfactor, TVL1_PRESMOOTH_SIGMA);
+    int rc = pyramid_build(&P, I0, I1, u1, u2, nx, ny, nscales, zfactor, TVL1_PRESMOOTH_SIGMA, 0);
     for (int s = nscales - 1; s >= 0 && !rc; s--) {
         if (verbose) fprintf(stderr, "Scale %d: %dx%d\n", s, P.nx[s], P.ny[s]);
         tvl1_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], tau, lambda, theta,
                           warps, epsilon, verbose, iters ? iters + s * warps : NULL,
                           errs ? errs + s * warps : NULL, relaxed);
-        if (s) pyramid_upsample(&P, s, zfactor);
+        if (s) pyramid_upsample(&P, s, zfactor, 0);
     }
     pyramid_free(&P);
     return rc;
@@ -704,7 +728,10 @@ int orc_tvl1_multiscale_mode(const double *I0, const double *I1, double *u1, dou
 /* Horn-Schunck SOR point update, src/horn_schunck_pyramidal.cpp:31-71.  nb[0..3] = diagonal
  * neighbours (weight 1/12), nb[4..7] = axial neighbours (weight 1/6), in the reference order
  * p1..p8; v is updated with the NEW u (:66-67). */
-static inline double hs_sor_point(const double *Au, const double *Av, const double *Du,
+/* f32 (here and in every function below that takes it): the HIP path's float storage -- the new u and v are rounded to float
+ * before they are stored and reused (hs_point_finish<float>, csrc/ofx_sor.hip); with f32 = 0 nothing changes. */
+#define ST32(x) (f32 ? rnd_f32(x) : (x))
+static inline double hs_sor_point(int f32, const double *Au, const double *Av, const double *Du,
                                   const double *Dv, const double *D, double *u, double *v,
                                   double al, int p, int p1, int p2, int p3, int p4, int p5, int p6,
                                   int p7, int p8)
@@ -713,8 +740,8 @@ static inline double hs_sor_point(const double *Au, const double *Av, const doub
     const double ula = 1. / 12. * (u[p1] + u[p2] + u[p3] + u[p4]) + 1. / 6. * (u[p5] + u[p6] + u[p7] + u[p8]);
     const double vla = 1. / 12. * (v[p1] + v[p2] + v[p3] + v[p4]) + 1. / 6. * (v[p5] + v[p6] + v[p7] + v[p8]);
     const double uk = u[p], vk = v[p];
-    u[p] = (1.0 - w) * uk + w * (Au[p] - D[p] * v[p] + al * ula) / Du[p];
-    v[p] = (1.0 - w) * vk + w * (Av[p] - D[p] * u[p] + al * vla) / Dv[p];
+    u[p] = ST32((1.0 - w) * uk + w * (Au[p] - D[p] * v[p] + al * ula) / Du[p]);
+    v[p] = ST32((1.0 - w) * vk + w * (Av[p] - D[p] * u[p] + al * vla) / Dv[p]);
     return (u[p] - uk) * (u[p] - uk) + (v[p] - vk) * (v[p] - vk);
 }
 
@@ -727,15 +754,15 @@ static inline double hs_sor_point(const double *Au, const double *Av, const doub
  * the bottom-right corner passes its four diagonal taps as (k-1, k, k-nx-1, k-nx)
  * (horn_schunck_pyramidal.cpp:222-228), i.e. the bottom pair first.  Same set, different summation
  * order, so it is kept to stay bit-identical. */
-static inline double hs_point_clamped(const double *Au, const double *Av, const double *Du, const double *Dv,
+static inline double hs_point_clamped(int f32, const double *Au, const double *Av, const double *Du, const double *Dv,
                                       const double *D, double *u, double *v, double a2, int i, int j, int nx, int ny)
 {
     const int iu = i > 0 ? i - 1 : 0, id = i < ny - 1 ? i + 1 : ny - 1;
     const int jl = j > 0 ? j - 1 : 0, jr = j < nx - 1 ? j + 1 : nx - 1;
     if (i == ny - 1 && j == nx - 1)
-        return hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, i * nx + j, id * nx + jl, id * nx + jr, iu * nx + jl,
+        return hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, i * nx + j, id * nx + jl, id * nx + jr, iu * nx + jl,
                             iu * nx + jr, iu * nx + j, i * nx + jl, id * nx + j, i * nx + jr);
-    return hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, i * nx + j, iu * nx + jl, iu * nx + jr, id * nx + jl,
+    return hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, i * nx + j, iu * nx + jl, iu * nx + jr, id * nx + jl,
                         id * nx + jr, iu * nx + j, i * nx + jl, id * nx + j, i * nx + jr);
 }
 
@@ -775,7 +802,7 @@ static int sor_order_of_solve(int k, int n)
     return g_sor_order;
 }
 
-static double hs_sweep_coloured(const double *Au, const double *Av, const double *Du, const double *Dv,
+static double hs_sweep_coloured(int f32, const double *Au, const double *Av, const double *Du, const double *Dv,
                                 const double *D, double *u, double *v, double a2, int nx, int ny)
 {
     double error = 0;
@@ -783,7 +810,7 @@ static double hs_sweep_coloured(const double *Au, const double *Av, const double
         const int ci = col >> 1, cj = col & 1;
         for (int i = ci; i < ny; i += 2)
             for (int j = cj; j < nx; j += 2)
-                error += hs_point_clamped(Au, Av, Du, Dv, D, u, v, a2, i, j, nx, ny);
+                error += hs_point_clamped(f32, Au, Av, Du, Dv, D, u, v, a2, i, j, nx, ny);
     }
     return error;
 }
@@ -844,7 +871,7 @@ static void plane_index_build(plane_index *P, int nx, int ny, int (*pos)(int, in
 static void plane_index_free(plane_index *P) { free(P->start); free(P->order); }
 
 /* runs sweeps [0, nsweeps) pipelined; errs[s] = sum of squared updates of sweep s */
-static void hs_sweeps_planes(const plane_index *P, const double *Au, const double *Av, const double *Du,
+static void hs_sweeps_planes(int f32, const plane_index *P, const double *Au, const double *Av, const double *Du,
                              const double *Dv, const double *D, double *u, double *v, double a2, int nx, int ny,
                              int nsweeps, double *errs)
 {
@@ -856,7 +883,7 @@ static void hs_sweeps_planes(const plane_index *P, const double *Au, const doubl
             if (q < 0 || q >= P->npos) continue;
             for (int e = P->start[q]; e < P->start[q + 1]; e++) {
                 const int k = P->order[e];
-                errs[s] += hs_point_clamped(Au, Av, Du, Dv, D, u, v, a2, k / nx, k % nx, nx, ny);
+                errs[s] += hs_point_clamped(f32, Au, Av, Du, Dv, D, u, v, a2, k / nx, k % nx, nx, ny);
             }
         }
 }
@@ -864,47 +891,50 @@ static void hs_sweeps_planes(const plane_index *P, const double *Au, const doubl
 static int g_plane_batch = 64;      /* sweeps in flight per batch, like the HIP path */
 void orc_set_plane_batch(int b) { if (b > 0) g_plane_batch = b; }
 
-static double hs_sweep(const double *Au, const double *Av, const double *Du, const double *Dv,
+static double hs_sweep(int f32, const double *Au, const double *Av, const double *Du, const double *Dv,
                        const double *D, double *u, double *v, double a2, int nx, int ny)
 {
-    if (g_sor_order == 1) return hs_sweep_coloured(Au, Av, Du, Dv, D, u, v, a2, nx, ny);
+    if (g_sor_order == 1) return hs_sweep_coloured(f32, Au, Av, Du, Dv, D, u, v, a2, nx, ny);
     double error = 0;
     #pragma omp parallel for reduction(+:error)
     for (int i = 1; i < ny - 1; i++)
         for (int j = 1; j < nx - 1; j++) {
             const int k = i * nx + j;
-            error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx + 1,
+            error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx + 1,
                                   k + nx - 1, k + nx + 1, k - nx, k - 1, k + nx, k + 1);
         }
     for (int j = 1; j < nx - 1; j++) {
         int k = j;
-        error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k + 1, k + nx - 1, k + nx + 1,
+        error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k + 1, k + nx - 1, k + nx + 1,
                               k, k - 1, k + nx, k + 1);
         k = (ny - 1) * nx + j;
-        error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx + 1, k - 1, k + 1,
+        error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx + 1, k - 1, k + 1,
                               k - nx, k - 1, k, k + 1);
     }
     for (int i = 1; i < ny - 1; i++) {
         int k = i * nx;
-        error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - nx, k - nx + 1, k + nx, k + nx + 1,
+        error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - nx, k - nx + 1, k + nx, k + nx + 1,
                               k - nx, k, k + nx, k + 1);
         k = (i + 1) * nx - 1;
-        error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx, k + nx - 1, k + nx,
+        error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - nx - 1, k - nx, k + nx - 1, k + nx,
                               k - nx, k - 1, k + nx, k);
     }
-    error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, 0, 0, 1, nx, nx + 1, 0, 0, nx, 1);
+    error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, 0, 0, 1, nx, nx + 1, 0, 0, nx, 1);
     int k = nx - 1;
-    error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k, k + nx - 1, k + nx, k, k - 1, k + nx, k);
+    error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k, k + nx - 1, k + nx, k, k - 1, k + nx, k);
     k = (ny - 1) * nx;
-    error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - nx, k - nx + 1, k, k + 1, k - nx, k, k, k + 1);
+    error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - nx, k - nx + 1, k, k + 1, k - nx, k, k, k + 1);
     k = ny * nx - 1;
-    error += hs_sor_point(Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k, k - nx - 1, k - nx, k - nx, k - 1, k, k);
+    error += hs_sor_point(f32, Au, Av, Du, Dv, D, u, v, a2, k, k - 1, k, k - nx - 1, k - nx, k - nx, k - 1, k, k);
     return error;
 }
 
-/* src/horn_schunck_pyramidal.cpp:78-249 */
-void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
-                         double alpha, int warps, double TOL, int maxiter, int verbose, int *iters)
+/* src/horn_schunck_pyramidal.cpp:78-249.  f32 (hs_single_scale_dev<float>, csrc/ofx_sor.hip): I1, I2, u, v hold floats; the
+ * centred gradient of I2, the warped gradient (I2wx, I2wy) and dif are stored as floats, u and v after every update; the
+ * warped image I2w stays a double (k_hs_warp keeps it in a register) and Au .. D are recomputed in double from the stored
+ * values. */
+static void hs_single_scale(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                            double alpha, int warps, double TOL, int maxiter, int verbose, int *iters, int f32)
 {
     const int size = nx * ny;
     const size_t n = (size_t) size;
@@ -917,14 +947,16 @@ void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *
                 nx, ny, alpha, warps, TOL, maxiter, verbose);
 
     orc_centered_gradient(I2, I2x, I2y, nx, ny);                       /* :114 */
+    if (f32) { round_f32(I2x, n); round_f32(I2y, n); }
     for (int w = 0; w < warps; w++) {
         if (verbose) fprintf(stderr, "Warping %d:", w);
         orc_bicubic_warp(I2,  u, v, I2w,  nx, ny, 1);                  /* :123-125 */
         orc_bicubic_warp(I2x, u, v, I2wx, nx, ny, 1);
         orc_bicubic_warp(I2y, u, v, I2wy, nx, ny, 1);
+        if (f32) { round_f32(I2wx, n); round_f32(I2wy, n); }
         for (int i = 0; i < size; i++) {                               /* :128-137 */
             const double I2wl = I2wx[i] * u[i] + I2wy[i] * v[i];
-            const double dif = I1[i] - I2w[i] + I2wl;
+            const double dif = ST32(I1[i] - I2w[i] + I2wl);
             Au[i] = dif * I2wx[i];
             Av[i] = dif * I2wy[i];
             Du[i] = I2wx[i] * I2wx[i] + alpha2;
@@ -945,13 +977,13 @@ void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *
                 const int b = (maxiter - niter < g_plane_batch) ? maxiter - niter : g_plane_batch;
                 memcpy(cu, u, n * sizeof(double));
                 memcpy(cv, v, n * sizeof(double));
-                hs_sweeps_planes(&PI, Au, Av, Du, Dv, D, u, v, alpha2, nx, ny, b, errs);
+                hs_sweeps_planes(f32, &PI, Au, Av, Du, Dv, D, u, v, alpha2, nx, ny, b, errs);
                 int used = b;
                 for (int q = 0; q < b; q++) { error = sqrt(errs[q] / size); if (!(error > TOL)) { used = q + 1; break; } }
                 if (used < b) {
                     memcpy(u, cu, n * sizeof(double));
                     memcpy(v, cv, n * sizeof(double));
-                    hs_sweeps_planes(&PI, Au, Av, Du, Dv, D, u, v, alpha2, nx, ny, used, errs);
+                    hs_sweeps_planes(f32, &PI, Au, Av, Du, Dv, D, u, v, alpha2, nx, ny, used, errs);
                     error = sqrt(errs[used - 1] / size);
                 }
                 niter += used;
@@ -961,7 +993,7 @@ void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *
         } else
         while (error > TOL && niter < maxiter) {                       /* :143 */
             niter++;
-            error = hs_sweep(Au, Av, Du, Dv, D, u, v, alpha2, nx, ny);
+            error = hs_sweep(f32, Au, Av, Du, Dv, D, u, v, alpha2, nx, ny);
             error = sqrt(error / size);                                /* :230 */
         }
         g_sor_order = order_all;
@@ -972,26 +1004,63 @@ void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *
     free(Au); free(Av); free(Du); free(Dv); free(D);
 }
 
+void orc_hs_single_scale(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                         double alpha, int warps, double TOL, int maxiter, int verbose, int *iters)
+{
+    hs_single_scale(I1, I2, u, v, nx, ny, alpha, warps, TOL, maxiter, verbose, iters, 0);
+}
+
+/* store_f32: the images and the incoming flow are rounded to float first (they are uploaded into float planes) */
+void orc_hs_single_scale_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                              double alpha, int warps, double TOL, int maxiter, int verbose, int *iters, int store_f32)
+{
+    if (!store_f32) {
+        hs_single_scale(I1, I2, u, v, nx, ny, alpha, warps, TOL, maxiter, verbose, iters, 0);
+        return;
+    }
+    const size_t n = (size_t) nx * ny;
+    double *A = dalloc(n), *B = dalloc(n);
+    for (size_t i = 0; i < n; i++) { A[i] = rnd_f32(I1[i]); B[i] = rnd_f32(I2[i]); }
+    round_f32(u, n);
+    round_f32(v, n);
+    hs_single_scale(A, B, u, v, nx, ny, alpha, warps, TOL, maxiter, verbose, iters, 1);
+    free(A); free(B);
+}
+
 /* src/horn_schunck_pyramidal.cpp:258-370 */
-int orc_hs_pyramidal(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
-                     double alpha, int nscales, double zfactor, int warps, double TOL, int maxiter,
-                     int verbose, int *iters)
+static int hs_pyramidal(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                        double alpha, int nscales, double zfactor, int warps, double TOL, int maxiter,
+                        int verbose, int *iters, int f32)
 {
     if (verbose)
         fprintf(stderr, "Multiscale Horn-Schunck of a %dx%d pair\n\ta=%g ns=%d zf=%g nw=%d eps=%g mi=%d\n",
                 nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter);
     pyramid P;
-    int rc = pyramid_build(&P, I1, I2, u, v, nx, ny, nscales, zfactor, HS_PRESMOOTH_SIGMA);
+    int rc = pyramid_build(&P, I1, I2, u, v, nx, ny, nscales, zfactor, HS_PRESMOOTH_SIGMA, f32);
     for (int s = nscales - 1; s >= 0 && !rc; s--) {
         if (verbose) fprintf(stderr, "Scale: %d %dx%d\n", s, P.nx[s], P.ny[s]);
         const int order = sor_order_enter_level(s);
-        orc_hs_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], alpha, warps, TOL,
-                            maxiter, verbose, iters ? iters + s * warps : NULL);
+        hs_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], alpha, warps, TOL,
+                        maxiter, verbose, iters ? iters + s * warps : NULL, f32);
         g_sor_order = order;
-        if (s) pyramid_upsample(&P, s, zfactor);
+        if (s) pyramid_upsample(&P, s, zfactor, f32);
     }
     pyramid_free(&P);
     return rc;
+}
+
+int orc_hs_pyramidal(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                     double alpha, int nscales, double zfactor, int warps, double TOL, int maxiter,
+                     int verbose, int *iters)
+{
+    return hs_pyramidal(I1, I2, u, v, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter, verbose, iters, 0);
+}
+
+int orc_hs_pyramidal_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                          double alpha, int nscales, double zfactor, int warps, double TOL, int maxiter,
+                          int verbose, int *iters, int store_f32)
+{
+    return hs_pyramidal(I1, I2, u, v, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter, verbose, iters, store_f32);
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1042,7 +1111,7 @@ static void brox_divergence_u(const double *u, const double *v, const double *ps
 /* src/brox_optic_flow_spatial.cpp:129-172.  (i0, i1, j0, j1) are the OFFSETS to the previous /
  * following row and column; the reference passes 0 for a missing neighbour so the tap lands on
  * the pixel itself (:332-388), with psi = 0 there. */
-static inline double brox_sor_point(const double *Au, const double *Av, const double *Du,
+static inline double brox_sor_point(int f32, const double *Au, const double *Av, const double *Du,
                                     const double *Dv, const double *D, double *du, double *dv,
                                     double alpha, const double *psi1, const double *psi2,
                                     const double *psi3, const double *psi4, int i, int i0, int i1,
@@ -1053,15 +1122,18 @@ static inline double brox_sor_point(const double *Au, const double *Av, const do
     const double div_du = psi1[k] * du[k + i1] + psi2[k] * du[k - i0] + psi3[k] * du[k + j1] + psi4[k] * du[k - j0];
     const double div_dv = psi1[k] * dv[k + i1] + psi2[k] * dv[k - i0] + psi3[k] * dv[k + j1] + psi4[k] * dv[k - j0];
     const double duk = du[k], dvk = dv[k];
-    du[k] = (1. - w) * du[k] + w * (Au[k] - D[k] * dv[k] + alpha * div_du) / Du[k];
-    dv[k] = (1. - w) * dv[k] + w * (Av[k] - D[k] * du[k] + alpha * div_dv) / Dv[k];
+    du[k] = ST32((1. - w) * du[k] + w * (Au[k] - D[k] * dv[k] + alpha * div_du) / Du[k]);
+    dv[k] = ST32((1. - w) * dv[k] + w * (Av[k] - D[k] * du[k] + alpha * div_dv) / Dv[k]);
     return (du[k] - duk) * (du[k] - duk) + (dv[k] - dvk) * (dv[k] - dvk);
 }
 
-/* src/brox_optic_flow_spatial.cpp:179-444 */
+/* src/brox_optic_flow_spatial.cpp:179-444.  f32 (brox_single_scale_dev<float>, csrc/ofx_sor.hip): I1, I2, u, v hold floats;
+ * stored as floats are the derivatives of the images (I1x, I1y, I2x .. I2yy), the six warps, psis, div_u, div_v, div_d, psid,
+ * psig, Au .. D, du and dv after every update and u, v after the increment is added; psi1 .. psi4 are recomputed in double from
+ * the stored psis. */
 static void brox_single_scale(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
                               double alpha, double gamma, double TOL, int inner_iter, int outer_iter,
-                              int nthreads, int verbose, int *iters)
+                              int nthreads, int verbose, int *iters, int f32)
 {
     const int size = nx * ny;
     const size_t n = (size_t) size;
@@ -1082,6 +1154,8 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
     orc_dxx(I2, I2xx, nx, ny);                                 /* :239-241 */
     orc_dyy(I2, I2yy, nx, ny);
     orc_dxy(I2, I2xy, nx, ny);
+    if (f32) for (int q = 6; q <= 9; q++) round_f32(a[q], n);       /* I1x, I1y, I2x, I2y */
+    if (f32) for (int q = 13; q <= 15; q++) round_f32(a[q], n);     /* I2xx, I2yy, I2xy */
 
     for (int no = 0; no < outer_iter; no++) {                  /* :244 */
         orc_bicubic_warp(I2,   u, v, I2w,   nx, ny, 1);        /* :246-251 */
@@ -1090,6 +1164,8 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
         orc_bicubic_warp(I2xx, u, v, I2wxx, nx, ny, 1);
         orc_bicubic_warp(I2xy, u, v, I2wxy, nx, ny, 1);
         orc_bicubic_warp(I2yy, u, v, I2wyy, nx, ny, 1);
+        if (f32) for (int q = 10; q <= 12; q++) round_f32(a[q], n);     /* I2w, I2wx, I2wy */
+        if (f32) for (int q = 16; q <= 18; q++) round_f32(a[q], n);     /* I2wxx, I2wyy, I2wxy */
 
         orc_centered_gradient(u, ux, uy, nx, ny);              /* :254-255 */
         orc_centered_gradient(v, vx, vy, nx, ny);
@@ -1099,14 +1175,15 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
             const double gu = ux[i] * ux[i] + uy[i] * uy[i];
             const double gv = vx[i] * vx[i] + vy[i] * vy[i];
             const double d2 = gu + gv;
-            psis[i] = 1. / sqrt(d2 + BROX_EPSILON * BROX_EPSILON);
+            psis[i] = ST32(1. / sqrt(d2 + BROX_EPSILON * BROX_EPSILON));
         }
         brox_psi_divergence(psis, psi1, psi2, psi3, psi4, nx, ny);                   /* :261 */
         brox_divergence_u(u, v, psi1, psi2, psi3, psi4, div_u, div_v, nx, ny);       /* :264 */
+        if (f32) { round_f32(div_u, n); round_f32(div_v, n); }
 
         #pragma omp parallel for
         for (int i = 0; i < size; i++) {                       /* :266-274 */
-            div_d[i] = alpha * (psi1[i] + psi2[i] + psi3[i] + psi4[i]);
+            div_d[i] = ST32(alpha * (psi1[i] + psi2[i] + psi3[i] + psi4[i]));
             du[i] = dv[i] = 0;
         }
 
@@ -1115,14 +1192,14 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
             for (int i = 0; i < size; i++) {                   /* psi_data :33-57 */
                 const double dI = I2w[i] - I1[i] + I2wx[i] * du[i] + I2wy[i] * dv[i];
                 const double dI2 = dI * dI;
-                psid[i] = 1. / sqrt(dI2 + BROX_EPSILON * BROX_EPSILON);
+                psid[i] = ST32(1. / sqrt(dI2 + BROX_EPSILON * BROX_EPSILON));
             }
             #pragma omp parallel for
             for (int i = 0; i < size; i++) {                   /* psi_gradient :64-92 */
                 const double dIx = I2wx[i] - I1x[i] + I2wxx[i] * du[i] + I2wxy[i] * dv[i];
                 const double dIy = I2wy[i] - I1y[i] + I2wxy[i] * du[i] + I2wyy[i] * dv[i];
                 const double dI2 = dIx * dIx + dIy * dIy;
-                psig[i] = 1. / sqrt(dI2 + BROX_EPSILON * BROX_EPSILON);
+                psig[i] = ST32(1. / sqrt(dI2 + BROX_EPSILON * BROX_EPSILON));
             }
             for (int i = 0; i < size; i++) {                   /* :283-309 */
                 const double p = psid[i];
@@ -1140,11 +1217,11 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
                 const double GDv = g * (I2wyy[i] * I2wyy[i] + I2wxy[i] * I2wxy[i]);
                 const double DI = (I2wxx[i] + I2wyy[i]) * I2wxy[i];
                 const double Duv = p * I2wy[i] * I2wx[i] + g * DI;
-                Au[i] = BNu + GNu + alpha * div_u[i];
-                Av[i] = BNv + GNv + alpha * div_v[i];
-                Du[i] = BDu + GDu + div_d[i];
-                Dv[i] = BDv + GDv + div_d[i];
-                D[i] = Duv;
+                Au[i] = ST32(BNu + GNu + alpha * div_u[i]);
+                Av[i] = ST32(BNv + GNv + alpha * div_v[i]);
+                Du[i] = ST32(BDu + GDu + div_d[i]);
+                Dv[i] = ST32(BDv + GDv + div_d[i]);
+                D[i] = ST32(Duv);
             }
 
             double error = 1000;
@@ -1171,7 +1248,7 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
                                 if (pq < 0 || pq >= PI.npos) continue;
                                 for (int e = PI.start[pq]; e < PI.start[pq + 1]; e++) {
                                     const int k = PI.order[e], i = k / nx, j = k % nx;
-                                    errs[q] += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
+                                    errs[q] += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
                                                               i > 0 ? nx : 0, i < ny - 1 ? nx : 0, j, nx, j > 0 ? 1 : 0,
                                                               j < nx - 1 ? 1 : 0);
                                 }
@@ -1198,7 +1275,7 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
                                 const int i1e = ti + g_tile_h < ny ? ti + g_tile_h : ny, j1e = tj + g_tile_w < nx ? tj + g_tile_w : nx;
                                 for (int i = ti; i < i1e; i++)
                                     for (int j = tj; j < j1e; j++)
-                                        error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
+                                        error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
                                                                 i > 0 ? nx : 0, i < ny - 1 ? nx : 0, j, nx, j > 0 ? 1 : 0,
                                                                 j < nx - 1 ? 1 : 0);
                             }
@@ -1209,7 +1286,7 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
                     for (int col = 0; col < 2; col++)
                         for (int i = 0; i < ny; i++)
                             for (int j = (i + col) & 1; j < nx; j += 2)
-                                error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
+                                error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i,
                                                         i > 0 ? nx : 0, i < ny - 1 ? nx : 0, j, nx, j > 0 ? 1 : 0,
                                                         j < nx - 1 ? 1 : 0);
                     error = sqrt(error / size);
@@ -1218,27 +1295,27 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
                 #pragma omp parallel for reduction(+:error)
                 for (int i = 1; i < ny - 1; i++)
                     for (int j = 1; j < nx - 1; j++)
-                        error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                        error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                                 i, nx, nx, j, nx, 1, 1);
                 for (int j = 1; j < nx - 1; j++) {
-                    error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                    error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                             0, 0, nx, j, nx, 1, 1);
-                    error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                    error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                             ny - 1, nx, 0, j, nx, 1, 1);
                 }
                 for (int i = 1; i < ny - 1; i++) {
-                    error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                    error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                             i, nx, nx, 0, nx, 0, 1);
-                    error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                    error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                             i, nx, nx, nx - 1, nx, 1, 0);
                 }
-                error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                         0, 0, nx, 0, nx, 0, 1);
-                error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                         0, 0, nx, nx - 1, nx, 1, 0);
-                error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                         ny - 1, nx, 0, 0, nx, 0, 1);
-                error += brox_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
+                error += brox_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4,
                                         ny - 1, nx, 0, nx - 1, nx, 1, 0);
                 error = sqrt(error / size);                    /* :389 */
             }
@@ -1247,30 +1324,44 @@ static void brox_single_scale(const double *I1, const double *I2, double *u, dou
             if (iters) iters[solve] = nsor;
             solve++;
         }
-        for (int i = 0; i < size; i++) { u[i] += du[i]; v[i] += dv[i]; }   /* :398-401 */
+        for (int i = 0; i < size; i++) { u[i] = ST32(u[i] + du[i]); v[i] = ST32(v[i] + dv[i]); }   /* :398-401 */
     }
     for (int q = 0; q < NARR; q++) free(a[q]);
 }
 
 /* src/brox_optic_flow_spatial.cpp:451-549.  `iters` is laid out [scale][outer*inner]. */
-int orc_brox_spatial(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
-                     double alpha, double gamma, int nscales, double nu, double TOL,
-                     int inner_iter, int outer_iter, int verbose, int *iters)
+static int brox_spatial(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                        double alpha, double gamma, int nscales, double nu, double TOL,
+                        int inner_iter, int outer_iter, int verbose, int *iters, int f32)
 {
     pyramid P;
-    int rc = pyramid_build(&P, I1, I2, u, v, nx, ny, nscales, nu, BROX_SIGMA);
+    int rc = pyramid_build(&P, I1, I2, u, v, nx, ny, nscales, nu, BROX_SIGMA, f32);
     const int nthreads = orc_max_threads();
     for (int s = nscales - 1; s >= 0 && !rc; s--) {
         if (verbose) printf("Scale: %d\n", s);
         const int order = sor_order_enter_level(s);
         brox_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], alpha, gamma, TOL,
                           inner_iter, outer_iter, nthreads, verbose,
-                          iters ? iters + s * inner_iter * outer_iter : NULL);
+                          iters ? iters + s * inner_iter * outer_iter : NULL, f32);
         g_sor_order = order;
-        if (s) pyramid_upsample(&P, s, nu);
+        if (s) pyramid_upsample(&P, s, nu, f32);
     }
     pyramid_free(&P);
     return rc;
+}
+
+int orc_brox_spatial(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                     double alpha, double gamma, int nscales, double nu, double TOL,
+                     int inner_iter, int outer_iter, int verbose, int *iters)
+{
+    return brox_spatial(I1, I2, u, v, nx, ny, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, verbose, iters, 0);
+}
+
+int orc_brox_spatial_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                          double alpha, double gamma, int nscales, double nu, double TOL,
+                          int inner_iter, int outer_iter, int verbose, int *iters, int store_f32)
+{
+    return brox_spatial(I1, I2, u, v, nx, ny, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, verbose, iters, store_f32);
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1558,7 +1649,7 @@ int orc_robust_expo(const double *I1, const double *I2, double *u, double *v, in
         if (verbose) printf("Scale: %d\n", s);
         rexpo_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], method, alpha_adapted_for_nchannels, gamma, lambda,
                            TOL, inner_iter, outer_iter, verbose, iters ? iters + s * inner_iter * outer_iter : NULL);
-        if (s) pyramid_upsample(&P, s, nu);
+        if (s) pyramid_upsample(&P, s, nu, 0);
     }
     pyramid_free(&P);
     return rc;
@@ -1917,7 +2008,9 @@ static inline double hsc_p(const double *x, int w, int h, int i, int j)
     return x[j * w + i];
 }
 
-void orc_hs_classic(double *u, double *v, const double *a, const double *b, int w, int h, int n, double alpha)
+/* f32 (hs_classic_host<float>, csrc/ofx_sor.hip): a and b hold floats; Ex, Ey, Et and the new u, v are stored as floats, ubar
+ * and vbar stay doubles (k_hsc_iter keeps them in registers) */
+static void hs_classic(double *u, double *v, const double *a, const double *b, int w, int h, int n, double alpha, int f32)
 {
     const size_t sz = (size_t) w * h;
     double *Ex = dalloc(sz), *Ey = dalloc(sz), *Et = dalloc(sz), *ubar = dalloc(sz), *vbar = dalloc(sz);
@@ -1933,6 +2026,7 @@ void orc_hs_classic(double *u, double *v, const double *a, const double *b, int 
                                          hsc_p(a, w, h, i + 1, j) + hsc_p(b, w, h, i, j + 1) - hsc_p(a, w, h, i, j + 1) +
                                          hsc_p(b, w, h, i + 1, j + 1) - hsc_p(a, w, h, i + 1, j + 1));
         }
+    if (f32) { round_f32(Ex, sz); round_f32(Ey, sz); round_f32(Et, sz); }
     for (size_t i = 0; i < sz; i++) u[i] = v[i] = 0;                                  /* :139-141 */
     for (int it = 0; it < n; it++) {                                                  /* hs_iteration :97-122 */
         for (int pass = 0; pass < 2; pass++) {                                        /* compute_bar :76-94 */
@@ -1948,11 +2042,30 @@ void orc_hs_classic(double *u, double *v, const double *a, const double *b, int 
         for (size_t i = 0; i < sz; i++) {
             double t = Ex[i] * ubar[i] + Ey[i] * vbar[i] + Et[i];
             t /= alpha * alpha + Ex[i] * Ex[i] + Ey[i] * Ey[i];
-            u[i] = ubar[i] - Ex[i] * t;
-            v[i] = vbar[i] - Ey[i] * t;
+            u[i] = ST32(ubar[i] - Ex[i] * t);
+            v[i] = ST32(vbar[i] - Ey[i] * t);
         }
     }
     free(Ex); free(Ey); free(Et); free(ubar); free(vbar);
+}
+
+void orc_hs_classic(double *u, double *v, const double *a, const double *b, int w, int h, int n, double alpha)
+{
+    hs_classic(u, v, a, b, w, h, n, alpha, 0);
+}
+
+/* store_f32: the images are rounded to float first (they are uploaded into float planes) */
+void orc_hs_classic_mode(double *u, double *v, const double *a, const double *b, int w, int h, int n, double alpha, int store_f32)
+{
+    if (!store_f32) {
+        hs_classic(u, v, a, b, w, h, n, alpha, 0);
+        return;
+    }
+    const size_t sz = (size_t) w * h;
+    double *A = dalloc(sz), *B = dalloc(sz);
+    for (size_t i = 0; i < sz; i++) { A[i] = rnd_f32(a[i]); B[i] = rnd_f32(b[i]); }
+    hs_classic(u, v, A, B, w, h, n, alpha, 1);
+    free(A); free(B);
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -108,6 +108,31 @@ int  orc_brox_spatial(const double *I1, const double *I2, double *u, double *v, 
                       double alpha, double gamma, int nscales, double nu, double TOL,
                       int inner_iter, int outer_iter, int verbose, int *iters);
 
+/* The SOR solvers in the HIP path's float storage (OFX_F32: float in memory, double arithmetic), restated.  Checker aids of this
+ * project, not the reference: with store_f32 = 0 each equals its counterpart (above; orc_hs_classic below) bit for bit.  The
+ * sweep orders 0 .. 3 and the tile / wave-level switches apply as they do there.  With store_f32 = 1 a value is rounded to
+ * float exactly where the float instantiation has a float in memory or calls rnd_to / tile_rnd; all arithmetic and every value
+ * not listed stays double.  THE CONTRACT OF THE MODE -- rounded are:
+ *   pyramid       the input images; the normalised images; the Gaussian and the zoom-out as orc_gaussian_mode /
+ *                 orc_zoom_out_mode; the flow zoomed in and multiplied by 1 / zfactor (one rounding, after the product);
+ *   Horn-Schunck  I1, I2 and the incoming u, v (single-scale entry); I2x, I2y; I2wx, I2wy; dif = I1 - I2w + I2wl; u and v after
+ *                 every update.  NOT rounded: the warped image I2w; Au, Av, Du, Dv, D (recomputed in double from I2wx, I2wy, dif);
+ *   Brox spatial  I1x, I1y, I2x, I2y, I2xx, I2xy, I2yy; the six warps I2w .. I2wyy; psis; div_u, div_v, div_d; psid, psig;
+ *                 Au, Av, Du, Dv, D; du and dv after every update; u and v after du, dv are added.  NOT rounded: psi1 .. psi4
+ *                 (half-sums recomputed in double from psis);
+ *   classic HS    a, b; Ex, Ey, Et; u and v after every iteration.  NOT rounded: ubar, vbar.
+ * The stopping sums add the squared differences of the rounded values, in double. */
+void orc_hs_single_scale_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                              double alpha, int warps, double TOL, int maxiter, int verbose, int *iters, int store_f32);
+int  orc_hs_pyramidal_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                           double alpha, int nscales, double zfactor, int warps, double TOL, int maxiter,
+                           int verbose, int *iters, int store_f32);
+int  orc_brox_spatial_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny,
+                           double alpha, double gamma, int nscales, double nu, double TOL,
+                           int inner_iter, int outer_iter, int verbose, int *iters, int store_f32);
+void orc_hs_classic_mode(double *u, double *v, const double *a, const double *b, int w, int h, int n, double alpha,
+                         int store_f32);
+
 /* robust_expo_methods.cpp + robust_expo_smoothness.cpp + robust_expo_generic_tensor.cpp, one channel */
 void orc_gaussian_dirichlet(double *I, int nx, int ny, double sigma);
 void orc_rexpo_exponential(const double *Ix, const double *Iy, int n, double alpha, double lambda, int method, double *expo);

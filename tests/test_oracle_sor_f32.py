@@ -1,0 +1,139 @@
+"""The oracle's restatement of the SOR solvers in float storage (oracle/ofx_oracle.c: orc_hs_single_scale_mode,
+orc_hs_pyramidal_mode, orc_brox_spatial_mode, orc_hs_classic_mode; the list of rounded quantities is in ofx_oracle.h), on the CPU:
+
+* with store_f32 = 0 every entry IS its counterpart, bit for bit, in every sweep order;
+* with store_f32 = 1 only float-representable values come back, and the pipelined schedule (order 2) still equals the
+  sequential sweep (order 0) bit for bit -- the rounding sits inside the point update, so the argument of DESIGN 5.3 holds;
+* the restated float solve stays in the band the project already asserts for the GPU's float storage: Horn-Schunck within
+  30 x the drift of the reference's own float build + 1e-5 (tests/test_gpu_tvl1.py), Brox -- no float reference build -- 1e-3.
+
+tests/test_gpu_sor_f32.py compares the GPU with these entries bit for bit."""
+import os
+
+import numpy as np
+import pytest
+from conftest import aepe, require_or_skip
+
+HS_KW = dict(alpha=20.0, nscales=3, zfactor=0.5, warps=4, TOL=1e-4, maxiter=150)
+BROX_KW = dict(alpha=50.0, gamma=10.0, nscales=2, nu=0.5, TOL=1e-4, inner=2, outer=3)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
+
+
+def is_f32(a):
+    return same_bits(a, np.asarray(a, np.float64).astype(np.float32).astype(np.float64))
+
+
+def same_solve(a, b):
+    return same_bits(a[0], b[0]) and same_bits(a[1], b[1]) and np.array_equal(np.asarray(a[2]), np.asarray(b[2]))
+
+
+# (set_sor_order, set_sor_wave_levels, tile width): the reference's order, the colour orders, the pipelined schedule, the
+# checkerboard of tiles asked for directly and through the wave levels of order 1
+ORDERS = [(0, 0, 128), (1, 0, 128), (2, 0, 128), (3, 0, 32), (1, 1, 32), (1, 2, 64)]
+
+
+@pytest.mark.parametrize("order,levels,tw", ORDERS)
+def test_mode_off_is_the_existing_entry(orc, synth, order, levels, tw):
+    orc.set_sor_order(order)
+    orc.set_sor_wave_levels(levels)
+    orc.set_sor_tile(tw, 64)
+    for pair, nx, ny in (("P0", 64, 48), ("P1", 75, 53)):
+        I1, I2 = synth.pair(pair, nx, ny)
+        assert same_solve(orc.hs_pyramidal(I1, I2, **HS_KW), orc.hs_pyramidal_mode(I1, I2, store_f32=0, **HS_KW))
+        assert same_solve(orc.brox_spatial(I1, I2, **BROX_KW), orc.brox_spatial_mode(I1, I2, store_f32=0, **BROX_KW))
+        rng = np.random.default_rng(3)
+        u0, v0 = rng.uniform(-2, 2, (ny, nx)), rng.uniform(-2, 2, (ny, nx))
+        assert same_solve(orc.hs_single_scale(I1, I2, u0, v0, alpha=15.0, warps=2),
+                          orc.hs_single_scale_mode(I1, I2, u0, v0, alpha=15.0, warps=2, store_f32=0))
+    for nx, ny, niter in ((64, 48, 50), (33, 21, 7), (5, 4, 3), (2, 2, 1), (40, 30, 0)):
+        a, b = synth.pair("P1", max(nx, 8), max(ny, 8))
+        a, b = np.ascontiguousarray(a[:ny, :nx]), np.ascontiguousarray(b[:ny, :nx])
+        want, got = orc.hs_classic(a, b, niter, 15.0), orc.hs_classic_mode(a, b, niter, 15.0, store_f32=0)
+        assert same_bits(want[0], got[0]) and same_bits(want[1], got[1])
+
+
+@pytest.mark.parametrize("order,levels,tw", ORDERS)
+def test_float_storage_leaves_floats(orc, synth, order, levels, tw):
+    orc.set_sor_order(order)
+    orc.set_sor_wave_levels(levels)
+    orc.set_sor_tile(tw, 64)
+    I1, I2 = synth.pair("P1", 75, 53)
+    rng = np.random.default_rng(3)
+    u0, v0 = rng.uniform(-2, 2, (53, 75)), rng.uniform(-2, 2, (53, 75))          # not floats: the entry rounds them
+    for u, v, it in (orc.hs_pyramidal_mode(I1, I2, store_f32=1, **HS_KW), orc.brox_spatial_mode(I1, I2, store_f32=1, **BROX_KW),
+                     orc.hs_single_scale_mode(I1, I2, u0, v0, alpha=15.0, warps=2, store_f32=1)):
+        assert np.isfinite(u).all() and np.isfinite(v).all() and u.any() and v.any() and np.sum(it) > 0
+        assert is_f32(u) and is_f32(v)
+    u, v = orc.hs_classic_mode(I1 + 0.3, I2 * 1.01, 20, 15.0, store_f32=1)
+    assert u.any() and is_f32(u) and is_f32(v)
+
+
+def test_float_storage_differs_from_double(orc, synth):
+    """the switch does something: a float solve is not the double solve rounded at the end"""
+    I1, I2 = synth.pair("P1", 75, 53)
+    for fn, kw in ((orc.hs_pyramidal_mode, HS_KW), (orc.brox_spatial_mode, BROX_KW)):
+        d, f = fn(I1, I2, store_f32=0, **kw), fn(I1, I2, store_f32=1, **kw)
+        assert not same_bits(f[0], d[0].astype(np.float32).astype(np.float64))
+    d, f = orc.hs_classic_mode(I1, I2, 20, 15.0, store_f32=0), orc.hs_classic_mode(I1, I2, 20, 15.0, store_f32=1)
+    assert not same_bits(f[0], d[0].astype(np.float32).astype(np.float64))
+
+
+@pytest.mark.parametrize("pair,nx,ny", [("P0", 64, 48), ("P1", 75, 53), ("P1", 9, 8), ("P1", 33, 47)])
+def test_float_storage_pipelined_schedule_equals_the_sequential_sweep(orc, synth, pair, nx, ny):
+    I1, I2 = synth.pair(pair, nx, ny)
+    z = np.zeros((ny, nx))
+    res = {}
+    for order in (0, 2):
+        orc.set_sor_order(order)
+        res[order] = [orc.hs_single_scale_mode(I1, I2, z, z, alpha=15.0, warps=3, store_f32=1)]
+        if min(nx, ny) >= 40:
+            res[order] += [orc.hs_pyramidal_mode(I1, I2, store_f32=1, **HS_KW), orc.brox_spatial_mode(I1, I2, store_f32=1, **BROX_KW)]
+        elif min(nx, ny) >= 6:
+            res[order] += [orc.brox_spatial_mode(I1, I2, store_f32=1, **dict(BROX_KW, nscales=1))]
+    for a, b in zip(res[0], res[2]):
+        assert np.sum(a[2]) > 0
+        assert same_solve(a, b)
+
+
+def test_float_hs_stays_in_the_band_of_the_reference_float_build(orc, oracle_mod, synth):
+    """the restated float solve against the double oracle, next to the reference's own float build (ofpix_t = float) against its
+    double build: AEPE < 30 x that drift + 1e-5, the bar of test_f32_mode_is_as_accurate_as_the_reference_own_float_build.
+    Measured: P0 2.2e-7 against a reference drift of 9.9e-7, P1 2.5e-6 against 3.3e-6."""
+    require_or_skip(oracle_mod.have_ref() and os.path.exists(oracle_mod.REF32_SO), "compiled reference (double + float builds) not present")
+    r64, r32 = oracle_mod.Ref(), oracle_mod.Ref32()
+    r64.set_num_threads(1)
+    r32.set_num_threads(1)
+    kw = dict(alpha=20.0, nscales=4, warps=5)
+    for pair in ("P0", "P1"):
+        I0, I1 = synth.pair(pair, 320, 240)
+        u, v = r64.hs_pyramidal(I0, I1, **kw)
+        a, b = r32.hs_pyramidal(I0, I1, **kw)
+        ud, vd, _ = orc.hs_pyramidal(I0, I1, **kw)
+        uf, vf, _ = orc.hs_pyramidal_mode(I0, I1, store_f32=1, **kw)
+        ref_drift, drift = aepe(a, b, u, v), aepe(uf, vf, ud, vd)
+        print("%s: float restatement drifts %.3e, the reference's float build %.3e" % (pair, drift, ref_drift))
+        assert drift < 1e-3 and drift < 30 * ref_drift + 1e-5, (pair, drift, ref_drift)
+
+
+# Brox in float storage against the double oracle, measured with this restatement on the CPU (order 0, nscales / outer below):
+#   (nx, ny, pair): (AEPE, max |delta|)
+BROX_DRIFT = {(160, 120, "P0"): (2.625e-05, 2.130e-03), (160, 120, "P1"): (9.894e-07, 4.412e-04),
+              (135, 68, "P0"): (3.959e-06, 2.178e-04), (135, 68, "P1"): (4.877e-06, 3.579e-03)}
+
+
+@pytest.mark.parametrize("nx,ny,pair", list(BROX_DRIFT))
+def test_float_brox_stays_in_the_band(orc, synth, nx, ny, pair):
+    """the project's bar for float storage (1e-3) and, beside it, 10 x the drift measured on this input: solves that stop
+    unconverged amplify a rounding differently per input, hence the factor"""
+    I1, I2 = synth.pair(pair, nx, ny)
+    kw = dict(nscales=3 if nx == 160 else 2, outer=5)
+    ud, vd, _ = orc.brox_spatial(I1, I2, **kw)
+    uf, vf, _ = orc.brox_spatial_mode(I1, I2, store_f32=1, **kw)
+    drift, worst = aepe(uf, vf, ud, vd), max(float(np.abs(uf - ud).max()), float(np.abs(vf - vd).max()))
+    print("%dx%d %s: AEPE %.3e, max |delta| %.3e" % (nx, ny, pair, drift, worst))
+    assert drift < 1e-3
+    assert drift < 10 * BROX_DRIFT[nx, ny, pair][0], (drift, BROX_DRIFT[nx, ny, pair])
+    assert worst < 10 * BROX_DRIFT[nx, ny, pair][1], (worst, BROX_DRIFT[nx, ny, pair])
