@@ -38,6 +38,7 @@
 #include <chrono>
 #include <cmath>
 #include <thread>
+#include <type_traits>
 
 #define TVL1_GRAD_IS_ZERO 1E-10          // src/tvl1flow.cpp:24
 #define TVL1_PRESMOOTHING_SIGMA 0.8      // src/tvl1flow.cpp:23
@@ -632,9 +633,21 @@ struct Tvl1Ring {
 // Measured and dropped (profiles/r03_q_ab_three_iterations_per_launch.txt): 2 waves per SIMD instead of 3 (same speed: the
 // launch is not bound by resident waves); the pipeline registers in row-indexed rings with a four-step loop body instead of
 // shifting ~50 doubles per step (v_mov_b64 119 -> 57 per step, 210 VGPRs: 1.5 % SLOWER -- VALU issue is not the bound either).
+// That verdict is the three-iteration kernel's while it was bound by memory and lost a wave per SIMD to the ring slots.  With
+// four iterations per launch the kernel is bound by VALU issue and pays for every v_mov_b64: k_tvl1_iter4 now marches its full
+// units in three phases (tvl1_iter3_march, "three phases") and rotates the delay lines by name, inside the 168 VGPRs of 3
+// waves per SIMD.
 #ifndef OFX_ITER3_WAVES
 #define OFX_ITER3_WAVES 3
 #endif
+// The steady-state body of the marching loop is three steps of straight-line code, and left to itself the compiler sinks
+// every computation to its first use: the four dual stages of a step to the step's end, the twelve error terms of a body to
+// the body's end -- with their inputs alive until then (193 VGPRs for a body that needs 160: spills at 3 waves per SIMD), and
+// it turns every row offset and ring index of the three steps into an induction variable of its own.  These empty statements
+// keep a value where the program computes it (a result is "used" at once; an offset is opaque, so derived from ONE counter).
+OFX_DEV void pin_here(double &a) { asm volatile("" : "+v"(a)); }
+OFX_DEV void pin_here(double2 &a, double2 &b) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y)); }
+OFX_DEV void pin_counters(unsigned &off, unsigned &so, unsigned &ri) { asm volatile("" : "+v"(off), "+v"(so), "+s"(ri)); }
 // The marching loop of a launch unit of CNT iterations in the kernel of up to N (3: k_tvl1_iter3, 4: k_tvl1_iter4; the kernel
 // loads rows y0-(N-1) .. yend+(N-1), and stage j of N starts N - j rows above the strip).  CNT = 4 keeps the delay lines of
 // (I1wx, I1wy) and rho_c in `ring` (this lane's column of it); the shorter units keep them in registers.
@@ -678,33 +691,44 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
     const unsigned off0 = off;
 #endif
 
-    auto step = [&](const int y) {
+    // One step of the march: row y enters the pipeline.  G (guarded): every stage tests whether its row exists -- the step of the
+    // short units and of a full unit's fill and drain.  !G: the step of a full unit's steady state, where every stage has a row that
+    // is neither the image's first (but for the last dual stage, which does not look) nor its last: no tests, no defaults for skipped
+    // stages, the rows' boundary flags constants; the next row's loads go out in the middle of the step instead of at its
+    // start (18 VGPRs less in the first stages, and still more than half a step ahead of their use).
+    auto step = [&](const int y, auto steady) {
+        constexpr bool G = !decltype(steady)::value;
         RowIn<T> nxt = cur;
+        auto load_next = [&] {
 #ifdef OFX_CEIL_ALU   // ceiling experiment (tools/ceilings.sh): arithmetic kept, loads alternate between the strip's first two rows
-        if (y + 1 <= ylc) nxt = tvl1_load_row<T>(Uin, P1in, P2in, A, R, off0 + ((y & 1) ? row2 : 0u));
+            nxt = tvl1_load_row<T>(Uin, P1in, P2in, A, R, off0 + ((y & 1) ? row2 : 0u));
 #else
-        if (y + 1 <= ylc) nxt = tvl1_load_row<T>(Uin, P1in, P2in, A, R, off + row2);
+            nxt = tvl1_load_row<T>(Uin, P1in, P2in, A, R, off + row2);
 #endif
+        };
+        if (G && y + 1 <= ylc) load_next();
         unsigned stu = OFX_OOB, stp = OFX_OOB;               // this step's stores: u (one row), p (the row above it)
         double2 su = z2, sp1 = z2, sp2 = z2;
 
         // S1: u_A(y)
-        if (y <= ylc) {
+        if (!G || y <= ylc) {
             const double l11 = wave_shift_up(cur.p1.x);
             const double l21 = wave_shift_up(cur.p2.x);
-            uA0 = tvl1_primal<T, STRICT>(cur.u, cur.a, cur.r, cur.p1, cur.p2, l11, l21, up12, up22, lef, rig, y == 0, y == nyl, l_t,
-                                         theta);
+            uA0 = tvl1_primal<T, STRICT>(cur.u, cur.a, cur.r, cur.p1, cur.p2, l11, l21, up12, up22, lef, rig, G && y == 0,
+                                         G && y == nyl, l_t, theta);
             const bool mine = owner && y >= y0 && y < yend;
             const double dA = (uA0.x - cur.u.x) * (uA0.x - cur.u.x) + (uA0.y - cur.u.y) * (uA0.y - cur.u.y);
             accA += mine ? dA : 0.0;
+            if constexpr (!G) pin_here(accA);
             if (CNT == 1 && mine) { stu = so; su = uA0; }
         }
         // S2: p_A(y-1)
         double2 pAna = z2, pAnb = z2;
-        if (y - 1 >= ys && y - 1 <= hiA) {
+        if (!G || (y - 1 >= ys && y - 1 <= hiA)) {
             const double n1 = wave_shift_down(uA1.x);
             const double n2 = wave_shift_down(uA1.y);
-            tvl1_dual<T, STRICT>(p0a, p0b, uA1, n1, n2, uA0, rig, y - 1 == nyl, taut, pAna, pAnb);
+            tvl1_dual<T, STRICT>(p0a, p0b, uA1, n1, n2, uA0, rig, G && y - 1 == nyl, taut, pAna, pAnb);
+            if constexpr (!G) pin_here(pAna, pAnb);
             pAna.x = rnd_to<T>(pAna.x); pAna.y = rnd_to<T>(pAna.y);
             pAnb.x = rnd_to<T>(pAnb.x); pAnb.y = rnd_to<T>(pAnb.y);
             if (CNT == 1 && owner && y - 1 >= y0 && y - 1 < yend) { stp = so - row2; sp1 = pAna; sp2 = pAnb; }
@@ -719,24 +743,26 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
         double2 pBna = z2, pBnb = z2;
         if (CNT >= 2) {
             // S3: u_B(y-2)
-            if (y - 2 >= yB0 && y - 2 <= hiA) {
+            if (!G || (y - 2 >= yB0 && y - 2 <= hiA)) {
                 double2 ad = a2;
                 double rd = r2c;
                 if constexpr (RING) { ad = ring->a[(ri - 2u) % TVL1_RING_ROWS][lane]; rd = ring->r[(ri - 2u) % TVL1_RING_ROWS][lane]; }
                 const double l11 = wave_shift_up(pA1a.x);
                 const double l21 = wave_shift_up(pA1b.x);
-                uB0 = tvl1_primal<T, STRICT>(uA2, ad, rd, pA1a, pA1b, l11, l21, pA2a.y, pA2b.y, lef, rig, y - 2 == 0, y - 2 == nyl,
-                                             l_t, theta);
+                uB0 = tvl1_primal<T, STRICT>(uA2, ad, rd, pA1a, pA1b, l11, l21, pA2a.y, pA2b.y, lef, rig, G && y - 2 == 0,
+                                             G && y - 2 == nyl, l_t, theta);
                 const bool mine = owner && y - 2 >= y0 && y - 2 < yend;
                 const double dB = (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
                 accB += mine ? dB : 0.0;
+                if constexpr (!G) pin_here(accB);
                 if (CNT == 2 && mine) { stu = so - 2 * row2; su = uB0; }
             }
             // S4: p_B(y-3)
-            if (y - 3 >= yB0 && y - 3 <= hiB) {
+            if (!G || (y - 3 >= yB0 && y - 3 <= hiB)) {
                 const double n1 = wave_shift_down(uB1.x);
                 const double n2 = wave_shift_down(uB1.y);
-                tvl1_dual<T, STRICT>(pA2a, pA2b, uB1, n1, n2, uB0, rig, y - 3 == nyl, taut, pBna, pBnb);
+                tvl1_dual<T, STRICT>(pA2a, pA2b, uB1, n1, n2, uB0, rig, G && y - 3 == nyl, taut, pBna, pBnb);
+                if constexpr (!G) pin_here(pBna, pBnb);
                 pBna.x = rnd_to<T>(pBna.x); pBna.y = rnd_to<T>(pBna.y);
                 pBnb.x = rnd_to<T>(pBnb.x); pBnb.y = rnd_to<T>(pBnb.y);
                 if (CNT == 2 && owner && y - 3 >= y0 && y - 3 < yend) { stp = so - 3 * row2; sp1 = pBna; sp2 = pBnb; }
@@ -744,28 +770,31 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
         }
         double2 pCna = z2, pCnb = z2;
         if (CNT >= 3) {
+            if constexpr (!G) load_next();
             // S5: u_C(y-4)
-            if (y - 4 >= yC0 && y - 4 <= hiB) {
+            if (!G || (y - 4 >= yC0 && y - 4 <= hiB)) {
                 double2 ad = a4;
                 double rd = r4c;
                 if constexpr (RING) { ad = ring->a[(ri - 4u) % TVL1_RING_ROWS][lane]; rd = ring->r[(ri - 4u) % TVL1_RING_ROWS][lane]; }
                 const double l11 = wave_shift_up(pB1a.x);
                 const double l21 = wave_shift_up(pB1b.x);
-                uC0 = tvl1_primal<T, STRICT>(uB2, ad, rd, pB1a, pB1b, l11, l21, pB2a.y, pB2b.y, lef, rig, y - 4 == 0, y - 4 == nyl,
-                                             l_t, theta);
+                uC0 = tvl1_primal<T, STRICT>(uB2, ad, rd, pB1a, pB1b, l11, l21, pB2a.y, pB2b.y, lef, rig, G && y - 4 == 0,
+                                             G && y - 4 == nyl, l_t, theta);
                 const bool mine = owner && y - 4 >= y0 && y - 4 < yend;
                 const double dC = (uC0.x - uB2.x) * (uC0.x - uB2.x) + (uC0.y - uB2.y) * (uC0.y - uB2.y);
                 accC += mine ? dC : 0.0;
+                if constexpr (!G) pin_here(accC);
                 if (CNT == 3) {
                     stu = mine ? so - 4 * row2 : stu;
                     su = uC0;
                 }
             }
             // S6: p_C(y-5)
-            if (y - 5 >= yC0 && y - 5 <= hiC) {
+            if (!G || (y - 5 >= yC0 && y - 5 <= hiC)) {
                 const double n1 = wave_shift_down(uC1.x);
                 const double n2 = wave_shift_down(uC1.y);
-                tvl1_dual<T, STRICT>(pB2a, pB2b, uC1, n1, n2, uC0, rig, y - 5 == nyl, taut, pCna, pCnb);
+                tvl1_dual<T, STRICT>(pB2a, pB2b, uC1, n1, n2, uC0, rig, G && y - 5 == nyl, taut, pCna, pCnb);
+                if constexpr (!G) pin_here(pCna, pCnb);
                 if (CNT == 3) {                              // the unit's last stage: the store rounds
                     sp1 = pCna; sp2 = pCnb;
                     if (owner && y - 5 >= y0) stp = so - 5 * row2;
@@ -777,24 +806,26 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
         }
         if constexpr (CNT == 4) {
             // S7: u_D(y-6)
-            if (y - 6 >= y0 && y - 6 <= hiC) {
+            if (!G || (y - 6 >= y0 && y - 6 <= hiC)) {
                 const double2 ad = ring->a[(ri - 6u) % TVL1_RING_ROWS][lane];
                 const double rd = ring->r[(ri - 6u) % TVL1_RING_ROWS][lane];
                 const double l11 = wave_shift_up(pC1a.x);
                 const double l21 = wave_shift_up(pC1b.x);
-                uD0 = tvl1_primal<T, STRICT>(uC2, ad, rd, pC1a, pC1b, l11, l21, pC2a.y, pC2b.y, lef, rig, y - 6 == 0, y - 6 == nyl,
-                                             l_t, theta);
+                uD0 = tvl1_primal<T, STRICT>(uC2, ad, rd, pC1a, pC1b, l11, l21, pC2a.y, pC2b.y, lef, rig, G && y - 6 == 0,
+                                             G && y - 6 == nyl, l_t, theta);
                 const bool mine = owner && y - 6 < yend;
                 const double dD = (uD0.x - uC2.x) * (uD0.x - uC2.x) + (uD0.y - uC2.y) * (uD0.y - uC2.y);
                 accD += mine ? dD : 0.0;
+                if constexpr (!G) pin_here(accD);
                 stu = mine ? so - 6 * row2 : stu;
                 su = uD0;
             }
             // S8: p_D(y-7)
-            if (y - 7 >= y0 && y - 7 < yend) {
+            if (!G || (y - 7 >= y0 && y - 7 < yend)) {
                 const double n1 = wave_shift_down(uD1.x);
                 const double n2 = wave_shift_down(uD1.y);
-                tvl1_dual<T, STRICT>(pC2a, pC2b, uD1, n1, n2, uD0, rig, y - 7 == nyl, taut, sp1, sp2);
+                tvl1_dual<T, STRICT>(pC2a, pC2b, uD1, n1, n2, uD0, rig, G && y - 7 == nyl, taut, sp1, sp2);
+                if constexpr (!G) pin_here(sp1, sp2);
                 if (owner) stp = so - 7 * row2;
             }
         }
@@ -824,8 +855,37 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
         cur = nxt;
         off += row2;
         so += row2;
+        if constexpr (!G) pin_counters(off, so, ri);
     };
-    for (int y = ys; y <= ylast; y++) step(y);
+    const std::false_type guarded;
+    int y = ys;
+    if constexpr (CNT == 4) {
+        // The full unit of k_tvl1_iter4 marches in three phases: fill (guarded steps until the last stage has its first row:
+        // step y0 + 7, which is past the first row of every earlier stage), steady state, drain (guarded steps from the first
+        // one at which the loads or ANY stage run out of rows).  Interior bands: steps y0 + 7 .. yend + 2; the bottom band stops
+        // at ny - 2, before a stage works on the image's last row.  The steady body is three steps written out: a delay line of
+        // three registers is back in place after three shifts, so the shifts at the end of a step are renamings inside the body
+        // and cost no instruction -- with one step per loop iteration each is a v_mov_b64, 68 per step, a sixth of the VALU
+        // cycles of a kernel that is bound by them.  What is left of the steady range after the last whole body (0 - 2 steps)
+        // goes to the drain.  (k_tvl1_iter3 keeps the one loop: its (I1wx, I1wy) / rho_c lines are in registers, not in LDS,
+        // and the written-out body of its tolerance instantiation needs ten dwords of scratch at 3 waves per SIMD.)
+        const int lo = y0 + 2 * N - 1;
+        int hi = ylc - 1;                                    // the loads of row y + 1 (S1 has row y then)
+        hi = hi < hiA + 1 ? hi : hiA + 1;                    // S2 (S3: hiA + 2)
+        hi = hi < hiB + 3 ? hi : hiB + 3;                    // S4 (S5: hiB + 4)
+        hi = hi < hiC + 5 ? hi : hiC + 5;                    // S6 (S7: hiC + 6, S8: yend + 6)
+        const int nsteady = hi >= lo ? (hi - lo + 1) / 3 * 3 : 0;
+        for (; y < lo && y <= ylast; y++) step(y, guarded);
+        if (nsteady > 0) {
+            const std::true_type steady;
+            for (const int yt = y + nsteady; y < yt; y += 3) {
+                step(y, steady);
+                step(y + 1, steady);
+                step(y + 2, steady);
+            }
+        }
+    }
+    for (; y <= ylast; y++) step(y, guarded);                // the drain of a full unit; the whole march of the others
     loop_accumulate(err, slot0, accA, gw);
     if (CNT >= 2) loop_accumulate(err, slot0 + slot_step, accB, gw);
     if (CNT >= 3) loop_accumulate(err, slot0 + 2 * slot_step, accC, gw);
