@@ -184,7 +184,7 @@ int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
 /* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
  * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
- * _sequence_dev / _triples_group_dev / _triples_dev, and ofx_normalize_frames_dev -- read elements of this kind wherever their
+ * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev and ofx_pyramid_group_dev -- read elements of this kind wherever their
  * comments say "the context's storage precision"; a frame is aligned to its element (OFX_IN_RGB8: to a byte).  Every sample
  * converts exactly to double, so payloads, occlusion maps and iteration / sweep tables are BIT-IDENTICAL to the same call under
  * OFX_IN_STORAGE on planes that hold the same values (stopping values too, up to the order in which the pair solvers' atomics add
@@ -256,6 +256,16 @@ int ofx_getminmax(ofx_ctx *ctx, const double *x, int n, double *min, double *max
 /* dst[q][e] = normalisation of src[q][e] (elements of the context's "input" kind) into the storage type: nsets sets of `per`
  * sources share {min, max} per channel; guard as image_normalization_2 (copy where max - min <= 0); nsets * per <= 32 */
 int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard);
+/* The whole pyramid head of the pyramidal *_dev solvers on its own, for n_pairs = 1..16 pairs in lockstep: per pair
+ * image_normalization_2, the presmoothing gaussian(sigma) and nscales - 1 times zoom_out(zfactor), built by the schedule that the
+ * option "gauss_fused" selects (every schedule gives the same planes).  dI0[g], dI1[g]: the nx x ny device images of pair g, read
+ * exactly as the *_group_dev solvers read them (the context's "input" kind).  dL0[s], dL1[s], s < nscales: level s of all first /
+ * all second images -- n_pairs planes of nxs[s] * nys[s] elements of the storage precision back to back, level 0 being nx x ny and
+ * level s the ofx_zoom_size of level s - 1.  OFX_ERR_ARG for a group size outside 1..16, OFX_ERR_SIGMA where a level is too small
+ * for the Gaussian that is taken on it (kernel radius + 1 >= width or height): a refused call writes nothing.  Asynchronous on the
+ * context's stream. */
+int ofx_pyramid_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1, int nx, int ny, int nscales,
+                          double zfactor, double sigma, void *const *dL0, void *const *dL1);
 
 /* ---- TV-L1 (replace src/tvl1flow.h:36-70) ----------------------------------------------------*/
 /* single scale: u1/u2 are read as the initial flow and overwritten with the result */

@@ -112,6 +112,7 @@ def lib():
         "ofx_image_normalization_1": (_i, [_vp, _dp, _dp, _i]),
         "ofx_getminmax": (_i, [_vp, _dp, _i, C.POINTER(_d), C.POINTER(_d)]),
         "ofx_normalize_frames_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
+        "ofx_pyramid_group_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, C.POINTER(_vp), C.POINTER(_vp)]),
         "ofx_centered_gradient3": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_bicubic_at_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i]),
         "ofx_zoom_out_color": (_i, [_vp, _dp, _dp, _i, _i, _i, _d]),
@@ -499,6 +500,40 @@ class Ofx:
             raise ValueError("normalize_frames_dev: %d sources, %d destinations, sets of %d" % (len(src), len(dst), per))
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_normalize_frames_dev(self.h, len(src) // per, per, arr(src), arr(dst), npix, nz, guard))
+
+    PYRAMID_GUARD, PYRAMID_SENTINEL = 64, -12345.0
+
+    def pyramid_group_dev(self, dI0, dI1, nx, ny, nscales=5, zfactor=0.5, sigma=0.8):
+        """ofx_pyramid_group_dev: dI0, dI1 = device pointers (ints) of the nx x ny images of len(dI0) pairs in the context's "input"
+        kind -> (L0, L1, guards).  L0[s] / L1[s]: level s of all first / second images, a numpy array (pairs, nys[s], nxs[s]) of
+        the storage type.  The level arrays are torch tensors of this call with PYRAMID_GUARD elements of PYRAMID_SENTINEL before
+        and after the planes, filled with it throughout before the call; guards[s, k, 0 | 1] = the elements before | after level
+        s of image k as they are afterwards.  Waits for the result.  A refused call raises OfxError with the same triple in its
+        attribute `outputs` (everything still the sentinel: the library writes nothing then)."""
+        import torch
+        G, gd = len(dI0), self.PYRAMID_GUARD
+        if len(dI1) != G:
+            raise ValueError("pyramid_group_dev: %d first and %d second images" % (G, len(dI1)))
+        sizes = [(nx, ny)]
+        for _ in range(1, nscales):
+            sizes.append(zoom_size(sizes[-1][0], sizes[-1][1], zfactor))
+        dtype = torch.float64 if self.precision == F64 else torch.float32
+        bufs = [[torch.full((2 * gd + G * max(w, 0) * max(h, 0),), self.PYRAMID_SENTINEL, dtype=dtype, device="cuda") for w, h in sizes]
+                for _ in range(2)]
+        torch.cuda.synchronize()
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        lev = [arr([t.data_ptr() + gd * t.element_size() for t in bufs[k]]) for k in range(2)]
+        s = self.L.ofx_pyramid_group_dev(self.h, G, arr(dI0), arr(dI1), nx, ny, nscales, zfactor, sigma, lev[0], lev[1])
+        detail = (self.L.ofx_last_error(self.h) or b"").decode() if s else ""
+        self.synchronize()
+        host = [[t.cpu().numpy() for t in bufs[k]] for k in range(2)]
+        L = [[h[gd:h.size - gd].reshape(G, max(sz[1], 0), max(sz[0], 0)) for h, sz in zip(host[k], sizes)] for k in range(2)]
+        guards = np.array([[[host[k][i][:gd], host[k][i][host[k][i].size - gd:]] for k in range(2)] for i in range(len(sizes))])
+        if s:
+            e = OfxError(s, detail)
+            e.outputs = (L[0], L[1], guards)
+            raise e
+        return L[0], L[1], guards
 
     # ---- TV-L1 ---------------------------------------------------------------------------------
     def tvl1_single_scale(self, I0, I1, u1, u2, tau=0.25, lam=0.15, theta=0.3, warps=5, epsilon=0.01, verbose=0):

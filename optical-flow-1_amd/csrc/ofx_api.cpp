@@ -449,6 +449,54 @@ int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const
                                      : op_normalize_sets_in<float>(ctx, kind, in, out, nsets, per, (size_t) npix, nz, scr, guard);
 }
 
+// the rest of that head on its own: op_build_pyramid_group straight into the caller's level arrays (include/ofx.h)
+int ofx_pyramid_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1, int nx, int ny, int nscales,
+                          double zfactor, double sigma, void *const *dL0, void *const *dL1)
+{
+    OFX_ENTER(ctx);
+    if (!dI0 || !dI1 || !dL0 || !dL1) return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: NULL pointer array");
+    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
+    if (!(sigma > 0)) return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: sigma=%g", sigma);
+    if (nx < 2 || ny < 2 || (long long) 2 * n_pairs * nx * ny > 0x7fffffffLL)
+        return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: %d pairs of %dx%d", n_pairs, nx, ny);
+    std::vector<int> nxs, nys;
+    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
+    // the builder's own refusals (gauss_taps_checked per Gaussian), taken before anything is enqueued: a refused call writes nothing
+    for (int s = 0; s < nscales; s++) {
+        GaussTaps taps;
+        const double sg = s ? 0.6 * sqrt(1.0 / (zfactor * zfactor) - 1.0) : sigma;      // level s is smoothed from level max(s - 1, 0)
+        const int w = nxs[s ? s - 1 : 0], h = nys[s ? s - 1 : 0];
+        if (ofx_gauss_taps(sg, &taps) != OFX_OK)
+            return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: sigma %g needs more than %d taps", sg, OFX_GAUSS_MAX_TAPS);
+        if (taps.size >= w || taps.size >= h)
+            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d, scale %d)", taps.size, w, h, s);
+    }
+    const int kind = ofx_src_kind(ctx);
+    const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
+    for (int g = 0; g < n_pairs; g++)
+        if (!dI0[g] || !dI1[g] || reinterpret_cast<uintptr_t>(dI0[g]) % ofx_src_align(kind) || reinterpret_cast<uintptr_t>(dI1[g]) % ofx_src_align(kind))
+            return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: image of pair %d NULL or misaligned", g);
+    for (int s = 0; s < nscales; s++)
+        if (!dL0[s] || !dL1[s] || reinterpret_cast<uintptr_t>(dL0[s]) % el || reinterpret_cast<uintptr_t>(dL1[s]) % el)
+            return ofx_fail(ctx, OFX_ERR_ARG, "pyramid: level %d NULL or misaligned", s);
+    const size_t full = (size_t) 2 * n_pairs * nx * ny;
+    double *scr;
+    OFX_TRY(ofx_alloc(ctx, (size_t) n_pairs * op_pyramid_scratch_doubles(), &scr));
+    if (ctx->precision == OFX_F64) {
+        double *tmpA, *tmpB;
+        OFX_TRY(ofx_alloc(ctx, full, &tmpA));
+        OFX_TRY(ofx_alloc(ctx, full, &tmpB));
+        return op_build_pyramid_group<double>(ctx, n_pairs, dI0, dI1, nscales, zfactor, sigma, nxs.data(), nys.data(),
+                                              (double *const *) dL0, (double *const *) dL1, tmpA, tmpB, scr, kind);
+    }
+    float *tmpA, *tmpB;
+    OFX_TRY(ofx_alloc(ctx, full, &tmpA));
+    OFX_TRY(ofx_alloc(ctx, full, &tmpB));
+    return op_build_pyramid_group<float>(ctx, n_pairs, dI0, dI1, nscales, zfactor, sigma, nxs.data(), nys.data(),
+                                         (float *const *) dL0, (float *const *) dL1, tmpA, tmpB, scr, kind);
+}
+
 int ofx_image_normalization_2(ofx_ctx *ctx, const double *I1, const double *I2, double *I1n, double *I2n, int size)
 {
     OFX_ENTER(ctx);

@@ -1,8 +1,11 @@
 """GPU parity: every operator of the C ABI against the oracle on the same seeded inputs.
 f64 storage: bit-exact (the kernels keep the reference's IEEE association order, no FMA contraction).
-f32 storage: inputs/outputs rounded to float -> relative tolerance 1e-5 of the data range."""
+f32 storage: inputs/outputs rounded to float -> relative tolerance 1e-5 of the data range at the large size, and at two small
+ones the exact contract: the oracle on the rounded input, rounded wherever the kernels store an element (test_ops_f32_storage_exact)."""
 import numpy as np
 import pytest
+
+import pyramid_head_ref as ph
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +34,33 @@ def test_stencils_bitexact(gpu64, orc, nx, ny):
 def test_gaussian_bitexact(gpu64, orc, nx, ny, sigma):
     a = rnd(3, ny, nx, 50, 100)
     assert np.array_equal(gpu64.gaussian(a, sigma), orc.gaussian(a, sigma))
+
+
+GAUSS_SIGMAS = [0.8, 0.6 * np.sqrt(3.0), 1.7]
+
+
+@pytest.mark.parametrize("sigma", GAUSS_SIGMAS)
+def test_gaussian_bitexact_narrowest_legal_shapes(gpu64, orc, sigma):
+    """size = int(5 sigma) + 1 taps a side need size < nx, ny: at size + 1 every output but one reflects on both borders"""
+    size = int(5 * sigma) + 1
+    for nx, ny in [(size + 1, size + 1), (size + 1, 40), (40, size + 1)]:
+        a = rnd(3, ny, nx, 50, 100)
+        assert np.array_equal(gpu64.gaussian(a, sigma), orc.gaussian(a, sigma)), (nx, ny)
+
+
+@pytest.mark.parametrize("sigma", GAUSS_SIGMAS)
+def test_gaussian_refusal_border(gpu64, gpu32, orc, ofx_mod, sigma):
+    """nx == size or ny == size: status 2 (the reference throws or reads out of bounds there); one more column or row succeeds"""
+    size = int(5 * sigma) + 1
+    for gpu in (gpu64, gpu32):
+        for nx, ny in [(size, 40), (40, size), (size, size)]:
+            with pytest.raises(ofx_mod.OfxError) as e:
+                gpu.gaussian(rnd(3, ny, nx), sigma)
+            assert e.value.status == 2, (nx, ny)
+    for nx, ny in [(size + 1, 40), (40, size + 1)]:
+        a = rnd(3, ny, nx, 50, 100)
+        assert np.array_equal(gpu64.gaussian(a, sigma), orc.gaussian(a, sigma)), (nx, ny)
+        assert np.array_equal(gpu32.gaussian(a, sigma), ph.gaussian(ph.f32(a), sigma, ph.f32)), (nx, ny)
 
 
 def test_gaussian_sigma_too_large(gpu64, ofx_mod):
@@ -79,6 +109,38 @@ def test_ops_f32_storage(gpu32, orc, nx, ny):
     u, v = rnd(5, ny, nx, 3), rnd(6, ny, nx, 3)
     assert np.abs(gpu32.bicubic_warp(a, u, v, True) - orc.bicubic_warp(a, u, v, True)).max() < 5e-3
     assert np.abs(gpu32.zoom_out(a, 0.5) - orc.zoom_out(a, 0.5)).max() < tol
+
+
+@pytest.mark.parametrize("nx,ny", [(47, 33), (65, 25)])
+def test_ops_f32_storage_exact(gpu32, orc, nx, ny):
+    """Float storage holds the planes as float and computes every kernel in double (ldw widens, stn rounds: csrc/ofx_device.h), so
+    an operator of ONE stage is the oracle on the rounded input, rounded once: gpu32.op(x) == f32(orc.op(f32(x))), u and v of a
+    warp rounded as the upload rounds them.  gaussian and zoom_out store intermediates of the storage type -- the row pass
+    (k_gauss_pass_g<T, true> / k_gauss_row_ch_g), the column pass (k_gauss_pass_g<T, false>) and, for zoom_out, the sample
+    (k_resample_ch_g) -- and are the staged restatement of tests/pyramid_head_ref.py with a rounding at each of those stores."""
+    f32 = ph.f32
+    a, b = f32(rnd(1, ny, nx, 50, 100)), f32(rnd(2, ny, nx, 50, 100))
+    raw = rnd(1, ny, nx, 50, 100)                                    # not representable: the upload rounds it
+    assert not np.array_equal(raw, a)
+    assert np.array_equal(gpu32.divergence(raw, b), f32(orc.divergence(a, b)))
+    assert np.array_equal(gpu32.divergence(a, b), f32(orc.divergence(a, b)))
+    for g, o in zip(gpu32.forward_gradient(a), orc.forward_gradient(a)):
+        assert np.array_equal(g, f32(o))
+    for g, o in zip(gpu32.centered_gradient(a), orc.centered_gradient(a)):
+        assert np.array_equal(g, f32(o))
+    assert np.array_equal(gpu32.dxx(a), f32(orc.dxx(a)))
+    assert np.array_equal(gpu32.dyy(a), f32(orc.dyy(a)))
+    assert np.array_equal(gpu32.dxy(a), f32(orc.dxy(a)))
+    u, v = rnd(5, ny, nx, 3), rnd(6, ny, nx, 3)
+    for bo in (True, False):
+        assert np.array_equal(gpu32.bicubic_warp(a, u, v, bo), f32(orc.bicubic_warp(a, f32(u), f32(v), bo)))
+    assert np.array_equal(gpu32.zoom_in(a, 2 * nx - 1, 2 * ny), f32(orc.zoom_in(a, 2 * nx - 1, 2 * ny)))
+    for sigma in GAUSS_SIGMAS:
+        assert np.array_equal(gpu32.gaussian(raw, sigma), ph.gaussian(a, sigma, f32)), sigma
+    for zf in (0.5, 0.7):
+        assert np.array_equal(gpu32.zoom_out(raw, zf), ph.zoom_out(orc, a, zf, f32)), zf
+    # the staging is what makes these exact: one rounding of the oracle's result is a different plane
+    assert not np.array_equal(ph.gaussian(a, 0.8, f32), f32(orc.gaussian(a, 0.8)))
 
 
 def test_colour_sequence_and_minmax_operators(gpu64, orc, ofx_mod):
