@@ -470,6 +470,30 @@ class Oracle(_Lib):
             raise ValueError("GaussianSmooth: sigma too large")
         return u, v, np.array(list(iters)).reshape(nscales, inner * outer)
 
+    def robust_expo_mode(self, I1, I2, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4, inner=1, outer=15,
+                         verbose=0, store_f32=0):
+        """robust_expo in the HIP path's float storage (ofx_oracle.h: what is rounded); store_f32 = 0: robust_expo, bit for bit"""
+        ny, nx = I1.shape
+        u, v = np.zeros((ny, nx)), np.zeros((ny, nx))
+        iters = (C.c_int * (inner * outer * nscales))()
+        rc = self._fn("robust_expo_mode", C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _ip, C.c_int)(
+            _f64(I1), _f64(I2), u, v, nx, ny, method, alpha, gamma, lam, nscales, nu, TOL, inner, outer, verbose, iters, int(store_f32))
+        if rc:
+            raise ValueError("GaussianSmooth: sigma too large")
+        return u, v, np.array(list(iters)).reshape(nscales, inner * outer)
+
+    def rexpo_single_scale_mode(self, I1, I2, u, v, method=1, alpha=50.0, gamma=10.0, lam=1.0, TOL=1e-4, inner=1, outer=15,
+                                verbose=0, store_f32=0):
+        """the level solve of robust_expo from the flow (u, v): no normalisation, no presmoothing, alpha as given"""
+        ny, nx = I1.shape
+        u, v = _f64(u).copy(), _f64(v).copy()
+        iters = (C.c_int * (inner * outer))()
+        self._fn("rexpo_single_scale_mode", None, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                 C.c_double, C.c_int, C.c_int, C.c_int, _ip, C.c_int)(
+            _f64(I1), _f64(I2), u, v, nx, ny, method, alpha, gamma, lam, TOL, inner, outer, verbose, iters, int(store_f32))
+        return u, v, np.array(list(iters)).reshape(1, inner * outer)
+
     def gaussian_dirichlet(self, I, sigma):
         out = _f64(I).copy()
         self._fn("gaussian_dirichlet", None, _dp, C.c_int, C.c_int, C.c_double)(out, I.shape[1], I.shape[0], sigma)

@@ -12,9 +12,10 @@
  * The *_mode entry points restate the HIP path's non-strict modes and are no reference behaviour; each takes its switches as
  * arguments and equals its counterpart bit for bit with all of them 0.  store_f32 = 1 is float storage (OFX_F32): double
  * arithmetic, a value rounded to float exactly where the float instantiation of the kernels holds a float in memory or calls
- * rnd_to / tile_rnd.  For the SOR solvers (Horn-Schunck single scale / pyramidal / classic, Brox spatial) the rounded
- * quantities are listed in ofx_oracle.h -- that list is the contract of the mode (tests/test_oracle_sor_f32.py on the CPU,
- * tests/test_gpu_sor_f32.py against the kernels, bit for bit).
+ * rnd_to / tile_rnd.  For the SOR solvers (Horn-Schunck single scale / pyramidal / classic, Brox spatial, robust_expo on one
+ * channel) the rounded quantities are listed in ofx_oracle.h -- that list is the contract of the mode
+ * (tests/test_oracle_sor_f32.py on the CPU, tests/test_gpu_sor_f32.py and tests/test_gpu_sor_f32_temporal_rexpo.py against the
+ * kernels, bit for bit).  Temporal Brox in float storage is restated in tests/broxt_colour_ref.c, which has both of its sweep orders.
  */
 #include "ofx_oracle.h"
 
@@ -1386,7 +1387,9 @@ int orc_brox_spatial_mode(const double *I1, const double *I2, double *u, double 
 
 /* src/operators.cpp:506-624 with boundary_condition = BOUNDARY_CONDITION_DIRICHLET: samples outside the image are 0 and
  * there is no size check (the padded line always has room) */
-void orc_gaussian_dirichlet(double *I, int nx, int ny, double sigma)
+/* f32 (op_gaussian_planes<float> with dirichlet = 1, csrc/ofx_ops.hip): the row pass is stored into a float plane, the column
+ * pass into the float image */
+static void gaussian_dirichlet(double *I, int nx, int ny, double sigma, int f32)
 {
     double *B;
     const int size = gauss_taps(sigma, &B);
@@ -1397,7 +1400,7 @@ void orc_gaussian_dirichlet(double *I, int nx, int ny, double sigma)
             double sum = B[0] * row[x];
             for (int j = 1; j < size; j++)
                 sum += B[j] * ((x - j >= 0 ? row[x - j] : 0.0) + (x + j < nx ? row[x + j] : 0.0));
-            line[x] = sum;
+            line[x] = ST32(sum);
         }
         memcpy(row, line, (size_t) nx * sizeof(double));
     }
@@ -1406,12 +1409,16 @@ void orc_gaussian_dirichlet(double *I, int nx, int ny, double sigma)
             double sum = B[0] * I[(size_t) y * nx + k];
             for (int j = 1; j < size; j++)
                 sum += B[j] * ((y - j >= 0 ? I[(size_t) (y - j) * nx + k] : 0.0) + (y + j < ny ? I[(size_t) (y + j) * nx + k] : 0.0));
-            line[y] = sum;
+            line[y] = ST32(sum);
         }
         for (int y = 0; y < ny; y++) I[(size_t) y * nx + k] = line[y];
     }
     free(line);
     free(B);
+}
+void orc_gaussian_dirichlet(double *I, int nx, int ny, double sigma)
+{
+    gaussian_dirichlet(I, nx, ny, sigma, 0);
 }
 
 static int rexpo_cmp(const void *a, const void *b)
@@ -1422,13 +1429,16 @@ static int rexpo_cmp(const void *a, const void *b)
 
 /* src/robust_expo_smoothness.cpp:128-187 (nz = 1): expo = exp(-lambda |grad I1|) (+ BETA for method 2); method 3 picks lambda
  * per pixel, bounded by the value at the TAU quantile of the sorted gradients */
-void orc_rexpo_exponential(const double *Ix, const double *Iy, int n, double alpha, double lambda, int method, double *expo)
+/* f32 (k_rexpo_maxgrad + rexpo_pair_expo<float>, csrc/ofx_sor.hip): Ix, Iy hold floats; the magnitudes are doubles (L.Mg), the
+ * sort, the quantile and every lambda run on them as they are; only the weight is stored as a float */
+static void rexpo_exponential(const double *Ix, const double *Iy, int n, double alpha, double lambda, int method, double *expo,
+                              int f32)
 {
     double *mg = dalloc((size_t) n);
     for (int i = 0; i < n; i++) mg[i] = sqrt(Ix[i] * Ix[i] + Iy[i] * Iy[i]);                       /* max_gradients, one channel */
     if (method == 1 || method == 2) {
         const double beta = method == 2 ? REXPO_BETA : 0;
-        for (int i = 0; i < n; i++) expo[i] = exp(-lambda * mg[i]) + beta;
+        for (int i = 0; i < n; i++) expo[i] = ST32(exp(-lambda * mg[i]) + beta);
     } else if (method == 3) {
         double *lp = dalloc((size_t) n), *ord = dalloc((size_t) n);
         for (int i = 0; i < n; i++) lp[i] = (-log(REXPO_XI) + log(alpha)) / mg[i];
@@ -1443,11 +1453,15 @@ void orc_rexpo_exponential(const double *Ix, const double *Iy, int n, double alp
         for (int i = 0; i < n; i++) {
             double lambda_pi = lambda_omega;
             if (lambda_omega > lp[i]) lambda_pi = lp[i];
-            expo[i] = exp(-lambda_pi * mg[i]);
+            expo[i] = ST32(exp(-lambda_pi * mg[i]));
         }
         free(lp); free(ord);
     }
     free(mg);
+}
+void orc_rexpo_exponential(const double *Ix, const double *Iy, int n, double alpha, double lambda, int method, double *expo)
+{
+    rexpo_exponential(Ix, Iy, n, alpha, lambda, method, expo, 0);
 }
 
 /* generic_tensor.cpp:97-168: existing terms in the order right, left, down, up */
@@ -1465,7 +1479,7 @@ static inline double rexpo_div_at(const double *f, const double *pr, const doubl
 }
 
 /* methods.cpp:111-154; psi1..4 = right, left, down, up */
-static inline double rexpo_sor_point(const double *Au, const double *Av, const double *Du, const double *Dv, const double *D,
+static inline double rexpo_sor_point(int f32, const double *Au, const double *Av, const double *Du, const double *Dv, const double *D,
                                      double *du, double *dv, double alpha, const double *psi1, const double *psi2,
                                      const double *psi3, const double *psi4, int i, int i0, int i1, int j, int nx, int j0, int j1)
 {
@@ -1474,15 +1488,17 @@ static inline double rexpo_sor_point(const double *Au, const double *Av, const d
     const double div_du = psi1[k] * du[k + j1] + psi2[k] * du[k - j0] + psi3[k] * du[k + i1] + psi4[k] * du[k - i0];
     const double div_dv = psi1[k] * dv[k + j1] + psi2[k] * dv[k - j0] + psi3[k] * dv[k + i1] + psi4[k] * dv[k - i0];
     const double duk = du[k], dvk = dv[k];
-    du[k] = (1. - w) * du[k] + w * (Au[k] - D[k] * dv[k] + alpha * div_du) / Du[k];
-    dv[k] = (1. - w) * dv[k] + w * (Av[k] - D[k] * du[k] + alpha * div_dv) / Dv[k];
+    du[k] = ST32((1. - w) * du[k] + w * (Au[k] - D[k] * dv[k] + alpha * div_du) / Du[k]);
+    dv[k] = ST32((1. - w) * dv[k] + w * (Av[k] - D[k] * du[k] + alpha * div_dv) / Dv[k]);
     return (du[k] - duk) * (du[k] - duk) + (dv[k] - dvk) * (dv[k] - dvk);
 }
 
-/* methods.cpp:161-455, one channel, one thread (the reference's interior loop is a racy omp parallel for like Brox's) */
+/* methods.cpp:161-455, one channel, one thread (the reference's interior loop is a racy omp parallel for like Brox's).
+ * f32 (brox_single_scale_dev<float> with P.robust, csrc/ofx_sor.hip): I1, I2, u, v hold floats; what is rounded is listed in
+ * ofx_oracle.h */
 static void rexpo_single_scale(const double *I1, const double *I2, double *u, double *v, int nx, int ny, int method,
                                double alpha, double gamma, double lambda, double TOL, int inner_iter, int outer_iter,
-                               int verbose, int *iters)
+                               int verbose, int *iters, int f32)
 {
     const int size = nx * ny;
     const size_t n = (size_t) size;
@@ -1502,7 +1518,9 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
     orc_dxx(I2, I2xx, nx, ny);                                 /* :225-227 */
     orc_dyy(I2, I2yy, nx, ny);
     orc_dxy(I2, I2xy, nx, ny);
-    orc_rexpo_exponential(I1x, I1y, size, alpha, lambda, method, expo);     /* :231 */
+    if (f32) for (int q = 6; q <= 9; q++) round_f32(a[q], n);       /* k_rexpo_prepare_c: I1x, I1y, I2x, I2y */
+    if (f32) for (int q = 13; q <= 15; q++) round_f32(a[q], n);     /* I2xx, I2yy, I2xy */
+    rexpo_exponential(I1x, I1y, size, alpha, lambda, method, expo, f32);    /* :231 */
 
     for (int no = 0; no < outer_iter; no++) {                  /* :234 */
         orc_bicubic_warp(I2,   u, v, I2w,   nx, ny, 1);        /* :236-241 (bicubic_interpolation_warp_color, nz = 1) */
@@ -1511,13 +1529,15 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
         orc_bicubic_warp(I2xx, u, v, I2wxx, nx, ny, 1);
         orc_bicubic_warp(I2xy, u, v, I2wxy, nx, ny, 1);
         orc_bicubic_warp(I2yy, u, v, I2wyy, nx, ny, 1);
+        if (f32) for (int q = 10; q <= 12; q++) round_f32(a[q], n);     /* k_rexpo_warp_c: I2w, I2wx, I2wy */
+        if (f32) for (int q = 16; q <= 18; q++) round_f32(a[q], n);     /* I2wxx, I2wyy, I2wxy */
         orc_centered_gradient(u, ux, uy, nx, ny);              /* :244-245 */
         orc_centered_gradient(v, vx, vy, nx, ny);
         for (int i = 0; i < size; i++) {                       /* robust_expo_psi_smooth, smoothness.cpp:36-43 */
             const double gu = expo[i] * ux[i] * ux[i] + expo[i] * uy[i] * uy[i];
             const double gv = expo[i] * vx[i] * vx[i] + expo[i] * vy[i] * vy[i];
             const double normFlow = gu + gv;
-            psis[i] = expo[i] / sqrt(normFlow + REXPO_EPSILON * REXPO_EPSILON);
+            psis[i] = ST32(expo[i] / sqrt(normFlow + REXPO_EPSILON * REXPO_EPSILON));
         }
         for (int i = 0; i < ny; i++)                           /* robust_expo_psi_divergence */
             for (int j = 0; j < nx; j++) {
@@ -1529,11 +1549,11 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
             }
         for (int i = 0; i < ny; i++)                           /* robust_expo_divergence of u and of v, :257-258 */
             for (int j = 0; j < nx; j++) {
-                div_u[i * nx + j] = rexpo_div_at(u, psi1, psi2, psi3, psi4, i, j, nx, ny);
-                div_v[i * nx + j] = rexpo_div_at(v, psi1, psi2, psi3, psi4, i, j, nx, ny);
+                div_u[i * nx + j] = ST32(rexpo_div_at(u, psi1, psi2, psi3, psi4, i, j, nx, ny));
+                div_v[i * nx + j] = ST32(rexpo_div_at(v, psi1, psi2, psi3, psi4, i, j, nx, ny));
             }
         for (int i = 0; i < size; i++) {                       /* :261-267 */
-            div_d[i] = alpha * (psi1[i] + psi2[i] + psi3[i] + psi4[i]);
+            div_d[i] = ST32(alpha * (psi1[i] + psi2[i] + psi3[i] + psi4[i]));
             du[i] = dv[i] = 0;
         }
         for (int ni = 0; ni < inner_iter; ni++) {              /* :270 */
@@ -1541,14 +1561,14 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
                 double dI2 = 0;
                 const double dI = I2w[i] + I2wx[i] * du[i] + I2wy[i] * dv[i] - I1[i];
                 dI2 += dI * dI;
-                psid[i] = (1. / sqrt(dI2 + REXPO_EPSILON * REXPO_EPSILON));
+                psid[i] = ST32(1. / sqrt(dI2 + REXPO_EPSILON * REXPO_EPSILON));
             }
             for (int i = 0; i < size; i++) {                   /* psi_gradient :85-102 */
                 double dI2 = 0;
                 const double dIx = I2wx[i] + I2wxx[i] * du[i] + I2wxy[i] * dv[i] - I1x[i];
                 const double dIy = I2wy[i] + I2wxy[i] * du[i] + I2wyy[i] * dv[i] - I1y[i];
                 dI2 += dIx * dIx + dIy * dIy;
-                psig[i] = (1. / sqrt(dI2 + REXPO_EPSILON * REXPO_EPSILON));
+                psig[i] = ST32(1. / sqrt(dI2 + REXPO_EPSILON * REXPO_EPSILON));
             }
             for (int i = 0; i < size; i++) {                   /* :279-322 */
                 double BNu = 0, BNv = 0, BDu = 0, BDv = 0, GNu = 0, GNv = 0, GDu = 0, GDv = 0, DI_Gradient = 0, DI_Data = 0;
@@ -1574,11 +1594,11 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
                 GNv = -g * GNv;
                 GDu = g * GDu;
                 GDv = g * GDv;
-                Au[i] = BNu + GNu + alpha * div_u[i];
-                Av[i] = BNv + GNv + alpha * div_v[i];
-                Du[i] = BDu + GDu + div_d[i];
-                Dv[i] = BDv + GDv + div_d[i];
-                D[i] = psid[i] * DI_Data + g * DI_Gradient;
+                Au[i] = ST32(BNu + GNu + alpha * div_u[i]);
+                Av[i] = ST32(BNv + GNv + alpha * div_v[i]);
+                Du[i] = ST32(BDu + GDu + div_d[i]);
+                Dv[i] = ST32(BDv + GDv + div_d[i]);
+                D[i] = ST32(psid[i] * DI_Data + g * DI_Gradient);
             }
             double error = 1000;
             int nsor = 0;
@@ -1587,34 +1607,55 @@ static void rexpo_single_scale(const double *I1, const double *I2, double *u, do
                 nsor++;
                 for (int i = 1; i < ny - 1; i++)
                     for (int j = 1; j < nx - 1; j++)
-                        error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, j, nx, 1, 1);
+                        error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, j, nx, 1, 1);
                 for (int j = 1; j < nx - 1; j++) {
-                    error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, j, nx, 1, 1);
-                    error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, j, nx, 1, 1);
+                    error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, j, nx, 1, 1);
+                    error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, j, nx, 1, 1);
                 }
                 for (int i = 1; i < ny - 1; i++) {
-                    error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, 0, nx, 0, 1);
-                    error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, nx - 1, nx, 1, 0);
+                    error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, 0, nx, 0, 1);
+                    error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, i, nx, nx, nx - 1, nx, 1, 0);
                 }
-                error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, 0, nx, 0, 1);
-                error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, nx - 1, nx, 1, 0);
-                error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, 0, nx, 0, 1);
-                error += rexpo_sor_point(Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, nx - 1, nx, 1, 0);
+                error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, 0, nx, 0, 1);
+                error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, 0, 0, nx, nx - 1, nx, 1, 0);
+                error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, 0, nx, 0, 1);
+                error += rexpo_sor_point(f32, Au, Av, Du, Dv, D, du, dv, alpha, psi1, psi2, psi3, psi4, ny - 1, nx, 0, nx - 1, nx, 1, 0);
                 error = sqrt(error / size);                    /* :411 (size = pixels x channels) */
             }
             if (verbose) printf("Iterations: %d Error: %g\n", nsor, error);
             if (iters) iters[solve] = nsor;
             solve++;
         }
-        for (int i = 0; i < size; i++) { u[i] += du[i]; v[i] += dv[i]; }   /* :419-422 */
+        for (int i = 0; i < size; i++) { u[i] = ST32(u[i] + du[i]); v[i] = ST32(v[i] + dv[i]); }   /* :419-422 */
     }
     for (int q = 0; q < NARR; q++) free(a[q]);
 }
 
 /* methods.cpp:463-567 with nzz = 1.  `iters` is laid out [scale][outer*inner].  Returns 1 where zoom_out's Gaussian throws. */
-int orc_robust_expo(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
-                    double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter, int verbose,
-                    int *iters)
+/* store_f32: the level solve of ofx_robust_expo_single_scale -- the images and the incoming flow are rounded to float first (they
+ * are uploaded into float planes); alpha as given */
+void orc_rexpo_single_scale_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny, int method, double alpha,
+                                 double gamma, double lambda, double TOL, int inner_iter, int outer_iter, int verbose, int *iters,
+                                 int store_f32)
+{
+    if (!store_f32) {
+        rexpo_single_scale(I1, I2, u, v, nx, ny, method, alpha, gamma, lambda, TOL, inner_iter, outer_iter, verbose, iters, 0);
+        return;
+    }
+    const size_t n = (size_t) nx * ny;
+    double *A = dalloc(n), *B = dalloc(n);
+    for (size_t i = 0; i < n; i++) { A[i] = rnd_f32(I1[i]); B[i] = rnd_f32(I2[i]); }
+    round_f32(u, n);
+    round_f32(v, n);
+    rexpo_single_scale(A, B, u, v, nx, ny, method, alpha, gamma, lambda, TOL, inner_iter, outer_iter, verbose, iters, 1);
+    free(A); free(B);
+}
+
+/* f32: ofx_robust_expo with one channel (rexpo_pyramid_host<float, float>) -- the images are uploaded into float planes BEFORE the
+ * normalisation, the normalised images are stored as floats */
+static int robust_expo(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
+                       double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter, int verbose,
+                       int *iters, int f32)
 {
     const int nzz = 1;
     pyramid P;
@@ -1630,15 +1671,24 @@ int orc_robust_expo(const double *I1, const double *I2, double *u, double *v, in
     P.B[0] = dalloc((size_t) nxx * nyy);
     P.u[0] = u; P.v[0] = v;
     int rc = 0;
-    orc_image_normalization_2_color(I1, I2, P.A[0], P.B[0], nxx * nyy * nzz, nzz);     /* :494 */
-    orc_gaussian_dirichlet(P.A[0], nxx, nyy, (double) nzz);                              /* :497-498: sigma = nzz, bc = (int) 0.8 */
-    orc_gaussian_dirichlet(P.B[0], nxx, nyy, (double) nzz);
+    if (f32) {
+        const size_t n0 = (size_t) nxx * nyy;
+        double *a = dalloc(n0), *b = dalloc(n0);
+        for (size_t i = 0; i < n0; i++) { a[i] = rnd_f32(I1[i]); b[i] = rnd_f32(I2[i]); }
+        orc_image_normalization_2_color(a, b, P.A[0], P.B[0], nxx * nyy * nzz, nzz);
+        round_f32(P.A[0], n0);
+        round_f32(P.B[0], n0);
+        free(a); free(b);
+    } else
+        orc_image_normalization_2_color(I1, I2, P.A[0], P.B[0], nxx * nyy * nzz, nzz);     /* :494 */
+    gaussian_dirichlet(P.A[0], nxx, nyy, (double) nzz, f32);                             /* :497-498: sigma = nzz, bc = (int) 0.8 */
+    gaussian_dirichlet(P.B[0], nxx, nyy, (double) nzz, f32);
     for (int s = 1; s < nscales && !rc; s++) {
         orc_zoom_size(P.nx[s - 1], P.ny[s - 1], &P.nx[s], &P.ny[s], nu);
         const size_t n = (size_t) P.nx[s] * P.ny[s];
         P.A[s] = dalloc(n); P.B[s] = dalloc(n); P.u[s] = dalloc(n); P.v[s] = dalloc(n);
-        rc |= orc_zoom_out(P.A[s - 1], P.A[s], P.nx[s - 1], P.ny[s - 1], nu);           /* zoom_out_color, nz = 1 */
-        rc |= orc_zoom_out(P.B[s - 1], P.B[s], P.nx[s - 1], P.ny[s - 1], nu);
+        rc |= zoom_out(P.A[s - 1], P.A[s], P.nx[s - 1], P.ny[s - 1], nu, f32);          /* zoom_out_color, nz = 1 */
+        rc |= zoom_out(P.B[s - 1], P.B[s], P.nx[s - 1], P.ny[s - 1], nu, f32);
     }
     if (!rc) {
         const int c = nscales - 1;
@@ -1648,11 +1698,24 @@ int orc_robust_expo(const double *I1, const double *I2, double *u, double *v, in
     for (int s = nscales - 1; s >= 0 && !rc; s--) {
         if (verbose) printf("Scale: %d\n", s);
         rexpo_single_scale(P.A[s], P.B[s], P.u[s], P.v[s], P.nx[s], P.ny[s], method, alpha_adapted_for_nchannels, gamma, lambda,
-                           TOL, inner_iter, outer_iter, verbose, iters ? iters + s * inner_iter * outer_iter : NULL);
-        if (s) pyramid_upsample(&P, s, nu, 0);
+                           TOL, inner_iter, outer_iter, verbose, iters ? iters + s * inner_iter * outer_iter : NULL, f32);
+        if (s) pyramid_upsample(&P, s, nu, f32);
     }
     pyramid_free(&P);
     return rc;
+}
+int orc_robust_expo(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
+                    double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter, int verbose,
+                    int *iters)
+{
+    return robust_expo(I1, I2, u, v, nxx, nyy, method, alpha, gamma, lambda, nscales, nu, TOL, inner_iter, outer_iter, verbose, iters, 0);
+}
+int orc_robust_expo_mode(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
+                         double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter, int verbose,
+                         int *iters, int store_f32)
+{
+    return robust_expo(I1, I2, u, v, nxx, nyy, method, alpha, gamma, lambda, nscales, nu, TOL, inner_iter, outer_iter, verbose, iters,
+                       store_f32);
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -139,6 +139,39 @@ void orc_rexpo_exponential(const double *Ix, const double *Iy, int n, double alp
 int  orc_robust_expo(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
                      double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter, int verbose,
                      int *iters);
+/* robust_expo, one channel, in the HIP path's float storage; store_f32 = 0: orc_robust_expo bit for bit.  The restatement follows
+ * ofx_robust_expo (rexpo_pyramid_host<float, float>), which uploads a one-channel image into a float plane BEFORE the
+ * normalisation; ofx_robust_expo_pyramid and the device entries round after it and equal it on float-representable images.
+ * orc_rexpo_single_scale_mode is the level solve alone (ofx_robust_expo_single_scale): the images as they come, (u, v) the
+ * starting flow, alpha as given (no truncation to an int).
+ * THE CONTRACT OF THE MODE -- rounded are (each a store of a T in csrc/ofx_sor.hip / ofx_ops.hip):
+ *   head          the input images (upload_plane); the normalised images (op_normalize_sets); the Dirichlet Gaussian's row pass
+ *                 and its column pass (k_gauss_pass_g with dirichlet = 1: tmp, then the image); the zoom-out as
+ *                 orc_zoom_out_mode; the flow zoomed in and multiplied by 1 / nu (one rounding, after the product);
+ *                 single-scale entry: I1, I2 (upload_plane) and the incoming u, v (op_interleave2);
+ *   level         I1x, I1y, I2x, I2y, I2xx, I2xy, I2yy (k_rexpo_prepare_c: G1, PA, PB); expo (rexpo_pair_expo: (T) (exp(..) + beta),
+ *                 (T) exp(..)); the six warps I2w .. I2wyy (k_rexpo_warp_c: WA, WB); psis (k_brox_psis with Expo); div_u, div_v,
+ *                 div_d (k_brox_div, rx: DV, Dd); psid, psig (rnd_to in k_rexpo_coeff_c); Au, Av, Du, Dv, D (CO, Dm); du and dv
+ *                 after every update (rnd_to in brox_point_finish); u and v after du, dv are added (k_brox_add).
+ *   NOT rounded   the gradient magnitudes sqrt(I1x^2 + I1y^2) of the ROUNDED I1x, I1y (k_rexpo_maxgrad writes doubles, L.Mg):
+ *                 method 3 sorts them, takes its quantile and every per-pixel lambda from them as doubles; psi1 .. psi4
+ *                 (half-sums recomputed in double from psis); the per-pixel sums of k_rexpo_coeff_c before psid / psig multiply.
+ * The stopping sums add the squared differences of the rounded values, in double. */
+int  orc_robust_expo_mode(const double *I1, const double *I2, double *u, double *v, int nxx, int nyy, int method, double alpha,
+                          double gamma, double lambda, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
+                          int verbose, int *iters, int store_f32);
+void orc_rexpo_single_scale_mode(const double *I1, const double *I2, double *u, double *v, int nx, int ny, int method, double alpha,
+                                 double gamma, double lambda, double TOL, int inner_iter, int outer_iter, int verbose, int *iters,
+                                 int store_f32);
+
+/* Temporal Brox in float storage is restated in tests/broxt_colour_ref.c (both sweep orders; broxt_colour_ref_mode), whose header
+ * lists what is rounded; orc_brox_temporal below stays the double solve in the reference's order.
+ * THE CONTRACT OF THE MODE there -- rounded are: the input frames; the normalised frames (one min / max per sequence); the Gaussian and
+ * the zoom-out as orc_gaussian_mode / orc_zoom_out_mode; the zoomed-in flow times 1 / nu (one rounding); Ix, Iy of every frame, Ixx,
+ * Ixy, Iyy of frames 1 .. (k_brox_prepare); the six warps (k_brox_warp); psis (k_broxt_psis); div_u, div_v, div_d (k_broxt_div);
+ * psid, psig (rnd_to in brox_coeff_px); Au, Av, Du, Dv, D (CO, Dm); du, dv after every update (rnd_to in broxt_point, tile_rnd in
+ * bxt_update of k_broxt_rb / k_broxt_tile); u, v after du, dv are added (k_brox_add).  NOT rounded: psi1 .. psi6 (half-sums recomputed in
+ * double from psis, broxt_psi6), ux .. vt of the flow. */
 
 /* brox_optic_flow_temporal.cpp + brox_temporal_mask.cpp (+ operators.cpp centered_gradient3, utils.cpp
  * image_normalization_1) */

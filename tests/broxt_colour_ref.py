@@ -39,17 +39,26 @@ def lib(oracle_mod):
         _lib.broxt_colour_ref.restype = C.c_int
         _lib.broxt_colour_ref.argtypes = [dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
                                           C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        _lib.broxt_colour_ref_mode.restype = C.c_int
+        _lib.broxt_colour_ref_mode.argtypes = [dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                               C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     return _lib
 
 
-def brox_temporal(oracle_mod, I, order, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15):
+def brox_temporal(oracle_mod, I, order, alpha=18.0, gamma=7.0, nscales=10, nu=0.75, TOL=1e-4, inner=1, outer=15, store_f32=None):
     """I: (frames, ny, nx).  Returns u, v of shape (frames - 1, ny, nx) and the sweep counts [scale][solve], as Oracle.brox_temporal.
-    The oracle's thread count must be 1 (the `orc` fixture sets it): the operators are liboracle.so's."""
+    The oracle's thread count must be 1 (the `orc` fixture sets it): the operators are liboracle.so's.
+    store_f32: None = the entry without the switch (broxt_colour_ref); 0 / 1 = broxt_colour_ref_mode in double / float storage
+    (the header of broxt_colour_ref.c lists what float storage rounds)."""
     frames, ny, nx = I.shape
     u, v = np.zeros((frames - 1, ny, nx)), np.zeros((frames - 1, ny, nx))
     iters = (C.c_int * (inner * outer * nscales))()
-    rc = lib(oracle_mod).broxt_colour_ref(np.ascontiguousarray(I, dtype=np.float64), u, v, nx, ny, frames, alpha, gamma, nscales, nu, TOL,
-                                          inner, outer, order, iters)
+    I = np.ascontiguousarray(I, dtype=np.float64)
+    if store_f32 is None:
+        rc = lib(oracle_mod).broxt_colour_ref(I, u, v, nx, ny, frames, alpha, gamma, nscales, nu, TOL, inner, outer, order, iters)
+    else:
+        rc = lib(oracle_mod).broxt_colour_ref_mode(I, u, v, nx, ny, frames, alpha, gamma, nscales, nu, TOL, inner, outer, order,
+                                                   int(store_f32), iters)
     if rc == 1:
         raise ValueError("GaussianSmooth: sigma too large")
     if rc:

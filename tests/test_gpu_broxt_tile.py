@@ -99,7 +99,10 @@ def test_loop_ends(tol, gpu64, oracle_mod, orc, synth, K):
 
 
 def test_float_storage(tol, gpu32, orc, synth):
-    """float storage through the same kernels: as close to the double reference as the exact mode's float storage (1e-3)"""
+    """float storage through the same kernels: as close to the double reference as the exact mode's float storage (1e-3).  This
+    is the coarse guard only -- a temporal weight taken from the wrong field in the float instantiation stays under it.  What the
+    right float answer is, bit for bit, is pinned by tests/test_gpu_sor_f32_temporal_rexpo.py against tests/broxt_colour_ref.c
+    with store_f32 = 1; on this input that restatement drifts 1.0e-5 from the double checker (tests/test_broxt_colour_ref.py)."""
     I = synth.sequence(160, 120, 4)
     uo, vo, _ = orc.brox_temporal(I, nscales=3)
     ug, vg = gpu32.brox_temporal(I, nscales=3)
