@@ -174,6 +174,9 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *   "rows_per_wave", "rows_per_wave2", "chunk"   tuning of the TV-L1 kernels / launch batching
  *   "input"          element type of the FRAMES that the *_dev entries read (OFX_IN_* below; default OFX_IN_STORAGE); any other
  *                         value is OFX_ERR_ARG
+ *   "input_pitch"    bytes from the start of one row of a FRAME that the *_dev entries read to the start of the next (default 0 =
+ *                         dense: the rows lie back to back).  One pitch per call, for all its frames; see option "input" below.  A
+ *                         negative, fractional or >= 2^31 value is OFX_ERR_ARG and leaves the option as it was.
  *   "input_vec"      1/0  the byte kinds of "input" through the kernels that load a run of four elements per lane as aligned
  *                         32-bit words (default 1); 0 = one element per thread (A/B).  Results do not depend on it.
  *   "input_lut"      1/0  ... and the 8-bit kinds take 255 (x - min) / (max - min) from a per-workgroup table of its 256 possible
@@ -184,13 +187,27 @@ int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
 /* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
  * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
- * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev and ofx_pyramid_group_dev -- read elements of this kind wherever their
+ * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev and ofx_pyramid_group_dev -- read
+ * elements of this kind wherever their
  * comments say "the context's storage precision"; a frame is aligned to its element (OFX_IN_RGB8: to a byte).  Every sample
  * converts exactly to double, so payloads, occlusion maps and iteration / sweep tables are BIT-IDENTICAL to the same call under
  * OFX_IN_STORAGE on planes that hold the same values (stopping values too, up to the order in which the pair solvers' atomics add
  * them, which no two runs of one call share).  Entries that take host planes ignore the option; entries
- * that take several contexts want the same value on all of them (OFX_ERR_ARG otherwise, before any work).  Frames are dense:
- * element (or pixel) e of a frame is at e times the element size, there is no row pitch -- a pitched surface is not supported.
+ * that take several contexts want the same value on all of them (OFX_ERR_ARG otherwise, before any work).
+ * Option "input_pitch": the row pitch of those frames, for the same entries and every kind, OFX_IN_STORAGE included.  A frame
+ * is ny rows of nx * nz elements (OFX_IN_RGB8: of nx pixels of three bytes; the interleaved colour images of
+ * ofx_robust_expo_group_dev / _batch_dev: of nxx * nzz elements); 0, the default, means dense -- element (or pixel) e of a frame
+ * at e times the element size -- and otherwise row i starts pitch * i bytes after the frame pointer, as in a decoder's surface,
+ * a crop of a larger image or a torch slice video[:, y0:y1, x0:x1].  A region of interest needs nothing else: pass the address of
+ * its first element and its parent's pitch.  No byte outside the rows is read, neither the padding between them nor any after
+ * the last row's end, and the results are BIT-IDENTICAL to the same call on dense copies of the rows.  A pitch equal to the row's
+ * bytes is the dense layout.  A non-zero pitch below the row's bytes, or not a multiple of the element's alignment (8 for double, 4
+ * for float, 2 for OFX_IN_U16, 1 for OFX_IN_U8 and OFX_IN_RGB8), is OFX_ERR_ARG before any work, nothing written (ofx_last_error
+ * names the pitch and the row's bytes); the frame pointer stays aligned to its element.  One pitch serves all frames of a call;
+ * host-plane entries ignore it, entries that take several contexts want the same value on all of them, and
+ * ofx_normalize_frames_dev, which has no row length, is OFX_ERR_ARG while it is non-zero (ofx_normalize_frames2d_dev takes
+ * one).  ofx_tvl1_batch_dev stages a frame that is not on its context's device as it lies, (ny - 1) * pitch + the row's bytes.
+ * Payloads and maps are written dense; a pitched frame has fewer than 2^31 - 1024 rows.
  * ofx_robust_expo_group_dev / _batch_dev with nzz > 1 keep their channels interleaved (an HWC uint8 image is that layout as it
  * stands); OFX_IN_RGB8 there is OFX_ERR_ARG unless nzz == 1. */
 #define OFX_IN_STORAGE 0   /* the context's storage precision (double | float): the default                                    */
@@ -256,6 +273,10 @@ int ofx_getminmax(ofx_ctx *ctx, const double *x, int n, double *min, double *max
 /* dst[q][e] = normalisation of src[q][e] (elements of the context's "input" kind) into the storage type: nsets sets of `per`
  * sources share {min, max} per channel; guard as image_normalization_2 (copy where max - min <= 0); nsets * per <= 32 */
 int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard);
+/* ... on frames of ny rows of nx * nz elements (OFX_IN_RGB8: nx pixels), read under the options "input" and "input_pitch"; dst[q]
+ * is dense, nx * ny * nz elements.  With "input_pitch" = 0 it is ofx_normalize_frames_dev with npix = nx * ny, bit for bit; the
+ * same limits and errors, and those of the pitch (option "input" above). */
+int ofx_normalize_frames2d_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int nx, int ny, int nz, int guard);
 /* The whole pyramid head of the pyramidal *_dev solvers on its own, for n_pairs = 1..16 pairs in lockstep: per pair
  * image_normalization_2, the presmoothing gaussian(sigma) and nscales - 1 times zoom_out(zfactor), built by the schedule that the
  * option "gauss_fused" selects (every schedule gives the same planes).  dI0[g], dI1[g]: the nx x ny device images of pair g, read

@@ -112,6 +112,7 @@ def lib():
         "ofx_image_normalization_1": (_i, [_vp, _dp, _dp, _i]),
         "ofx_getminmax": (_i, [_vp, _dp, _i, C.POINTER(_d), C.POINTER(_d)]),
         "ofx_normalize_frames_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
+        "ofx_normalize_frames2d_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i]),
         "ofx_pyramid_group_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, C.POINTER(_vp), C.POINTER(_vp)]),
         "ofx_centered_gradient3": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i]),
         "ofx_bicubic_at_color": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _i, _i, _i, _i]),
@@ -500,6 +501,16 @@ class Ofx:
             raise ValueError("normalize_frames_dev: %d sources, %d destinations, sets of %d" % (len(src), len(dst), per))
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_normalize_frames_dev(self.h, len(src) // per, per, arr(src), arr(dst), npix, nz, guard))
+
+    def normalize_frames2d_dev(self, src, dst, nx, ny, nz=1, per=None, guard=1):
+        """ofx_normalize_frames2d_dev: normalize_frames_dev on frames of ny rows of nx * nz elements (IN_RGB8: nx pixels), the
+        rows set_option("input_pitch", bytes) apart (0, the default: back to back); a region of interest is the address of its
+        first element under its parent's pitch.  dst = dense results, nx * ny * nz elements of the storage type each."""
+        per = len(src) if per is None else per
+        if per < 1 or len(src) % per or len(dst) != len(src):
+            raise ValueError("normalize_frames2d_dev: %d sources, %d destinations, sets of %d" % (len(src), len(dst), per))
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_normalize_frames2d_dev(self.h, len(src) // per, per, arr(src), arr(dst), nx, ny, nz, guard))
 
     PYRAMID_GUARD, PYRAMID_SENTINEL = 64, -12345.0
 

@@ -422,15 +422,16 @@ int ofx_getminmax(ofx_ctx *ctx, const double *x, int n, double *min, double *max
     return DISPATCH(ctx, minmax_t, ctx, x, n, min, max);
 }
 
-// the head of the *_dev solvers on its own: sources in the context's "input" kind, results in the storage type (include/ofx.h)
-int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard)
+// the head of the *_dev solvers on its own: sources in the context's "input" kind, ny rows of nx * nz elements `pitch` bytes apart
+// (0: back to back), results in the storage type (include/ofx.h)
+static int normalize_frames(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int nx, int ny, int nz, int guard,
+                            size_t pitch)
 {
-    OFX_ENTER(ctx);
     if (!src || !dst) return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: NULL pointer array");
     if (nsets < 1 || per < 1 || (long long) nsets * per > OFX_MM_MAX_SRC)
         return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: %d sets of %d sources (at most %d sources)", nsets, per, OFX_MM_MAX_SRC);
-    if (npix < 1 || nz < 1 || (long long) npix * nz > 0x7fffffffLL)
-        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: %d x %d elements", npix, nz);
+    if (nx < 1 || ny < 1 || nz < 1 || (long long) nx * ny * nz > 0x7fffffffLL)
+        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: %lld x %d elements", (long long) nx * ny, nz);
     const int kind = ofx_src_kind(ctx);
     if (kind == OFX_SRC_RGB8 && nz != 1)
         return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: OFX_IN_RGB8 sources give one gray channel (nz = %d)", nz);
@@ -444,9 +445,23 @@ int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const
         out.p[q] = dst[q];
     }
     double *scr;
-    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(nsets, (size_t) npix, nz), &scr));
-    return ctx->precision == OFX_F64 ? op_normalize_sets_in<double>(ctx, kind, in, out, nsets, per, (size_t) npix, nz, scr, guard)
-                                     : op_normalize_sets_in<float>(ctx, kind, in, out, nsets, per, (size_t) npix, nz, scr, guard);
+    OFX_TRY(ofx_alloc(ctx, op_minmax_scratch_doubles(nsets, (size_t) nx * ny, nz), &scr));
+    return ctx->precision == OFX_F64 ? op_normalize_sets_in<double>(ctx, kind, in, out, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                     : op_normalize_sets_in<float>(ctx, kind, in, out, nsets, per, nx, ny, pitch, nz, scr, guard);
+}
+int ofx_normalize_frames_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int npix, int nz, int guard)
+{
+    OFX_ENTER(ctx);
+    if (ctx->input_pitch != 0)
+        return ofx_fail(ctx, OFX_ERR_ARG, "normalize_frames: no row length to take the input_pitch of %lld bytes by (ofx_normalize_frames2d_dev)",
+                        ctx->input_pitch);
+    return normalize_frames(ctx, nsets, per, src, dst, npix, 1, nz, guard, 0);
+}
+int ofx_normalize_frames2d_dev(ofx_ctx *ctx, int nsets, int per, const void *const *src, void *const *dst, int nx, int ny, int nz, int guard)
+{
+    OFX_ENTER(ctx);
+    if (nx >= 1 && nz >= 1 && (long long) nx * nz <= 0x7fffffffLL) OFX_TRY(ofx_pitch_check(ctx, "normalize_frames", nx * nz));
+    return normalize_frames(ctx, nsets, per, src, dst, nx, ny, nz, guard, (nx >= 1 && nz >= 1) ? ofx_src_pitch(ctx, nx * nz) : 0);
 }
 
 // the rest of that head on its own: op_build_pyramid_group straight into the caller's level arrays (include/ofx.h)
@@ -473,6 +488,8 @@ int ofx_pyramid_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, con
             return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d, scale %d)", taps.size, w, h, s);
     }
     const int kind = ofx_src_kind(ctx);
+    OFX_TRY(ofx_pitch_check(ctx, "pyramid", nx));
+    const size_t pitch = ofx_src_pitch(ctx, nx);
     const size_t el = ctx->precision == OFX_F64 ? sizeof(double) : sizeof(float);
     for (int g = 0; g < n_pairs; g++)
         if (!dI0[g] || !dI1[g] || reinterpret_cast<uintptr_t>(dI0[g]) % ofx_src_align(kind) || reinterpret_cast<uintptr_t>(dI1[g]) % ofx_src_align(kind))
@@ -488,13 +505,13 @@ int ofx_pyramid_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, con
         OFX_TRY(ofx_alloc(ctx, full, &tmpA));
         OFX_TRY(ofx_alloc(ctx, full, &tmpB));
         return op_build_pyramid_group<double>(ctx, n_pairs, dI0, dI1, nscales, zfactor, sigma, nxs.data(), nys.data(),
-                                              (double *const *) dL0, (double *const *) dL1, tmpA, tmpB, scr, kind);
+                                              (double *const *) dL0, (double *const *) dL1, tmpA, tmpB, scr, kind, pitch);
     }
     float *tmpA, *tmpB;
     OFX_TRY(ofx_alloc(ctx, full, &tmpA));
     OFX_TRY(ofx_alloc(ctx, full, &tmpB));
     return op_build_pyramid_group<float>(ctx, n_pairs, dI0, dI1, nscales, zfactor, sigma, nxs.data(), nys.data(),
-                                         (float *const *) dL0, (float *const *) dL1, tmpA, tmpB, scr, kind);
+                                         (float *const *) dL0, (float *const *) dL1, tmpA, tmpB, scr, kind, pitch);
 }
 
 int ofx_image_normalization_2(ofx_ctx *ctx, const double *I1, const double *I2, double *I1n, double *I2n, int size)

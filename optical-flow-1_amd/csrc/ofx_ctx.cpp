@@ -20,6 +20,19 @@ int ofx_fail(ofx_ctx *ctx, int status, const char *fmt, ...)
     return status;
 }
 
+int ofx_pitch_check(ofx_ctx *ctx, const char *who, int row_elems)
+{
+    if (ctx->input_pitch == 0 || row_elems < 1) return OFX_OK;
+    const int kind = ofx_src_kind(ctx);
+    const long long row = (long long) row_elems * (long long) ofx_src_bytes(kind);
+    if (ctx->input_pitch < row)
+        return ofx_fail(ctx, OFX_ERR_ARG, "%s: input_pitch of %lld bytes is less than a row's %lld bytes", who, ctx->input_pitch, row);
+    if (ctx->input_pitch % (long long) ofx_src_align(kind))
+        return ofx_fail(ctx, OFX_ERR_ARG, "%s: input_pitch of %lld bytes (a row holds %lld bytes) is not a multiple of the element's %d",
+                        who, ctx->input_pitch, row, (int) ofx_src_align(kind));
+    return OFX_OK;
+}
+
 extern "C" const char *ofx_strerror(int status)
 {
     switch (status) {
@@ -116,6 +129,7 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->input = OFX_IN_STORAGE;
     ctx->input_vec = 1;
     ctx->input_lut = 1;         // measured faster in both storage precisions
+    ctx->input_pitch = 0;
     ctx->poll_seq = 0;
     ctx->errmsg[0] = 0;
     ctx->expo_host_ms = 0.0;
@@ -288,6 +302,12 @@ extern "C" int ofx_set_option(ofx_ctx *ctx, const char *name, double value)
         if (value != OFX_IN_STORAGE && value != OFX_IN_U8 && value != OFX_IN_U16 && value != OFX_IN_F32 && value != OFX_IN_RGB8)
             return ofx_fail(ctx, OFX_ERR_ARG, "input must be one of OFX_IN_STORAGE .. OFX_IN_RGB8 (0 .. 4)");
         ctx->input = (int) value;
+        return OFX_OK;
+    }
+    if (!strcmp(name, "input_pitch")) {
+        if (!(value >= 0) || value >= 2147483648.0 || value != (double) (long long) value)
+            return ofx_fail(ctx, OFX_ERR_ARG, "input_pitch must be a whole number of bytes in 0 .. 2^31 - 1 (got %g)", value);
+        ctx->input_pitch = (long long) value;
         return OFX_OK;
     }
     if (!strcmp(name, "input_vec")) { ctx->input_vec = value != 0; return OFX_OK; }

@@ -32,6 +32,18 @@ OFX_DEV void stn(double *p, double v) { *p = v; }
 OFX_DEV void stn(float *p, double v)  { *p = (float) v; }
 OFX_DEV void stn2(double2 *p, double2 v) { *p = v; }
 OFX_DEV void stn2(float2 *p, double2 v)  { *p = make_float2((float) v.x, (float) v.y); }
+// Tile t of a launch over pitched rows (OfxRows, ofx_ops.h), for a workgroup of 256: the tile is 1 << lbx slots of a row by
+// (256 >> lbx) * rpt rows, tile t at row piece t / cx, column piece t % cx -- t is the same in all lanes, so this is the one
+// division of the thread.  The thread's slot q (the caller tests it against the row's length) and its rows i0, i0 + di, .. < i1.
+OFX_DEV void rows_tile(int t, int cx, int lbx, int ny, int rpt, int &q, int &i0, int &i1, int &di)
+{
+    const int ty = t / cx, tx = t - ty * cx;
+    di = 256 >> lbx;
+    q = (tx << lbx) + ((int) threadIdx.x & ((1 << lbx) - 1));
+    i0 = ty * di * rpt + ((int) threadIdx.x >> lbx);
+    i1 = (ty + 1) * di * rpt;                                   // ny <= 2^31 - 1025 (rows_check, ofx_ops.hip)
+    if (i1 > ny) i1 = ny;
+}
 // Non-temporal stores for results that no kernel will find in cache again (working set of the level
 // larger than the 256 MiB Infinity Cache): measured +3.7 % on the 4K iteration kernel, -3 % at 1080p
 // where the ping-pong output of one launch is still resident when the next launch reads it.

@@ -123,6 +123,7 @@ struct ofx_ctx {
     int input;          // element kind of the frames the *_dev entries read (OFX_IN_*, include/ofx.h); host-plane entries ignore it
     int input_vec;      // 1 (default): the byte kinds through the four-elements-per-lane kernels; 0: one element per thread
     int input_lut;      // ... 1 (default): the 8-bit kinds look the 256 possible results up in a per-workgroup LDS table; 0: divide per element
+    long long input_pitch;  // bytes from one row of a frame of the *_dev entries to the next; 0 (default): the rows lie back to back
     double mem_budget;  // bytes all contexts of a batch may use for level arrays (0 = half of the free device memory)
     unsigned long long poll_seq;
 
@@ -185,6 +186,15 @@ static inline int ofx_src_kind(const ofx_ctx *ctx)
 // bytes of one element (OFX_SRC_RGB8: of one pixel) and the alignment a frame pointer needs
 static inline size_t ofx_src_bytes(int kind) { static const size_t b[5] = {8, 4, 1, 2, 3}; return b[kind]; }
 static inline size_t ofx_src_align(int kind) { static const size_t a[5] = {8, 4, 1, 2, 1}; return a[kind]; }
+// Option "input_pitch" against rows of row_elems elements (OFX_SRC_RGB8: pixels) of the context's "input" kind: OFX_ERR_ARG for a
+// pitch below the row's bytes or off the element's alignment.  A row count that is not positive is left to the entry's own checks.
+int ofx_pitch_check(ofx_ctx *ctx, const char *who, int row_elems);
+// ... and the pitch the launchers take: 0 where the rows lie back to back (no pitch, or one equal to the row's bytes)
+static inline size_t ofx_src_pitch(const ofx_ctx *ctx, int row_elems)
+{
+    const size_t row = (size_t) row_elems * ofx_src_bytes(ofx_src_kind(ctx));
+    return ctx->input_pitch > 0 && (size_t) ctx->input_pitch != row ? (size_t) ctx->input_pitch : 0;
+}
 
 // ---- API entry boilerplate ---------------------------------------------------------------------
 #define OFX_ENTER(ctx)                                                                           \

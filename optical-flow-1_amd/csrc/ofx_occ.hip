@@ -1674,6 +1674,17 @@ template <typename TIN> __global__ void k_occ_seq_in(OccSeqIn in, double *__rest
     if (i >= n) return;
     dst[(size_t) blockIdx.z * n + i] = ldw(static_cast<const TIN *>(in.f[blockIdx.z]) + i);
 }
+// ... from frames whose rows are R.pitch bytes apart (context option "input_pitch"): a thread keeps its column over four rows of
+// its tile (rows_tile, ofx_device.h)
+template <typename TIN> __global__ __launch_bounds__(256) void k_occ_seq_in_p(OccSeqIn in, double *__restrict__ dst, OfxRows R)
+{
+    int q, i0, i1, di;
+    rows_tile(blockIdx.x, R.cx, R.lbx, R.ny, 4, q, i0, i1, di);
+    if (q >= R.w) return;
+    const unsigned char *__restrict__ f = static_cast<const unsigned char *>(in.f[blockIdx.z]);
+    double *__restrict__ d = dst + (size_t) blockIdx.z * R.w * R.ny;
+    for (int i = i0; i < i1; i += di) d[(size_t) i * R.w + q] = ldw(reinterpret_cast<const TIN *>(f + (size_t) i * R.pitch) + q);
+}
 // Results of triple g = blockIdx.z: the .flo payload (float) u1, (float) u2 interleaved, and the map 255 (chi > THR_CHI) as
 // bytes.  A block serves 1024 pixels under two lane mappings.  Payload: pixel = 256 k + lane, k = 0 .. 3 -- a float2 per lane,
 // 512 contiguous bytes per wave and store.  Map: a lane owns one ALIGNED 32-bit word of the destination, i.e. the pixels
@@ -1710,11 +1721,12 @@ __global__ __launch_bounds__(256) void k_occ_seq_out(const double *__restrict__ 
 
 namespace {
 
-// what must hold before any work: the pyramid's sizes, its coarsest level, and room for both Gaussians on the levels they
-// smooth (op_gaussian_planes' rule, which the host entries meet while they build the pyramid)
+// what must hold before any work: the pyramid's sizes, its coarsest level, room for both Gaussians on the levels they
+// smooth (op_gaussian_planes' rule, which the host entries meet while they build the pyramid), and the frames' row pitch
 int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor, std::vector<int> &nxs, std::vector<int> &nys)
 {
     OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
+    OFX_TRY(ofx_pitch_check(ctx, "tvl1occ", nxx));
     if (nxs[nscales - 1] < 2 || nys[nscales - 1] < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: coarsest level %dx%d", nxs[nscales - 1], nys[nscales - 1]);
     for (int s = 0; s < nscales; s++) {
         const double sigma = s ? 0.6 * sqrt(1.0 / (zfactor * zfactor) - 1.0) : OCC_PRESMOOTHING_SIGMA;     // smooths level s - 1 | 0
@@ -1747,7 +1759,7 @@ int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *
 template <typename TIN>
 int occ_planes_group_impl(ofx_ctx *ctx, int kind, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
                           const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
-                          ofx_stats *stats)
+                          ofx_stats *stats, size_t pitch)       // bytes between the rows of the planes dF, 0 = dense
 {
     const int nxx = nxs[0], nyy = nys[0];
     for (int g = 0; g < G; g++) {
@@ -1779,11 +1791,16 @@ int occ_planes_group_impl(ofx_ctx *ctx, int kind, int G, int F, const void *cons
             OfxSrcPtrs src = {};
             OfxDstPtrs dst = {};
             for (int k = 0; k < cnt; k++) { src.p[k] = dF[k0 + k]; dst.p[k] = lv[0].fr + (k0 + k) * size; }
-            OFX_TRY(op_convert_sources_in<double>(ctx, kind, src, dst, cnt, size));
+            OFX_TRY(op_convert_sources_in<double>(ctx, kind, src, dst, cnt, nxx, nyy, pitch));
             continue;
         }
         OccSeqIn in = {};
         for (int k = 0; k < cnt; k++) in.f[k] = dF[k0 + k];
+        if (pitch) {
+            const OfxRows R = op_rows_geom(nxx, nyy, pitch, false);
+            hipLaunchKernelGGL(k_occ_seq_in_p<TIN>, dim3(R.tiles, 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, R);
+            continue;
+        }
         hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, (int) size);
     }
     OFX_LAUNCH_CHECK(ctx);
@@ -1828,9 +1845,10 @@ int occ_planes_group(ofx_ctx *ctx, int G, int F, const void *const *dF, const Oc
     std::vector<ofx_stats> local(stats_out ? 0 : G);
     ofx_stats *st = stats_out ? stats_out : local.data();
     const int kind = ofx_src_kind(ctx);                     // the frames come in the context's "input" kind
+    const size_t pitch = ofx_src_pitch(ctx, nxs[0]);
     const int s = kind == OFX_SRC_F64
-                      ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st)
-                      : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st);
+                      ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch)
+                      : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch);
     if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
     const double ms = ofx_now_ms() - t0;
     for (int g = 0; g < G; g++) st[g].total_ms = ms;
@@ -1844,7 +1862,7 @@ int occ_dev_check_ctxs(ofx_ctx *const *ctxs, int n_ctx)
     if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
     for (int w = 0; w < n_ctx; w++)
         if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision ||
-            ctxs[w]->input != ctxs[0]->input)
+            ctxs[w]->input != ctxs[0]->input || ctxs[w]->input_pitch != ctxs[0]->input_pitch)
             return OFX_ERR_ARG;
     return OFX_OK;
 }

@@ -60,17 +60,30 @@ int op_normalize_sets(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst
 // of three bytes and nz must be 1) run the kernels of ofx_ops.hip that load four elements per lane as aligned 32-bit words, or,
 // with the context's input_vec = 0 and for the min / max of nz > 1 channels, the kernels above on S = unsigned char / unsigned
 // short / OfxRgb8.  Same scratch, same results: every sample is exact in double.
-int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr,
-                         int chunk = 0, int chunks = 1);
+// The frames are ny rows of nx * nz elements (OFX_SRC_RGB8: of nx pixels), `pitch` bytes from one row's start to the next's.
+// pitch = 0: the rows lie back to back, and the launches are those of the flat element count nx * ny (a pitch equal to the row's
+// bytes is passed as 0: ofx_src_pitch).  Otherwise the pitched kernels of ofx_ops.hip: the same values from the same
+// expressions, no byte outside a row read; pitch is a multiple of the element's alignment and at least the row's bytes.
+int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, int nx, int ny, size_t pitch, int nz,
+                         double *scr, int chunk = 0, int chunks = 1);
 template <typename T>
-int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
-                        const double *scr, int guard = 1);
+int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, int nx, int ny,
+                        size_t pitch, int nz, const double *scr, int guard = 1);
 template <typename T>
-int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
-                         double *scr, int guard = 1);
-// dst[q][e] = src[q][e] for e < n and the `count` <= OFX_MM_MAX_SRC sources of a byte kind (no normalisation)
+int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, int nx, int ny,
+                         size_t pitch, int nz, double *scr, int guard = 1);
+// rows of a pitched frame and the tiles a launch cuts them into (ofx_ops.hip; rows_tile in ofx_device.h), passed to kernels by value
+struct OfxRows {
+    int    w, ny;       // elements (OFX_SRC_RGB8: pixels) per row, rows
+    size_t pitch;       // bytes from one row's start to the next's
+    int    lbx;         // a tile is 1 << lbx slots of a row wide
+    int    cx, tiles;   // tiles per row's length, tiles in all
+};
+// groups = false: a slot is one of the row's w elements; true: a group of four of them.  A thread takes its slot of 4 rows.
+OfxRows op_rows_geom(int w, int ny, size_t pitch, bool groups);
+// dst[q][i * nx + j] = element j of row i of src[q], for the `count` <= OFX_MM_MAX_SRC sources of a byte kind (no normalisation)
 template <typename T>
-int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, size_t n);
+int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, int nx, int ny, size_t pitch);
 
 // generic bicubic resampling out(i1,j1) = bicubic(in, j1/fx, i1/fy, border_out=false)
 // (zoom_out: fx=fy=factor, src/zoom.cpp:67-75; zoom_in: per-axis factors, src/zoom.cpp:142-154)
@@ -141,7 +154,8 @@ struct OfxGroupPtrs {
 template <typename T>
 int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const void *const *dB, int nscales, double zfactor,
                            double presmooth_sigma, const int *nxs, const int *nys, T *const *lvA, T *const *lvB, T *tmpA,
-                           T *tmpB, double *scr, int kind = -1);       // kind: OFX_SRC_* of dA / dB; -1 = the storage type
+                           T *tmpB, double *scr, int kind = -1,        // kind: OFX_SRC_* of dA / dB; -1 = the storage type
+                           size_t pitch = 0);                          // kind >= 0: bytes between the rows of dA / dB, 0 = dense
 
 #define OFX_LAUNCH_CHECK(ctx)                                                                    \
     do {                                                                                         \

@@ -388,57 +388,293 @@ static int normalize_map_bytes(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDst
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
-static int rgb8_check(ofx_ctx *ctx, int kind, int nz)
+// ---- ... and for frames whose rows are `pitch` bytes apart (context option "input_pitch") ------------------------------------
+// A frame is ny rows of w elements (RGB8: pixels), row i at byte i * pitch; the results are dense, element j of row i at i * w + j.
+// A workgroup takes a TILE (OfxRows, rows_tile in ofx_device.h): 1 << lbx consecutive SLOTS of a row by (256 >> lbx) * 4 rows, a
+// thread one slot of four of those rows; the tile's place is found with one division per workgroup, so a lane's column never
+// costs one.  lbx follows the row's length, which keeps the lanes busy on short rows (a 64-column region: 16 or 32 rows per
+// workgroup) and a wave on one row of a long one.  Slot = element for the one-element-per-thread kernels, a group of four for the
+// byte kinds' (below).  Four rows per thread also spread a workgroup's table of quotients (LUT) over four times the elements.
+OfxRows op_rows_geom(int w, int ny, size_t pitch, bool groups)
+{
+    OfxRows R;
+    const int slots = groups ? w / 4 + 2 : w;                  // a row's groups: below
+    R.w = w;
+    R.ny = ny;
+    R.pitch = pitch;
+    R.lbx = 2;
+    while ((1 << R.lbx) < slots && R.lbx < 8) R.lbx++;
+    R.cx = ofx_cdiv(slots, 1 << R.lbx);
+    R.tiles = R.cx * ofx_cdiv(ny, (256 >> R.lbx) * 4);
+    return R;
+}
+// k_minmax_partial on pitched rows: block (c * nb + b, set) strides over the tiles, a slot is a PIXEL of nz channels
+template <typename S>
+__global__ __launch_bounds__(256) void k_minmax_partial_p(OfxSrcPtrs src, int per, OfxRows R, int nz, int nb, int first, int count,
+                                                          double *__restrict__ scr)
+{
+    const int c = blockIdx.x / nb, b = blockIdx.x - c * nb, set = blockIdx.y;
+    const int nslots = gridDim.y * nz, slot = set * nz + c;
+    double lo = ldw((const S *) src.p[set * per] + c), hi = lo;
+    for (int k = 0; k < per; k += 2) {
+        const unsigned char *__restrict__ I1 = static_cast<const unsigned char *>(src.p[set * per + k]);
+        const unsigned char *__restrict__ I2 = static_cast<const unsigned char *>(src.p[set * per + (k + 1 < per ? k + 1 : k)]);
+        for (int t = b; t < R.tiles; t += nb) {
+            int q, i0, i1, di;
+            rows_tile(t, R.cx, R.lbx, R.ny, 4, q, i0, i1, di);
+            if (q >= R.w) continue;
+            const size_t e = (size_t) q * nz + c;
+            for (int i = i0; i < i1; i += di) {
+                const size_t o = (size_t) i * R.pitch;
+                const double x = ldw(reinterpret_cast<const S *>(I1 + o) + e), y = ldw(reinterpret_cast<const S *>(I2 + o) + e);
+                lo = x < lo ? x : lo; hi = x > hi ? x : hi;
+                lo = y < lo ? y : lo; hi = y > hi ? y : hi;
+            }
+        }
+    }
+    double *part = scr + 2 * (size_t) nslots + (size_t) slot * count + first + b;
+    minmax_block_reduce(lo, hi, part, part + (size_t) nslots * count);
+}
+// k_normalize_map on pitched rows: a slot is an ELEMENT of the row of w = nx * nz, its channel the column modulo nz -- taken once
+// per thread, which keeps its column over the rows of the tile.  The expression is k_normalize_map's.
+template <typename T, typename S>
+__global__ __launch_bounds__(256) void k_normalize_map_p(OfxSrcPtrs src, OfxDstPtrs dst, int per, OfxRows R, int nz,
+                                                         const double *__restrict__ mm, int guard)
+{
+    int q, i0, i1, di;
+    rows_tile(blockIdx.x, R.cx, R.lbx, R.ny, 4, q, i0, i1, di);
+    if (q >= R.w) return;
+    const int set = blockIdx.y, slot = set * nz + (nz == 1 ? 0 : (int) ((unsigned) q % (unsigned) nz));
+    const double lo = mm[2 * slot], den = mm[2 * slot + 1] - mm[2 * slot];
+    const bool map = !guard || den > 0;
+    for (int i = i0; i < i1; i += di) {
+        const size_t o = (size_t) i * R.pitch, e = (size_t) i * R.w + q;
+        for (int k = 0; k < per; k += 2) {                       // two sources at a time: both loads before the stores
+            const bool two = k + 1 < per;
+            const double x = ldw(reinterpret_cast<const S *>(static_cast<const unsigned char *>(src.p[set * per + k]) + o) + q);
+            const double y = two ? ldw(reinterpret_cast<const S *>(static_cast<const unsigned char *>(src.p[set * per + k + 1]) + o) + q) : 0.0;
+            stn((T *) dst.p[set * per + k] + e, map ? 255.0 * (x - lo) / den : x);
+            if (two) stn((T *) dst.p[set * per + k + 1] + e, map ? 255.0 * (y - lo) / den : y);
+        }
+    }
+}
+// The byte kinds, four elements per lane PER ROW.  A row starts anywhere (base + i * pitch: its head rotates from row to row when
+// pitch % 4 != 0), so the row is cut into GROUPS of four columns [4 g - s, 4 g - s + 4), s = (4 - head) & 3 with head the row's
+// elements up to its own 32-bit boundary: group 0 holds the head (its first s places lie before the row), the groups wholly
+// inside the row start on a 32-bit boundary and are loaded as SrcVec's aligned words, the last one holds the tail.  A place outside
+// [0, w) is never read: the groups across the row's ends, and every group of a row shorter than a word, go element by element.
+// At most w / 4 + 2 groups.
+// k_minmax_vec on pitched rows (one channel)
+template <typename S>
+__global__ __launch_bounds__(256) void k_minmax_vec_p(OfxSrcPtrs src, int per, OfxRows R, int nb, int first, int count,
+                                                      double *__restrict__ scr)
+{
+    using V = SrcVec<S>;
+    const int b = blockIdx.x, set = blockIdx.y, nslots = gridDim.y;
+    unsigned lo = V::load1(static_cast<const unsigned char *>(src.p[set * per])), hi = lo;
+    for (int k = 0; k < per; k++) {
+        const unsigned char *__restrict__ p = static_cast<const unsigned char *>(src.p[set * per + k]);
+        for (int t = b; t < R.tiles; t += nb) {
+            int g, i0, i1, di;
+            rows_tile(t, R.cx, R.lbx, R.ny, 4, g, i0, i1, di);
+            for (int i = i0; i < i1; i += di) {
+                const unsigned char *row = p + (size_t) i * R.pitch;
+                const long long col0 = 4LL * g - ((4 - V::head(reinterpret_cast<uintptr_t>(row))) & 3);
+                if (col0 >= R.w) continue;
+                if (col0 >= 0 && col0 + 4 <= R.w) {
+                    unsigned v[4];
+                    V::load4(row + (size_t) col0 * V::BYTES, v);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) { lo = v[j] < lo ? v[j] : lo; hi = v[j] > hi ? v[j] : hi; }
+                } else {
+                    for (int j = 0; j < 4; j++) {
+                        const long long col = col0 + j;
+                        if (col < 0 || col >= R.w) continue;
+                        const unsigned x = V::load1(row + (size_t) col * V::BYTES);
+                        lo = x < lo ? x : lo; hi = x > hi ? x : hi;
+                    }
+                }
+            }
+        }
+    }
+    double *part = scr + 2 * (size_t) nslots + (size_t) set * count + first + b;
+    minmax_block_reduce((double) lo, (double) hi, part, part + (size_t) nslots * count);
+}
+// k_normalize_vec on pitched rows: thread = one group of four rows of its tile, of every source of set blockIdx.y; w = nx * nz elements
+// per row.
+// A row holds whole pixels, so the channel of a place is its column modulo nz: (4 g) % nz once per thread, then by counting.
+// mm == nullptr and LUT as k_normalize_vec; the expression is k_normalize_map's.
+template <typename T, typename S, bool LUT>
+__global__ __launch_bounds__(256) void k_normalize_vec_p(OfxSrcPtrs src, OfxDstPtrs dst, int per, OfxRows R, int nz,
+                                                         const double *__restrict__ mm, int guard)
+{
+    using V = SrcVec<S>;
+    const int set = blockIdx.y;
+    auto eval = [&](int c, unsigned v) -> double {
+        const double x = (double) v;
+        if (!mm) return x;
+        const int slot = set * nz + c;
+        const double lo = mm[2 * slot], den = mm[2 * slot + 1] - mm[2 * slot];
+        return (!guard || den > 0) ? 255.0 * (x - lo) / den : x;
+    };
+    __shared__ double tbl[LUT ? VEC_LUT_NZ * 256 : 1];
+    if (LUT) {
+        for (int c = 0; c < nz; c++) tbl[c * 256 + threadIdx.x] = eval(c, threadIdx.x);
+        __syncthreads();
+    }
+    auto norm = [&](int c, unsigned v) -> double { return LUT ? tbl[c * 256 + v] : eval(c, v); };
+    int g, i0, i1, di;
+    rows_tile(blockIdx.x, R.cx, R.lbx, R.ny, 4, g, i0, i1, di);
+    const int cg = nz == 1 ? 0 : (int) ((4u * (unsigned) g) % (unsigned) nz);
+    for (int i = i0; i < i1; i += di) {
+        for (int k = 0; k < per; k++) {
+            const unsigned char *__restrict__ row = static_cast<const unsigned char *>(src.p[set * per + k]) + (size_t) i * R.pitch;
+            T *__restrict__ d = static_cast<T *>(dst.p[set * per + k]) + (size_t) i * R.w;
+            const int s = (4 - V::head(reinterpret_cast<uintptr_t>(row))) & 3;
+            const long long col0 = 4LL * g - s;
+            if (col0 >= R.w) continue;
+            int c = cg - s;                                      // channel of place col0, which may lie before the row: s <= 3, nz >= 2
+            if (nz == 1) c = 0;
+            if (c < 0) c += nz;
+            if (c < 0) c += nz;
+            if (col0 >= 0 && col0 + 4 <= R.w) {
+                unsigned v[4];
+                V::load4(row + (size_t) col0 * V::BYTES, v);
+                double o[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) { o[j] = norm(c, v[j]); c = c + 1 == nz ? 0 : c + 1; }
+                store_run4(d + col0, o);
+            } else {
+                for (int j = 0; j < 4; j++) {
+                    const long long col = col0 + j;
+                    if (col >= 0 && col < R.w) stn(d + col, norm(c, V::load1(row + (size_t) col * V::BYTES)));
+                    c = c + 1 == nz ? 0 : c + 1;
+                }
+            }
+        }
+    }
+}
+
+static int rows_check(ofx_ctx *ctx, int kind, int nsets, int per, int nx, int ny, size_t pitch, int nz)
 {
     if (kind < OFX_SRC_F64 || kind > OFX_SRC_RGB8) return ofx_fail(ctx, OFX_ERR_ARG, "source kind %d", kind);
     if (kind == OFX_SRC_RGB8 && nz != 1) return ofx_fail(ctx, OFX_ERR_ARG, "RGB8 sources give one gray channel (nz = %d)", nz);
+    if (nx < 1 || ny < 1) return ofx_fail(ctx, OFX_ERR_ARG, "minmax: frames of %d x %d", nx, ny);
+    OFX_TRY(minmax_check(ctx, nsets, per, (size_t) nx * ny, nz));
+    if (pitch && ny > 0x7fffffff - 1024)                      // rows_tile counts rows in int, a tile past the last one included
+        return ofx_fail(ctx, OFX_ERR_ARG, "minmax: %d pitched rows (at most 2^31 - 1025)", ny);
+    if (pitch && (pitch < (size_t) nx * nz * ofx_src_bytes(kind) || pitch % ofx_src_align(kind)))
+        return ofx_fail(ctx, OFX_ERR_ARG, "minmax: pitch of %zu bytes for rows of %zu bytes", pitch, (size_t) nx * nz * ofx_src_bytes(kind));
     return OFX_OK;
 }
-int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, size_t npix, int nz, double *scr, int chunk,
-                         int chunks)
+template <typename S, bool BYTES>                               // BYTES: S is a byte kind (SrcVec<S> exists)
+static int minmax_partial_rows(ofx_ctx *ctx, const OfxSrcPtrs &src, int nsets, int per, int nx, int ny, size_t pitch, int nz,
+                               double *scr, int chunk, int chunks)
 {
-    OFX_TRY(rgb8_check(ctx, kind, nz));
+    const int nb = mm_blocks((size_t) nx * ny);                 // the flat launch's pieces: one scratch layout, one k_minmax_final
+    bool vec = false;
+    if constexpr (BYTES) {
+        vec = ctx->input_vec && nz == 1;
+        if (vec)
+            hipLaunchKernelGGL(k_minmax_vec_p<S>, dim3(nb, nsets), dim3(256), 0, ctx->stream, src, per, op_rows_geom(nx, ny, pitch, true),
+                               nb, chunk * nb, chunks * nb, scr);
+    }
+    if (!vec)
+        hipLaunchKernelGGL(k_minmax_partial_p<S>, dim3(nb * nz, nsets), dim3(256), 0, ctx->stream, src, per,
+                           op_rows_geom(nx, ny, pitch, false), nz, nb, chunk * nb, chunks * nb, scr);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+template <typename T, typename S, bool BYTES>
+static int normalize_map_rows(ofx_ctx *ctx, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, int nx, int ny,
+                              size_t pitch, int nz, const double *scr, int guard)
+{
+    bool vec = false;
+    if constexpr (BYTES) vec = ctx->input_vec != 0;
+    if (!vec) {
+        const OfxRows R = op_rows_geom(nx * nz, ny, pitch, false);
+        hipLaunchKernelGGL((k_normalize_map_p<T, S>), dim3(R.tiles, nsets), dim3(256), 0, ctx->stream, src, dst, per, R, nz, scr, guard);
+    } else if constexpr (BYTES) {
+        const OfxRows R = op_rows_geom(nx * nz, ny, pitch, true);
+        if (ctx->input_lut && sizeof(S) != sizeof(unsigned short) && nz <= VEC_LUT_NZ)
+            hipLaunchKernelGGL((k_normalize_vec_p<T, S, true>), dim3(R.tiles, nsets), dim3(256), 0, ctx->stream, src, dst, per, R, nz, scr, guard);
+        else
+            hipLaunchKernelGGL((k_normalize_vec_p<T, S, false>), dim3(R.tiles, nsets), dim3(256), 0, ctx->stream, src, dst, per, R, nz, scr, guard);
+    }
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+int op_minmax_partial_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, int nsets, int per, int nx, int ny, size_t pitch, int nz,
+                         double *scr, int chunk, int chunks)
+{
+    OFX_TRY(rows_check(ctx, kind, nsets, per, nx, ny, pitch, nz));
+    const size_t npix = (size_t) nx * ny;
     switch (kind) {
-    case OFX_SRC_F64: return op_minmax_partial<double>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
-    case OFX_SRC_F32: return op_minmax_partial<float>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
-    case OFX_SRC_U8:  return minmax_partial_bytes<unsigned char>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
-    case OFX_SRC_U16: return minmax_partial_bytes<unsigned short>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
-    default:          return minmax_partial_bytes<OfxRgb8>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_F64: return pitch ? minmax_partial_rows<double, false>(ctx, src, nsets, per, nx, ny, pitch, nz, scr, chunk, chunks)
+                                   : op_minmax_partial<double>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_F32: return pitch ? minmax_partial_rows<float, false>(ctx, src, nsets, per, nx, ny, pitch, nz, scr, chunk, chunks)
+                                   : op_minmax_partial<float>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_U8:  return pitch ? minmax_partial_rows<unsigned char, true>(ctx, src, nsets, per, nx, ny, pitch, nz, scr, chunk, chunks)
+                                   : minmax_partial_bytes<unsigned char>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    case OFX_SRC_U16: return pitch ? minmax_partial_rows<unsigned short, true>(ctx, src, nsets, per, nx, ny, pitch, nz, scr, chunk, chunks)
+                                   : minmax_partial_bytes<unsigned short>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
+    default:          return pitch ? minmax_partial_rows<OfxRgb8, true>(ctx, src, nsets, per, nx, ny, pitch, nz, scr, chunk, chunks)
+                                   : minmax_partial_bytes<OfxRgb8>(ctx, src, nsets, per, npix, nz, scr, chunk, chunks);
     }
 }
 template <typename T>
-int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
-                        const double *scr, int guard)
+int op_normalize_map_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, int nx, int ny,
+                        size_t pitch, int nz, const double *scr, int guard)
 {
-    OFX_TRY(rgb8_check(ctx, kind, nz));
+    OFX_TRY(rows_check(ctx, kind, nsets, per, nx, ny, pitch, nz));
+    const size_t npix = (size_t) nx * ny;
     switch (kind) {
-    case OFX_SRC_F64: return op_normalize_map<T, double>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
-    case OFX_SRC_F32: return op_normalize_map<T, float>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
-    case OFX_SRC_U8:  return normalize_map_bytes<T, unsigned char>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
-    case OFX_SRC_U16: return normalize_map_bytes<T, unsigned short>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
-    default:          return normalize_map_bytes<T, OfxRgb8>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_F64: return pitch ? normalize_map_rows<T, double, false>(ctx, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                   : op_normalize_map<T, double>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_F32: return pitch ? normalize_map_rows<T, float, false>(ctx, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                   : op_normalize_map<T, float>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_U8:  return pitch ? normalize_map_rows<T, unsigned char, true>(ctx, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                   : normalize_map_bytes<T, unsigned char>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    case OFX_SRC_U16: return pitch ? normalize_map_rows<T, unsigned short, true>(ctx, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                   : normalize_map_bytes<T, unsigned short>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
+    default:          return pitch ? normalize_map_rows<T, OfxRgb8, true>(ctx, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard)
+                                   : normalize_map_bytes<T, OfxRgb8>(ctx, src, dst, nsets, per, npix, nz, scr, guard);
     }
 }
 template <typename T>
-int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, size_t npix, int nz,
-                         double *scr, int guard)
+int op_normalize_sets_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int nsets, int per, int nx, int ny,
+                         size_t pitch, int nz, double *scr, int guard)
 {
-    OFX_TRY(op_minmax_partial_in(ctx, kind, src, nsets, per, npix, nz, scr));
-    OFX_TRY(op_minmax_final(ctx, nsets, npix, nz, scr));
-    return op_normalize_map_in<T>(ctx, kind, src, dst, nsets, per, npix, nz, scr, guard);
+    OFX_TRY(op_minmax_partial_in(ctx, kind, src, nsets, per, nx, ny, pitch, nz, scr));
+    OFX_TRY(op_minmax_final(ctx, nsets, (size_t) nx * ny, nz, scr));
+    return op_normalize_map_in<T>(ctx, kind, src, dst, nsets, per, nx, ny, pitch, nz, scr, guard);
 }
 template <typename T>
-int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, size_t n)
+int op_convert_sources_in(ofx_ctx *ctx, int kind, const OfxSrcPtrs &src, const OfxDstPtrs &dst, int count, int nx, int ny, size_t pitch)
 {
     if (kind != OFX_SRC_U8 && kind != OFX_SRC_U16 && kind != OFX_SRC_RGB8) return ofx_fail(ctx, OFX_ERR_ARG, "source kind %d", kind);
-    OFX_TRY(minmax_check(ctx, 1, count, n, 1));
+    OFX_TRY(rows_check(ctx, kind, 1, count, nx, ny, pitch, 1));
+    const size_t n = (size_t) nx * ny;
+    const double *none = nullptr;
+    if (pitch) {
+        const OfxRows R = op_rows_geom(nx, ny, pitch, true);
+        const dim3 grid(R.tiles, 1);
+        if (kind == OFX_SRC_U8)
+            hipLaunchKernelGGL((k_normalize_vec_p<T, unsigned char, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, R, 1, none, 0);
+        else if (kind == OFX_SRC_U16)
+            hipLaunchKernelGGL((k_normalize_vec_p<T, unsigned short, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, R, 1, none, 0);
+        else
+            hipLaunchKernelGGL((k_normalize_vec_p<T, OfxRgb8, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, R, 1, none, 0);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    }
     const dim3 grid(vec_grid(n), 1);
     if (kind == OFX_SRC_U8)
-        hipLaunchKernelGGL((k_normalize_vec<T, unsigned char, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+        hipLaunchKernelGGL((k_normalize_vec<T, unsigned char, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, none, 0);
     else if (kind == OFX_SRC_U16)
-        hipLaunchKernelGGL((k_normalize_vec<T, unsigned short, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+        hipLaunchKernelGGL((k_normalize_vec<T, unsigned short, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, none, 0);
     else
-        hipLaunchKernelGGL((k_normalize_vec<T, OfxRgb8, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, (const double *) nullptr, 0);
+        hipLaunchKernelGGL((k_normalize_vec<T, OfxRgb8, false>), grid, dim3(256), 0, ctx->stream, src, dst, count, n, 1, none, 0);
     OFX_LAUNCH_CHECK(ctx);
     return OFX_OK;
 }
@@ -1160,7 +1396,7 @@ int op_pyramid_sizes(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor
 template <typename T>
 int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const void *const *dB, int nscales, double zfactor,
                            double sigma, const int *nxs, const int *nys, T *const *lvA, T *const *lvB, T *tmpA, T *tmpB,
-                           double *scr, int kind)
+                           double *scr, int kind, size_t pitch)
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "pyramid group of %d", G);
     const int nxx = nxs[0], nyy = nys[0], size = nxx * nyy;
@@ -1180,7 +1416,7 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
         dst.p[2 * g + 1] = n1 + (size_t) g * size;
     }
     if (kind < 0) OFX_TRY((op_normalize_sets<T, T>(ctx, src, dst, G, 2, (size_t) size, 1, scr)));
-    else OFX_TRY(op_normalize_sets_in<T>(ctx, kind, src, dst, G, 2, (size_t) size, 1, scr));
+    else OFX_TRY(op_normalize_sets_in<T>(ctx, kind, src, dst, G, 2, nxx, nyy, pitch, 1, scr));
     auto gauss_xy = [&](const T *ia, const T *ib, T *oa, T *ob, int nx, int ny, double sg) -> int {
         GaussTaps taps;
         OFX_TRY(gauss_taps_checked(ctx, sg, nx, ny, 0, &taps));
@@ -1290,15 +1526,15 @@ template <typename T> int op_gradient_dz(ofx_ctx *ctx, const T *in, T *dz, int n
     template int op_bicubic_at<T>(ofx_ctx *, const T *, const double *, const double *, double *, int, int, int, int);           \
     template int op_grad_pack<T>(ofx_ctx *, const T *, Pix<T>::v2 *, T *, int, int, int);                                       \
     template int op_build_pyramid_group<T>(ofx_ctx *, int, const void *const *, const void *const *, int, double, double,       \
-                                           const int *, const int *, T *const *, T *const *, T *, T *, double *, int);         \
+                                           const int *, const int *, T *const *, T *const *, T *, T *, double *, int, size_t); \
     template int op_bicubic_at_color<T>(ofx_ctx *, const T *, const double *, const double *, double *, int, int, int, int, int, int); \
     template int op_gradient_dz<T>(ofx_ctx *, const T *, T *, int, int, int);                                                   \
     template int op_minmax_partial<T>(ofx_ctx *, const OfxSrcPtrs &, int, int, size_t, int, double *, int, int);             \
     template int op_normalize_map<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, const double *, int); \
     template int op_normalize_sets<T, T>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int); \
-    template int op_normalize_map_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, const double *, int); \
-    template int op_normalize_sets_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int); \
-    template int op_convert_sources_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, size_t);
+    template int op_normalize_map_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, int, int, size_t, int, const double *, int); \
+    template int op_normalize_sets_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, int, int, size_t, int, double *, int); \
+    template int op_convert_sources_in<T>(ofx_ctx *, int, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, int, size_t);
 
 OFX_INSTANTIATE(double)
 OFX_INSTANTIATE(float)

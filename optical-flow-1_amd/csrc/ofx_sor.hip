@@ -1082,7 +1082,8 @@ static int hs_single_scale_host(ofx_ctx *ctx, const double *I1, const double *I2
 // On success lv[0].flow(g) holds the flow of pair g.
 template <typename T>
 static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *const *dI2, int nx, int ny, const HsParams &P,
-                            int nscales, double zfactor, std::vector<HsLevel<T>> &lv, ofx_stats *stats, int kind = -1)
+                            int nscales, double zfactor, std::vector<HsLevel<T>> &lv, ofx_stats *stats, int kind = -1,
+                            size_t pitch = 0)               // kind >= 0: bytes between the images' rows, 0 = dense
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "hs: group of %d pairs", G);
     if (P.verbose && G == 1)
@@ -1105,7 +1106,8 @@ static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
         std::vector<T *> lA(nscales), lB(nscales);
         for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }
         OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI1, (const void *const *) dI2, nscales, zfactor,
-                                          HS_PRESMOOTH_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind));
+                                          HS_PRESMOOTH_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind,
+                                          pitch));
     }
     HsLevel<T> &C = lv[nscales - 1];
     OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                          // :320-323
@@ -1162,7 +1164,7 @@ static int hs_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const vo
 {
     std::vector<HsLevel<T>> lv;
     OFX_TRY(hs_pyramidal_dev<T>(ctx, G, (const T *const *) dI1, (const T *const *) dI2, nx, ny, P, nscales, zfactor, lv, stats,
-                                ofx_src_kind(ctx)));
+                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0));
     const size_t n = (size_t) nx * ny;
     for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].flow(g), (float2 *) d_flo[g], n));
     return OFX_OK;
@@ -1208,7 +1210,7 @@ extern "C" int ofx_hs_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI
     auto check = [&]() -> int {
         if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", warps);
         if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
-        return OFX_OK;
+        return ofx_pitch_check(ctx, "hs", nx);
     };
     return sor_group_entry(ctx, "hs", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
         return ctx->precision == OFX_F64 ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st)
@@ -2327,7 +2329,8 @@ static int brox_single_scale_dev(ofx_ctx *ctx, BroxLevel<T> &L, const BroxParams
 template <typename T>
 static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *const *dI2, int nx, int ny,
                             const BroxParams &P, int nscales, double nu, std::vector<BroxLevel<T>> &lv, ofx_stats *stats,
-                            int kind = -1)                  // kind >= 0: the images are of that element kind (OFX_SRC_*), not T
+                            int kind = -1,                  // kind >= 0: the images are of that element kind (OFX_SRC_*), not T
+                            size_t pitch = 0)               // ... their rows that many bytes apart, 0 = dense
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "brox: group of %d pairs", G);
     std::vector<int> nxs, nys;
@@ -2347,7 +2350,7 @@ static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
         std::vector<T *> lA(nscales), lB(nscales);
         for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }
         OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI1, (const void *const *) dI2, nscales, nu,
-                                          BROX_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind));
+                                          BROX_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind, pitch));
     }
     BroxLevel<T> &C = lv[nscales - 1];
     OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                     // :507-509
@@ -2382,7 +2385,7 @@ static int brox_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const 
 {
     std::vector<BroxLevel<T>> lv;
     OFX_TRY(brox_spatial_dev<T>(ctx, G, (const T *const *) dI1, (const T *const *) dI2, nx, ny, P, nscales, nu, lv, stats,
-                                ofx_src_kind(ctx)));
+                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0));
     const size_t n = (size_t) nx * ny;
     for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) d_flo[g], n));
     return OFX_OK;
@@ -2408,7 +2411,8 @@ extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2
 // S (kind >= 0: in that element kind, OFX_SRC_*), nz interleaved channels each; A, B = the level-0 images, G * nx * ny * nz
 // elements each, pair g at g * nx * ny * nz.
 template <typename T, typename S>
-static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nx, int ny, int nz, T *A, T *B, int kind)
+static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nx, int ny, int nz, T *A, T *B, int kind,
+                                         size_t pitch)         // kind >= 0: bytes between the rows of nx * nz elements, 0 = dense
 {
     const size_t n = (size_t) nx * ny, nc = n * nz;
     double *scr;
@@ -2426,7 +2430,7 @@ static int rexpo_normalise_presmooth_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs
         out.p[2 * g + 1] = B + g * nc;
     }
     if (kind < 0) OFX_TRY((op_normalize_sets<T, S>(ctx, in, out, G, 2, n, nz, scr)));
-    else OFX_TRY(op_normalize_sets_in<T>(ctx, kind, in, out, G, 2, n, nz, scr));
+    else OFX_TRY(op_normalize_sets_in<T>(ctx, kind, in, out, G, 2, nx, ny, pitch, nz, scr));
     // :497-498: gaussian(I, nxx, nyy, nzz, GAUSSIAN_SIGMA) against gaussian(I, xdim, ydim, sigma, boundary_condition, window):
     // sigma = the number of channels, boundary condition (int) 0.8 = Dirichlet, and the buffer is taken for ONE nx x ny plane --
     // so only the first nx * ny elements of each interleaved image are smoothed (across pixels and channels alike)
@@ -2492,7 +2496,7 @@ template <typename T, typename S>
 static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int nz, const BroxParams &P, int nscales, double nu,
                              const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxLevel<T>> &lv,
                              ofx_stats *stats, bool t0_recorded = false,   // the caller has started the pyramid phase's clock
-                             int kind = -1)
+                             int kind = -1, size_t pitch = 0)
 {
     const size_t nc = (size_t) nxs[0] * nys[0] * nz;
     for (int g = 0; g < G; g++) {
@@ -2506,7 +2510,7 @@ static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int n
         OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[s] * nys[s] * nz, &lv[s].I2c));
     }
     if (ctx->profile && !t0_recorded) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    OFX_TRY((rexpo_normalise_presmooth_dev<T, S>(ctx, G, src, nxs[0], nys[0], nz, lv[0].I1c, lv[0].I2c, kind)));  // :494-498
+    OFX_TRY((rexpo_normalise_presmooth_dev<T, S>(ctx, G, src, nxs[0], nys[0], nz, lv[0].I1c, lv[0].I2c, kind, pitch)));  // :494-498
     if (nscales > 1) {
         T *tmpA, *tmpB;                                   // all 2 G images of a level per launch
         OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nc, &tmpA));
@@ -2576,7 +2580,8 @@ static int rexpo_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const
     OfxGroupPtrs src;
     for (int g = 0; g < OFX_MAX_GROUP; g++) { src.a[g] = g < G ? dI1[g] : nullptr; src.b[g] = g < G ? dI2[g] : nullptr; }
     std::vector<BroxLevel<T>> lv;
-    OFX_TRY((rexpo_pyramid_dev<T, T>(ctx, G, src, nz, P, nscales, nu, nxs, nys, lv, stats, false, ofx_src_kind(ctx))));
+    OFX_TRY((rexpo_pyramid_dev<T, T>(ctx, G, src, nz, P, nscales, nu, nxs, nys, lv, stats, false, ofx_src_kind(ctx),
+                                     ofx_src_pitch(ctx, nxs[0] * nz))));
     const size_t n = (size_t) nxs[0] * nys[0];
     for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) d_flo[g], n));
     return OFX_OK;
@@ -2676,7 +2681,7 @@ extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
     auto check = [&]() -> int {
         if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
-        return OFX_OK;
+        return ofx_pitch_check(ctx, "brox", nxx);
     };
     return sor_group_entry(ctx, "brox", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
         return ctx->precision == OFX_F64 ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st)
@@ -2696,7 +2701,8 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
         OFX_TRY(rexpo_check_params(ctx, nzz, method_type, inner_iter, outer_iter));
         if (ctx->input == OFX_IN_RGB8 && nzz != 1)
             return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: OFX_IN_RGB8 frames give one gray channel (nzz = %d); interleaved channels are OFX_IN_U8", nzz);
-        return rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys);
+        OFX_TRY(rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys));
+        return ofx_pitch_check(ctx, "robust_expo", nxx * nzz);
     };
     return sor_group_entry(ctx, "robust_expo", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
         BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter, 0);
@@ -2756,7 +2762,7 @@ static int sor_batch_check(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, const v
     if (!ctxs || n_ctx < 1 || n_pairs < 0 || !a || !b || !c) return OFX_ERR_ARG;
     for (int w = 0; w < n_ctx; w++)
         if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision ||
-            ctxs[w]->input != ctxs[0]->input)
+            ctxs[w]->input != ctxs[0]->input || ctxs[w]->input_pitch != ctxs[0]->input_pitch)
             return OFX_ERR_ARG;
     return OFX_OK;
 }
@@ -3177,7 +3183,7 @@ static int broxt_check(ofx_ctx *ctx, int frames, int nxx, int nyy, int nscales, 
 template <typename T>
 static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const *dF, const BroxParams &P, int nscales, double nu,
                               const std::vector<int> &nxs, const std::vector<int> &nys, std::vector<BroxtLevel<T>> &lv, ofx_stats *stats,
-                              int kind = -1)
+                              int kind = -1, size_t pitch = 0)       // kind >= 0: bytes between the frames' rows, 0 = dense
 {
     const int nx = nxs[0], ny = nys[0], MF = OFX_BROXT_MAX_FRAMES;
     if (kind < 0) kind = ofx_storage_kind(ctx);
@@ -3204,7 +3210,7 @@ static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const
             const int cnt = frames - f0 < MF ? frames - f0 : MF;
             OfxSrcPtrs in = {};
             for (int k = 0; k < cnt; k++) in.p[k] = dF[f0 + k];
-            OFX_TRY(op_minmax_partial_in(ctx, kind, in, 1, cnt, n, 1, mm, f0 / MF, chunks));
+            OFX_TRY(op_minmax_partial_in(ctx, kind, in, 1, cnt, nx, ny, pitch, 1, mm, f0 / MF, chunks));
         }
         OFX_TRY(op_minmax_final(ctx, 1, n, 1, mm, chunks));
         for (int f0 = 0; f0 < frames; f0 += MF) {
@@ -3212,7 +3218,7 @@ static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const
             OfxSrcPtrs in = {};
             OfxDstPtrs out = {};
             for (int k = 0; k < cnt; k++) { in.p[k] = dF[f0 + k]; out.p[k] = lv[0].I + (f0 + k) * n; }
-            OFX_TRY(op_normalize_map_in<T>(ctx, kind, in, out, 1, cnt, n, 1, mm));
+            OFX_TRY(op_normalize_map_in<T>(ctx, kind, in, out, 1, cnt, nx, ny, pitch, 1, mm));
         }
     } else {
         for (int g0 = 0; g0 < G; g0 += per_launch) {
@@ -3220,7 +3226,7 @@ static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const
             OfxSrcPtrs in = {};
             OfxDstPtrs out = {};
             for (int k = 0; k < sets * frames; k++) { in.p[k] = dF[g0 * frames + k]; out.p[k] = lv[0].I + (size_t) (g0 * frames + k) * n; }
-            OFX_TRY(op_normalize_sets_in<T>(ctx, kind, in, out, sets, frames, n, 1, mm + (g0 / per_launch) * mm_doubles));
+            OFX_TRY(op_normalize_sets_in<T>(ctx, kind, in, out, sets, frames, nx, ny, pitch, 1, mm + (g0 / per_launch) * mm_doubles));
         }
     }
     for (int f0 = 0; f0 < planes; f0 += MF) {                                                        // :551-553
@@ -3299,6 +3305,7 @@ static int broxt_dev_check(ofx_ctx *ctx, int n_seq, int frames, const void *cons
     OFX_TRY(broxt_check(ctx, frames, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
     if (frames > OFX_BROXT_MAX_FRAMES)
         return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: %d frames (a device-resident sequence holds at most %d)", frames, OFX_BROXT_MAX_FRAMES);
+    OFX_TRY(ofx_pitch_check(ctx, "brox temporal", nxx));
     return broxt_check_ptrs(ctx, n_seq, frames, dF, d_flo);
 }
 
@@ -3308,7 +3315,7 @@ static int broxt_devapi(ofx_ctx *ctx, int G, int frames, const void *const *dF, 
                         double nu, const std::vector<int> &nxs, const std::vector<int> &nys, ofx_stats *stats)
 {
     std::vector<BroxtLevel<T>> lv;
-    OFX_TRY(broxt_sequence_dev<T>(ctx, G, frames, dF, P, nscales, nu, nxs, nys, lv, stats, ofx_src_kind(ctx)));
+    OFX_TRY(broxt_sequence_dev<T>(ctx, G, frames, dF, P, nscales, nu, nxs, nys, lv, stats, ofx_src_kind(ctx), ofx_src_pitch(ctx, nxs[0])));
     const size_t n = (size_t) nxs[0] * nys[0];
     const int fields = G * (frames - 1);
     for (int f0 = 0; f0 < fields; f0 += OFX_BROXT_MAX_FRAMES) {
@@ -3386,8 +3393,9 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
     ofx_ctx *ctx = ctxs[0];
     OFX_ENTER(ctx);
     for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctx->device || ctxs[w]->precision != ctx->precision || ctxs[w]->input != ctx->input)
-            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: context %d NULL, on another device, of another precision or \"input\"", w);
+        if (!ctxs[w] || ctxs[w]->device != ctx->device || ctxs[w]->precision != ctx->precision || ctxs[w]->input != ctx->input ||
+            ctxs[w]->input_pitch != ctx->input_pitch)
+            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: context %d NULL, on another device, of another precision, \"input\" or \"input_pitch\"", w);
     if (n_seq < 1) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: %d sequences", n_seq);
     std::vector<int> nxs, nys;
     OFX_TRY(broxt_dev_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));

@@ -1843,7 +1843,7 @@ static void stats_begin(ofx_stats *st, int nscales, int nsolves)
 template <typename T>
 static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T *const *dI1, int nxx, int nyy,
                                const Tvl1Params &P, int nscales, double zfactor, std::vector<Tvl1Level<T>> &lv,
-                               ofx_stats *stats, int kind = -1)
+                               ofx_stats *stats, int kind = -1, size_t pitch = 0)      // pitch: bytes between the frames' rows, 0 = dense
 {
     if (P.warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", P.warps);
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: group of %d pairs", G);
@@ -1865,7 +1865,8 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
         std::vector<T *> lA(nscales), lB(nscales);
         for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I0; lB[s] = lv[s].I1; }
         OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI0, (const void *const *) dI1, nscales, zfactor,
-                                          TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind));
+                                          TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind,
+                                          pitch));
     }
     Tvl1Level<T> &C = lv[nscales - 1];
     OFX_TRY(op_fill2<T>(ctx, C.U[0], C.n() * G));                                                // :278-280
@@ -2003,6 +2004,10 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
 {
     const size_t n = (size_t) nx * ny;
     const int kind = ofx_src_kind(ctx);                      // the frames come in the context's "input" kind
+    OFX_TRY(ofx_pitch_check(ctx, "tvl1", nx));
+    const size_t pitch = nx > 0 ? ofx_src_pitch(ctx, nx) : 0;
+    // a frame's bytes as they lie: with a pitch, from its first row's start to its last row's end
+    const size_t span = pitch && ny > 0 ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
     // Images and payloads that do not live on this context's GPU (a batch spread over several GPUs by ofx_tvl1_batch_dev, or
     // host buffers) are staged: in through arena buffers before the solve, out after it, all on the context's stream.
     const void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
@@ -2012,9 +2017,9 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
         const void **dst[2] = {&dI0[g], &dI1[g]};
         for (int k = 0; k < 2; k++) {
             if (ofx_ptr_is_local(ctx, src[k])) { *dst[k] = src[k]; continue; }
-            char *stage;                                     // sized by the source element
-            OFX_TRY(ofx_alloc(ctx, n * ofx_src_bytes(kind), &stage));
-            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], n * ofx_src_bytes(kind)));
+            char *stage;                                     // sized by the source element; a pitched frame keeps its pitch
+            OFX_TRY(ofx_alloc(ctx, span, &stage));
+            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], span));
             *dst[k] = stage;
         }
         d_flo[g] = d_flo_in[g];
@@ -2026,7 +2031,7 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
     }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv,
-                                   stats, kind));
+                                   stats, kind, pitch));
     OfxGroupPtrs out;
     for (int g = 0; g < OFX_MAX_GROUP; g++) { out.a[g] = g < G ? d_flo[g] : nullptr; out.b[g] = nullptr; }
     hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
@@ -2278,7 +2283,9 @@ extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
     // are not on its context's GPU is staged there and its payloads are copied back into the caller's arrays (tvl1_group_devapi)
     // -- the C caller's multi-GPU path, no launcher and no collective library needed (pairs are independent).
     for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input) return OFX_ERR_ARG;
+        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input ||
+            ctxs[w]->input_pitch != ctxs[0]->input_pitch)
+            return OFX_ERR_ARG;
     const int G = ofx_tvl1_batch_group_size(ctxs, n_ctx, n_pairs, nx, ny, nscales, zfactor);
     if (G < 1) return G < 0 ? -G : OFX_ERR_ARG;                 // negative = -status of the failing check
     const int n_groups = (n_pairs + G - 1) / G;
