@@ -117,6 +117,34 @@ OFX_DEV double rcp_tol(double d)
     return __builtin_fma(r, e, r);
 #endif
 }
+// The f64 tolerance mode (T = double, STRICT = false) goes further: its three bars (AEPE < 1e-8 against strict, equal iteration
+// tables, 3e-13 against the oracle's restatement) do not ask for the reference's association order, and the marching kernels
+// pay for every VALU instruction.  So in that instantiation ONLY -- the strict one is the reference bit for bit, and float
+// storage is pinned to its restatement at 0 ulps, where a moved double rounding can move a float one: both keep their
+// expressions as they were --
+//  * every a * b + c of the two stages and of the error term is an explicit FMA (the library is built -ffp-contract=off);
+//  * the thresholding is a clamp: with fi = -rho / grad the reference's three cases rho < -l_t grad, rho > l_t grad, otherwise are
+//    d = clamp(fi, -l_t, +l_t) (I1wx, I1wy) -- where the choice of the case can differ (|rho| within 2^-45 of the threshold) the
+//    cases agree to 2^-45.  No l_t grad, no compares against it, no products +-l_t I1w, one select instead of a three-way one
+//    over two doubles;
+//  * the flat-pixel rule (grad < TVL1_GRAD_IS_ZERO and |rho| <= l_t grad: d = 0) is kept exactly: where grad is below the
+//    threshold and the clamp did not bite, the factor is 0.  grad is clamped to 2^-600 before the reciprocal, so fi is finite
+//    at grad = 0, where d = (anything finite) * 0 = 0 as in the reference.
+template <typename T, bool STRICT> constexpr bool TVL1_TOL64 = !STRICT && std::is_same<T, double>::value;
+// clamp(x, -lim, +lim) with `lim` a kernel argument: fmin(fmax(x, -lim), lim) first quiets an argument it cannot know to be no
+// signalling NaN -- two canonical copies of +-lim in four VGPRs for the whole march, which k_tvl1_iter4 does not have (8 bytes
+// of scratch at 168).  The instructions themselves take the limit, and its negation, straight from the scalar registers.
+OFX_DEV double clamp_uniform(double x, double lim)
+{
+    double lo, r;
+    asm("v_max_f64 %0, %1, -%2" : "=v"(lo) : "v"(x), "s"(lim));
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(lo), "s"(lim));
+    return r;
+}
+
+// |u_new - u|^2 at one pixel, the term of the convergence error (src/tvl1flow.cpp:159-160), in the f64 tolerance mode; the other
+// instantiations keep the reference's expression where they had it, behind the constant TVL1_TOL64 test
+OFX_DEV double du2_fma(double2 un, double2 u) { return __builtin_fma(un.y - u.y, un.y - u.y, (un.x - u.x) * (un.x - u.x)); }
 
 // Stage "primal" at one pixel: thresholding TH (src/tvl1flow.cpp:117-143), divergence of p
 // (src/operators.cpp:35-78) and u = v + theta div p (:156-157).  l11/l21 = p11/p21 of the left pixel,
@@ -134,6 +162,16 @@ OFX_DEV double2 tvl1_primal(double2 u, double2 a, double r, double2 p1, double2 
     const double div1 = div_backward(p1.x, l11, p1.y, up12, lef, rig, top, bot);
     const double div2 = div_backward(p2.x, l21, p2.y, up22, lef, rig, top, bot);
     const double ix = a.x, iy = a.y;
+    if constexpr (TVL1_TOL64<T, STRICT>) {
+        // the clamp form (above): d = clamp(fi, -l_t, l_t) (I1wx, I1wy), zero where the gradient is flat and the clamp idle
+        const double grad = __builtin_fma(iy, iy, ix * ix);
+        const double rho = __builtin_fma(iy, u.y, __builtin_fma(ix, u.x, r));
+        const double fi = -rho * rcp_tol(fmax(grad, 0x1p-600));
+        double fic = clamp_uniform(fi, l_t);
+        fic = (grad < TVL1_GRAD_IS_ZERO && fic == fi) ? 0.0 : fic;
+        return make_double2(__builtin_fma(theta, div1, __builtin_fma(fic, ix, u.x)),
+                            __builtin_fma(theta, div2, __builtin_fma(fic, iy, u.y)));
+    }
     const double grad = ix * ix + iy * iy;                  // :100-104
     const double rho = r + (ix * u.x + iy * u.y);           // :119-120
     const double ltg = l_t * grad;
@@ -177,7 +215,8 @@ OFX_DEV double div_by_rcp(double n, double d, double r)
 // the double arithmetic buys nothing; hypot is sqrt(x*x + y*y) and each denominator is inverted once
 // (2 divisions instead of 6 per pixel).  This stage is ~60 % of the kernel's VALU work, and the kernel is
 // VALU-bound, so the fast mode runs ~1.5x faster; AEPE vs the double reference stays ~1e-5 (tests).
-// STRICT = false with T = double is the "tolerance" mode (option "relaxed_dual"): double storage, the fast mode's dual stage.
+// STRICT = false with T = double is the "tolerance" mode (option "relaxed_dual"): double storage, the fast mode's dual stage with
+// its a * b + c as FMAs (TVL1_TOL64, above).
 template <typename T, bool STRICT>
 OFX_DEV void tvl1_dual(double2 p1, double2 p2, double2 un, double r1, double r2, double2 dn, bool rig, bool lastrow,
                        double taut, double2 &q1, double2 &q2)
@@ -227,6 +266,16 @@ OFX_DEV void tvl1_dual(double2 p1, double2 p2, double2 un, double r1, double r2,
         q2.x = (p2.x + taut * u2x) / ng2;
         q2.y = (p2.y + taut * u2y) / ng2;
 #endif
+    } else if constexpr (TVL1_TOL64<T, STRICT>) {
+        // the f64 tolerance mode: the stage below with its eight a * b + c as FMAs
+        const double g1 = sqrt_tol(fmax(__builtin_fma(u1x, u1x, u1y * u1y), 0x1p-600));
+        const double g2 = sqrt_tol(fmax(__builtin_fma(u2x, u2x, u2y * u2y), 0x1p-600));
+        const double i1 = rcp_tol(__builtin_fma(taut, g1, 1.0));
+        const double i2 = rcp_tol(__builtin_fma(taut, g2, 1.0));
+        q1.x = __builtin_fma(taut, u1x, p1.x) * i1;
+        q1.y = __builtin_fma(taut, u1y, p1.y) * i1;
+        q2.x = __builtin_fma(taut, u2x, p2.x) * i2;
+        q2.y = __builtin_fma(taut, u2y, p2.y) * i2;
     } else {
         // no bit-exactness to keep here: the square root and the reciprocal are one refinement step on the rsq / rcp estimates
         // (sqrt_tol / rcp_tol, ~2^-45), without range scaling and fix-ups -- the clamp keeps rsq finite at |grad u| = 0, where
@@ -381,7 +430,8 @@ __global__ __launch_bounds__(256) OFX_ITER1_ATTR void k_tvl1_iter(
                                         l_t, theta);
             if (owner && y < yend) {
                 st_u = so;
-                acc += (un.x - cur.u.x) * (un.x - cur.u.x) + (un.y - cur.u.y) * (un.y - cur.u.y);   // :159-160
+                acc += TVL1_TOL64<T, STRICT> ? du2_fma(un, cur.u)   // :159-160
+                    : (un.x - cur.u.x) * (un.x - cur.u.x) + (un.y - cur.u.y) * (un.y - cur.u.y);
             }
         }
         double2 q1 = make_double2(0.0, 0.0), q2 = q1;
@@ -475,7 +525,8 @@ OFX_DEV void tvl1_iter2_march(const typename Pix<T>::v2 *__restrict__ Uin, const
             uA0 = tvl1_primal<T, STRICT>(cur.u, cur.a, cur.r, cur.p1, cur.p2, l11, l21, up12, up22, lef, rig, y == 0,
                                          y == ny - 1, l_t, theta);
             if (owner && y >= y0 && y < yend) {
-                accA += (uA0.x - cur.u.x) * (uA0.x - cur.u.x) + (uA0.y - cur.u.y) * (uA0.y - cur.u.y);
+                accA += TVL1_TOL64<T, STRICT> ? du2_fma(uA0, cur.u)
+                    : (uA0.x - cur.u.x) * (uA0.x - cur.u.x) + (uA0.y - cur.u.y) * (uA0.y - cur.u.y);
                 sa1 = so;
             }
         }
@@ -498,7 +549,8 @@ OFX_DEV void tvl1_iter2_march(const typename Pix<T>::v2 *__restrict__ Uin, const
                                          y - 2 == ny - 1, l_t, theta);
             if (owner && y - 2 < yend) {
                 st3 = so - 2 * row2;
-                accB += (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
+                accB += TVL1_TOL64<T, STRICT> ? du2_fma(uB0, uA2)
+                    : (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
             }
         }
         // S4: p_B(y-3)
@@ -717,7 +769,8 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
             uA0 = tvl1_primal<T, STRICT>(cur.u, cur.a, cur.r, cur.p1, cur.p2, l11, l21, up12, up22, lef, rig, G && y == 0,
                                          G && y == nyl, l_t, theta);
             const bool mine = owner && y >= y0 && y < yend;
-            const double dA = (uA0.x - cur.u.x) * (uA0.x - cur.u.x) + (uA0.y - cur.u.y) * (uA0.y - cur.u.y);
+            const double dA = TVL1_TOL64<T, STRICT> ? du2_fma(uA0, cur.u)
+                : (uA0.x - cur.u.x) * (uA0.x - cur.u.x) + (uA0.y - cur.u.y) * (uA0.y - cur.u.y);
             accA += mine ? dA : 0.0;
             if constexpr (!G) pin_here(accA);
             if (CNT == 1 && mine) { stu = so; su = uA0; }
@@ -752,7 +805,8 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
                 uB0 = tvl1_primal<T, STRICT>(uA2, ad, rd, pA1a, pA1b, l11, l21, pA2a.y, pA2b.y, lef, rig, G && y - 2 == 0,
                                              G && y - 2 == nyl, l_t, theta);
                 const bool mine = owner && y - 2 >= y0 && y - 2 < yend;
-                const double dB = (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
+                const double dB = TVL1_TOL64<T, STRICT> ? du2_fma(uB0, uA2)
+                    : (uB0.x - uA2.x) * (uB0.x - uA2.x) + (uB0.y - uA2.y) * (uB0.y - uA2.y);
                 accB += mine ? dB : 0.0;
                 if constexpr (!G) pin_here(accB);
                 if (CNT == 2 && mine) { stu = so - 2 * row2; su = uB0; }
@@ -781,7 +835,8 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
                 uC0 = tvl1_primal<T, STRICT>(uB2, ad, rd, pB1a, pB1b, l11, l21, pB2a.y, pB2b.y, lef, rig, G && y - 4 == 0,
                                              G && y - 4 == nyl, l_t, theta);
                 const bool mine = owner && y - 4 >= y0 && y - 4 < yend;
-                const double dC = (uC0.x - uB2.x) * (uC0.x - uB2.x) + (uC0.y - uB2.y) * (uC0.y - uB2.y);
+                const double dC = TVL1_TOL64<T, STRICT> ? du2_fma(uC0, uB2)
+                    : (uC0.x - uB2.x) * (uC0.x - uB2.x) + (uC0.y - uB2.y) * (uC0.y - uB2.y);
                 accC += mine ? dC : 0.0;
                 if constexpr (!G) pin_here(accC);
                 if (CNT == 3) {
@@ -814,7 +869,8 @@ OFX_DEV void tvl1_iter3_march(const typename Pix<T>::v2 *__restrict__ Uin, const
                 uD0 = tvl1_primal<T, STRICT>(uC2, ad, rd, pC1a, pC1b, l11, l21, pC2a.y, pC2b.y, lef, rig, G && y - 6 == 0,
                                              G && y - 6 == nyl, l_t, theta);
                 const bool mine = owner && y - 6 < yend;
-                const double dD = (uD0.x - uC2.x) * (uD0.x - uC2.x) + (uD0.y - uC2.y) * (uD0.y - uC2.y);
+                const double dD = TVL1_TOL64<T, STRICT> ? du2_fma(uD0, uC2)
+                    : (uD0.x - uC2.x) * (uD0.x - uC2.x) + (uD0.y - uC2.y) * (uD0.y - uC2.y);
                 accD += mine ? dD : 0.0;
                 if constexpr (!G) pin_here(accD);
                 stu = mine ? so - 6 * row2 : stu;
@@ -1081,7 +1137,8 @@ __global__ __launch_bounds__(64 * TILE_RH) void k_tvl1_tile(
             const double2 up = s_p[it & 1][w > 0 ? w - 1 : 0][lane];     // row 0 of the region: halo (or the image's top row)
             const double l11 = wave_shift_up(p1.x), l21 = wave_shift_up(p2.x);
             const double2 un = tvl1_primal<T, STRICT>(u, a, r, p1, p2, l11, l21, up.x, up.y, lef, rig, top, bot, l_t, theta);
-            if (owner) acc[it] = (un.x - u.x) * (un.x - u.x) + (un.y - u.y) * (un.y - u.y);   // :159-160
+            if (owner) acc[it] = TVL1_TOL64<T, STRICT> ? du2_fma(un, u)   // :159-160
+                : (un.x - u.x) * (un.x - u.x) + (un.y - u.y) * (un.y - u.y);
             s_u[it & 1][w][lane] = un;
             __syncthreads();
             const double2 dn = s_u[it & 1][w < TILE_RH - 1 ? w + 1 : w][lane];
