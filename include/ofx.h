@@ -185,7 +185,7 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
 int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
 
 /* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
- * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
+ * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_tvl1_bidir_group_dev / _bidir_batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
  * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev and ofx_pyramid_group_dev -- read
  * elements of this kind wherever their
@@ -339,6 +339,53 @@ int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, 
  * -OFX_ERR_SIGMA for a pyramid that cannot be built) on error. */
 int ofx_tvl1_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, int nx, int ny, int nscales,
                               double zfactor);
+
+/* Forward-backward consistency of two .flo payloads, from any solver (Sundaram, Brox, Keutzer, ECCV 2010): the per-pixel
+ * occlusion / reliability maps of n_pairs >= 1 pairs of flow fields, both directions, on the device.
+ * d_flo_fwd[g], d_flo_bwd[g]: payloads as every *_dev solver writes them, nx * ny interleaved (u, v) float32, 8-byte aligned; the
+ * forward one is A -> B on A's grid, the backward one B -> A on B's grid.  d_occ_fwd[g], d_occ_bwd[g]: nx * ny bytes each, at ANY
+ * byte alignment, written dense; 255 = the vector fails the check, 0 = it passes (the convention of the tvl1occ maps).  No byte
+ * outside a map's nx * ny is written.  The pointers are DEVICE memory of the context's GPU, used in place; a payload or a map
+ * that lives elsewhere (pinned or pageable host memory, another GPU) is staged through the context's workspace as
+ * ofx_tvl1_batch_dev stages its buffers -- the front-end's route, at the cost of the copies.
+ * The forward map at row i, column j, in double, every operation rounded, nothing contracted, association as written:
+ *     u = F[i][j].x, v = F[i][j].y;  xt = j + u, yt = i + v
+ *     255 unless 0 <= xt <= nx - 1 and 0 <= yt <= ny - 1         (the vector leaves the image; NaN and Inf land here)
+ *     (bu, bv) = bicubic_interpolation_at_color(B, xt, yt, nx, ny, 2, 0 / 1, false), B = the backward payload as a 2-channel
+ *                interleaved image (src/bicubic_interpolation.h:30-43: Neumann boundary, the reference's tap rule)
+ *     du = u + bu, dv = v + bv
+ *     0 if du du + dv dv <= alpha ((u u + v v) + (bu bu + bv bv)) + beta, else 255                   (a NaN anywhere: 255)
+ * and the backward map is the same with the payloads exchanged.  The paper's thresholds are alpha = 0.01, beta = 0.5.  A pure
+ * function of the float payloads: the same bytes in every precision and mode.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: a NULL table or entry, n_pairs < 1, nx < 2 or
+ * ny < 2 (or nx * ny beyond an int), alpha or beta negative or not finite, a payload that is not 8-byte aligned.
+ * Asynchronous on the context's stream. */
+int ofx_flow_consistency_dev(ofx_ctx *ctx, int n_pairs, const void *const *d_flo_fwd, const void *const *d_flo_bwd,
+                             void *const *d_occ_fwd, void *const *d_occ_bwd, int nx, int ny, double alpha, double beta);
+
+/* TV-L1 in both directions with the consistency maps: n_pairs (1..8) pairs in 2 * n_pairs lockstep slots of ONE context -- slot g
+ * solves (dI0[g], dI1[g]), slot n_pairs + g solves (dI1[g], dI0[g]) -- over one pyramid: image_normalization_2 takes its
+ * min / max over both images, so each image is normalised, presmoothed and zoomed once and serves as first image of one slot
+ * and second image of the other.  d_flo_fwd[g] is BIT FOR BIT what ofx_tvl1_multiscale_dev(dI0[g], dI1[g]) writes, d_flo_bwd[g]
+ * what ofx_tvl1_multiscale_dev(dI1[g], dI0[g]) writes, with equal iteration tables, in every mode and under every option.
+ * d_occ_fwd[g], d_occ_bwd[g]: the maps of ofx_flow_consistency_dev(alpha = fb_alpha, beta = fb_beta) on those payloads, written
+ * by one launch for all slots.  Frames as ofx_tvl1_group_dev reads them (options "input", "input_pitch"); frames, payloads and
+ * maps that are not on the context's GPU are staged as ofx_tvl1_batch_dev stages them.  stats_out: optional, 2 * n_pairs
+ * records, the forward slots first.  Refusals (OFX_ERR_ARG before any work): those of ofx_tvl1_group_dev and of
+ * ofx_flow_consistency_dev; a group size outside 1..8 names the limit.  Asynchronous like ofx_tvl1_group_dev. */
+int ofx_tvl1_bidir_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
+                             void *const *d_flo_fwd, void *const *d_flo_bwd, void *const *d_occ_fwd, void *const *d_occ_bwd,
+                             int nx, int ny, double tau, double lambda, double theta, int nscales, double zfactor, int warps,
+                             double epsilon, double fb_alpha, double fb_beta, ofx_stats *stats_out);
+/* ... a batch of them, with the shape of ofx_tvl1_batch_dev: groups of consecutive pairs, group q on ctxs[q % n_ctx], one host
+ * thread per context, the contexts agreeing on precision, "input" and "input_pitch"; the first failing group's status is
+ * returned.  Option "lockstep" counts SLOTS: a group holds max(1, lockstep / 2) pairs, else
+ * max(1, ofx_tvl1_batch_group_size(ctxs, n_ctx, 2 * n_pairs, ...) / 2).  work_pix_iters: optional, 2 * n_pairs doubles, the forward
+ * solves first, then the backward ones. */
+int ofx_tvl1_bidir_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                             void *const *d_flo_fwd, void *const *d_flo_bwd, void *const *d_occ_fwd, void *const *d_occ_bwd,
+                             int n_pairs, int nx, int ny, double tau, double lambda, double theta, int nscales, double zfactor,
+                             int warps, double epsilon, double fb_alpha, double fb_beta, double *work_pix_iters);
 
 /* Fixed-work inner loop only (src/tvl1flow.cpp:113-182 run exactly n_iter times on linearised
  * data, all arrays host double planes; u/p updated in place).  Returns the last error in *error.

@@ -126,6 +126,11 @@ def lib():
         "ofx_tvl1_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, _d,
                                     _i, _d, _i, _d, C.POINTER(_d)]),
         "ofx_tvl1_batch_group_size": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _d]),
+        "ofx_flow_consistency_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d]),
+        "ofx_tvl1_bidir_group_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _d, _d, _d, _i, _d, _i, _d, _d, _d,
+                                                                             C.POINTER(Stats)]),
+        "ofx_tvl1_bidir_batch_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _i, _d, _d, _d, _i, _d, _i, _d, _d,
+                                                                                        _d, C.POINTER(_d)]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9 + [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
         "ofx_hs_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _i, _d, _i, _i]),
         "ofx_hs_pyramidal": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _i, _d, _i, _d, _i, _i]),
@@ -206,6 +211,22 @@ def tvl1_batch_dev(ctxs, dI0, dI1, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3,
     if s:
         raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
     return [work[i] for i in range(n)]
+
+
+def tvl1_bidir_batch_dev(ctxs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, tau=0.25, lam=0.15, theta=0.3,
+                         nscales=5, zfactor=0.5, warps=5, epsilon=0.01, fb_alpha=0.01, fb_beta=0.5):
+    """ofx_tvl1_bidir_batch_dev: TV-L1 in both directions with the forward-backward consistency maps, lists of pointers (ints),
+    one entry per pair; groups of consecutive pairs, group q on ctxs[q % len(ctxs)].  Returns the work (pixel-iterations) of
+    the forward solves followed by that of the backward solves."""
+    n = len(dI0)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(2 * n, 1))()
+    s = lib().ofx_tvl1_bidir_batch_dev(arr([c.h.value for c in ctxs]), len(ctxs), arr(dI0), arr(dI1), arr(d_flo_fwd),
+                                       arr(d_flo_bwd), arr(d_occ_fwd), arr(d_occ_bwd), n, nx, ny, tau, lam, theta, nscales,
+                                       zfactor, warps, epsilon, fb_alpha, fb_beta, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(2 * n)]
 
 
 def _batch_call(fn, ctxs, dA, dB, d_flo, *args):
@@ -580,6 +601,27 @@ class Ofx:
         self._ck(self.L.ofx_tvl1_group_dev(self.h, n, arr(dI0), arr(dI1), arr(d_flo), nx, ny, tau, lam, theta, nscales,
                                            zfactor, warps, epsilon, st))
         return [st[i] for i in range(n)]
+
+    def flow_consistency_dev(self, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, alpha=0.01, beta=0.5):
+        """ofx_flow_consistency_dev: lists of device pointers (ints), one entry per pair of .flo payloads (from any solver);
+        writes the forward and the backward consistency map (bytes, 255 = fails) of every pair.  Enqueues on the context's
+        stream."""
+        n = len(d_flo_fwd)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_consistency_dev(self.h, n, arr(d_flo_fwd), arr(d_flo_bwd), arr(d_occ_fwd), arr(d_occ_bwd), nx, ny,
+                                                 alpha, beta))
+
+    def tvl1_bidir_group_dev(self, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, tau=0.25, lam=0.15, theta=0.3,
+                             nscales=5, zfactor=0.5, warps=5, epsilon=0.01, fb_alpha=0.01, fb_beta=0.5):
+        """ofx_tvl1_bidir_group_dev: 1..8 pairs solved in both directions in lockstep over one pyramid, payloads and consistency
+        maps of both directions.  Returns 2 * len(dI0) Stats records, the forward solves first."""
+        n = len(dI0)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(2 * n, 1))()
+        self._ck(self.L.ofx_tvl1_bidir_group_dev(self.h, n, arr(dI0), arr(dI1), arr(d_flo_fwd), arr(d_flo_bwd), arr(d_occ_fwd),
+                                                 arr(d_occ_bwd), nx, ny, tau, lam, theta, nscales, zfactor, warps, epsilon,
+                                                 fb_alpha, fb_beta, st))
+        return [st[i] for i in range(2 * n)]
 
     def _group_call(self, fn, dA, dB, d_flo, *args):
         n = len(dA)

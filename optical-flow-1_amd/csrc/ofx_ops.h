@@ -157,7 +157,26 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
                            T *tmpB, double *scr, int kind = -1,        // kind: OFX_SRC_* of dA / dB; -1 = the storage type
                            size_t pitch = 0);                          // kind >= 0: bytes between the rows of dA / dB, 0 = dense
 
-#define OFX_LAUNCH_CHECK(ctx)                                                                    \
+// ---- buffers that are not on the context's GPU (ofx_tvl1.hip) ----
+// is p device memory of this context's GPU?  Everything else is reached through a staging copy:
+bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p);
+// dst <- src, one of them on this context's GPU, the other anywhere (ofx_staging_route), on the context's stream
+int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes);
+
+// ---- forward-backward consistency of .flo payloads (ofx_flow.hip) ----
+// slot z of a launch: payload f[z] checked against payload b[z] into the byte map occ[z] (any alignment)
+struct OfxFlowSlots {
+    const float2  *f[OFX_MAX_GROUP];
+    const float2  *b[OFX_MAX_GROUP];
+    unsigned char *occ[OFX_MAX_GROUP];
+};
+// sizes and thresholds every entry refuses before any work (OFX_ERR_ARG, `who` opens the message)
+int op_flow_consistency_check(ofx_ctx *ctx, const char *who, int nx, int ny, double alpha, double beta);
+// slots <= OFX_MAX_GROUP maps in one launch; the pointers are memory of the context's GPU, the payloads 8-byte aligned
+int op_flow_consistency(ofx_ctx *ctx, int slots, const void *const *f, const void *const *b, void *const *occ, int nx, int ny,
+                        double alpha, double beta);
+
+#define OFX_LAUNCH_CHECK(ctx)                                                                   \
     do {                                                                                         \
         hipError_t e__ = hipGetLastError();                                                      \
         if (e__ != hipSuccess)                                                                   \

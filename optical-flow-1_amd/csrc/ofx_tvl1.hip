@@ -1351,6 +1351,9 @@ template <typename T> struct Tvl1Level {
     using v2 = typename Pix<T>::v2;
     using v4 = typename Pix<T>::v4;
     int nx, ny, G;
+    int shared;     // 0: pair g warps I1[g] towards I0[g].  > 0: a bidirectional group of `shared` pairs in G = 2 * shared slots over
+                    // ONE set of planes, I0 = [A_0 .. A_{shared-1}, B_0 .. B_{shared-1}]; slot g's second image is plane
+                    // (g + shared) % G of I0, and there is no I1
     T  *I0, *I1;
     v2 *pa;         // (I1, I1x): gathered by the warp
     T  *pb;         // I1y
@@ -1374,18 +1377,19 @@ struct Tvl1Params {
     bool fixed;     // run exactly max_iter iterations (stopping test disabled)
 };
 
-template <typename T> static int tvl1_level_alloc(ofx_ctx *ctx, Tvl1Level<T> &L, int nx, int ny, int G, bool images)
+template <typename T> static int tvl1_level_alloc(ofx_ctx *ctx, Tvl1Level<T> &L, int nx, int ny, int G, bool images, int shared = 0)
 {
     const size_t n = (size_t) nx * ny * G;
     L.nx = nx;
     L.ny = ny;
     L.G = G;
+    L.shared = shared;
     L.cur = 0;
     for (int g = 0; g < OFX_MAX_GROUP; g++) L.last_n[g] = 0;
     L.I0 = L.I1 = nullptr;
     if (images) {
         OFX_TRY(ofx_alloc(ctx, n, &L.I0));
-        OFX_TRY(ofx_alloc(ctx, n, &L.I1));
+        if (!shared) OFX_TRY(ofx_alloc(ctx, n, &L.I1));
     }
     OFX_TRY(ofx_alloc(ctx, n, &L.pa));
     OFX_TRY(ofx_alloc(ctx, n, &L.pb));
@@ -1846,7 +1850,14 @@ static int tvl1_single_scale_dev(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params
     const dim3 g2(ofx_cdiv(nx, OFX_WARP_BX), ofx_cdiv(ny, OFX_WARP_BY), G), b2(OFX_WARP_BX, OFX_WARP_BY);
     if (nx < 2 || ny < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: level %dx%d too small", nx, ny);
 
-    OFX_TRY(op_grad_pack<T>(ctx, L.I1, L.pa, L.pb, nx, ny, G));                                                    // :84
+    if (!L.shared) {
+        OFX_TRY(op_grad_pack<T>(ctx, L.I1, L.pa, L.pb, nx, ny, G));                                                // :84
+    } else {
+        // the only reader of a slot's second image: the forward slots take the B planes, the backward slots the A planes
+        const size_t half = n * L.shared;
+        OFX_TRY(op_grad_pack<T>(ctx, L.I0 + half, L.pa, L.pb, nx, ny, L.shared));
+        OFX_TRY(op_grad_pack<T>(ctx, L.I0, L.pa + half, L.pb + half, nx, ny, L.shared));
+    }
     // p = 0 in the buffer each pair's u lives in (:87-90)
     for (int h = 0; h < 3; h++) {
         bool used = false;
@@ -1897,11 +1908,18 @@ static void stats_begin(ofx_stats *st, int nscales, int nsolves)
 
 // src/tvl1flow.cpp:219-328 for G pairs in lockstep.  dI0[g] / dI1[g]: device images of storage type T, or with kind >= 0
 // of that element kind (OFX_SRC_*).  On success lv[0].U[half of lv[0].cur] holds the flows.
+// shared > 0: both directions of `shared` pairs in G = 2 * shared slots -- slot g solves (dI0[g], dI1[g]), slot shared + g
+// solves (dI1[g], dI0[g]) -- over ONE pyramid: image_normalization_2 takes min / max over both images of a pair, the Gaussian
+// and the zoom act on each plane alone, so the planes of (A, B) ARE the planes of (B, A) and each image is built once
+// (Tvl1Level::shared).  Everything after the pyramid is what a group of G pairs runs.
 template <typename T>
 static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T *const *dI1, int nxx, int nyy,
                                const Tvl1Params &P, int nscales, double zfactor, std::vector<Tvl1Level<T>> &lv,
-                               ofx_stats *stats, int kind = -1, size_t pitch = 0)      // pitch: bytes between the frames' rows, 0 = dense
+                               ofx_stats *stats, int kind = -1, size_t pitch = 0,      // pitch: bytes between the frames' rows, 0 = dense
+                               int shared = 0)
 {
+    const int Gp = shared ? shared : G;                 // pairs whose images the pyramid builds
+    if (shared && G != 2 * shared) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: %d slots for %d bidirectional pairs", G, shared);
     if (P.warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", P.warps);
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: group of %d pairs", G);
 
@@ -1912,16 +1930,16 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
-    for (int s = 0; s < nscales; s++) OFX_TRY(tvl1_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true));
+    for (int s = 0; s < nscales; s++) OFX_TRY(tvl1_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true, shared));
     {                                                                                              // :255-275
         T *tmpA, *tmpB;
         double *scr;
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nxx * nyy, &tmpA));
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nxx * nyy, &tmpB));
-        OFX_TRY(ofx_alloc(ctx, (size_t) G * op_pyramid_scratch_doubles(), &scr));
+        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * Gp * nxx * nyy, &tmpA));
+        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * Gp * nxx * nyy, &tmpB));
+        OFX_TRY(ofx_alloc(ctx, (size_t) Gp * op_pyramid_scratch_doubles(), &scr));
         std::vector<T *> lA(nscales), lB(nscales);
-        for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I0; lB[s] = lv[s].I1; }
-        OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI0, (const void *const *) dI1, nscales, zfactor,
+        for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I0; lB[s] = shared ? lv[s].I0 + (size_t) shared * lv[s].n() : lv[s].I1; }
+        OFX_TRY(op_build_pyramid_group<T>(ctx, Gp, (const void *const *) dI0, (const void *const *) dI1, nscales, zfactor,
                                           TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind,
                                           pitch));
     }
@@ -2004,7 +2022,7 @@ extern "C" int ofx_tvl1_multiscale(ofx_ctx *ctx, const double *I0, const double 
 // G device-resident pairs in lockstep; stats = G records
 // Is p device memory of this context's GPU?  Everything else -- another GPU's memory, pinned or pageable host memory -- is
 // reached through a staging copy (hipMemcpyDefault resolves the direction; between GPUs it is a peer copy over xGMI).
-static bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p)
+bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p)
 {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
@@ -2025,7 +2043,7 @@ extern "C" int ofx_staging_route(int ctx_device, int mem_device, int can_access_
 }
 // dst <- src (one of them on this context's GPU, the other anywhere), on the context's stream.  A route-2 copy is synchronous
 // and leaves a note in ofx_last_error (the call still succeeds).  UNEXECUTED on more than one GPU (no multi-GPU box in any round).
-static int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
+int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
     const void *other = ofx_ptr_is_local(ctx, dst) ? src : dst;
     int mem_device = -1, can = 1;
@@ -2133,6 +2151,101 @@ extern "C" int ofx_tvl1_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *
                 : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st);
     const double ms = ofx_now_ms() - t0;
     for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
+    ctx->stats = st[0];
+    return s;
+}
+
+// Both directions of Gp pairs in 2 Gp lockstep slots over one pyramid (tvl1_multiscale_dev, shared = Gp), then the payloads and,
+// from them, the forward-backward consistency maps (ofx_flow.hip) in one launch.  stats = 2 Gp records, forward slots first.
+// Frames, payloads and maps that are not on this context's GPU are staged as tvl1_group_devapi stages them.
+template <typename T>
+static int tvl1_bidir_devapi(ofx_ctx *ctx, int Gp, const void *const *dI0_in, const void *const *dI1_in, void *const *d_flo_fwd,
+                             void *const *d_flo_bwd, void *const *d_occ_fwd, void *const *d_occ_bwd, int nx, int ny,
+                             const Tvl1Params &P, int nscales, double zfactor, double fb_alpha, double fb_beta, ofx_stats *stats)
+{
+    const size_t n = (size_t) nx * ny;
+    const int G = 2 * Gp;
+    const int kind = ofx_src_kind(ctx);
+    OFX_TRY(ofx_pitch_check(ctx, "tvl1_bidir", nx));
+    const size_t pitch = ofx_src_pitch(ctx, nx);
+    const size_t span = pitch ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
+    const void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
+    void *flo_in[OFX_MAX_GROUP], *occ_in[OFX_MAX_GROUP], *flo[OFX_MAX_GROUP], *occ[OFX_MAX_GROUP];     // slot order
+    for (int g = 0; g < Gp; g++) {
+        const void *src[2] = {dI0_in[g], dI1_in[g]};
+        const void **dst[2] = {&dI0[g], &dI1[g]};
+        for (int k = 0; k < 2; k++) {
+            if (ofx_ptr_is_local(ctx, src[k])) { *dst[k] = src[k]; continue; }
+            char *stage;
+            OFX_TRY(ofx_alloc(ctx, span, &stage));
+            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], span));
+            *dst[k] = stage;
+        }
+        flo_in[g] = d_flo_fwd[g];
+        flo_in[Gp + g] = d_flo_bwd[g];
+        occ_in[g] = d_occ_fwd[g];
+        occ_in[Gp + g] = d_occ_bwd[g];
+    }
+    for (int z = 0; z < G; z++) {
+        flo[z] = flo_in[z];
+        occ[z] = occ_in[z];
+        if (!ofx_ptr_is_local(ctx, flo_in[z])) {
+            float2 *stage;
+            OFX_TRY(ofx_alloc(ctx, n, &stage));
+            flo[z] = stage;
+        }
+        if (!ofx_ptr_is_local(ctx, occ_in[z])) {
+            unsigned char *stage;
+            OFX_TRY(ofx_alloc(ctx, n, &stage));
+            occ[z] = stage;
+        }
+    }
+    std::vector<Tvl1Level<T>> lv;
+    OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv, stats,
+                                   kind, pitch, Gp));
+    OfxGroupPtrs out;
+    for (int z = 0; z < OFX_MAX_GROUP; z++) { out.a[z] = z < G ? flo[z] : nullptr; out.b[z] = nullptr; }
+    hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
+                       out, n);
+    OFX_LAUNCH_CHECK(ctx);
+    const void *against[OFX_MAX_GROUP];                         // slot z is checked against the opposite direction of its pair
+    for (int z = 0; z < G; z++) against[z] = flo[(z + Gp) % G];
+    OFX_TRY(op_flow_consistency(ctx, G, flo, against, occ, nx, ny, fb_alpha, fb_beta));
+    for (int z = 0; z < G; z++) {
+        if (flo[z] != flo_in[z]) OFX_TRY(ofx_copy_staged(ctx, flo_in[z], flo[z], n * sizeof(float2)));
+        if (occ[z] != occ_in[z]) OFX_TRY(ofx_copy_staged(ctx, occ_in[z], occ[z], n));
+    }
+    return OFX_OK;
+}
+
+extern "C" int ofx_tvl1_bidir_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
+                                        void *const *d_flo_fwd, void *const *d_flo_bwd, void *const *d_occ_fwd,
+                                        void *const *d_occ_bwd, int nx, int ny, double tau, double lambda, double theta, int nscales,
+                                        double zfactor, int warps, double epsilon, double fb_alpha, double fb_beta,
+                                        ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (!dI0 || !dI1 || !d_flo_fwd || !d_flo_bwd || !d_occ_fwd || !d_occ_bwd) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_bidir: NULL pointer");
+    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP / 2)
+        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_bidir: a bidirectional group holds 1..%d pairs (got %d)", OFX_MAX_GROUP / 2, n_pairs);
+    OFX_TRY(op_flow_consistency_check(ctx, "tvl1_bidir", nx, ny, fb_alpha, fb_beta));
+    for (int g = 0; g < n_pairs; g++) {
+        if (!dI0[g] || !dI1[g] || !d_flo_fwd[g] || !d_flo_bwd[g] || !d_occ_fwd[g] || !d_occ_bwd[g])
+            return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_bidir: NULL pointer (pair %d)", g);
+        if (reinterpret_cast<uintptr_t>(d_flo_fwd[g]) % sizeof(float2) || reinterpret_cast<uintptr_t>(d_flo_bwd[g]) % sizeof(float2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_bidir: payload of pair %d is not 8-byte aligned", g);
+    }
+    const double t0 = ofx_now_ms();
+    const Tvl1Params P = make_params(ctx, tau, lambda, theta, warps, epsilon, 0);
+    std::vector<ofx_stats> local(stats_out ? 0 : 2 * n_pairs);
+    ofx_stats *st = stats_out ? stats_out : local.data();
+    int s = ctx->precision == OFX_F64
+                ? tvl1_bidir_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
+                                            zfactor, fb_alpha, fb_beta, st)
+                : tvl1_bidir_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
+                                           zfactor, fb_alpha, fb_beta, st);
+    const double ms = ofx_now_ms() - t0;
+    for (int g = 0; g < 2 * n_pairs; g++) st[g].total_ms = ms;
     ctx->stats = st[0];
     return s;
 }
@@ -2357,6 +2470,49 @@ extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
             if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
             if (work_pix_iters)
                 for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
+        }
+        (void) hipStreamSynchronize(ctxs[w]->stream);
+    };
+    std::vector<std::thread> th;
+    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : th) t.join();
+    return status.load();
+}
+
+// ... of bidirectional pairs: groups of consecutive pairs, group q on context q % n_ctx through ofx_tvl1_bidir_group_dev.  Option
+// "lockstep" and ofx_tvl1_batch_group_size count solver SLOTS, of which a pair takes two; the sizing rule counts the shared images
+// of a pair twice, which errs on the safe side.
+extern "C" int ofx_tvl1_bidir_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                                        void *const *d_flo_fwd, void *const *d_flo_bwd, void *const *d_occ_fwd,
+                                        void *const *d_occ_bwd, int n_pairs, int nx, int ny, double tau, double lambda, double theta,
+                                        int nscales, double zfactor, int warps, double epsilon, double fb_alpha, double fb_beta,
+                                        double *work_pix_iters)
+{
+    if (!ctxs || n_ctx < 1 || n_pairs < 0 || !dI0 || !dI1 || !d_flo_fwd || !d_flo_bwd || !d_occ_fwd || !d_occ_bwd) return OFX_ERR_ARG;
+    for (int w = 0; w < n_ctx; w++)
+        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input ||
+            ctxs[w]->input_pitch != ctxs[0]->input_pitch)
+            return OFX_ERR_ARG;
+    const int slots = ofx_tvl1_batch_group_size(ctxs, n_ctx, 2 * n_pairs, nx, ny, nscales, zfactor);
+    if (slots < 1) return slots < 0 ? -slots : OFX_ERR_ARG;
+    const int G = slots / 2 > 1 ? slots / 2 : 1;                // pairs per group, at most OFX_MAX_GROUP / 2
+    const int n_groups = (n_pairs + G - 1) / G;
+    std::atomic<int> status(OFX_OK);
+    auto worker = [&](int w) {
+        std::vector<ofx_stats> st(2 * G);
+        for (int q = w; q < n_groups; q += n_ctx) {
+            if (status.load() != OFX_OK) return;
+            const int first = q * G, cnt = (n_pairs - first < G) ? n_pairs - first : G;
+            const int s = ofx_tvl1_bidir_group_dev(ctxs[w], cnt, dI0 + first, dI1 + first, d_flo_fwd + first, d_flo_bwd + first,
+                                                   d_occ_fwd + first, d_occ_bwd + first, nx, ny, tau, lambda, theta, nscales, zfactor,
+                                                   warps, epsilon, fb_alpha, fb_beta, st.data());
+            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
+            if (work_pix_iters)
+                for (int g = 0; g < cnt; g++) {                 // forward first, then backward
+                    work_pix_iters[first + g] = st[g].work_pix_iters;
+                    work_pix_iters[n_pairs + first + g] = st[cnt + g].work_pix_iters;
+                }
         }
         (void) hipStreamSynchronize(ctxs[w]->stream);
     };
