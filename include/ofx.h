@@ -185,7 +185,8 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
 int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
 
 /* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
- * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_tvl1_bidir_group_dev / _bidir_batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
+ * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_tvl1_group_init_dev / ofx_tvl1_batch_init_dev / ofx_tvl1_sequence_group_dev,
+ * ofx_tvl1_bidir_group_dev / _bidir_batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
  * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev and ofx_pyramid_group_dev -- read
  * elements of this kind wherever their
@@ -339,6 +340,54 @@ int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, 
  * -OFX_ERR_SIGMA for a pyramid that cannot be built) on error. */
 int ofx_tvl1_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, int nx, int ny, int nscales,
                               double zfactor);
+
+/* ---- TV-L1 warm start: a flow to start from, and the video chain ------------------------------------------------
+ * The start of a pair is a .flo payload P as every solver writes it: nx * ny interleaved (u, v) float32, 8-byte aligned.  It
+ * enters the solve as follows (restated in tests/tvl1_warm_ref.py):
+ *   W_0 = ((double) P.u, (double) P.v), a component that is not finite (NaN, +-Inf) taken as 0.0 -- part of the result: no input
+ *         can put a NaN into the warp's coordinates;
+ *   W_s = zoom_out(W_{s-1}, zfactor) * zfactor for s = 1 .. nscales - 1, per component: the reference's zoom_out (src/zoom.cpp)
+ *         exactly as ofx_zoom_out and the image pyramid compute it, then ONE rounded multiply -- the mirror of the
+ *         `*= 1.0 / zfactor` of src/tvl1flow.cpp:306-309 -- in double storage and arithmetic whatever the context's precision;
+ *   the flow at the coarsest level is W_{nscales-1}, rounded once to the storage type; everything after that is the driver of
+ *   ofx_tvl1_group_dev, unchanged.
+ * A pair without a start (NULL) begins at zero as it always did, a NULL table is ofx_tvl1_group_dev itself, and an all-zero
+ * payload therefore gives ofx_tvl1_group_dev's result bit for bit.
+ * Out of scope: a start for the bidirectional entries (ofx_tvl1_bidir_*) and for the host-plane entries (ofx_tvl1_multiscale;
+ * ofx_tvl1_single_scale has always read u1 / u2 as its start).
+ *
+ * ofx_tvl1_group_init_dev is ofx_tvl1_group_dev with that start: d_flo_init is NULL, or n_pairs pointers, each NULL or a payload.
+ * d_flo_init[g] == d_flo[g] is allowed: the start is consumed before any payload is written.  Per pair the result is what the same
+ * call computes for that pair alone; warm and cold pairs may share a group.  Frames are read under "input" / "input_pitch" like
+ * ofx_tvl1_group_dev's; start payloads that are not on the context's GPU are staged as ofx_tvl1_batch_dev stages its buffers.
+ * Refusals, before any work, nothing written, the reason in ofx_last_error: those of ofx_tvl1_group_dev; a start pointer that is
+ * not 8-byte aligned (OFX_ERR_ARG, its pair index named); OFX_ERR_SIGMA as the image pyramid gives it (same levels, same sigma). */
+int ofx_tvl1_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
+                            const void *const *d_flo_init, void *const *d_flo, int nx, int ny, double tau, double lambda,
+                            double theta, int nscales, double zfactor, int warps, double epsilon, ofx_stats *stats_out);
+/* ofx_tvl1_batch_dev with the same extra table after dI1; the same grouping rule (ofx_tvl1_batch_group_size, whose memory rule
+ * counts the start's scratch).  Groups run concurrently: a start may be the pair's own slot of d_flo, not another pair's. */
+int ofx_tvl1_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                            const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double tau,
+                            double lambda, double theta, int nscales, double zfactor, int warps, double epsilon,
+                            double *work_pix_iters);
+/* The video chain for n_seq (1..16) device-resident sequences (cameras) of n_frames >= 2 frames: sequence q is the frames
+ * dF[q * n_frames + t] and the payloads d_flo[q * (n_frames - 1) + t].  Step t solves the pairs (F[q][t], F[q][t + 1]) of all
+ * sequences as one lockstep group: step 0 cold with nscales_first scales, step t > 0 from d_flo[q][t - 1] with nscales_next
+ * scales -- that payload is on the device already, so there is no host round trip between steps.  Each payload is bit for bit
+ * what the chained ofx_tvl1_group_init_dev calls write.  Consecutive steps do not share a frame's pyramid: image_normalization_2
+ * takes min / max over the two images of a pair, so a frame is a different plane in each of its two pairs.  stats_out: NULL or
+ * n_seq * (n_frames - 1) records, laid out like d_flo.  Both pyramids (nscales_first, nscales_next) are validated before any
+ * work.  Refusals as ofx_tvl1_group_init_dev, and OFX_ERR_ARG for n_seq outside 1..16, n_frames < 2, a payload that is not
+ * 8-byte aligned. */
+int ofx_tvl1_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nx, int ny,
+                                double tau, double lambda, double theta, int nscales_first, int nscales_next, double zfactor,
+                                int warps, double epsilon, ofx_stats *stats_out);
+/* The start's pyramid alone, a test and inspection hook like ofx_pyramid_group_dev: d_flo[g], g < n_flows (1..16): a payload on
+ * the context's GPU; d_uv[g] receives W_{nscales-1} as nxs * nys interleaved (u, v) DOUBLES, 16-byte aligned, in either
+ * precision.  nscales = 1 is the conversion with the non-finite rule alone.  Refusals as above.  Asynchronous. */
+int ofx_flow_pyramid_dev(ofx_ctx *ctx, int n_flows, const void *const *d_flo, int nx, int ny, int nscales, double zfactor,
+                         void *const *d_uv);
 
 /* Forward-backward consistency of two .flo payloads, from any solver (Sundaram, Brox, Keutzer, ECCV 2010): the per-pixel
  * occlusion / reliability maps of n_pairs >= 1 pairs of flow fields, both directions, on the device.

@@ -126,6 +126,12 @@ def lib():
         "ofx_tvl1_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, _d,
                                     _i, _d, _i, _d, C.POINTER(_d)]),
         "ofx_tvl1_batch_group_size": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _d]),
+        "ofx_tvl1_group_init_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d, _d, _i, _d, _i, _d, C.POINTER(Stats)]),
+        "ofx_tvl1_batch_init_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _i, _d, _d, _d, _i, _d, _i, _d,
+                                                                                     C.POINTER(_d)]),
+        "ofx_tvl1_sequence_group_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _d, _i, _i, _d, _i, _d,
+                                             C.POINTER(Stats)]),
+        "ofx_flow_pyramid_dev": (_i, [_vp, _i, C.POINTER(_vp), _i, _i, _i, _d, C.POINTER(_vp)]),
         "ofx_flow_consistency_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d]),
         "ofx_tvl1_bidir_group_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _d, _d, _d, _i, _d, _i, _d, _d, _d,
                                                                              C.POINTER(Stats)]),
@@ -208,6 +214,22 @@ def tvl1_batch_dev(ctxs, dI0, dI1, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3,
     work = (_d * max(n, 1))()
     s = lib().ofx_tvl1_batch_dev(arr([c.h.value for c in ctxs]), len(ctxs), arr(dI0), arr(dI1), arr(d_flo), n, nx, ny, tau,
                                  lam, theta, nscales, zfactor, warps, epsilon, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(n)]
+
+
+def tvl1_batch_init_dev(ctxs, dI0, dI1, d_flo_init, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5,
+                        epsilon=0.01):
+    """ofx_tvl1_batch_init_dev: tvl1_batch_dev with a start per pair -- d_flo_init is None (the plain batch) or a list with one
+    entry per pair, a device pointer (int) of a .flo payload or None / 0 for a pair that starts from zero.  Returns the per-pair
+    work (pixel-iterations)."""
+    n = len(dI0)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n, 1))()
+    init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
+    s = lib().ofx_tvl1_batch_init_dev(arr([c.h.value for c in ctxs]), len(ctxs), arr(dI0), arr(dI1), init, arr(d_flo), n, nx, ny,
+                                      tau, lam, theta, nscales, zfactor, warps, epsilon, work)
     if s:
         raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
     return [work[i] for i in range(n)]
@@ -601,6 +623,42 @@ class Ofx:
         self._ck(self.L.ofx_tvl1_group_dev(self.h, n, arr(dI0), arr(dI1), arr(d_flo), nx, ny, tau, lam, theta, nscales,
                                            zfactor, warps, epsilon, st))
         return [st[i] for i in range(n)]
+
+    def tvl1_group_init_dev(self, dI0, dI1, d_flo_init, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5,
+                            warps=5, epsilon=0.01):
+        """ofx_tvl1_group_init_dev: tvl1_group_dev with a start per pair.  d_flo_init: None (the plain group), or one entry per
+        pair, the device pointer (int) of a .flo payload to start from or None / 0 for a pair that starts from zero; an entry
+        may be the pair's own d_flo.  Returns the per-pair Stats records."""
+        n = len(dI0)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n, 1))()
+        init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
+        self._ck(self.L.ofx_tvl1_group_init_dev(self.h, n, arr(dI0), arr(dI1), init, arr(d_flo), nx, ny, tau, lam, theta, nscales,
+                                                zfactor, warps, epsilon, st))
+        return [st[i] for i in range(n)]
+
+    def tvl1_sequence_group_dev(self, dF, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales_first=5, nscales_next=2,
+                                zfactor=0.5, warps=5, epsilon=0.01):
+        """ofx_tvl1_sequence_group_dev, the video chain: dF[q] = the device pointers (ints) of the frames of sequence q, d_flo[q] =
+        those of its len(dF[q]) - 1 payloads.  Step 0 is solved cold with nscales_first scales, every later step from the payload
+        of the step before with nscales_next.  Returns the Stats records, [sequence][step]."""
+        n_seq = len(dF)
+        n_frames = len(dF[0]) if n_seq else 0
+        if any(len(f) != n_frames for f in dF) or len(d_flo) != n_seq or any(len(p) != max(n_frames - 1, 0) for p in d_flo):
+            raise ValueError("tvl1_sequence_group_dev: every sequence needs the same number of frames and one payload per step")
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        steps = max(n_frames - 1, 0)
+        st = (Stats * max(n_seq * steps, 1))()
+        self._ck(self.L.ofx_tvl1_sequence_group_dev(self.h, n_seq, n_frames, arr([p for f in dF for p in f]),
+                                                    arr([p for f in d_flo for p in f]), nx, ny, tau, lam, theta, nscales_first,
+                                                    nscales_next, zfactor, warps, epsilon, st))
+        return [[st[q * steps + t] for t in range(steps)] for q in range(n_seq)]
+
+    def flow_pyramid_dev(self, d_flo, d_uv, nx, ny, nscales=5, zfactor=0.5):
+        """ofx_flow_pyramid_dev: the pyramid of a start alone.  d_flo: device pointers (ints) of .flo payloads; d_uv[g] receives
+        level nscales - 1 of flow g as interleaved (u, v) float64.  Enqueues on the context's stream."""
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_pyramid_dev(self.h, len(d_flo), arr(d_flo), nx, ny, nscales, zfactor, arr(d_uv)))
 
     def flow_consistency_dev(self, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, alpha=0.01, beta=0.5):
         """ofx_flow_consistency_dev: lists of device pointers (ints), one entry per pair of .flo payloads (from any solver);

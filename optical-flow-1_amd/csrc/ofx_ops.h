@@ -157,6 +157,20 @@ int op_build_pyramid_group(ofx_ctx *ctx, int G, const void *const *dA, const voi
                            T *tmpB, double *scr, int kind = -1,        // kind: OFX_SRC_* of dA / dB; -1 = the storage type
                            size_t pitch = 0);                          // kind >= 0: bytes between the rows of dA / dB, 0 = dense
 
+// ---- the pyramid of a start flow (TV-L1 warm start: ofx_tvl1_group_init_dev, include/ofx.h) ----
+// init[g]: the .flo payload (nx * ny interleaved (u, v) float32, 8-byte aligned, memory of the context's GPU) pair g starts from,
+// or NULL for a pair that starts from zero.  W_0 = the payload widened to double, a component that is not finite taken as 0;
+// W_s = zoom_out(W_{s-1}, zfactor) * zfactor per component, in double storage and arithmetic whatever OUT is.  out[g] receives
+// W_{nscales-1} of pair g -- nxs[nscales-1] * nys[nscales-1] interleaved pairs rounded once to OUT (double2 | float2) -- and zeros
+// for a pair without a start, from the same launch.  One launch per level for all pairs (two where zfactor != 1/2); the scratch
+// comes from the arena.  OFX_ERR_SIGMA under op_build_pyramid_group's rule (op_flow_pyramid_check), before anything is launched.
+int op_flow_pyramid_check(ofx_ctx *ctx, int nscales, double zfactor, const int *nxs, const int *nys);
+template <typename OUT>
+int op_flow_pyramid(ofx_ctx *ctx, int G, const void *const *init, int nscales, double zfactor, const int *nxs, const int *nys,
+                    void *const *out);
+// bytes of arena scratch op_flow_pyramid takes per pair (the memory rule of ofx_tvl1_batch_group_size)
+double op_flow_pyramid_scratch_bytes(int nscales, double zfactor, const int *nxs, const int *nys);
+
 // ---- buffers that are not on the context's GPU (ofx_tvl1.hip) ----
 // is p device memory of this context's GPU?  Everything else is reached through a staging copy:
 bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p);

@@ -1502,6 +1502,357 @@ template <typename T> int op_gradient_dz(ofx_ctx *ctx, const T *in, T *dz, int n
     return OFX_OK;
 }
 
+// ---- the pyramid of a start flow (TV-L1 warm start) --------------------------------------------------
+// Not the image pyramid run twice: (u, v) stay interleaved, both components share every tap index, Gaussian weight and bicubic
+// coefficient, and a tap is ONE 8-byte (the float payload, level 0) or 16-byte (double2) load.  Per component the sums and their
+// order are those of gauss_pass_px / resample_px, i.e. of the reference's zoom_out; the chain is double throughout.
+struct OfxFlowPlanes {
+    const void *in[OFX_MAX_GROUP];      // the finer level of pair blockIdx.z; NULL: the pair has no start
+    void       *out[OFX_MAX_GROUP];     // the level to write; NULL: nothing (a pair without a start above the last level)
+};
+// a payload component that is not finite (NaN, +-Inf) counts as 0: no input can put a NaN into the warp's coordinates
+OFX_DEV float flow_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 0.0f : x; }
+OFX_DEV float2 ldflow(const float2 *p) { const float2 v = *p; return make_float2(flow_finite(v.x), flow_finite(v.y)); }
+OFX_DEV double2 ldflow(const double2 *p) { return *p; }
+OFX_DEV double2 widen2(float2 v) { return make_double2((double) v.x, (double) v.y); }
+OFX_DEV double2 widen2(double2 v) { return v; }
+OFX_DEV bool is_neg_zero(double x) { return __double_as_longlong(x) == (long long) 0x8000000000000000ull; }
+
+// One value of the separable Gaussian straight from memory (the column pass over row-pass values, operators.cpp:541-611) and
+// zoom_out's sample of an output pixel from sixteen of them: the reference's operations one by one, for the pixels that the
+// fused kernel below cannot settle.  Slow, and all but never taken.
+template <typename IN>
+OFX_DEV double2 flow_gauss_row_at(const IN *__restrict__ in, int nx, int i, int j, const GaussTaps &taps)
+{
+    const IN *row = in + (size_t) i * nx;
+    const double2 c = widen2(ldflow(row + j));
+    double2 sum = make_double2(taps.B[0] * c.x, taps.B[0] * c.y);
+#pragma unroll 1
+    for (int k = 1; k < taps.size; k++) {
+        const double2 a = widen2(ldflow(row + gauss_reflect(j - k, nx))), b = widen2(ldflow(row + gauss_reflect(j + k, nx)));
+        sum.x += taps.B[k] * (a.x + b.x);
+        sum.y += taps.B[k] * (a.y + b.y);
+    }
+    return sum;
+}
+template <typename IN>
+OFX_DEV double2 flow_gauss_at(const IN *__restrict__ in, int nx, int ny, int i, int j, const GaussTaps &taps)
+{
+    const double2 c = flow_gauss_row_at(in, nx, i, j, taps);
+    double2 sum = make_double2(taps.B[0] * c.x, taps.B[0] * c.y);
+#pragma unroll 1
+    for (int k = 1; k < taps.size; k++) {
+        const double2 a = flow_gauss_row_at(in, nx, gauss_reflect(i - k, ny), j, taps);
+        const double2 b = flow_gauss_row_at(in, nx, gauss_reflect(i + k, ny), j, taps);
+        sum.x += taps.B[k] * (a.x + b.x);
+        sum.y += taps.B[k] * (a.y + b.y);
+    }
+    return sum;
+}
+template <typename IN>
+OFX_DEV double2 flow_zoom_out_at(const IN *__restrict__ in, int nx, int ny, int i1, int j1, double factor, const GaussTaps &taps)
+{
+    const BicubicTaps t = bicubic_taps(j1 / factor, i1 / factor, nx, ny);
+    double2 c[4];
+#pragma unroll                                                   // (unrolled: no array is indexed by a variable)
+    for (int k = 0; k < 4; k++) {
+        double2 v[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = flow_gauss_at(in, nx, ny, t.row[q], t.col[k], taps);
+        c[k].x = cubic_cell(v[0].x, v[1].x, v[2].x, v[3].x, t.fy);
+        c[k].y = cubic_cell(v[0].y, v[1].y, v[2].y, v[3].y, t.fy);
+    }
+    return make_double2(cubic_cell(c[0].x, c[1].x, c[2].x, c[3].x, t.fx), cubic_cell(c[0].y, c[1].y, c[2].y, c[3].y, t.fx));
+}
+
+// zoom_out with zfactor = 1/2 and the `* zfactor` in ONE launch per level for all pairs, in the manner of k_gauss_xy_dec: the
+// bicubic sample of the smoothed field at (2 j1, 2 i1) is the smoothed value v itself, v + 0.5 * 0 * (...) in both directions --
+// unless v is -0.0, where the sign of the sum depends on the sign of the bracket (an image is >= 0 and never meets this; a flow
+// can): such a pixel, a (2 R + 1)^2 window of -0.0 in the finer level, is taken through flow_zoom_out_at.  A block stages
+// (2 FPD_THO + 2 R) x (128 + 2 R) taps of the finer level in LDS, as the float payload at level 0.
+#define FPD_THO 8
+template <typename IN, typename OUT, int R>
+__global__ __launch_bounds__(256) void k_flow_pyr_dec(OfxFlowPlanes P, int nx, int ny, int nxo, int nyo, double scale, GaussTaps taps)
+{
+    constexpr int W = 128 + 2 * R, H = 2 * FPD_THO + 2 * R, SEG = FPD_THO / 4;
+    __shared__ IN s_in[H * W];
+    __shared__ double2 s_mid[H * 64];
+    const IN *__restrict__ in = static_cast<const IN *>(P.in[blockIdx.z]);
+    OUT *__restrict__ out = static_cast<OUT *>(P.out[blockIdx.z]);
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int jo = blockIdx.x * 64 + tx;
+    if (!in) {                                                   // no start: zeros into the last level (the block's pair is one)
+        if (!out || jo >= nxo) return;
+        for (int o = 0; o < SEG; o++) {
+            const int io = blockIdx.y * FPD_THO + ty * SEG + o;
+            if (io < nyo) stn2(out + (size_t) io * nxo + jo, make_double2(0.0, 0.0));
+        }
+        return;
+    }
+    const int j0 = blockIdx.x * 128, i0 = blockIdx.y * 2 * FPD_THO;
+    int jc[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        int j = gauss_reflect(j0 - R + tx + 64 * q, nx);
+        jc[q] = j < 0 ? 0 : (j > nx - 1 ? nx - 1 : j);           // beyond the image on the far side of a border block: never used
+    }
+    for (int r = ty; r < H; r += 4) {
+        int i = gauss_reflect(i0 - R + r, ny);
+        i = i < 0 ? 0 : (i > ny - 1 ? ny - 1 : i);
+        const IN *__restrict__ row = in + (size_t) i * nx;
+        s_in[r * W + tx] = ldflow(row + jc[0]);
+        s_in[r * W + tx + 64] = ldflow(row + jc[1]);
+        if (tx < 2 * R) s_in[r * W + tx + 128] = ldflow(row + jc[2]);
+    }
+    __syncthreads();
+    for (int r = ty; r < H; r += 4) {                            // row pass at the even columns
+        const IN *row = s_in + r * W + R + 2 * tx;
+        const double2 c = widen2(row[0]);
+        double2 sum = make_double2(taps.B[0] * c.x, taps.B[0] * c.y);
+#pragma unroll
+        for (int k = 1; k <= R; k++) {
+            const double2 a = widen2(row[-k]), b = widen2(row[k]);
+            sum.x += taps.B[k] * (a.x + b.x);
+            sum.y += taps.B[k] * (a.y + b.y);
+        }
+        s_mid[r * 64 + tx] = sum;
+    }
+    __syncthreads();
+    if (jo >= nxo) return;
+#pragma unroll
+    for (int o = 0; o < SEG; o++) {                              // column pass at the even rows, then the scale
+        const int lo = ty * SEG + o, io = blockIdx.y * FPD_THO + lo;
+        if (io >= nyo) break;
+        const double2 *c = s_mid + (R + 2 * lo) * 64 + tx;
+        double2 sum = make_double2(taps.B[0] * c[0].x, taps.B[0] * c[0].y);
+#pragma unroll
+        for (int k = 1; k <= R; k++) {
+            const double2 a = c[-k * 64], b = c[k * 64];
+            sum.x += taps.B[k] * (a.x + b.x);
+            sum.y += taps.B[k] * (a.y + b.y);
+        }
+        if (is_neg_zero(sum.x) || is_neg_zero(sum.y)) sum = flow_zoom_out_at(in, nx, ny, io, jo, 0.5, taps);
+        stn2(out + (size_t) io * nxo + jo, make_double2(sum.x * scale, sum.y * scale));
+    }
+}
+
+// Any other zfactor: the row and the column pass in one launch through LDS (k_gauss_xy_g on pairs; radius <= FPG_RMAX), the
+// smoothed field into scratch, ...
+#define FPG_TH 16
+#define FPG_RMAX 8
+template <typename IN>
+__global__ __launch_bounds__(256) void k_flow_gauss_xy(OfxFlowPlanes P, int nx, int ny, GaussTaps taps)
+{
+    __shared__ IN s_in[(FPG_TH + 2 * FPG_RMAX) * (64 + 2 * FPG_RMAX)];
+    __shared__ double2 s_mid[(FPG_TH + 2 * FPG_RMAX) * 64];
+    const IN *__restrict__ in = static_cast<const IN *>(P.in[blockIdx.z]);
+    double2 *__restrict__ out = static_cast<double2 *>(P.out[blockIdx.z]);
+    if (!in || !out) return;
+    const int R = taps.size - 1, W = 64 + 2 * R, H = FPG_TH + 2 * R;
+    const int j0 = blockIdx.x * 64, i0 = blockIdx.y * FPG_TH;
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    for (int k = tid; k < W * H; k += 256) {
+        const int r = k / W, c = k - r * W;
+        int i = gauss_reflect(i0 - R + r, ny), j = gauss_reflect(j0 - R + c, nx);
+        i = i < 0 ? 0 : (i > ny - 1 ? ny - 1 : i);
+        j = j < 0 ? 0 : (j > nx - 1 ? nx - 1 : j);
+        s_in[r * W + c] = ldflow(in + (size_t) i * nx + j);
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < H; r += 4) {
+        const IN *row = s_in + r * W + R + threadIdx.x;
+        const double2 c = widen2(row[0]);
+        double2 sum = make_double2(taps.B[0] * c.x, taps.B[0] * c.y);
+        for (int k = 1; k < taps.size; k++) {
+            const double2 a = widen2(row[-k]), b = widen2(row[k]);
+            sum.x += taps.B[k] * (a.x + b.x);
+            sum.y += taps.B[k] * (a.y + b.y);
+        }
+        s_mid[r * 64 + threadIdx.x] = sum;
+    }
+    __syncthreads();
+    const int j = j0 + threadIdx.x;
+    if (j >= nx) return;
+    for (int r = threadIdx.y; r < FPG_TH; r += 4) {
+        const int i = i0 + r;
+        if (i >= ny) break;
+        const double2 *col = s_mid + (r + R) * 64 + threadIdx.x;
+        double2 sum = make_double2(taps.B[0] * col[0].x, taps.B[0] * col[0].y);
+        for (int k = 1; k < taps.size; k++) {
+            const double2 a = col[-k * 64], b = col[k * 64];
+            sum.x += taps.B[k] * (a.x + b.x);
+            sum.y += taps.B[k] * (a.y + b.y);
+        }
+        out[(size_t) i * nx + j] = sum;
+    }
+}
+// ... or, for a wider radius, one pass per launch (gauss_pass_px on pairs)
+template <typename IN, bool ALONG_X>
+__global__ void k_flow_gauss_pass(OfxFlowPlanes P, int nx, int ny, GaussTaps taps)
+{
+    const IN *__restrict__ in = static_cast<const IN *>(P.in[blockIdx.z]);
+    double2 *__restrict__ out = static_cast<double2 *>(P.out[blockIdx.z]);
+    const int j = blockIdx.x * BX + threadIdx.x;
+    const int i = blockIdx.y * BY + threadIdx.y;
+    if (!in || !out || j >= nx || i >= ny) return;
+    const double2 c = widen2(ldflow(in + (size_t) i * nx + j));
+    double2 sum = make_double2(taps.B[0] * c.x, taps.B[0] * c.y);
+    for (int k = 1; k < taps.size; k++) {
+        const size_t pa = ALONG_X ? (size_t) i * nx + gauss_reflect(j - k, nx) : (size_t) gauss_reflect(i - k, ny) * nx + j;
+        const size_t pb = ALONG_X ? (size_t) i * nx + gauss_reflect(j + k, nx) : (size_t) gauss_reflect(i + k, ny) * nx + j;
+        const double2 a = widen2(ldflow(in + pa)), b = widen2(ldflow(in + pb));
+        sum.x += taps.B[k] * (a.x + b.x);
+        sum.y += taps.B[k] * (a.y + b.y);
+    }
+    out[(size_t) i * nx + j] = sum;
+}
+// ... and the last pass takes zoom_out's bicubic sample (resample_px on pairs) and the `* zfactor` with it
+template <typename OUT>
+__global__ void k_flow_resample(OfxFlowPlanes P, int nx, int ny, int nxx, int nyy, double factor, double scale)
+{
+    const double2 *__restrict__ in = static_cast<const double2 *>(P.in[blockIdx.z]);
+    OUT *__restrict__ out = static_cast<OUT *>(P.out[blockIdx.z]);
+    const int j1 = blockIdx.x * BX + threadIdx.x;
+    const int i1 = blockIdx.y * BY + threadIdx.y;
+    if (!out || j1 >= nxx || i1 >= nyy) return;
+    double2 r = make_double2(0.0, 0.0);
+    if (in) {
+        const BicubicTaps t = bicubic_taps(j1 / factor, i1 / factor, nx, ny);
+        double2 c[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double2 v0 = in[(size_t) t.row[0] * nx + t.col[k]], v1 = in[(size_t) t.row[1] * nx + t.col[k]];
+            const double2 v2 = in[(size_t) t.row[2] * nx + t.col[k]], v3 = in[(size_t) t.row[3] * nx + t.col[k]];
+            c[k].x = cubic_cell(v0.x, v1.x, v2.x, v3.x, t.fy);
+            c[k].y = cubic_cell(v0.y, v1.y, v2.y, v3.y, t.fy);
+        }
+        r.x = cubic_cell(c[0].x, c[1].x, c[2].x, c[3].x, t.fx) * scale;
+        r.y = cubic_cell(c[0].y, c[1].y, c[2].y, c[3].y, t.fx) * scale;
+    }
+    stn2(out + (size_t) i1 * nxx + j1, r);
+}
+// one level: W_0 itself (the conversion with the non-finite rule), or zeros for a pair without a start
+template <typename OUT>
+__global__ void k_flow_convert(OfxFlowPlanes P, size_t n)
+{
+    const float2 *__restrict__ in = static_cast<const float2 *>(P.in[blockIdx.y]);
+    OUT *__restrict__ out = static_cast<OUT *>(P.out[blockIdx.y]);
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (!out || i >= n) return;
+    stn2(out + i, in ? widen2(ldflow(in + i)) : make_double2(0.0, 0.0));
+}
+
+static double flow_zoom_sigma(double zfactor) { return 0.6 * sqrt(1.0 / (zfactor * zfactor) - 1.0); }    // zoom.cpp:15,60
+// level s >= 1 is smoothed from level s - 1 with zoom_out's Gaussian: the refusals of op_build_pyramid_group for those levels
+int op_flow_pyramid_check(ofx_ctx *ctx, int nscales, double zfactor, const int *nxs, const int *nys)
+{
+    for (int s = 1; s < nscales; s++) {
+        GaussTaps taps;
+        OFX_TRY(gauss_taps_checked(ctx, flow_zoom_sigma(zfactor), nxs[s - 1], nys[s - 1], 0, &taps));
+    }
+    return OFX_OK;
+}
+// does level s come from the 2:1 kernel?  (the conditions of k_gauss_xy_dec in op_build_pyramid_group)
+static bool flow_level_dec(double zfactor, const GaussTaps &tz, int nx, int ny, int nxo, int nyo)
+{
+    return zfactor == 0.5 && tz.size - 1 == 5 && tz.size < nx && tz.size < ny && 2 * (nxo - 1) <= nx - 1 && 2 * (nyo - 1) <= ny - 1;
+}
+double op_flow_pyramid_scratch_bytes(int nscales, double zfactor, const int *nxs, const int *nys)
+{
+    GaussTaps tz;
+    if (nscales < 2 || ofx_gauss_taps(flow_zoom_sigma(zfactor), &tz) != OFX_OK) return 0.0;
+    double px = 0.0;
+    if (nscales > 2) px += (double) nxs[1] * nys[1];
+    if (nscales > 3) px += (double) nxs[2] * nys[2];
+    if (!flow_level_dec(zfactor, tz, nxs[0], nys[0], nxs[1], nys[1])) px += (tz.size - 1 > FPG_RMAX ? 2.0 : 1.0) * nxs[0] * nys[0];
+    return px * sizeof(double2);
+}
+
+template <typename IN, typename O>
+static int flow_pyramid_level(ofx_ctx *ctx, int G, const OfxFlowPlanes &P, double2 *smooth, double2 *rows, int nx, int ny, int nxo,
+                              int nyo, double zfactor, const GaussTaps &tz)
+{
+    if (flow_level_dec(zfactor, tz, nx, ny, nxo, nyo)) {
+        hipLaunchKernelGGL((k_flow_pyr_dec<IN, O, 5>), dim3(ofx_cdiv(nxo, 64), ofx_cdiv(nyo, FPD_THO), G), dim3(64, 4), 0, ctx->stream, P,
+                           nx, ny, nxo, nyo, zfactor, tz);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    }
+    const size_t n = (size_t) nx * ny;
+    OfxFlowPlanes S = {}, Z = {};                               // smoothing into scratch, then the sample
+    for (int g = 0; g < G; g++) {
+        S.in[g] = P.in[g];
+        S.out[g] = P.in[g] ? smooth + (size_t) g * n : nullptr;
+        Z.in[g] = S.out[g];
+        Z.out[g] = P.out[g];
+    }
+    if (tz.size - 1 <= FPG_RMAX) {
+        hipLaunchKernelGGL(k_flow_gauss_xy<IN>, dim3(ofx_cdiv(nx, 64), ofx_cdiv(ny, FPG_TH), G), dim3(64, 4), 0, ctx->stream, S, nx, ny, tz);
+        OFX_LAUNCH_CHECK(ctx);
+    } else {
+        OfxFlowPlanes X = S, Y = S;
+        for (int g = 0; g < G; g++) {
+            X.out[g] = P.in[g] ? rows + (size_t) g * n : nullptr;
+            Y.in[g] = X.out[g];
+        }
+        dim3 grid = grid2d(nx, ny);
+        grid.z = G;
+        hipLaunchKernelGGL((k_flow_gauss_pass<IN, true>), grid, block2d(), 0, ctx->stream, X, nx, ny, tz);
+        OFX_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL((k_flow_gauss_pass<double2, false>), grid, block2d(), 0, ctx->stream, Y, nx, ny, tz);
+        OFX_LAUNCH_CHECK(ctx);
+    }
+    dim3 grid = grid2d(nxo, nyo);
+    grid.z = G;
+    hipLaunchKernelGGL(k_flow_resample<O>, grid, block2d(), 0, ctx->stream, Z, nx, ny, nxo, nyo, zfactor, zfactor);
+    OFX_LAUNCH_CHECK(ctx);
+    return OFX_OK;
+}
+
+template <typename OUT>
+int op_flow_pyramid(ofx_ctx *ctx, int G, const void *const *init, int nscales, double zfactor, const int *nxs, const int *nys,
+                    void *const *out)
+{
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "flow pyramid: group of %d", G);
+    OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs, nys));
+    bool warm = false;
+    for (int g = 0; g < G; g++) warm = warm || init[g];
+    OfxFlowPlanes P = {};
+    if (nscales == 1 || !warm) {                                // the conversion alone, or nothing but zeros
+        const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1];
+        for (int g = 0; g < G; g++) { P.in[g] = warm ? init[g] : nullptr; P.out[g] = out[g]; }
+        hipLaunchKernelGGL(k_flow_convert<OUT>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, P, n);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    }
+    GaussTaps tz;
+    if (ofx_gauss_taps(flow_zoom_sigma(zfactor), &tz) != OFX_OK) return ofx_fail(ctx, OFX_ERR_ARG, "flow pyramid: zoom factor %g", zfactor);
+    double2 *lev[2] = {nullptr, nullptr}, *smooth = nullptr, *rows = nullptr;
+    if (nscales > 2) OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[1] * nys[1], &lev[1]));
+    if (nscales > 3) OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[2] * nys[2], &lev[0]));
+    if (!flow_level_dec(zfactor, tz, nxs[0], nys[0], nxs[1], nys[1])) {
+        OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[0] * nys[0], &smooth));
+        if (tz.size - 1 > FPG_RMAX) OFX_TRY(ofx_alloc(ctx, (size_t) G * nxs[0] * nys[0], &rows));
+    }
+    for (int s = 1; s < nscales; s++) {                         // level s from level s - 1, ping-pong in lev[s & 1]
+        const bool last = s == nscales - 1;
+        const size_t nin = (size_t) nxs[s - 1] * nys[s - 1], nout = (size_t) nxs[s] * nys[s];
+        for (int g = 0; g < G; g++) {
+            P.in[g] = !init[g] ? nullptr : s == 1 ? init[g] : (const void *) (lev[(s - 1) & 1] + (size_t) g * nin);
+            P.out[g] = last ? out[g] : init[g] ? (void *) (lev[s & 1] + (size_t) g * nout) : nullptr;
+        }
+        int st;
+        if (s == 1) st = last ? flow_pyramid_level<float2, OUT>(ctx, G, P, smooth, rows, nxs[0], nys[0], nxs[1], nys[1], zfactor, tz)
+                              : flow_pyramid_level<float2, double2>(ctx, G, P, smooth, rows, nxs[0], nys[0], nxs[1], nys[1], zfactor, tz);
+        else st = last ? flow_pyramid_level<double2, OUT>(ctx, G, P, smooth, rows, nxs[s - 1], nys[s - 1], nxs[s], nys[s], zfactor, tz)
+                       : flow_pyramid_level<double2, double2>(ctx, G, P, smooth, rows, nxs[s - 1], nys[s - 1], nxs[s], nys[s], zfactor, tz);
+        OFX_TRY(st);
+    }
+    return OFX_OK;
+}
+template int op_flow_pyramid<double2>(ofx_ctx *, int, const void *const *, int, double, const int *, const int *, void *const *);
+template int op_flow_pyramid<float2>(ofx_ctx *, int, const void *const *, int, double, const int *, const int *, void *const *);
+
 // ---- explicit instantiations -----------------------------------------------------------------------
 #define OFX_INSTANTIATE(T)                                                                                           \
     template int op_convert_in<T>(ofx_ctx *, const double *, T *, size_t);                                            \

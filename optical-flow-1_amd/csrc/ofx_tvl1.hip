@@ -1916,7 +1916,8 @@ template <typename T>
 static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T *const *dI1, int nxx, int nyy,
                                const Tvl1Params &P, int nscales, double zfactor, std::vector<Tvl1Level<T>> &lv,
                                ofx_stats *stats, int kind = -1, size_t pitch = 0,      // pitch: bytes between the frames' rows, 0 = dense
-                               int shared = 0)
+                               int shared = 0,
+                               const void *const *init = nullptr)     // G start payloads (NULL entry: zero start); nullptr: all zero
 {
     const int Gp = shared ? shared : G;                 // pairs whose images the pyramid builds
     if (shared && G != 2 * shared) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: %d slots for %d bidirectional pairs", G, shared);
@@ -1944,7 +1945,14 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
                                           pitch));
     }
     Tvl1Level<T> &C = lv[nscales - 1];
-    OFX_TRY(op_fill2<T>(ctx, C.U[0], C.n() * G));                                                // :278-280
+    if (!init) {
+        OFX_TRY(op_fill2<T>(ctx, C.U[0], C.n() * G));                                            // :278-280
+    } else {
+        // the start in place of the zeros: the payloads' own pyramid (op_flow_pyramid), its last level rounded into U
+        void *dst[OFX_MAX_GROUP];
+        for (int g = 0; g < G; g++) dst[g] = C.U[0] + (size_t) g * C.n();
+        OFX_TRY(op_flow_pyramid<typename Pix<T>::v2>(ctx, G, init, nscales, zfactor, nxs.data(), nys.data(), dst));
+    }
 
     for (int s = nscales - 1; s >= 0; s--) {                                                     // :283
         if (P.verbose && G == 1) fprintf(stderr, "Scale %d: %dx%d\n", s, lv[s].nx, lv[s].ny);
@@ -2075,7 +2083,8 @@ int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
 
 template <typename T>
 static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, const void *const *dI1_in, void *const *d_flo_in,
-                             int nx, int ny, const Tvl1Params &P, int nscales, double zfactor, ofx_stats *stats)
+                             int nx, int ny, const Tvl1Params &P, int nscales, double zfactor, ofx_stats *stats,
+                             const void *const *init_in = nullptr)     // G start payloads (NULL entry: zero start), or nullptr
 {
     const size_t n = (size_t) nx * ny;
     const int kind = ofx_src_kind(ctx);                      // the frames come in the context's "input" kind
@@ -2104,9 +2113,18 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
             d_flo[g] = stage;
         }
     }
+    const void *init[OFX_MAX_GROUP];                         // a start that is not on this GPU is staged like a frame
+    for (int g = 0; init_in && g < G; g++) {
+        init[g] = init_in[g];
+        if (!init_in[g] || ofx_ptr_is_local(ctx, init_in[g])) continue;
+        float2 *stage;
+        OFX_TRY(ofx_alloc(ctx, n, &stage));
+        OFX_TRY(ofx_copy_staged(ctx, stage, init_in[g], n * sizeof(float2)));
+        init[g] = stage;
+    }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv,
-                                   stats, kind, pitch));
+                                   stats, kind, pitch, 0, init_in ? init : nullptr));
     OfxGroupPtrs out;
     for (int g = 0; g < OFX_MAX_GROUP; g++) { out.a[g] = g < G ? d_flo[g] : nullptr; out.b[g] = nullptr; }
     hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
@@ -2132,9 +2150,10 @@ extern "C" int ofx_tvl1_multiscale_dev(ofx_ctx *ctx, const void *dI0, const void
     return s;
 }
 
-extern "C" int ofx_tvl1_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
-                                  void *const *d_flo, int nx, int ny, double tau, double lambda, double theta,
-                                  int nscales, double zfactor, int warps, double epsilon, ofx_stats *stats_out)
+// the lockstep group behind ofx_tvl1_group_dev (d_flo_init = nullptr) and ofx_tvl1_group_init_dev
+static int tvl1_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1, const void *const *d_flo_init,
+                            void *const *d_flo, int nx, int ny, double tau, double lambda, double theta, int nscales, double zfactor,
+                            int warps, double epsilon, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
     if (!dI0 || !dI1 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: NULL pointer");
@@ -2142,17 +2161,112 @@ extern "C" int ofx_tvl1_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *
         return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
     for (int g = 0; g < n_pairs; g++)
         if (!dI0[g] || !dI1[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: NULL pointer (pair %d)", g);
+    if (d_flo_init) {                                           // the start's own refusals, before any work
+        for (int g = 0; g < n_pairs; g++)
+            if (reinterpret_cast<uintptr_t>(d_flo_init[g]) % sizeof(float2))
+                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: start payload of pair %d is not 8-byte aligned", g);
+        std::vector<int> nxs, nys;
+        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
+        OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
+    }
     const double t0 = ofx_now_ms();
     const Tvl1Params P = make_params(ctx, tau, lambda, theta, warps, epsilon, 0);
     std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);      // ~25 KB per record: not on the stack
     ofx_stats *st = stats_out ? stats_out : local.data();
     int s = ctx->precision == OFX_F64
-                ? tvl1_group_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st)
-                : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st);
+                ? tvl1_group_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init)
+                : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init);
     const double ms = ofx_now_ms() - t0;
     for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
     ctx->stats = st[0];
     return s;
+}
+
+extern "C" int ofx_tvl1_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
+                                  void *const *d_flo, int nx, int ny, double tau, double lambda, double theta,
+                                  int nscales, double zfactor, int warps, double epsilon, ofx_stats *stats_out)
+{
+    return tvl1_group_entry(ctx, n_pairs, dI0, dI1, nullptr, d_flo, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon,
+                            stats_out);
+}
+
+extern "C" int ofx_tvl1_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
+                                       const void *const *d_flo_init, void *const *d_flo, int nx, int ny, double tau, double lambda,
+                                       double theta, int nscales, double zfactor, int warps, double epsilon, ofx_stats *stats_out)
+{
+    return tvl1_group_entry(ctx, n_pairs, dI0, dI1, d_flo_init, d_flo, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon,
+                            stats_out);
+}
+
+// The video chain (include/ofx.h): step t solves the pairs (F[q][t], F[q][t + 1]) of all sequences as one lockstep group, from
+// the payloads of step t - 1 where there is one.  Every step is tvl1_group_entry on the context's stream, so the start of step t
+// is read after step t - 1 has written it and never leaves the device.  Consecutive steps do NOT share a frame's pyramid:
+// image_normalization_2 takes its min / max over the two images of a PAIR, so frame t + 1 as second image of step t and as first
+// image of step t + 1 are two different planes.
+extern "C" int ofx_tvl1_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nx,
+                                           int ny, double tau, double lambda, double theta, int nscales_first, int nscales_next,
+                                           double zfactor, int warps, double epsilon, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (!dF || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: NULL pointer");
+    if (n_seq < 1 || n_seq > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: a lockstep group holds 1..%d sequences (got %d)", OFX_MAX_GROUP, n_seq);
+    if (n_frames < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: %d frames (a sequence has at least 2)", n_frames);
+    if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", warps);
+    const int steps = n_frames - 1;
+    for (int q = 0; q < n_seq; q++) {
+        for (int t = 0; t < n_frames; t++)
+            if (!dF[(size_t) q * n_frames + t]) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: NULL frame %d of sequence %d", t, q);
+        for (int t = 0; t < steps; t++) {
+            const void *p = d_flo[(size_t) q * steps + t];
+            if (!p || reinterpret_cast<uintptr_t>(p) % sizeof(float2))
+                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: payload %d of sequence %d NULL or not 8-byte aligned", t, q);
+        }
+    }
+    OFX_TRY(ofx_pitch_check(ctx, "tvl1_sequence", nx));
+    for (int k = 0; k < 2; k++) {                               // both pyramids, every Gaussian of either, before any work
+        const int nscales = k ? nscales_next : nscales_first;
+        std::vector<int> nxs, nys;
+        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
+        GaussTaps taps;
+        if (ofx_gauss_taps(TVL1_PRESMOOTHING_SIGMA, &taps) == OFX_OK && (taps.size >= nx || taps.size >= ny))
+            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+        OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
+    }
+    std::vector<ofx_stats> st(n_seq);
+    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
+    void *out[OFX_MAX_GROUP];
+    for (int t = 0; t < steps; t++) {
+        for (int q = 0; q < n_seq; q++) {
+            a[q] = dF[(size_t) q * n_frames + t];
+            b[q] = dF[(size_t) q * n_frames + t + 1];
+            init[q] = t ? d_flo[(size_t) q * steps + t - 1] : nullptr;
+            out[q] = d_flo[(size_t) q * steps + t];
+        }
+        OFX_TRY(tvl1_group_entry(ctx, n_seq, a, b, t ? init : nullptr, out, nx, ny, tau, lambda, theta, t ? nscales_next : nscales_first,
+                                 zfactor, warps, epsilon, st.data()));
+        for (int q = 0; stats_out && q < n_seq; q++) stats_out[(size_t) q * steps + t] = st[q];
+    }
+    return OFX_OK;
+}
+
+// The start's pyramid alone (include/ofx.h): op_flow_pyramid into the caller's arrays as doubles, in either precision.
+extern "C" int ofx_flow_pyramid_dev(ofx_ctx *ctx, int n_flows, const void *const *d_flo, int nx, int ny, int nscales, double zfactor,
+                                    void *const *d_uv)
+{
+    OFX_ENTER(ctx);
+    if (!d_flo || !d_uv) return ofx_fail(ctx, OFX_ERR_ARG, "flow_pyramid: NULL pointer");
+    if (n_flows < 1 || n_flows > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "flow_pyramid: a lockstep group holds 1..%d flows (got %d)", OFX_MAX_GROUP, n_flows);
+    for (int g = 0; g < n_flows; g++) {
+        if (!d_flo[g] || !d_uv[g]) return ofx_fail(ctx, OFX_ERR_ARG, "flow_pyramid: NULL pointer (flow %d)", g);
+        if (reinterpret_cast<uintptr_t>(d_flo[g]) % sizeof(float2) || reinterpret_cast<uintptr_t>(d_uv[g]) % sizeof(double2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "flow_pyramid: flow %d: the payload is not 8-byte or the result not 16-byte aligned", g);
+    }
+    std::vector<int> nxs, nys;
+    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
+    OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
+    return op_flow_pyramid<double2>(ctx, n_flows, d_flo, nscales, zfactor, nxs.data(), nys.data(), d_uv);
 }
 
 // Both directions of Gp pairs in 2 Gp lockstep slots over one pyramid (tvl1_multiscale_dev, shared = Gp), then the payloads and,
@@ -2379,7 +2493,9 @@ extern "C" int ofx_tvl1_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_
     const double elem = ctxs[0]->precision == OFX_F32 ? 4.0 : 8.0;
     // tvl1_level_alloc: I0, I1, pb, R (1 element per pixel each) + pa, U[3], P1[3], P2[3], A (2 each) = 26 per level
     // + the pyramid temporaries: two scratch arrays of 2 full-size images per pair (op_build_pyramid_group)
-    const double per_pair = (26.0 * px + 4.0 * (double) nx * ny) * elem;
+    // + the scratch of a start's pyramid (ofx_tvl1_batch_init_dev; counted for every batch: a few per cent, on the safe side)
+    const double per_pair = (26.0 * px + 4.0 * (double) nx * ny) * elem +
+                            op_flow_pyramid_scratch_bytes(nscales, zfactor, nxs.data(), nys.data());
     const double per_ctx = 64e6;                                    // error slots, arena slack
     // the budget is per DEVICE: the contexts of a batch may sit on several GPUs (ofx_tvl1_batch_dev), each of which holds the level
     // arrays of its own contexts only -- free memory of every distinct device, divided by the contexts on it; the tightest fit wins
@@ -2443,10 +2559,9 @@ extern "C" int ofx_hypot(ofx_ctx *ctx, const double *x, const double *y, double 
 // solved by context q % n_ctx with ofx_tvl1_group_dev, i.e. its pairs share every launch.  On the small
 // pyramid levels a launch is a latency chain that leaves most of the GPU idle, so G pairs per launch cost
 // the time of one; and the convergence polls (one host round trip per warp) are paid once per group.
-extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
-                                  void *const *d_flo, int n_pairs, int nx, int ny, double tau, double lambda,
-                                  double theta, int nscales, double zfactor, int warps, double epsilon,
-                                  double *work_pix_iters)
+static int tvl1_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                           const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double tau, double lambda,
+                           double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
 {
     if (!ctxs || n_ctx < 1 || n_pairs < 0 || !dI0 || !dI1 || !d_flo) return OFX_ERR_ARG;
     // The contexts may live on DIFFERENT GPUs of the node (one process, one host thread per context): a group whose images
@@ -2465,8 +2580,8 @@ extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
         for (int q = w; q < n_groups; q += n_ctx) {
             if (status.load() != OFX_OK) return;
             const int first = q * G, cnt = (n_pairs - first < G) ? n_pairs - first : G;
-            const int s = ofx_tvl1_group_dev(ctxs[w], cnt, dI0 + first, dI1 + first, d_flo + first, nx, ny, tau, lambda, theta,
-                                             nscales, zfactor, warps, epsilon, st.data());
+            const int s = tvl1_group_entry(ctxs[w], cnt, dI0 + first, dI1 + first, d_flo_init ? d_flo_init + first : nullptr,
+                                           d_flo + first, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon, st.data());
             if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
             if (work_pix_iters)
                 for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
@@ -2478,6 +2593,25 @@ extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
     worker(0);
     for (auto &t : th) t.join();
     return status.load();
+}
+extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                                  void *const *d_flo, int n_pairs, int nx, int ny, double tau, double lambda,
+                                  double theta, int nscales, double zfactor, int warps, double epsilon,
+                                  double *work_pix_iters)
+{
+    return tvl1_batch_entry(ctxs, n_ctx, dI0, dI1, nullptr, d_flo, n_pairs, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon,
+                            work_pix_iters);
+}
+// ... with a start per pair (NULL table: the entry above; NULL entry: that pair starts from zero).  A group's start payloads are
+// read by the group that writes the same slots of d_flo, or by no other group's writes: d_flo_init[g] == d_flo[g] is allowed,
+// a start that is ANOTHER pair's payload of the same batch is not (groups run concurrently).
+extern "C" int ofx_tvl1_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
+                                       const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double tau,
+                                       double lambda, double theta, int nscales, double zfactor, int warps, double epsilon,
+                                       double *work_pix_iters)
+{
+    return tvl1_batch_entry(ctxs, n_ctx, dI0, dI1, d_flo_init, d_flo, n_pairs, nx, ny, tau, lambda, theta, nscales, zfactor, warps,
+                            epsilon, work_pix_iters);
 }
 
 // ... of bidirectional pairs: groups of consecutive pairs, group q on context q % n_ctx through ofx_tvl1_bidir_group_dev.  Option
