@@ -32,6 +32,10 @@ OFX_DEV void stn(double *p, double v) { *p = v; }
 OFX_DEV void stn(float *p, double v)  { *p = (float) v; }
 OFX_DEV void stn2(double2 *p, double2 v) { *p = v; }
 OFX_DEV void stn2(float2 *p, double2 v)  { *p = make_float2((float) v.x, (float) v.y); }
+// x as a store to T and a load back would leave it, for values that stay in registers
+template <typename T> OFX_DEV double rnd_to(double x);
+template <> OFX_DEV double rnd_to<double>(double x) { return x; }
+template <> OFX_DEV double rnd_to<float>(double x) { return (double) (float) x; }
 // Tile t of a launch over pitched rows (OfxRows, ofx_ops.h), for a workgroup of 256: the tile is 1 << lbx slots of a row by
 // (256 >> lbx) * rpt rows, tile t at row piece t / cx, column piece t % cx -- t is the same in all lanes, so this is the one
 // division of the thread.  The thread's slot q (the caller tests it against the row's length) and its rows i0, i0 + di, .. < i1.

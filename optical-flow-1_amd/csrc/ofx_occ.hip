@@ -7,9 +7,7 @@
 // against the compiled reference in tests/test_oracle_vs_ref.py).
 #include "ofx_ops.h"
 #include "ofx_device.h"
-
-#include <atomic>
-#include <thread>
+#include "ofx_batch.h"
 
 #define OCC_IS_ZERO 1E-10      // src/tvl1occflow_constants.h:31
 #define OCC_THR_CHI 0.75       // src/tvl1occflow_constants.h:32
@@ -1597,60 +1595,36 @@ extern "C" int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples,
                                  double *const *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
                                  int nscales, double zfactor, int warps, double epsilon)
 {
-    if (!ctxs || n_ctx < 1 || n_triples < 0 || !I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return OFX_ERR_ARG;
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device) return OFX_ERR_ARG;
+    if (n_triples < 0 || !I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return OFX_ERR_ARG;
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE));
     if (n_triples == 0) return OFX_OK;
+    // group size: option "lockstep" of ctxs[0], else as many as fit.  Per triple: 7 planes per pyramid level (occ_group: 4 images,
+    // u1, u2, chi) + 31 full-size row-major (OccWork's 27, 4 of gradients) and 13 hyperplane-major planes + 2 of Gaussian / zoom scratch
+    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
     {
         ofx_ctx *ctx = ctxs[0];
         OFX_ENTER(ctx);
         OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-    }
-    // group size: option "lockstep" of ctxs[0], else as many as fit.  Per triple: 7 planes per pyramid level (occ_group: 4 images,
-    // u1, u2, chi) + 31 full-size row-major (OccWork's 27, 4 of gradients) and 13 hyperplane-major planes + 2 of Gaussian / zoom scratch
-    int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
-    if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipSetDevice(ctxs[0]->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return OFX_ERR_HIP;
-        const double budget = (ctxs[0]->mem_budget > 0 ? ctxs[0]->mem_budget : 0.5 * (double) free_b) / n_ctx;
+        double budget;
+        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
         std::vector<int> nxs, nys;
-        OFX_TRY(op_pyramid_sizes(ctxs[0], nxx, nyy, nscales, zfactor, nxs, nys));
+        OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
         double level_px = 0.0;
         for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
         const double per = 8.0 * (7.0 * level_px + 33.0 * nxx * nyy + 13.0 * (double) rof_skew_elems(nxx, nyy)) * 1.05;
         const int fit = (int) (budget / per);
-        if (fit < 1) return ofx_fail(ctxs[0], OFX_ERR_NOMEM, "tvl1occ batch: %.1f GB per triple, %.1f GB per context available", per / 1e9, budget / 1e9);
+        if (fit < 1) return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ batch: %.1f GB per triple, %.1f GB per context available", per / 1e9, budget / 1e9);
         if (G > fit) G = fit;
     }
-    const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
-    if (G > per_ctx) G = per_ctx;
-    const int n_groups = (n_triples + G - 1) / G;
+    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
     const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
-    std::atomic<int> status(OFX_OK);
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_triples - first < G) ? n_triples - first : G;
-            ofx_ctx *ctx = ctxs[w];
-            int s = OFX_OK;
-            if (hipSetDevice(ctx->device) != hipSuccess) s = ofx_fail(ctx, OFX_ERR_NODEV, "hipSetDevice(%d) failed", ctx->device);
-            else {
-                ctx->errmsg[0] = 0;
-                ofx_arena_reset(ctx);
-                s = occ_group(ctx, cnt, I_1 + first, I0 + first, I1 + first, filtI0 + first, u1 + first, u2 + first, chi + first, nxx,
-                              nyy, P, nscales, zfactor, st.data());
-                ctx->stats = st[0];
-            }
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-        }
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    return status.load();
+    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, nullptr, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
+        OFX_ENTER(ctx);
+        const int s = occ_group(ctx, cnt, I_1 + first, I0 + first, I1 + first, filtI0 + first, u1 + first, u2 + first, chi + first, nxx, nyy,
+                                P, nscales, zfactor, st);
+        ctx->stats = st[0];
+        return s;
+    });
 }
 
 // ==== the same solve over a device-resident sequence (ofx_tvl1occ_sequence_group_dev / _dev) =====================================
@@ -1841,30 +1815,13 @@ int occ_planes_group(ofx_ctx *ctx, int G, int F, const void *const *dF, const Oc
                      const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
                      ofx_stats *stats_out)
 {
-    const double t0 = ofx_now_ms();
-    std::vector<ofx_stats> local(stats_out ? 0 : G);
-    ofx_stats *st = stats_out ? stats_out : local.data();
     const int kind = ofx_src_kind(ctx);                     // the frames come in the context's "input" kind
     const size_t pitch = ofx_src_pitch(ctx, nxs[0]);
-    const int s = kind == OFX_SRC_F64
-                      ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch)
-                      : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch);
-    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // as occ_group: nothing in flight when the arena is reset
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < G; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
-}
-
-// the contexts of a multi-context entry: one device, one precision
-int occ_dev_check_ctxs(ofx_ctx *const *ctxs, int n_ctx)
-{
-    if (!ctxs || n_ctx < 1) return OFX_ERR_ARG;
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision ||
-            ctxs[w]->input != ctxs[0]->input || ctxs[w]->input_pitch != ctxs[0]->input_pitch)
-            return OFX_ERR_ARG;
-    return OFX_OK;
+    return ofx_group_records(ctx, G, stats_out, [&](ofx_stats *st) {
+        return kind == OFX_SRC_F64
+                   ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch)
+                   : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch);
+    });
 }
 
 // bytes of a lockstep group of G triples over D planes: per level D planes and 3 G of (u1, u2, chi); full size 2 D of gradients /
@@ -1879,35 +1836,6 @@ struct OccDevMem {
     }
     double bytes(int G, int D) const { return 8.0 * 1.05 * ((D + 3.0 * G) * level_px + (2.0 * D + 27.0 * G) * full + 13.0 * G * skew); }
 };
-
-// groups of G consecutive triples, group q on context q mod n_ctx, a host thread per context; group(ctx, first, cnt, records)
-// enqueues triples first .. first + cnt - 1.  Returns when every payload is complete, with the first failing status.
-template <typename GroupFn>
-int occ_dev_run_groups(ofx_ctx *const *ctxs, int n_ctx, int n_triples, int G, double *work_pix_iters, GroupFn group)
-{
-    const int n_groups = (n_triples + G - 1) / G;
-    std::atomic<int> status(OFX_OK);
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_triples - first < G) ? n_triples - first : G;
-            int s = group(ctxs[w], first, cnt, st.data());
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-            if (work_pix_iters)
-                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
-        }
-        if (hipStreamSynchronize(ctxs[w]->stream) != hipSuccess) {
-            int expected = OFX_OK;
-            status.compare_exchange_strong(expected, ofx_fail(ctxs[w], OFX_ERR_HIP, "hipStreamSynchronize failed"));
-        }
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    return status.load();
-}
 
 }   // namespace
 
@@ -1935,9 +1863,8 @@ extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_f
                                         void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
                                         double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
 {
-    OFX_TRY(occ_dev_check_ctxs(ctxs, n_ctx));
-    int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
-    if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
     {
         ofx_ctx *ctx = ctxs[0];
         OFX_ENTER(ctx);
@@ -1946,18 +1873,16 @@ extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_f
         OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
         std::vector<int> nxs, nys;
         OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-        size_t free_b = 0, total_b = 0;
-        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-        const double budget = (ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b) / n_ctx;
+        double budget;
+        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
         const OccDevMem mem(nxs, nys);
         while (G >= 1 && mem.bytes(G, G + 2) > budget) G--;
         if (G < 1)
             return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ sequence: %.2f GB for one triple, %.2f GB per context available", mem.bytes(1, 3) / 1e9, budget / 1e9);
     }
     const int n_triples = n_frames - 2;
-    const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
-    if (G > per_ctx) G = per_ctx;
-    return occ_dev_run_groups(ctxs, n_ctx, n_triples, G, work_pix_iters, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
+    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
+    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, work_pix_iters, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
         return ofx_tvl1occ_sequence_group_dev(ctx, cnt + 2, dF + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta, theta,
                                               nscales, zfactor, warps, epsilon, st);
     });
@@ -2060,13 +1985,11 @@ extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_fr
                                        double lambda, double alpha, double beta, double theta, int nscales, double zfactor, int warps,
                                        double epsilon, double *work_pix_iters)
 {
-    OFX_TRY(occ_dev_check_ctxs(ctxs, n_ctx));
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
     if (n_triples < 0) return OFX_ERR_ARG;
     if (n_triples == 0) return OFX_OK;
-    int G = ctxs[0]->lockstep > 0 ? ctxs[0]->lockstep : OCC_MAX_GROUP;
-    if (G > OCC_MAX_GROUP) G = OCC_MAX_GROUP;
-    const int per_ctx = (n_triples + n_ctx - 1) / n_ctx;     // even the groups out over the contexts
-    if (G > per_ctx) G = per_ctx;
+    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
+    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
     {
         ofx_ctx *ctx = ctxs[0];
         OFX_ENTER(ctx);
@@ -2074,9 +1997,8 @@ extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_fr
         OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
         std::vector<int> nxs, nys;
         OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-        size_t free_b = 0, total_b = 0;
-        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-        const double budget = (ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b) / n_ctx;
+        double budget;
+        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
         const OccDevMem mem(nxs, nys);
         double need = 0.0;
         for (; G >= 1; G--) {                                 // the largest G whose groups all fit
@@ -2091,7 +2013,7 @@ extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_fr
         if (G < 1)
             return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ triples: %.2f GB for one triple, %.2f GB per context available", need / 1e9, budget / 1e9);
     }
-    return occ_dev_run_groups(ctxs, n_ctx, n_triples, G, work_pix_iters, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
+    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, work_pix_iters, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
         return ofx_tvl1occ_triples_group_dev(ctx, n_frames, dF, cnt, tr + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta,
                                              theta, nscales, zfactor, warps, epsilon, st);
     });

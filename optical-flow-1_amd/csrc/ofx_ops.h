@@ -26,6 +26,25 @@ template <typename T> int op_deinterleave2(ofx_ctx *ctx, const typename Pix<T>::
 template <typename T> int op_to_flo(ofx_ctx *ctx, const typename Pix<T>::v2 *src, float2 *dst, size_t n);
 template <typename T> int op_fill2(ofx_ctx *ctx, typename Pix<T>::v2 *dst, size_t n);   // zero
 
+// one host plane of n doubles into a new arena array of the storage type
+template <typename T>
+static int upload_plane(ofx_ctx *ctx, const double *h, size_t n, T **out)
+{
+    double *stage;
+    OFX_TRY(ofx_alloc(ctx, n, &stage));
+    OFX_TRY(ofx_alloc(ctx, n, out));
+    OFX_HIP(ctx, hipMemcpyAsync(stage, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return op_convert_in<T>(ctx, stage, *out, n);
+}
+
+// a solve's record before its first level: zeros but for the two counts
+static inline void ofx_stats_begin(ofx_stats *st, int nscales, int nsolves)
+{
+    memset(st, 0, sizeof(*st));
+    st->nscales = nscales;
+    st->nsolves = nsolves;
+}
+
 // ---- joint min / max and the normalisation map (getminmax, image_normalization_1 / _2 / _2_color / _3 / _4, src/utils.cpp) ----
 // The sources of one launch reach the kernels through a by-value table of OFX_MM_MAX_SRC (== 2 * OFX_MAX_GROUP ==
 // OFX_BROXT_MAX_FRAMES) pointers of type S (double, or the storage type; converted exactly to double).  `per` consecutive

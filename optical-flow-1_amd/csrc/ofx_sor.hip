@@ -21,10 +21,9 @@
 #include "ofx_device.h"
 #include "ofx_loop.h"
 #include "ofx_sor_tile.h"
+#include "ofx_batch.h"
 
 #include <algorithm>
-
-#include <atomic>
 #include <cmath>
 #include <new>
 #include <thread>
@@ -36,10 +35,6 @@
 #define BROX_EPSILON 0.001           // src/brox_optic_flow_spatial.cpp:23
 #define BROX_SOR_W 1.9               // src/brox_optic_flow_spatial.cpp:25
 #define BROX_SIGMA 0.8               // src/brox_optic_flow_spatial.cpp:26
-
-template <typename T> OFX_DEV double rnd_to(double x);
-template <> OFX_DEV double rnd_to<double>(double x) { return x; }
-template <> OFX_DEV double rnd_to<float>(double x) { return (double) (float) x; }
 
 static inline dim3 g2d(int nx, int ny) { return dim3(ofx_cdiv(nx, 64), ofx_cdiv(ny, 4)); }
 static inline dim3 b2d() { return dim3(64, 4); }
@@ -1026,16 +1021,6 @@ static int hs_single_scale_dev(ofx_ctx *ctx, HsLevel<T> &L, const HsParams &P, i
 }
 
 template <typename T>
-static int upload_plane(ofx_ctx *ctx, const double *h, size_t n, T **out)
-{
-    double *stage;
-    OFX_TRY(ofx_alloc(ctx, n, &stage));
-    OFX_TRY(ofx_alloc(ctx, n, out));
-    OFX_HIP(ctx, hipMemcpyAsync(stage, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    return op_convert_in<T>(ctx, stage, *out, n);
-}
-
-template <typename T>
 static int download_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, double *u, double *v, size_t n)
 {
     double *d1, *d2;
@@ -1048,20 +1033,12 @@ static int download_flow(ofx_ctx *ctx, const typename Pix<T>::v2 *U, double *u, 
     return OFX_OK;
 }
 
-static void sor_stats_begin(ofx_stats *st, int nscales, int nsolves)
-{
-    memset(st, 0, sizeof(*st));
-    st->nscales = nscales;
-    st->nsolves = nsolves;
-}
-static void sor_stats_begin(ofx_ctx *ctx, int nscales, int nsolves) { sor_stats_begin(&ctx->stats, nscales, nsolves); }
-
 template <typename T>
 static int hs_single_scale_host(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx, int ny,
                                 const HsParams &P)
 {
     const size_t n = (size_t) nx * ny;
-    sor_stats_begin(ctx, 1, P.warps);
+    ofx_stats_begin(&ctx->stats, 1, P.warps);
     ctx->stats.nx[0] = nx;
     ctx->stats.ny[0] = ny;
     HsLevel<T> L;
@@ -1092,7 +1069,7 @@ static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
     std::vector<int> nxs, nys;
     OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
     for (int g = 0; g < G; g++) {
-        sor_stats_begin(&stats[g], nscales, P.warps);
+        ofx_stats_begin(&stats[g], nscales, P.warps);
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
@@ -1137,7 +1114,7 @@ static int hs_pyramidal_host(ofx_ctx *ctx, const double *I1, const double *I2, d
 }
 
 // What the three ofx_*_group_dev entries share: the checks of the pointer tables and the group size, then the solver's own
-// (check), then solve(st) on the caller's records or, without stats_out, on local ones; pair 0's record stays in the context.
+// (check), then solve(st) under the group shell (ofx_group_records).
 template <class CheckFn, class SolveFn>
 static int sor_group_entry(ofx_ctx *ctx, const char *who, int n_pairs, const void *const *dI1, const void *const *dI2,
                            void *const *d_flo, ofx_stats *stats_out, CheckFn check, SolveFn solve)
@@ -1148,14 +1125,7 @@ static int sor_group_entry(ofx_ctx *ctx, const char *who, int n_pairs, const voi
     for (int g = 0; g < n_pairs; g++)
         if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer (pair %d)", who, g);
     OFX_TRY(check());
-    const double t0 = ofx_now_ms();
-    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    const int s = solve(st);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    return ofx_group_records(ctx, n_pairs, stats_out, solve);
 }
 
 template <typename T>
@@ -2128,7 +2098,7 @@ template <typename T> static void rexpo_pair_expo(const double *mg, T *expo, dou
 }
 
 // The G pairs of a lockstep group: ONE download of all gradient magnitudes, the pairs evaluated independently (method 3 sorts
-// and takes its quantile per pair) on up to 16 / concurrency host threads -- sor_batch_run sets `concurrency` to the number of
+// and takes its quantile per pair) on up to 16 / concurrency host threads -- ofx_run_groups sets `concurrency` to the number of
 // contexts working at once, so a batch runs at most 16 of them --, ONE upload.  A pair is evaluated by one thread in pixel
 // order whatever the thread count, so the result does not depend on it.  Levels of fewer than RX_EXPO_SERIAL pixels over all
 // pairs (the coarse ones, where starting a thread costs more than the pair's exp calls) are evaluated by the caller alone.
@@ -2336,7 +2306,7 @@ static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
     std::vector<int> nxs, nys;
     OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, nu, nxs, nys));
     for (int g = 0; g < G; g++) {
-        sor_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
+        ofx_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
@@ -2446,7 +2416,7 @@ static int rexpo_level_host(ofx_ctx *ctx, const double *I1, const double *I2, do
     if (nx < 1 || ny < 1) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: bad size %dx%d", nx, ny);
     const size_t n = (size_t) nx * ny, nc = n * nz;
     if ((long long) nc >= (1LL << 31)) return ofx_fail(ctx, OFX_ERR_ARG, "robust_expo: more than 2^31 image elements");
-    sor_stats_begin(&ctx->stats, 1, P.inner_iter * P.outer_iter);
+    ofx_stats_begin(&ctx->stats, 1, P.inner_iter * P.outer_iter);
     ctx->stats.nx[0] = nx;
     ctx->stats.ny[0] = ny;
     BroxLevel<T> L;
@@ -2500,7 +2470,7 @@ static int rexpo_pyramid_dev(ofx_ctx *ctx, int G, const OfxGroupPtrs &src, int n
 {
     const size_t nc = (size_t) nxs[0] * nys[0] * nz;
     for (int g = 0; g < G; g++) {
-        sor_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
+        ofx_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
@@ -2712,69 +2682,23 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
     });
 }
 
-// ---- batches of pairs for the SOR solvers: lockstep groups, one worker thread per context (as ofx_tvl1_batch_dev) ----
-template <class GroupFn>
-static int sor_batch_run(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, int G, double *work_pix_iters, GroupFn group)
-{
-    const int n_groups = (n_pairs + G - 1) / G;
-    std::atomic<int> status(OFX_OK);
-    const int n_workers = n_ctx < n_groups ? n_ctx : n_groups;
-    std::vector<int> conc(n_ctx);
-    for (int w = 0; w < n_ctx; w++) {                           // memory budgets are shared between the workers
-        conc[w] = ctxs[w]->concurrency;
-        if (ctxs[w]->concurrency < n_workers) ctxs[w]->concurrency = n_workers;
-    }
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_pairs - first < G) ? n_pairs - first : G;
-            const int s = group(ctxs[w], first, cnt, st.data());
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-            if (work_pix_iters)
-                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
-        }
-        (void) hipStreamSynchronize(ctxs[w]->stream);
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    for (int w = 0; w < n_ctx; w++) ctxs[w]->concurrency = conc[w];
-    return status.load();
-}
-
-// group size of the SOR batches: option "lockstep" of ctxs[0], else as large as possible (16), evened out over the
-// contexts like ofx_tvl1_batch_group_size
+// ---- batches of pairs for the SOR solvers: lockstep groups over the contexts (ofx_run_groups, with the `concurrency` hint:
+// memory budgets are shared between the workers) ----
+// group size: option "lockstep" of ctxs[0], else as large as possible (16), evened out over the contexts
 static int sor_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs)
 {
-    int G = ctxs[0]->lockstep;
-    if (G > 0) return G > OFX_MAX_GROUP ? OFX_MAX_GROUP : G;
-    if (n_pairs <= 1) return 1;
-    const int cap = OFX_MAX_GROUP;
-    const int rounds = (n_pairs + n_ctx * cap - 1) / (n_ctx * cap);
-    G = (n_pairs + n_ctx * rounds - 1) / (n_ctx * rounds);
-    return G < 1 ? 1 : G;
-}
-
-static int sor_batch_check(ofx_ctx *const *ctxs, int n_ctx, int n_pairs, const void *a, const void *b, const void *c)
-{
-    if (!ctxs || n_ctx < 1 || n_pairs < 0 || !a || !b || !c) return OFX_ERR_ARG;
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctxs[0]->device || ctxs[w]->precision != ctxs[0]->precision ||
-            ctxs[w]->input != ctxs[0]->input || ctxs[w]->input_pitch != ctxs[0]->input_pitch)
-            return OFX_ERR_ARG;
-    return OFX_OK;
+    return ofx_plan_lockstep(ctxs[0]->lockstep, OFX_MAX_GROUP, ofx_plan_even_rounds(n_pairs, n_ctx, OFX_MAX_GROUP));
 }
 
 extern "C" int ofx_hs_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
                                 void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales, double zfactor,
                                 int warps, double TOL, int maxiter, double *work_pix_iters)
 {
-    OFX_TRY(sor_batch_check(ctxs, n_ctx, n_pairs, dI1, dI2, d_flo));
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
     if (n_pairs == 0) return OFX_OK;
     const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return sor_batch_run(ctxs, n_ctx, n_pairs, G, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
         return ofx_hs_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nx, ny, alpha, nscales, zfactor, warps, TOL,
                                 maxiter, st);
     });
@@ -2784,10 +2708,11 @@ extern "C" int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
                                   void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha, double gamma, int nscales,
                                   double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
 {
-    OFX_TRY(sor_batch_check(ctxs, n_ctx, n_pairs, dI1, dI2, d_flo));
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
     if (n_pairs == 0) return OFX_OK;
     const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return sor_batch_run(ctxs, n_ctx, n_pairs, G, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
         return ofx_brox_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nxx, nyy, alpha, gamma, nscales, nu, TOL,
                                   inner_iter, outer_iter, st);
     });
@@ -2798,10 +2723,11 @@ extern "C" int ofx_robust_expo_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const 
                                          double alpha, double gamma, double lambda, int nscales, double nu, double TOL,
                                          int inner_iter, int outer_iter, double *work_pix_iters)
 {
-    OFX_TRY(sor_batch_check(ctxs, n_ctx, n_pairs, dI1, dI2, d_flo));
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
     if (n_pairs == 0) return OFX_OK;
     const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return sor_batch_run(ctxs, n_ctx, n_pairs, G, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
         return ofx_robust_expo_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nxx, nyy, nzz, method_type, alpha, gamma,
                                          lambda, nscales, nu, TOL, inner_iter, outer_iter, st);
     });
@@ -3190,7 +3116,7 @@ static int broxt_sequence_dev(ofx_ctx *ctx, int G, int frames, const void *const
     const size_t n = (size_t) nx * ny;
     if (G < 1 || G > OFX_MAX_GROUP || (G > 1 && frames > MF)) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal: group of %d sequences", G);
     const int planes = G * frames, tmp_planes = planes < MF ? planes : MF;
-    for (int g = 0; g < G; g++) sor_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
+    for (int g = 0; g < G; g++) ofx_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
     T *tmpA, *tmpB = nullptr;
     double *mm;
     // image_normalization_1 (:548) has one {min, max} set per SEQUENCE.  A table holds the frames of `per_launch` whole sequences
@@ -3329,19 +3255,16 @@ static int broxt_devapi(ofx_ctx *ctx, int G, int frames, const void *const *dF, 
     return OFX_OK;
 }
 
-// the checked solve of G sequences; stats: G records
+// the checked solve of G sequences under the group shell; stats_out: G records, or NULL
 static int broxt_dev_run(ofx_ctx *ctx, int G, int frames, const void *const *dF, void *const *d_flo, double alpha, double gamma,
                          int nscales, double nu, double TOL, int inner_iter, int outer_iter, const std::vector<int> &nxs,
-                         const std::vector<int> &nys, ofx_stats *stats)
+                         const std::vector<int> &nys, ofx_stats *stats_out)
 {
-    const double t0 = ofx_now_ms();
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
-    int s = ctx->precision == OFX_F64 ? broxt_devapi<double>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, stats)
-                                      : broxt_devapi<float>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, stats);
-    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);      // nothing in flight when the arena is reset
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < G; g++) stats[g].total_ms = ms;
-    return s;
+    return ofx_group_records(ctx, G, stats_out, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64 ? broxt_devapi<double>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, st)
+                                         : broxt_devapi<float>(ctx, G, frames, dF, d_flo, P, nscales, nu, nxs, nys, st);
+    });
 }
 
 // ofx_brox_temporal on a device-resident sequence (include/ofx.h)
@@ -3374,11 +3297,7 @@ extern "C" int ofx_brox_temporal_group_dev(ofx_ctx *ctx, int n_seq, int frames, 
     OFX_ENTER(ctx);
     std::vector<int> nxs, nys;
     OFX_TRY(broxt_group_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
-    std::vector<ofx_stats> local(stats_out ? 0 : n_seq);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    const int s = broxt_dev_run(ctx, n_seq, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, st);
-    ctx->stats = st[0];                                          // as the other *_group_dev entries: sequence 0's record
-    return s;
+    return broxt_dev_run(ctx, n_seq, frames, dF, d_flo, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, stats_out);
 }
 
 // n_seq independent sequences over the contexts (include/ofx.h).  Option "lockstep" of ctxs[0] = 0 or 1: sequence q alone on
@@ -3392,10 +3311,8 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
     if (!ctxs || n_ctx < 1 || !ctxs[0]) return OFX_ERR_ARG;
     ofx_ctx *ctx = ctxs[0];
     OFX_ENTER(ctx);
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->device != ctx->device || ctxs[w]->precision != ctx->precision || ctxs[w]->input != ctx->input ||
-            ctxs[w]->input_pitch != ctx->input_pitch)
-            return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: context %d NULL, on another device, of another precision, \"input\" or \"input_pitch\"", w);
+    if (ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT) != OFX_OK)
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: a context is NULL, on another device, of another precision, \"input\" or \"input_pitch\"");
     if (n_seq < 1) return ofx_fail(ctx, OFX_ERR_ARG, "brox temporal batch: %d sequences", n_seq);
     std::vector<int> nxs, nys;
     OFX_TRY(broxt_dev_check(ctx, n_seq, frames, dF, d_flo, nxx, nyy, nscales, nu, inner_iter, outer_iter, nxs, nys));
@@ -3404,9 +3321,8 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
     while (L > 1 && (long long) nxx * nyy * frames * L >= (1LL << 31)) L--;
     int n_use = 1;
     {
-        size_t free_b = 0, total_b = 0;
-        OFX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-        const double budget = ctx->mem_budget > 0 ? ctx->mem_budget : 0.5 * (double) free_b;
+        double budget;                                           // of the whole batch: this entry fits groups x contexts into it
+        OFX_TRY(ofx_batch_budget(ctx, 1, &budget));
         const double el = ctx->precision == OFX_F64 ? 8.0 : 4.0, B = ctx->sor_batch > 0 ? ctx->sor_batch : 64;
         double level_px = 0.0;
         for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
@@ -3424,22 +3340,19 @@ extern "C" int ofx_brox_temporal_batch_dev(ofx_ctx *const *ctxs, int n_ctx, int 
         if (fit < n_use) n_use = (int) fit;                      // ... then the contexts
     }
     if (ctx->lockstep < 2)
-        return sor_batch_run(ctxs, n_use, n_seq, 1, work_pix_iters, [&](ofx_ctx *c, int q, int, ofx_stats *st) {
+        return ofx_run_groups(ctxs, n_use, n_seq, 1, 1, work_pix_iters, true, [&](ofx_ctx *c, int q, int, ofx_stats *st) {
             OFX_ENTER(c);
-            const int s = broxt_dev_run(c, 1, frames, dF + (size_t) q * frames, d_flo + (size_t) q * (frames - 1), alpha, gamma, nscales,
-                                        nu, TOL, inner_iter, outer_iter, nxs, nys, &c->stats);
-            st[0] = c->stats;
-            return s;
+            return broxt_dev_run(c, 1, frames, dF + (size_t) q * frames, d_flo + (size_t) q * (frames - 1), alpha, gamma, nscales, nu, TOL,
+                                 inner_iter, outer_iter, nxs, nys, st);
         });
     const int exact = ctx->sor_exact, fuse = ctx->sor_fuse;
-    return sor_batch_run(ctxs, n_use, n_seq, L, work_pix_iters, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+    return ofx_run_groups(ctxs, n_use, n_seq, L, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
         OFX_ENTER(c);
         const int exact_c = c->sor_exact, fuse_c = c->sor_fuse;
         c->sor_exact = exact;
         c->sor_fuse = fuse;
         const int s = broxt_dev_run(c, cnt, frames, dF + (size_t) first * frames, d_flo + (size_t) first * (frames - 1), alpha, gamma,
                                     nscales, nu, TOL, inner_iter, outer_iter, nxs, nys, st);
-        c->stats = st[0];
         c->sor_exact = exact_c;
         c->sor_fuse = fuse_c;
         return s;
@@ -3526,7 +3439,7 @@ static int hs_classic_host(ofx_ctx *ctx, const double *a, const double *b, doubl
         cur ^= 1;
     }
     OFX_LAUNCH_CHECK(ctx);
-    sor_stats_begin(ctx, 1, 1);
+    ofx_stats_begin(&ctx->stats, 1, 1);
     ctx->stats.nx[0] = w;
     ctx->stats.ny[0] = h;
     ctx->stats.iters[0][0] = niter;

@@ -33,20 +33,15 @@
 #include "ofx_ops.h"
 #include "ofx_device.h"
 #include "ofx_loop.h"
+#include "ofx_batch.h"
 
-#include <atomic>
 #include <chrono>
 #include <cmath>
-#include <thread>
 #include <type_traits>
 
 #define TVL1_GRAD_IS_ZERO 1E-10          // src/tvl1flow.cpp:24
 #define TVL1_PRESMOOTHING_SIGMA 0.8      // src/tvl1flow.cpp:23
 #define STRIP_OUT 62                     // output columns per wave
-
-template <typename T> OFX_DEV double rnd_to(double x);
-template <> OFX_DEV double rnd_to<double>(double x) { return x; }
-template <> OFX_DEV double rnd_to<float>(double x) { return (double) (float) x; }
 
 // The wave index of the marching kernels: the same in every lane (256-thread blocks of four waves), but derived from threadIdx,
 // so the compiler takes it -- and the strip geometry, the row counter and every stage condition computed from it -- for
@@ -1899,13 +1894,6 @@ static int tvl1_single_scale_dev(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params
     return OFX_OK;
 }
 
-static void stats_begin(ofx_stats *st, int nscales, int nsolves)
-{
-    memset(st, 0, sizeof(*st));
-    st->nscales = nscales;
-    st->nsolves = nsolves;
-}
-
 // src/tvl1flow.cpp:219-328 for G pairs in lockstep.  dI0[g] / dI1[g]: device images of storage type T, or with kind >= 0
 // of that element kind (OFX_SRC_*).  On success lv[0].U[half of lv[0].cur] holds the flows.
 // shared > 0: both directions of `shared` pairs in G = 2 * shared slots -- slot g solves (dI0[g], dI1[g]), slot shared + g
@@ -1927,7 +1915,7 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
     std::vector<int> nxs, nys;
     OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
     for (int g = 0; g < G; g++) {
-        stats_begin(&stats[g], nscales, P.warps);
+        ofx_stats_begin(&stats[g], nscales, P.warps);
         for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
     }
     lv.resize(nscales);
@@ -1982,23 +1970,13 @@ static Tvl1Params make_params(const ofx_ctx *ctx, double tau, double lambda, dou
 }
 
 template <typename T>
-static int upload_image(ofx_ctx *ctx, const double *h, size_t n, T **out)
-{
-    double *stage;
-    OFX_TRY(ofx_alloc(ctx, n, &stage));
-    OFX_TRY(ofx_alloc(ctx, n, out));
-    OFX_HIP(ctx, hipMemcpyAsync(stage, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    return op_convert_in<T>(ctx, stage, *out, n);
-}
-
-template <typename T>
 static int tvl1_multiscale_host(ofx_ctx *ctx, const double *I0, const double *I1, double *u1, double *u2, int nx,
                                 int ny, const Tvl1Params &P, int nscales, double zfactor)
 {
     const size_t n = (size_t) nx * ny;
     T *dI0, *dI1;
-    OFX_TRY(upload_image<T>(ctx, I0, n, &dI0));
-    OFX_TRY(upload_image<T>(ctx, I1, n, &dI1));
+    OFX_TRY(upload_plane<T>(ctx, I0, n, &dI0));
+    OFX_TRY(upload_plane<T>(ctx, I1, n, &dI1));
     std::vector<Tvl1Level<T>> lv;
     const T *a = dI0, *b = dI1;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, 1, &a, &b, nx, ny, P, nscales, zfactor, lv, &ctx->stats));
@@ -2081,6 +2059,24 @@ int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
     return OFX_OK;
 }
 
+// Buffers that do not live on this context's GPU (a batch spread over several GPUs by ofx_tvl1_batch_dev, or host buffers) are
+// staged through the arena, on the context's stream.  In: *out = p itself where it is local, else an arena buffer of `bytes`
+// bytes -- filled from p (fill: what the solve reads) or left for the solve to write ...
+static int tvl1_stage_in(ofx_ctx *ctx, const void *p, size_t bytes, bool fill, void **out)
+{
+    *out = const_cast<void *>(p);
+    if (ofx_ptr_is_local(ctx, p)) return OFX_OK;
+    char *stage;
+    OFX_TRY(ofx_alloc(ctx, bytes, &stage));
+    *out = stage;
+    return fill ? ofx_copy_staged(ctx, stage, p, bytes) : OFX_OK;
+}
+// ... out: back into the caller's array where the solve wrote a stage
+static int tvl1_stage_out(ofx_ctx *ctx, void *p, const void *staged, size_t bytes)
+{
+    return staged != p ? ofx_copy_staged(ctx, p, staged, bytes) : OFX_OK;
+}
+
 template <typename T>
 static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, const void *const *dI1_in, void *const *d_flo_in,
                              int nx, int ny, const Tvl1Params &P, int nscales, double zfactor, ofx_stats *stats,
@@ -2092,35 +2088,15 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
     const size_t pitch = nx > 0 ? ofx_src_pitch(ctx, nx) : 0;
     // a frame's bytes as they lie: with a pitch, from its first row's start to its last row's end
     const size_t span = pitch && ny > 0 ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
-    // Images and payloads that do not live on this context's GPU (a batch spread over several GPUs by ofx_tvl1_batch_dev, or
-    // host buffers) are staged: in through arena buffers before the solve, out after it, all on the context's stream.
-    const void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
-    void *d_flo[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) {
-        const void *src[2] = {dI0_in[g], dI1_in[g]};
-        const void **dst[2] = {&dI0[g], &dI1[g]};
-        for (int k = 0; k < 2; k++) {
-            if (ofx_ptr_is_local(ctx, src[k])) { *dst[k] = src[k]; continue; }
-            char *stage;                                     // sized by the source element; a pitched frame keeps its pitch
-            OFX_TRY(ofx_alloc(ctx, span, &stage));
-            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], span));
-            *dst[k] = stage;
-        }
-        d_flo[g] = d_flo_in[g];
-        if (!ofx_ptr_is_local(ctx, d_flo_in[g])) {
-            float2 *stage;
-            OFX_TRY(ofx_alloc(ctx, n, &stage));
-            d_flo[g] = stage;
-        }
+    void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP], *d_flo[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
+    for (int g = 0; g < G; g++) {                            // a pitched frame keeps its pitch
+        OFX_TRY(tvl1_stage_in(ctx, dI0_in[g], span, true, &dI0[g]));
+        OFX_TRY(tvl1_stage_in(ctx, dI1_in[g], span, true, &dI1[g]));
+        OFX_TRY(tvl1_stage_in(ctx, d_flo_in[g], n * sizeof(float2), false, &d_flo[g]));
     }
-    const void *init[OFX_MAX_GROUP];                         // a start that is not on this GPU is staged like a frame
-    for (int g = 0; init_in && g < G; g++) {
-        init[g] = init_in[g];
-        if (!init_in[g] || ofx_ptr_is_local(ctx, init_in[g])) continue;
-        float2 *stage;
-        OFX_TRY(ofx_alloc(ctx, n, &stage));
-        OFX_TRY(ofx_copy_staged(ctx, stage, init_in[g], n * sizeof(float2)));
-        init[g] = stage;
+    for (int g = 0; init_in && g < G; g++) {                 // a start, where the pair has one
+        init[g] = nullptr;
+        if (init_in[g]) OFX_TRY(tvl1_stage_in(ctx, init_in[g], n * sizeof(float2), true, &init[g]));
     }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv,
@@ -2130,8 +2106,7 @@ static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, con
     hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
                        out, n);
     OFX_LAUNCH_CHECK(ctx);
-    for (int g = 0; g < G; g++)
-        if (d_flo[g] != d_flo_in[g]) OFX_TRY(ofx_copy_staged(ctx, d_flo_in[g], d_flo[g], n * sizeof(float2)));
+    for (int g = 0; g < G; g++) OFX_TRY(tvl1_stage_out(ctx, d_flo_in[g], d_flo[g], n * sizeof(float2)));
     return OFX_OK;
 }
 
@@ -2169,17 +2144,12 @@ static int tvl1_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI0, c
         OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
         OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
     }
-    const double t0 = ofx_now_ms();
     const Tvl1Params P = make_params(ctx, tau, lambda, theta, warps, epsilon, 0);
-    std::vector<ofx_stats> local(stats_out ? 0 : n_pairs);      // ~25 KB per record: not on the stack
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    int s = ctx->precision == OFX_F64
-                ? tvl1_group_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init)
-                : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    return ofx_group_records(ctx, n_pairs, stats_out, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64
+                   ? tvl1_group_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init)
+                   : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init);
+    });
 }
 
 extern "C" int ofx_tvl1_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI0, const void *const *dI1,
@@ -2283,36 +2253,19 @@ static int tvl1_bidir_devapi(ofx_ctx *ctx, int Gp, const void *const *dI0_in, co
     OFX_TRY(ofx_pitch_check(ctx, "tvl1_bidir", nx));
     const size_t pitch = ofx_src_pitch(ctx, nx);
     const size_t span = pitch ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
-    const void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
+    void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
     void *flo_in[OFX_MAX_GROUP], *occ_in[OFX_MAX_GROUP], *flo[OFX_MAX_GROUP], *occ[OFX_MAX_GROUP];     // slot order
     for (int g = 0; g < Gp; g++) {
-        const void *src[2] = {dI0_in[g], dI1_in[g]};
-        const void **dst[2] = {&dI0[g], &dI1[g]};
-        for (int k = 0; k < 2; k++) {
-            if (ofx_ptr_is_local(ctx, src[k])) { *dst[k] = src[k]; continue; }
-            char *stage;
-            OFX_TRY(ofx_alloc(ctx, span, &stage));
-            OFX_TRY(ofx_copy_staged(ctx, stage, src[k], span));
-            *dst[k] = stage;
-        }
+        OFX_TRY(tvl1_stage_in(ctx, dI0_in[g], span, true, &dI0[g]));
+        OFX_TRY(tvl1_stage_in(ctx, dI1_in[g], span, true, &dI1[g]));
         flo_in[g] = d_flo_fwd[g];
         flo_in[Gp + g] = d_flo_bwd[g];
         occ_in[g] = d_occ_fwd[g];
         occ_in[Gp + g] = d_occ_bwd[g];
     }
     for (int z = 0; z < G; z++) {
-        flo[z] = flo_in[z];
-        occ[z] = occ_in[z];
-        if (!ofx_ptr_is_local(ctx, flo_in[z])) {
-            float2 *stage;
-            OFX_TRY(ofx_alloc(ctx, n, &stage));
-            flo[z] = stage;
-        }
-        if (!ofx_ptr_is_local(ctx, occ_in[z])) {
-            unsigned char *stage;
-            OFX_TRY(ofx_alloc(ctx, n, &stage));
-            occ[z] = stage;
-        }
+        OFX_TRY(tvl1_stage_in(ctx, flo_in[z], n * sizeof(float2), false, &flo[z]));
+        OFX_TRY(tvl1_stage_in(ctx, occ_in[z], n, false, &occ[z]));
     }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv, stats,
@@ -2326,8 +2279,8 @@ static int tvl1_bidir_devapi(ofx_ctx *ctx, int Gp, const void *const *dI0_in, co
     for (int z = 0; z < G; z++) against[z] = flo[(z + Gp) % G];
     OFX_TRY(op_flow_consistency(ctx, G, flo, against, occ, nx, ny, fb_alpha, fb_beta));
     for (int z = 0; z < G; z++) {
-        if (flo[z] != flo_in[z]) OFX_TRY(ofx_copy_staged(ctx, flo_in[z], flo[z], n * sizeof(float2)));
-        if (occ[z] != occ_in[z]) OFX_TRY(ofx_copy_staged(ctx, occ_in[z], occ[z], n));
+        OFX_TRY(tvl1_stage_out(ctx, flo_in[z], flo[z], n * sizeof(float2)));
+        OFX_TRY(tvl1_stage_out(ctx, occ_in[z], occ[z], n));
     }
     return OFX_OK;
 }
@@ -2349,19 +2302,14 @@ extern "C" int ofx_tvl1_bidir_group_dev(ofx_ctx *ctx, int n_pairs, const void *c
         if (reinterpret_cast<uintptr_t>(d_flo_fwd[g]) % sizeof(float2) || reinterpret_cast<uintptr_t>(d_flo_bwd[g]) % sizeof(float2))
             return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_bidir: payload of pair %d is not 8-byte aligned", g);
     }
-    const double t0 = ofx_now_ms();
     const Tvl1Params P = make_params(ctx, tau, lambda, theta, warps, epsilon, 0);
-    std::vector<ofx_stats> local(stats_out ? 0 : 2 * n_pairs);
-    ofx_stats *st = stats_out ? stats_out : local.data();
-    int s = ctx->precision == OFX_F64
-                ? tvl1_bidir_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
-                                            zfactor, fb_alpha, fb_beta, st)
-                : tvl1_bidir_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
-                                           zfactor, fb_alpha, fb_beta, st);
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < 2 * n_pairs; g++) st[g].total_ms = ms;
-    ctx->stats = st[0];
-    return s;
+    return ofx_group_records(ctx, 2 * n_pairs, stats_out, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64
+                   ? tvl1_bidir_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
+                                               zfactor, fb_alpha, fb_beta, st)
+                   : tvl1_bidir_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, P, nscales,
+                                              zfactor, fb_alpha, fb_beta, st);
+    });
 }
 
 template <typename T>
@@ -2369,13 +2317,13 @@ static int tvl1_single_scale_host(ofx_ctx *ctx, const double *I0, const double *
                                   int ny, const Tvl1Params &P)
 {
     const size_t n = (size_t) nx * ny;
-    stats_begin(&ctx->stats, 1, P.warps);
+    ofx_stats_begin(&ctx->stats, 1, P.warps);
     ctx->stats.nx[0] = nx;
     ctx->stats.ny[0] = ny;
     Tvl1Level<T> L;
     OFX_TRY(tvl1_level_alloc<T>(ctx, L, nx, ny, 1, false));
-    OFX_TRY(upload_image<T>(ctx, I0, n, &L.I0));
-    OFX_TRY(upload_image<T>(ctx, I1, n, &L.I1));
+    OFX_TRY(upload_plane<T>(ctx, I0, n, &L.I0));
+    OFX_TRY(upload_plane<T>(ctx, I1, n, &L.I1));
     double *d1, *d2;
     OFX_TRY(ofx_alloc(ctx, n, &d1));
     OFX_TRY(ofx_alloc(ctx, n, &d2));
@@ -2411,7 +2359,7 @@ static int tvl1_iterations_host(ofx_ctx *ctx, double *u1, double *u2, double *p1
                                 int ny, const Tvl1Params &P, double *error)
 {
     const size_t n = (size_t) nx * ny;
-    stats_begin(&ctx->stats, 1, 1);
+    ofx_stats_begin(&ctx->stats, 1, 1);
     ctx->stats.nx[0] = nx;
     ctx->stats.ny[0] = ny;
     Tvl1Level<T> L;
@@ -2482,9 +2430,7 @@ extern "C" int ofx_tvl1_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_
                                          double zfactor)
 {
     if (!ctxs || n_ctx < 1 || !ctxs[0] || n_pairs < 0 || nx < 1 || ny < 1) return -OFX_ERR_ARG;
-    int G = ctxs[0]->lockstep;
-    if (G > 0) return G > OFX_MAX_GROUP ? OFX_MAX_GROUP : G;
-    if (n_pairs <= 1) return 1;
+    if (ctxs[0]->lockstep > 0 || n_pairs <= 1) return ofx_plan_lockstep(ctxs[0]->lockstep, OFX_MAX_GROUP, 1);
     std::vector<int> nxs, nys;
     const int st = op_pyramid_sizes(ctxs[0], nx, ny, nscales, zfactor, nxs, nys);
     if (st != OFX_OK) return -st;
@@ -2525,9 +2471,7 @@ extern "C" int ofx_tvl1_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_
         }
     }
     (void) hipSetDevice(dev_now);
-    const int rounds = (n_pairs + n_ctx * cap - 1) / (n_ctx * cap);
-    G = (n_pairs + n_ctx * rounds - 1) / (n_ctx * rounds);
-    return G < 1 ? 1 : G;
+    return ofx_plan_even_rounds(n_pairs, n_ctx, cap);
 }
 
 // libm's hypot as the dual update uses it (src/tvl1flow.cpp:172-173), n values: the device restatement of glibc's algorithm
@@ -2563,36 +2507,17 @@ static int tvl1_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *
                            const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double tau, double lambda,
                            double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
 {
-    if (!ctxs || n_ctx < 1 || n_pairs < 0 || !dI0 || !dI1 || !d_flo) return OFX_ERR_ARG;
+    if (n_pairs < 0 || !dI0 || !dI1 || !d_flo) return OFX_ERR_ARG;
     // The contexts may live on DIFFERENT GPUs of the node (one process, one host thread per context): a group whose images
     // are not on its context's GPU is staged there and its payloads are copied back into the caller's arrays (tvl1_group_devapi)
     // -- the C caller's multi-GPU path, no launcher and no collective library needed (pairs are independent).
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input ||
-            ctxs[w]->input_pitch != ctxs[0]->input_pitch)
-            return OFX_ERR_ARG;
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_FORMAT));
     const int G = ofx_tvl1_batch_group_size(ctxs, n_ctx, n_pairs, nx, ny, nscales, zfactor);
     if (G < 1) return G < 0 ? -G : OFX_ERR_ARG;                 // negative = -status of the failing check
-    const int n_groups = (n_pairs + G - 1) / G;
-    std::atomic<int> status(OFX_OK);
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_pairs - first < G) ? n_pairs - first : G;
-            const int s = tvl1_group_entry(ctxs[w], cnt, dI0 + first, dI1 + first, d_flo_init ? d_flo_init + first : nullptr,
-                                           d_flo + first, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon, st.data());
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-            if (work_pix_iters)
-                for (int g = 0; g < cnt; g++) work_pix_iters[first + g] = st[g].work_pix_iters;
-        }
-        (void) hipStreamSynchronize(ctxs[w]->stream);
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    return status.load();
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, false, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+        return tvl1_group_entry(c, cnt, dI0 + first, dI1 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nx, ny, tau,
+                                lambda, theta, nscales, zfactor, warps, epsilon, st);
+    });
 }
 extern "C" int ofx_tvl1_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI0, const void *const *dI1,
                                   void *const *d_flo, int n_pairs, int nx, int ny, double tau, double lambda,
@@ -2623,36 +2548,15 @@ extern "C" int ofx_tvl1_bidir_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const v
                                         int nscales, double zfactor, int warps, double epsilon, double fb_alpha, double fb_beta,
                                         double *work_pix_iters)
 {
-    if (!ctxs || n_ctx < 1 || n_pairs < 0 || !dI0 || !dI1 || !d_flo_fwd || !d_flo_bwd || !d_occ_fwd || !d_occ_bwd) return OFX_ERR_ARG;
-    for (int w = 0; w < n_ctx; w++)
-        if (!ctxs[w] || ctxs[w]->precision != ctxs[0]->precision || ctxs[w]->input != ctxs[0]->input ||
-            ctxs[w]->input_pitch != ctxs[0]->input_pitch)
-            return OFX_ERR_ARG;
+    if (n_pairs < 0 || !dI0 || !dI1 || !d_flo_fwd || !d_flo_bwd || !d_occ_fwd || !d_occ_bwd) return OFX_ERR_ARG;
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_FORMAT));
     const int slots = ofx_tvl1_batch_group_size(ctxs, n_ctx, 2 * n_pairs, nx, ny, nscales, zfactor);
     if (slots < 1) return slots < 0 ? -slots : OFX_ERR_ARG;
     const int G = slots / 2 > 1 ? slots / 2 : 1;                // pairs per group, at most OFX_MAX_GROUP / 2
-    const int n_groups = (n_pairs + G - 1) / G;
-    std::atomic<int> status(OFX_OK);
-    auto worker = [&](int w) {
-        std::vector<ofx_stats> st(2 * G);
-        for (int q = w; q < n_groups; q += n_ctx) {
-            if (status.load() != OFX_OK) return;
-            const int first = q * G, cnt = (n_pairs - first < G) ? n_pairs - first : G;
-            const int s = ofx_tvl1_bidir_group_dev(ctxs[w], cnt, dI0 + first, dI1 + first, d_flo_fwd + first, d_flo_bwd + first,
-                                                   d_occ_fwd + first, d_occ_bwd + first, nx, ny, tau, lambda, theta, nscales, zfactor,
-                                                   warps, epsilon, fb_alpha, fb_beta, st.data());
-            if (s != OFX_OK) { int expected = OFX_OK; status.compare_exchange_strong(expected, s); return; }
-            if (work_pix_iters)
-                for (int g = 0; g < cnt; g++) {                 // forward first, then backward
-                    work_pix_iters[first + g] = st[g].work_pix_iters;
-                    work_pix_iters[n_pairs + first + g] = st[cnt + g].work_pix_iters;
-                }
-        }
-        (void) hipStreamSynchronize(ctxs[w]->stream);
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < n_ctx && w < n_groups; w++) th.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : th) t.join();
-    return status.load();
+    // two records per pair: the work table is forward first, then backward, as a group's records are
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 2, work_pix_iters, false, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+        return ofx_tvl1_bidir_group_dev(c, cnt, dI0 + first, dI1 + first, d_flo_fwd + first, d_flo_bwd + first, d_occ_fwd + first,
+                                        d_occ_bwd + first, nx, ny, tau, lambda, theta, nscales, zfactor, warps, epsilon, fb_alpha,
+                                        fb_beta, st);
+    });
 }
