@@ -187,6 +187,8 @@ int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
 /* Option "input": what a frame pointer of a *_dev entry points at.  The entries that take frames as device pointers --
  * ofx_tvl1_multiscale_dev / _group_dev / _batch_dev, ofx_tvl1_group_init_dev / ofx_tvl1_batch_init_dev / ofx_tvl1_sequence_group_dev,
  * ofx_tvl1_bidir_group_dev / _bidir_batch_dev, ofx_hs_group_dev / _batch_dev, ofx_brox_group_dev / _batch_dev,
+ * ofx_hs_group_init_dev / ofx_hs_batch_init_dev / ofx_hs_sequence_group_dev, ofx_brox_group_init_dev / ofx_brox_batch_init_dev /
+ * ofx_brox_sequence_group_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
  * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev and ofx_pyramid_group_dev -- read
  * elements of this kind wherever their
@@ -493,6 +495,62 @@ int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const 
 int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
                        void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha, double gamma, int nscales,
                        double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters);
+
+/* ---- SOR warm start: a flow to start Horn-Schunck and Brox from, and their video chains ---------------------------
+ * The start of a pair is a .flo payload P as every solver writes it: nx * ny interleaved (u, v) float32, 8-byte aligned.  It
+ * enters exactly as the TV-L1 warm start does (above; restated in tests/sor_warm_ref.py), with z = zfactor for Horn-Schunck
+ * and z = nu for Brox:
+ *   W_0 = ((double) P.u, (double) P.v), a component that is not finite (NaN, +-Inf) taken as 0.0;
+ *   W_s = zoom_out(W_{s-1}, z) * z for s = 1 .. nscales - 1, per component, in double storage and arithmetic whatever the
+ *         context's precision -- the mirror of the `*= 1.0 / zfactor` of src/horn_schunck_pyramidal.cpp:345-352 and of the
+ *         1 / nu of src/brox_optic_flow_spatial.cpp:529-535;
+ *   the flow of the coarsest level is W_{nscales-1}, rounded once to the storage type, in place of the reference's zeros.
+ * Everything after the start is the driver of ofx_hs_group_dev / ofx_brox_group_dev, unchanged, under every setting of the
+ * options sor_exact, sor_fuse, sor_lds and sor_tile: the start does not depend on the sweep order.  A NULL table is the plain
+ * entry itself, a NULL entry is a zero start, and an all-zero payload gives the plain entry's payload, sweep table and, in
+ * exact mode, stopping values bit for bit.  d_flo_init[g] == d_flo[g] is allowed: the start is consumed before any payload is
+ * written.  Warm and cold pairs may share a group; each pair gets what the same call computes for that pair alone.  Frames are
+ * read under "input" / "input_pitch"; a start that is not on the context's GPU is staged as ofx_tvl1_batch_dev stages its
+ * buffers.
+ * Refusals, before any work, nothing written, the reason in ofx_last_error: those of the plain entries; a start pointer that is
+ * not 8-byte aligned (OFX_ERR_ARG, its pair index named); OFX_ERR_SIGMA as the image pyramid gives it (same levels, same sigma).
+ * Out of scope: a start for ofx_robust_expo_*, ofx_brox_temporal_* and ofx_tvl1occ_*, for the host-plane entries
+ * (ofx_hs_pyramidal, ofx_brox_spatial; ofx_hs_single_scale has always read u and v as its start), and bidirectional SOR entries.
+ *
+ * The batch entries take the same table after dI2 and keep the grouping rule of ofx_hs_batch_dev / ofx_brox_batch_dev (the
+ * start's scratch comes from the group's workspace and does not enter the group size).  Groups run concurrently: a start may be
+ * the pair's own slot of d_flo, not another pair's; the starts' refusals are raised for the whole batch before any group runs,
+ * the pair named by its index in the batch. */
+int ofx_hs_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                          const void *const *d_flo_init, void *const *d_flo, int nx, int ny, double alpha, int nscales,
+                          double zfactor, int warps, double TOL, int maxiter, ofx_stats *stats_out);
+int ofx_hs_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                          const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha,
+                          int nscales, double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters);
+int ofx_brox_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                            const void *const *d_flo_init, void *const *d_flo, int nxx, int nyy, double alpha, double gamma,
+                            int nscales, double nu, double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out);
+int ofx_brox_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                            const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha,
+                            double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
+                            double *work_pix_iters);
+/* The SOR video chains, with the layout of ofx_tvl1_sequence_group_dev: n_seq (1..16) device-resident sequences of n_frames >= 2
+ * frames, sequence q = the frames dF[q * n_frames + t] and the payloads d_flo[q * (n_frames - 1) + t].  Step t solves the pairs
+ * (F[q][t], F[q][t + 1]) of all sequences as one lockstep group: step 0 cold with nscales_first scales and warps_first warps
+ * (Brox: outer_first outer iterations), step t > 0 from d_flo[q][t - 1] with nscales_next and warps_next (outer_next) -- these
+ * loops run a fixed count whatever the start, so a warm step may be given fewer.  The payload of the step before is on the
+ * device already: no host round trip between steps.  Each payload is bit for bit what the chained ofx_*_group_init_dev calls
+ * write; consecutive steps do not share a frame's pyramid (image_normalization_2 works on a pair).  stats_out: NULL or
+ * n_seq * (n_frames - 1) records, laid out like d_flo.  Both pyramids are validated before any work.  Frames and payloads
+ * that are not on the context's GPU (host arrays: the front-ends' route) are staged step by step as ofx_tvl1_batch_dev stages
+ * its buffers, at the cost of the copies.  Refusals as the group entries, and OFX_ERR_ARG for n_seq outside 1..16,
+ * n_frames < 2, a payload that is NULL or not 8-byte aligned. */
+int ofx_hs_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nx, int ny,
+                              double alpha, int nscales_first, int nscales_next, double zfactor, int warps_first, int warps_next,
+                              double TOL, int maxiter, ofx_stats *stats_out);
+int ofx_brox_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nxx,
+                                int nyy, double alpha, double gamma, int nscales_first, int nscales_next, double nu, double TOL,
+                                int inner_iter, int outer_first, int outer_next, ofx_stats *stats_out);
 
 /* ---- robust_expo_methods (replace src/robust_expo_methods.h:21-38) -----------------------------------*/
 /* Brox's scheme with an image-driven weight in the smoothness term: method_type 1 = exp(-lambda |grad I1|), 2 = the same

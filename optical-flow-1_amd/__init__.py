@@ -149,6 +149,16 @@ def lib():
                                     _i, C.POINTER(Stats)]),
         "ofx_brox_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _d, _d, _i,
                                     _d, _d, _i, _i, C.POINTER(_d)]),
+        "ofx_hs_group_init_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _i, _d, _i, _d, _i, C.POINTER(Stats)]),
+        "ofx_hs_batch_init_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _i, _d, _i, _d, _i, _d, _i,
+                                                                                   C.POINTER(_d)]),
+        "ofx_hs_sequence_group_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _i, _i, _d, _i, _i, _d, _i,
+                                           C.POINTER(Stats)]),
+        "ofx_brox_group_init_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d, _i, _d, _d, _i, _i, C.POINTER(Stats)]),
+        "ofx_brox_batch_init_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _i, _d, _d, _i, _d, _d, _i, _i,
+                                                                                     C.POINTER(_d)]),
+        "ofx_brox_sequence_group_dev": (_i, [_vp, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _d, _d, _i, _i, _d, _d, _i, _i, _i,
+                                             C.POINTER(Stats)]),
         "ofx_robust_expo_group_dev": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _d, _d, _d, _i,
                                            _d, _d, _i, _i, C.POINTER(Stats)]),
         "ofx_robust_expo_batch_dev": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i,
@@ -270,6 +280,33 @@ def hs_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0
 def brox_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1, outer=15):
     """ofx_brox_batch_dev (see hs_batch_dev)"""
     return _batch_call(lib().ofx_brox_batch_dev, ctxs, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
+
+
+def _batch_init_call(fn, ctxs, dA, dB, d_flo_init, d_flo, *args):
+    n = len(dA)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n, 1))()
+    init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
+    s = fn(arr([c.h.value for c in ctxs]), len(ctxs), arr(dA), arr(dB), init, arr(d_flo), n, *args, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(n)]
+
+
+def hs_batch_init_dev(ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4,
+                      maxiter=150):
+    """ofx_hs_batch_init_dev: hs_batch_dev with a start per pair -- d_flo_init is None (the plain batch) or a list with one entry
+    per pair, a device pointer (int) of a .flo payload or None / 0 for a pair that starts from zero.  Returns the per-pair work
+    (pixel-sweeps)."""
+    return _batch_init_call(lib().ofx_hs_batch_init_dev, ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor, warps,
+                            TOL, maxiter)
+
+
+def brox_batch_init_dev(ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1,
+                        outer=15):
+    """ofx_brox_batch_init_dev (see hs_batch_init_dev)"""
+    return _batch_init_call(lib().ofx_brox_batch_init_dev, ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, gamma, nscales, nu,
+                            TOL, inner, outer)
 
 
 def robust_expo_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4,
@@ -695,6 +732,53 @@ class Ofx:
     def brox_group_dev(self, dI1, dI2, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1, outer=15):
         """ofx_brox_group_dev (see hs_group_dev)"""
         return self._group_call(self.L.ofx_brox_group_dev, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
+
+    def _group_init_call(self, fn, dA, dB, d_flo_init, d_flo, *args):
+        n = len(dA)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n, 1))()
+        init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
+        self._ck(fn(self.h, n, arr(dA), arr(dB), init, arr(d_flo), *args, st))
+        return [st[i] for i in range(n)]
+
+    def hs_group_init_dev(self, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4,
+                          maxiter=150):
+        """ofx_hs_group_init_dev: hs_group_dev with a start per pair.  d_flo_init: None (the plain group), or one entry per pair,
+        the device pointer (int) of a .flo payload to start from or None / 0 for a pair that starts from zero; an entry may be
+        the pair's own d_flo.  Returns the per-pair Stats records."""
+        return self._group_init_call(self.L.ofx_hs_group_init_dev, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor,
+                                     warps, TOL, maxiter)
+
+    def brox_group_init_dev(self, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4,
+                            inner=1, outer=15):
+        """ofx_brox_group_init_dev (see hs_group_init_dev)"""
+        return self._group_init_call(self.L.ofx_brox_group_init_dev, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, gamma, nscales,
+                                     nu, TOL, inner, outer)
+
+    def _sequence_call(self, fn, who, dF, d_flo, *args):
+        n_seq = len(dF)
+        n_frames = len(dF[0]) if n_seq else 0
+        if any(len(f) != n_frames for f in dF) or len(d_flo) != n_seq or any(len(p) != max(n_frames - 1, 0) for p in d_flo):
+            raise ValueError(who + ": every sequence needs the same number of frames and one payload per step")
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        steps = max(n_frames - 1, 0)
+        st = (Stats * max(n_seq * steps, 1))()
+        self._ck(fn(self.h, n_seq, n_frames, arr([p for f in dF for p in f]), arr([p for f in d_flo for p in f]), *args, st))
+        return [[st[q * steps + t] for t in range(steps)] for q in range(n_seq)]
+
+    def hs_sequence_group_dev(self, dF, d_flo, nx, ny, alpha=7.0, nscales_first=10, nscales_next=2, zfactor=0.5, warps_first=10,
+                              warps_next=10, TOL=1e-4, maxiter=150):
+        """ofx_hs_sequence_group_dev, the video chain: dF[q] = the device pointers (ints) of the frames of sequence q, d_flo[q] =
+        those of its len(dF[q]) - 1 payloads.  Step 0 is solved cold with nscales_first scales and warps_first warps, every later
+        step from the payload of the step before with nscales_next and warps_next.  Returns the Stats records, [sequence][step]."""
+        return self._sequence_call(self.L.ofx_hs_sequence_group_dev, "hs_sequence_group_dev", dF, d_flo, nx, ny, alpha,
+                                   nscales_first, nscales_next, zfactor, warps_first, warps_next, TOL, maxiter)
+
+    def brox_sequence_group_dev(self, dF, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales_first=10, nscales_next=2, nu=0.5,
+                                TOL=1e-4, inner=1, outer_first=15, outer_next=15):
+        """ofx_brox_sequence_group_dev (see hs_sequence_group_dev; outer_first / outer_next outer iterations)"""
+        return self._sequence_call(self.L.ofx_brox_sequence_group_dev, "brox_sequence_group_dev", dF, d_flo, nx, ny, alpha, gamma,
+                                   nscales_first, nscales_next, nu, TOL, inner, outer_first, outer_next)
 
     def robust_expo_group_dev(self, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5,
                               TOL=1e-4, inner=1, outer=15):

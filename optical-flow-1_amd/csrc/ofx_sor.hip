@@ -1055,12 +1055,85 @@ static int hs_single_scale_host(ofx_ctx *ctx, const double *I1, const double *I2
     return download_flow<T>(ctx, L.flow(0), u, v, n);
 }
 
+// The warm start of the two multiscale drivers (include/ofx.h): the payloads' own pyramid (op_flow_pyramid) in place of the zeros
+// of the coarsest level, its last level rounded once into U (pair g at U + g * n); a NULL entry of init gives that pair zeros.
+template <typename T>
+static int sor_start_flow(ofx_ctx *ctx, int G, const void *const *init, int nscales, double z, const std::vector<int> &nxs,
+                          const std::vector<int> &nys, typename Pix<T>::v2 *U, size_t n)
+{
+    void *dst[OFX_MAX_GROUP];
+    for (int g = 0; g < G; g++) dst[g] = U + (size_t) g * n;
+    return op_flow_pyramid<typename Pix<T>::v2>(ctx, G, init, nscales, z, nxs.data(), nys.data(), dst);
+}
+
+// the start's own refusals, before any work: the alignment of every payload, then the Gaussians of its pyramid
+static int sor_start_check(ofx_ctx *ctx, const char *who, int n_pairs, const void *const *d_flo_init, int nx, int ny, int nscales,
+                           double z)
+{
+    if (!d_flo_init) return OFX_OK;
+    for (int g = 0; g < n_pairs; g++)
+        if (reinterpret_cast<uintptr_t>(d_flo_init[g]) % sizeof(float2))
+            return ofx_fail(ctx, OFX_ERR_ARG, "%s: start payload of pair %d is not 8-byte aligned", who, g);
+    std::vector<int> nxs, nys;
+    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, z, nxs, nys));
+    return op_flow_pyramid_check(ctx, nscales, z, nxs.data(), nys.data());
+}
+
+// The buffers of a group as its solve uses them.  A start that is not on this context's GPU is read through a staging copy from
+// the arena, as the TV-L1 entries stage theirs; the video chains (stage_all) reach their frames and payloads the same way, which
+// is the front-ends' route.  The plain entries use the caller's frames and payloads in place, as they always did.
+struct SorGroupIO {
+    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
+    void *flo[OFX_MAX_GROUP];
+};
+static int sor_stage_in(ofx_ctx *ctx, const void *p, size_t bytes, bool fill, const void **out)
+{
+    *out = p;
+    if (!p || ofx_ptr_is_local(ctx, p)) return OFX_OK;
+    char *stage;
+    OFX_TRY(ofx_alloc(ctx, bytes, &stage));
+    *out = stage;
+    return fill ? ofx_copy_staged(ctx, stage, p, bytes) : OFX_OK;
+}
+static int sor_group_stage(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, const void *const *init_in,
+                           void *const *d_flo, int nx, int ny, bool stage_all, SorGroupIO &io)
+{
+    const size_t n = (size_t) nx * ny;
+    const int kind = ofx_src_kind(ctx);
+    const size_t pitch = nx > 0 ? ofx_src_pitch(ctx, nx) : 0;
+    // a frame's bytes as they lie: with a pitch, from its first row's start to its last row's end
+    const size_t span = pitch && ny > 0 ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
+    for (int g = 0; g < G; g++) {
+        io.a[g] = dI1[g];
+        io.b[g] = dI2[g];
+        io.flo[g] = d_flo[g];
+        io.init[g] = nullptr;
+        if (stage_all) {
+            const void *flo;
+            OFX_TRY(sor_stage_in(ctx, dI1[g], span, true, &io.a[g]));
+            OFX_TRY(sor_stage_in(ctx, dI2[g], span, true, &io.b[g]));
+            OFX_TRY(sor_stage_in(ctx, d_flo[g], n * sizeof(float2), false, &flo));
+            io.flo[g] = const_cast<void *>(flo);
+        }
+        if (init_in) OFX_TRY(sor_stage_in(ctx, init_in[g], n * sizeof(float2), true, &io.init[g]));
+    }
+    return OFX_OK;
+}
+// ... and back into the caller's payloads where the solve wrote a stage
+static int sor_group_unstage(ofx_ctx *ctx, int G, void *const *d_flo, const SorGroupIO &io, size_t n)
+{
+    for (int g = 0; g < G; g++)
+        if (io.flo[g] != d_flo[g]) OFX_TRY(ofx_copy_staged(ctx, d_flo[g], io.flo[g], n * sizeof(float2)));
+    return OFX_OK;
+}
+
 // src/horn_schunck_pyramidal.cpp:258-370 for G pairs in lockstep.  dI1[g] / dI2[g]: device images of storage type T.
 // On success lv[0].flow(g) holds the flow of pair g.
 template <typename T>
 static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *const *dI2, int nx, int ny, const HsParams &P,
                             int nscales, double zfactor, std::vector<HsLevel<T>> &lv, ofx_stats *stats, int kind = -1,
-                            size_t pitch = 0)               // kind >= 0: bytes between the images' rows, 0 = dense
+                            size_t pitch = 0,               // kind >= 0: bytes between the images' rows, 0 = dense
+                            const void *const *init = nullptr)     // G start payloads (NULL entry: zero start); nullptr: all zero
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "hs: group of %d pairs", G);
     if (P.verbose && G == 1)
@@ -1087,7 +1160,11 @@ static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
                                           pitch));
     }
     HsLevel<T> &C = lv[nscales - 1];
-    OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                          // :320-323
+    if (!init) {
+        OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                      // :320-323
+    } else {
+        OFX_TRY(sor_start_flow<T>(ctx, G, init, nscales, zfactor, nxs, nys, C.U, C.n()));
+    }
     for (int s = nscales - 1; s >= 0; s--) {                                                           // :326
         if (P.verbose && G == 1) fprintf(stderr, "Scale: %d %dx%d\n", s, lv[s].nx, lv[s].ny);
         OFX_TRY(hs_single_scale_dev<T>(ctx, lv[s], P, s, stats));
@@ -1130,14 +1207,18 @@ static int sor_group_entry(ofx_ctx *ctx, const char *who, int n_pairs, const voi
 
 template <typename T>
 static int hs_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx,
-                           int ny, const HsParams &P, int nscales, double zfactor, ofx_stats *stats)
+                           int ny, const HsParams &P, int nscales, double zfactor, ofx_stats *stats,
+                           const void *const *init_in = nullptr,     // G start payloads (NULL entry: zero start), or nullptr
+                           bool stage_all = false)                  // the video chain: frames and payloads may lie anywhere
 {
-    std::vector<HsLevel<T>> lv;
-    OFX_TRY(hs_pyramidal_dev<T>(ctx, G, (const T *const *) dI1, (const T *const *) dI2, nx, ny, P, nscales, zfactor, lv, stats,
-                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0));
     const size_t n = (size_t) nx * ny;
-    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].flow(g), (float2 *) d_flo[g], n));
-    return OFX_OK;
+    SorGroupIO io;
+    OFX_TRY(sor_group_stage(ctx, G, dI1, dI2, init_in, d_flo, nx, ny, stage_all, io));
+    std::vector<HsLevel<T>> lv;
+    OFX_TRY(hs_pyramidal_dev<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, zfactor, lv, stats,
+                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0, init_in ? io.init : nullptr));
+    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].flow(g), (float2 *) io.flo[g], n));
+    return sor_group_unstage(ctx, G, d_flo, io, n);
 }
 
 extern "C" int ofx_hs_single_scale(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx,
@@ -1171,21 +1252,112 @@ extern "C" int ofx_hs_pyramidal(ofx_ctx *ctx, const double *I1, const double *I2
     return s;
 }
 
-extern "C" int ofx_hs_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
-                                void *const *d_flo, int nx, int ny, double alpha, int nscales, double zfactor, int warps,
-                                double TOL, int maxiter, ofx_stats *stats_out)
+// the lockstep group behind ofx_hs_group_dev (d_flo_init = nullptr) and ofx_hs_group_init_dev
+static int hs_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2, const void *const *d_flo_init,
+                          void *const *d_flo, int nx, int ny, double alpha, int nscales, double zfactor, int warps, double TOL,
+                          int maxiter, ofx_stats *stats_out, bool stage_all = false)
 {
     OFX_ENTER(ctx);
     const HsParams P = {alpha, TOL, warps, maxiter, 0};
     auto check = [&]() -> int {
         if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", warps);
         if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
-        return ofx_pitch_check(ctx, "hs", nx);
+        OFX_TRY(ofx_pitch_check(ctx, "hs", nx));
+        return sor_start_check(ctx, "hs", n_pairs, d_flo_init, nx, ny, nscales, zfactor);
     };
     return sor_group_entry(ctx, "hs", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
-        return ctx->precision == OFX_F64 ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st)
-                                         : hs_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st);
+        return ctx->precision == OFX_F64
+                   ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init, stage_all)
+                   : hs_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init, stage_all);
     });
+}
+
+extern "C" int ofx_hs_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                                void *const *d_flo, int nx, int ny, double alpha, int nscales, double zfactor, int warps,
+                                double TOL, int maxiter, ofx_stats *stats_out)
+{
+    return hs_group_entry(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter, stats_out);
+}
+
+extern "C" int ofx_hs_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                                     const void *const *d_flo_init, void *const *d_flo, int nx, int ny, double alpha, int nscales,
+                                     double zfactor, int warps, double TOL, int maxiter, ofx_stats *stats_out)
+{
+    return hs_group_entry(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
+                          stats_out);
+}
+
+// What the two video chains check before any work (include/ofx.h): the tables, then both pyramids -- sizes, the pre-smoothing
+// Gaussian of the frames and the Gaussians of the start's pyramid.
+static int sor_sequence_check(ofx_ctx *ctx, const char *who, int n_seq, int n_frames, const void *const *dF, void *const *d_flo,
+                              int nx, int ny, int nscales_first, int nscales_next, double z, double sigma)
+{
+    if (!dF || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer", who);
+    if (n_seq < 1 || n_seq > OFX_MAX_GROUP)
+        return ofx_fail(ctx, OFX_ERR_ARG, "%s: a lockstep group holds 1..%d sequences (got %d)", who, OFX_MAX_GROUP, n_seq);
+    if (n_frames < 2) return ofx_fail(ctx, OFX_ERR_ARG, "%s: %d frames (a sequence has at least 2)", who, n_frames);
+    const int steps = n_frames - 1;
+    for (int q = 0; q < n_seq; q++) {
+        for (int t = 0; t < n_frames; t++)
+            if (!dF[(size_t) q * n_frames + t]) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL frame %d of sequence %d", who, t, q);
+        for (int t = 0; t < steps; t++) {
+            const void *p = d_flo[(size_t) q * steps + t];
+            if (!p || reinterpret_cast<uintptr_t>(p) % sizeof(float2))
+                return ofx_fail(ctx, OFX_ERR_ARG, "%s: payload %d of sequence %d NULL or not 8-byte aligned", who, t, q);
+        }
+    }
+    OFX_TRY(ofx_pitch_check(ctx, who, nx));
+    for (int k = 0; k < 2; k++) {
+        const int nscales = k ? nscales_next : nscales_first;
+        std::vector<int> nxs, nys;
+        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, z, nxs, nys));
+        GaussTaps taps;
+        if (ofx_gauss_taps(sigma, &taps) == OFX_OK && (taps.size >= nx || taps.size >= ny))
+            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
+        OFX_TRY(op_flow_pyramid_check(ctx, nscales, z, nxs.data(), nys.data()));
+    }
+    return OFX_OK;
+}
+
+// The chain itself: step t solves the pairs (F[q][t], F[q][t + 1]) of all sequences as one lockstep group through
+// step(t, a, b, init, out, st), from the payloads of step t - 1 where there is one.  Every step is a group entry on the context's
+// stream, so the start of step t is read after step t - 1 has written it and never leaves the device.  Frames and payloads that
+// are not on the context's GPU (the front-ends' host arrays) are staged step by step, as the TV-L1 chain stages them.
+template <class StepFn>
+static int sor_sequence_run(int n_seq, int n_frames, const void *const *dF, void *const *d_flo, ofx_stats *stats_out, StepFn step)
+{
+    const int steps = n_frames - 1;
+    std::vector<ofx_stats> st(n_seq);
+    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
+    void *out[OFX_MAX_GROUP];
+    for (int t = 0; t < steps; t++) {
+        for (int q = 0; q < n_seq; q++) {
+            a[q] = dF[(size_t) q * n_frames + t];
+            b[q] = dF[(size_t) q * n_frames + t + 1];
+            init[q] = t ? d_flo[(size_t) q * steps + t - 1] : nullptr;
+            out[q] = d_flo[(size_t) q * steps + t];
+        }
+        OFX_TRY(step(t, a, b, t ? init : nullptr, out, st.data()));
+        for (int q = 0; stats_out && q < n_seq; q++) stats_out[(size_t) q * steps + t] = st[q];
+    }
+    return OFX_OK;
+}
+
+extern "C" int ofx_hs_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nx,
+                                         int ny, double alpha, int nscales_first, int nscales_next, double zfactor, int warps_first,
+                                         int warps_next, double TOL, int maxiter, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (warps_first < 1 || warps_next < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs_sequence: warps=%d, %d", warps_first, warps_next);
+    if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs_sequence: maxiter > %d", OFX_HS_MAX_MAXITER);
+    OFX_TRY(sor_sequence_check(ctx, "hs_sequence", n_seq, n_frames, dF, d_flo, nx, ny, nscales_first, nscales_next, zfactor,
+                               HS_PRESMOOTH_SIGMA));
+    return sor_sequence_run(n_seq, n_frames, dF, d_flo, stats_out,
+                            [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
+                                ofx_stats *st) {
+                                return hs_group_entry(ctx, n_seq, a, b, init, out, nx, ny, alpha, t ? nscales_next : nscales_first,
+                                                      zfactor, t ? warps_next : warps_first, TOL, maxiter, st, true);
+                            });
 }
 
 // ============================================================================================
@@ -2300,7 +2472,8 @@ template <typename T>
 static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *const *dI2, int nx, int ny,
                             const BroxParams &P, int nscales, double nu, std::vector<BroxLevel<T>> &lv, ofx_stats *stats,
                             int kind = -1,                  // kind >= 0: the images are of that element kind (OFX_SRC_*), not T
-                            size_t pitch = 0)               // ... their rows that many bytes apart, 0 = dense
+                            size_t pitch = 0,               // ... their rows that many bytes apart, 0 = dense
+                            const void *const *init = nullptr)     // G start payloads (NULL entry: zero start); nullptr: all zero
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "brox: group of %d pairs", G);
     std::vector<int> nxs, nys;
@@ -2323,7 +2496,11 @@ static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
                                           BROX_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind, pitch));
     }
     BroxLevel<T> &C = lv[nscales - 1];
-    OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                     // :507-509
+    if (!init) {
+        OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                 // :507-509
+    } else {
+        OFX_TRY(sor_start_flow<T>(ctx, G, init, nscales, nu, nxs, nys, C.U, C.n()));
+    }
     for (int s = nscales - 1; s >= 0; s--) {                                                      // :516
         if (P.verbose && G == 1) { printf("Scale: %d\n", s); fflush(stdout); }
         OFX_TRY(brox_single_scale_dev<T>(ctx, lv[s], P, s, stats));
@@ -2351,14 +2528,18 @@ static int brox_spatial_host(ofx_ctx *ctx, const double *I1, const double *I2, d
 
 template <typename T>
 static int brox_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx,
-                             int ny, const BroxParams &P, int nscales, double nu, ofx_stats *stats)
+                             int ny, const BroxParams &P, int nscales, double nu, ofx_stats *stats,
+                             const void *const *init_in = nullptr,   // G start payloads (NULL entry: zero start), or nullptr
+                             bool stage_all = false)                // the video chain: frames and payloads may lie anywhere
 {
-    std::vector<BroxLevel<T>> lv;
-    OFX_TRY(brox_spatial_dev<T>(ctx, G, (const T *const *) dI1, (const T *const *) dI2, nx, ny, P, nscales, nu, lv, stats,
-                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0));
     const size_t n = (size_t) nx * ny;
-    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) d_flo[g], n));
-    return OFX_OK;
+    SorGroupIO io;
+    OFX_TRY(sor_group_stage(ctx, G, dI1, dI2, init_in, d_flo, nx, ny, stage_all, io));
+    std::vector<BroxLevel<T>> lv;
+    OFX_TRY(brox_spatial_dev<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, nu, lv, stats,
+                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0, init_in ? io.init : nullptr));
+    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) io.flo[g], n));
+    return sor_group_unstage(ctx, G, d_flo, io, n);
 }
 
 extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx,
@@ -2643,20 +2824,59 @@ extern "C" int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, cons
     return s;
 }
 
-extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
-                                  void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
-                                  double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out)
+// the lockstep group behind ofx_brox_group_dev (d_flo_init = nullptr) and ofx_brox_group_init_dev
+static int brox_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                            const void *const *d_flo_init, void *const *d_flo, int nxx, int nyy, double alpha, double gamma,
+                            int nscales, double nu, double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out,
+                            bool stage_all = false)
 {
     OFX_ENTER(ctx);
     const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
     auto check = [&]() -> int {
         if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
-        return ofx_pitch_check(ctx, "brox", nxx);
+        OFX_TRY(ofx_pitch_check(ctx, "brox", nxx));
+        return sor_start_check(ctx, "brox", n_pairs, d_flo_init, nxx, nyy, nscales, nu);
     };
     return sor_group_entry(ctx, "brox", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
-        return ctx->precision == OFX_F64 ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st)
-                                         : brox_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st);
+        return ctx->precision == OFX_F64
+                   ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st, d_flo_init, stage_all)
+                   : brox_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st, d_flo_init, stage_all);
     });
+}
+
+extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                                  void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
+                                  double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out)
+{
+    return brox_group_entry(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter,
+                            stats_out);
+}
+
+extern "C" int ofx_brox_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
+                                       const void *const *d_flo_init, void *const *d_flo, int nxx, int nyy, double alpha,
+                                       double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
+                                       ofx_stats *stats_out)
+{
+    return brox_group_entry(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
+                            outer_iter, stats_out);
+}
+
+extern "C" int ofx_brox_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nxx,
+                                           int nyy, double alpha, double gamma, int nscales_first, int nscales_next, double nu,
+                                           double TOL, int inner_iter, int outer_first, int outer_next, ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (inner_iter < 0 || outer_first < 0 || outer_next < 0)
+        return ofx_fail(ctx, OFX_ERR_ARG, "brox_sequence: negative iteration count");
+    OFX_TRY(sor_sequence_check(ctx, "brox_sequence", n_seq, n_frames, dF, d_flo, nxx, nyy, nscales_first, nscales_next, nu,
+                               BROX_SIGMA));
+    return sor_sequence_run(n_seq, n_frames, dF, d_flo, stats_out,
+                            [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
+                                ofx_stats *st) {
+                                return brox_group_entry(ctx, n_seq, a, b, init, out, nxx, nyy, alpha, gamma,
+                                                        t ? nscales_next : nscales_first, nu, TOL, inner_iter,
+                                                        t ? outer_next : outer_first, st, true);
+                            });
 }
 
 // ofx_robust_expo_pyramid for the pairs of a lockstep group on device-resident images (include/ofx.h)
@@ -2690,17 +2910,66 @@ static int sor_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs)
     return ofx_plan_lockstep(ctxs[0]->lockstep, OFX_MAX_GROUP, ofx_plan_even_rounds(n_pairs, n_ctx, OFX_MAX_GROUP));
 }
 
-extern "C" int ofx_hs_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
-                                void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales, double zfactor,
-                                int warps, double TOL, int maxiter, double *work_pix_iters)
+// The starts' refusals for the whole batch, before any group runs (groups run concurrently: a refusal inside one would find the
+// others at work).  The pair is named by its index in the batch, the reason is left in every context.
+static int sor_batch_start_check(ofx_ctx *const *ctxs, int n_ctx, const char *who, int n_pairs, const void *const *d_flo_init, int nx,
+                                 int ny, int nscales, double z)
+{
+    if (!d_flo_init) return OFX_OK;
+    int s = OFX_OK;
+    for (int w = 0; w < n_ctx; w++) {
+        const int sw = sor_start_check(ctxs[w], who, n_pairs, d_flo_init, nx, ny, nscales, z);
+        if (s == OFX_OK) s = sw;
+    }
+    return s;
+}
+
+// The batches behind ofx_*_batch_dev (d_flo_init = nullptr) and ofx_*_batch_init_dev: a start per pair where d_flo_init is a table
+// (NULL entry: that pair starts from zero).  d_flo_init[g] == d_flo[g] is allowed; a start that is ANOTHER pair's payload of the
+// same batch is not (groups run concurrently).  The start's scratch comes from the group's arena and does not enter the group size.
+static int hs_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                          const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales,
+                          double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters)
 {
     OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
     if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
     if (n_pairs == 0) return OFX_OK;
+    OFX_TRY(sor_batch_start_check(ctxs, n_ctx, "hs", n_pairs, d_flo_init, nx, ny, nscales, zfactor));
     const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
     return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
-        return ofx_hs_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nx, ny, alpha, nscales, zfactor, warps, TOL,
-                                maxiter, st);
+        return hs_group_entry(c, cnt, dI1 + first, dI2 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nx, ny,
+                              alpha, nscales, zfactor, warps, TOL, maxiter, st);
+    });
+}
+
+extern "C" int ofx_hs_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales, double zfactor,
+                                int warps, double TOL, int maxiter, double *work_pix_iters)
+{
+    return hs_batch_entry(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
+                          work_pix_iters);
+}
+
+extern "C" int ofx_hs_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                     const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha,
+                                     int nscales, double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters)
+{
+    return hs_batch_entry(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
+                          work_pix_iters);
+}
+
+static int brox_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                            const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha,
+                            double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
+{
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
+    if (n_pairs == 0) return OFX_OK;
+    OFX_TRY(sor_batch_start_check(ctxs, n_ctx, "brox", n_pairs, d_flo_init, nxx, nyy, nscales, nu));
+    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+        return brox_group_entry(c, cnt, dI1 + first, dI2 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nxx,
+                                nyy, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, st);
     });
 }
 
@@ -2708,14 +2977,17 @@ extern "C" int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *c
                                   void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha, double gamma, int nscales,
                                   double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
 {
-    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
-    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
-    if (n_pairs == 0) return OFX_OK;
-    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
-        return ofx_brox_group_dev(c, cnt, dI1 + first, dI2 + first, d_flo + first, nxx, nyy, alpha, gamma, nscales, nu, TOL,
-                                  inner_iter, outer_iter, st);
-    });
+    return brox_batch_entry(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
+                            outer_iter, work_pix_iters);
+}
+
+extern "C" int ofx_brox_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                       const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nxx, int nyy,
+                                       double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter,
+                                       int outer_iter, double *work_pix_iters)
+{
+    return brox_batch_entry(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
+                            outer_iter, work_pix_iters);
 }
 
 extern "C" int ofx_robust_expo_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
