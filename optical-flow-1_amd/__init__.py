@@ -214,19 +214,32 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+_NO_START = object()        # "this entry takes no table of starts" (None is a table's own value: the plain entry)
+
+
+def _start_table(d_flo_init):
+    """the start table of an *_init_dev entry as its argument list: nothing, NULL, or a pointer per pair (None / 0: zero start)"""
+    if d_flo_init is _NO_START:
+        return ()
+    return (None if d_flo_init is None else (_vp * max(len(d_flo_init), 1))(*[p or None for p in d_flo_init]),)
+
+
+def _batch_call(fn, ctxs, dA, dB, d_flo, *args, init=_NO_START):
+    n = len(dA)
+    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+    work = (_d * max(n, 1))()
+    s = fn(arr([c.h.value for c in ctxs]), len(ctxs), arr(dA), arr(dB), *_start_table(init), arr(d_flo), n, *args, work)
+    if s:
+        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
+    return [work[i] for i in range(n)]
+
+
 def tvl1_batch_dev(ctxs, dI0, dI1, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5,
                    epsilon=0.01):
     """ofx_tvl1_batch_dev: lists of device pointers (ints), one entry per pair; the pairs are cut into lockstep
     groups of tvl1_batch_group_size() pairs, group q runs on ctxs[q % len(ctxs)] with len(ctxs) groups in flight.
     Returns the per-pair work (pixel-iterations)."""
-    n = len(dI0)
-    arr = lambda xs: (_vp * len(xs))(*xs)
-    work = (_d * max(n, 1))()
-    s = lib().ofx_tvl1_batch_dev(arr([c.h.value for c in ctxs]), len(ctxs), arr(dI0), arr(dI1), arr(d_flo), n, nx, ny, tau,
-                                 lam, theta, nscales, zfactor, warps, epsilon, work)
-    if s:
-        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
-    return [work[i] for i in range(n)]
+    return _batch_call(lib().ofx_tvl1_batch_dev, ctxs, dI0, dI1, d_flo, nx, ny, tau, lam, theta, nscales, zfactor, warps, epsilon)
 
 
 def tvl1_batch_init_dev(ctxs, dI0, dI1, d_flo_init, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5,
@@ -234,15 +247,8 @@ def tvl1_batch_init_dev(ctxs, dI0, dI1, d_flo_init, d_flo, nx, ny, tau=0.25, lam
     """ofx_tvl1_batch_init_dev: tvl1_batch_dev with a start per pair -- d_flo_init is None (the plain batch) or a list with one
     entry per pair, a device pointer (int) of a .flo payload or None / 0 for a pair that starts from zero.  Returns the per-pair
     work (pixel-iterations)."""
-    n = len(dI0)
-    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-    work = (_d * max(n, 1))()
-    init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
-    s = lib().ofx_tvl1_batch_init_dev(arr([c.h.value for c in ctxs]), len(ctxs), arr(dI0), arr(dI1), init, arr(d_flo), n, nx, ny,
-                                      tau, lam, theta, nscales, zfactor, warps, epsilon, work)
-    if s:
-        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
-    return [work[i] for i in range(n)]
+    return _batch_call(lib().ofx_tvl1_batch_init_dev, ctxs, dI0, dI1, d_flo, nx, ny, tau, lam, theta, nscales, zfactor, warps, epsilon,
+                       init=d_flo_init)
 
 
 def tvl1_bidir_batch_dev(ctxs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, tau=0.25, lam=0.15, theta=0.3,
@@ -261,16 +267,6 @@ def tvl1_bidir_batch_dev(ctxs, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_
     return [work[i] for i in range(2 * n)]
 
 
-def _batch_call(fn, ctxs, dA, dB, d_flo, *args):
-    n = len(dA)
-    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-    work = (_d * max(n, 1))()
-    s = fn(arr([c.h.value for c in ctxs]), len(ctxs), arr(dA), arr(dB), arr(d_flo), n, *args, work)
-    if s:
-        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
-    return [work[i] for i in range(n)]
-
-
 def hs_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4, maxiter=150):
     """ofx_hs_batch_dev: lists of device pointers (ints), one entry per pair; lockstep groups on ctxs[q % len(ctxs)].
     Returns the per-pair work (pixel-sweeps)."""
@@ -282,31 +278,20 @@ def brox_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscale
     return _batch_call(lib().ofx_brox_batch_dev, ctxs, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
 
 
-def _batch_init_call(fn, ctxs, dA, dB, d_flo_init, d_flo, *args):
-    n = len(dA)
-    arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-    work = (_d * max(n, 1))()
-    init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
-    s = fn(arr([c.h.value for c in ctxs]), len(ctxs), arr(dA), arr(dB), init, arr(d_flo), n, *args, work)
-    if s:
-        raise OfxError(s, "; ".join((c.L.ofx_last_error(c.h) or b"").decode() for c in ctxs))
-    return [work[i] for i in range(n)]
-
-
 def hs_batch_init_dev(ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4,
                       maxiter=150):
     """ofx_hs_batch_init_dev: hs_batch_dev with a start per pair -- d_flo_init is None (the plain batch) or a list with one entry
     per pair, a device pointer (int) of a .flo payload or None / 0 for a pair that starts from zero.  Returns the per-pair work
     (pixel-sweeps)."""
-    return _batch_init_call(lib().ofx_hs_batch_init_dev, ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor, warps,
-                            TOL, maxiter)
+    return _batch_call(lib().ofx_hs_batch_init_dev, ctxs, dI1, dI2, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
+                       init=d_flo_init)
 
 
 def brox_batch_init_dev(ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4, inner=1,
                         outer=15):
     """ofx_brox_batch_init_dev (see hs_batch_init_dev)"""
-    return _batch_init_call(lib().ofx_brox_batch_init_dev, ctxs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, gamma, nscales, nu,
-                            TOL, inner, outer)
+    return _batch_call(lib().ofx_brox_batch_init_dev, ctxs, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer,
+                       init=d_flo_init)
 
 
 def robust_expo_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.0, gamma=10.0, lam=1.0, nscales=5, nu=0.5, TOL=1e-4,
@@ -650,46 +635,45 @@ class Ofx:
         self._ck(self.L.ofx_tvl1_multiscale_dev(self.h, dI0, dI1, d_flo, nx, ny, tau, lam, theta, nscales, zfactor,
                                                 warps, epsilon, verbose))
 
+    def _group_call(self, fn, dA, dB, d_flo, *args, init=_NO_START):
+        n = len(dA)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        st = (Stats * max(n, 1))()
+        self._ck(fn(self.h, n, arr(dA), arr(dB), *_start_table(init), arr(d_flo), *args, st))
+        return [st[i] for i in range(n)]
+
+    def _sequence_call(self, fn, who, dF, d_flo, *args):
+        n_seq = len(dF)
+        n_frames = len(dF[0]) if n_seq else 0
+        if any(len(f) != n_frames for f in dF) or len(d_flo) != n_seq or any(len(p) != max(n_frames - 1, 0) for p in d_flo):
+            raise ValueError(who + ": every sequence needs the same number of frames and one payload per step")
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        steps = max(n_frames - 1, 0)
+        st = (Stats * max(n_seq * steps, 1))()
+        self._ck(fn(self.h, n_seq, n_frames, arr([p for f in dF for p in f]), arr([p for f in d_flo for p in f]), *args, st))
+        return [[st[q * steps + t] for t in range(steps)] for q in range(n_seq)]
+
     def tvl1_group_dev(self, dI0, dI1, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5,
                        epsilon=0.01):
         """ofx_tvl1_group_dev: lists of device pointers (ints), all pairs solved in lockstep on this context.
         Returns the per-pair Stats records."""
-        n = len(dI0)
-        arr = lambda xs: (_vp * len(xs))(*xs)
-        st = (Stats * max(n, 1))()
-        self._ck(self.L.ofx_tvl1_group_dev(self.h, n, arr(dI0), arr(dI1), arr(d_flo), nx, ny, tau, lam, theta, nscales,
-                                           zfactor, warps, epsilon, st))
-        return [st[i] for i in range(n)]
+        return self._group_call(self.L.ofx_tvl1_group_dev, dI0, dI1, d_flo, nx, ny, tau, lam, theta, nscales, zfactor, warps, epsilon)
 
     def tvl1_group_init_dev(self, dI0, dI1, d_flo_init, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5,
                             warps=5, epsilon=0.01):
         """ofx_tvl1_group_init_dev: tvl1_group_dev with a start per pair.  d_flo_init: None (the plain group), or one entry per
         pair, the device pointer (int) of a .flo payload to start from or None / 0 for a pair that starts from zero; an entry
         may be the pair's own d_flo.  Returns the per-pair Stats records."""
-        n = len(dI0)
-        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-        st = (Stats * max(n, 1))()
-        init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
-        self._ck(self.L.ofx_tvl1_group_init_dev(self.h, n, arr(dI0), arr(dI1), init, arr(d_flo), nx, ny, tau, lam, theta, nscales,
-                                                zfactor, warps, epsilon, st))
-        return [st[i] for i in range(n)]
+        return self._group_call(self.L.ofx_tvl1_group_init_dev, dI0, dI1, d_flo, nx, ny, tau, lam, theta, nscales, zfactor, warps,
+                                epsilon, init=d_flo_init)
 
     def tvl1_sequence_group_dev(self, dF, d_flo, nx, ny, tau=0.25, lam=0.15, theta=0.3, nscales_first=5, nscales_next=2,
                                 zfactor=0.5, warps=5, epsilon=0.01):
         """ofx_tvl1_sequence_group_dev, the video chain: dF[q] = the device pointers (ints) of the frames of sequence q, d_flo[q] =
         those of its len(dF[q]) - 1 payloads.  Step 0 is solved cold with nscales_first scales, every later step from the payload
         of the step before with nscales_next.  Returns the Stats records, [sequence][step]."""
-        n_seq = len(dF)
-        n_frames = len(dF[0]) if n_seq else 0
-        if any(len(f) != n_frames for f in dF) or len(d_flo) != n_seq or any(len(p) != max(n_frames - 1, 0) for p in d_flo):
-            raise ValueError("tvl1_sequence_group_dev: every sequence needs the same number of frames and one payload per step")
-        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-        steps = max(n_frames - 1, 0)
-        st = (Stats * max(n_seq * steps, 1))()
-        self._ck(self.L.ofx_tvl1_sequence_group_dev(self.h, n_seq, n_frames, arr([p for f in dF for p in f]),
-                                                    arr([p for f in d_flo for p in f]), nx, ny, tau, lam, theta, nscales_first,
-                                                    nscales_next, zfactor, warps, epsilon, st))
-        return [[st[q * steps + t] for t in range(steps)] for q in range(n_seq)]
+        return self._sequence_call(self.L.ofx_tvl1_sequence_group_dev, "tvl1_sequence_group_dev", dF, d_flo, nx, ny, tau, lam, theta,
+                                   nscales_first, nscales_next, zfactor, warps, epsilon)
 
     def flow_pyramid_dev(self, d_flo, d_uv, nx, ny, nscales=5, zfactor=0.5):
         """ofx_flow_pyramid_dev: the pyramid of a start alone.  d_flo: device pointers (ints) of .flo payloads; d_uv[g] receives
@@ -718,13 +702,6 @@ class Ofx:
                                                  fb_alpha, fb_beta, st))
         return [st[i] for i in range(2 * n)]
 
-    def _group_call(self, fn, dA, dB, d_flo, *args):
-        n = len(dA)
-        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-        st = (Stats * max(n, 1))()
-        self._ck(fn(self.h, n, arr(dA), arr(dB), arr(d_flo), *args, st))
-        return [st[i] for i in range(n)]
-
     def hs_group_dev(self, dI1, dI2, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4, maxiter=150):
         """ofx_hs_group_dev: all pairs solved in lockstep on this context; returns the per-pair Stats records"""
         return self._group_call(self.L.ofx_hs_group_dev, dI1, dI2, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter)
@@ -733,38 +710,19 @@ class Ofx:
         """ofx_brox_group_dev (see hs_group_dev)"""
         return self._group_call(self.L.ofx_brox_group_dev, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner, outer)
 
-    def _group_init_call(self, fn, dA, dB, d_flo_init, d_flo, *args):
-        n = len(dA)
-        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-        st = (Stats * max(n, 1))()
-        init = None if d_flo_init is None else arr([p or None for p in d_flo_init])
-        self._ck(fn(self.h, n, arr(dA), arr(dB), init, arr(d_flo), *args, st))
-        return [st[i] for i in range(n)]
-
     def hs_group_init_dev(self, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=7.0, nscales=10, zfactor=0.5, warps=10, TOL=1e-4,
                           maxiter=150):
         """ofx_hs_group_init_dev: hs_group_dev with a start per pair.  d_flo_init: None (the plain group), or one entry per pair,
         the device pointer (int) of a .flo payload to start from or None / 0 for a pair that starts from zero; an entry may be
         the pair's own d_flo.  Returns the per-pair Stats records."""
-        return self._group_init_call(self.L.ofx_hs_group_init_dev, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor,
-                                     warps, TOL, maxiter)
+        return self._group_call(self.L.ofx_hs_group_init_dev, dI1, dI2, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
+                                init=d_flo_init)
 
     def brox_group_init_dev(self, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha=50.0, gamma=10.0, nscales=10, nu=0.5, TOL=1e-4,
                             inner=1, outer=15):
         """ofx_brox_group_init_dev (see hs_group_init_dev)"""
-        return self._group_init_call(self.L.ofx_brox_group_init_dev, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, gamma, nscales,
-                                     nu, TOL, inner, outer)
-
-    def _sequence_call(self, fn, who, dF, d_flo, *args):
-        n_seq = len(dF)
-        n_frames = len(dF[0]) if n_seq else 0
-        if any(len(f) != n_frames for f in dF) or len(d_flo) != n_seq or any(len(p) != max(n_frames - 1, 0) for p in d_flo):
-            raise ValueError(who + ": every sequence needs the same number of frames and one payload per step")
-        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
-        steps = max(n_frames - 1, 0)
-        st = (Stats * max(n_seq * steps, 1))()
-        self._ck(fn(self.h, n_seq, n_frames, arr([p for f in dF for p in f]), arr([p for f in d_flo for p in f]), *args, st))
-        return [[st[q * steps + t] for t in range(steps)] for q in range(n_seq)]
+        return self._group_call(self.L.ofx_brox_group_init_dev, dI1, dI2, d_flo, nx, ny, alpha, gamma, nscales, nu, TOL, inner,
+                                outer, init=d_flo_init)
 
     def hs_sequence_group_dev(self, dF, d_flo, nx, ny, alpha=7.0, nscales_first=10, nscales_next=2, zfactor=0.5, warps_first=10,
                               warps_next=10, TOL=1e-4, maxiter=150):

@@ -1,5 +1,5 @@
-/* ofx_seq_common.h -- what horn_schunck_seq and brox_seq share: the frames of a video read into host planes of the context's
- * storage precision, one payload per step, a chain entry called on them, the payloads written as out_prefix0000.flo, ...
+/* ofx_seq_common.h -- what tvl1flow_seq, horn_schunck_seq and brox_seq share: the frames of a video read into host planes of the
+ * context's storage precision, one payload per step, a chain entry called on them, the payloads written as out_prefix0000.flo, ...
  * The chain entries stage host arrays themselves (include/ofx.h). */
 #ifndef OFX_SEQ_COMMON_H
 #define OFX_SEQ_COMMON_H

@@ -1,6 +1,7 @@
 // ofx_batch.h -- what every multi-context entry (*_batch_dev, *_sequence_dev, *_triples_dev) and every lockstep-group entry
 // (*_group_dev) shares on the host: the contexts' agreement, the memory budget, the worker loop over the groups and the shell
-// around one group's solve.  Private to libofx.so; the group sizes are ofx_group_plan.h's.
+// around one group's solve.  Private to libofx.so; the group sizes are ofx_group_plan.h's, and the entries on PAIRS of frames
+// (TV-L1, Horn-Schunck, Brox) build their ladder -- group, group with starts, batch, video chain -- on ofx_pairs.h.
 #pragma once
 
 #include "ofx_internal.h"

@@ -12,6 +12,7 @@
 // every storage precision and mode.
 #include "ofx_device.h"
 #include "ofx_ops.h"
+#include "ofx_pairs.h"
 
 #include <climits>
 #include <cmath>
@@ -121,7 +122,7 @@ extern "C" int ofx_flow_consistency_dev(ofx_ctx *ctx, int n_pairs, const void *c
     }
     // the kernel's pointer tables hold OFX_MAX_GROUP slots = both directions of OFX_MAX_GROUP / 2 pairs: one launch per chunk.
     // Memory of the context's GPU is used in place; a payload or a map that lives elsewhere (host memory, another GPU) goes
-    // through the workspace, as the batch entries stage theirs.
+    // through the workspace, as the batch entries stage theirs (ofx_stage_in / ofx_stage_out).
     const size_t n = (size_t) nx * ny;
     const int per = OFX_MAX_GROUP / 2;
     for (int g0 = 0; g0 < n_pairs; g0 += per) {
@@ -129,27 +130,15 @@ extern "C" int ofx_flow_consistency_dev(ofx_ctx *ctx, int n_pairs, const void *c
         const void *f[OFX_MAX_GROUP], *b[OFX_MAX_GROUP];
         void *occ[OFX_MAX_GROUP], *occ_in[OFX_MAX_GROUP];
         for (int g = 0; g < cnt; g++) {
-            const void *pay[2] = {d_flo_fwd[g0 + g], d_flo_bwd[g0 + g]};
-            for (int k = 0; k < 2; k++) {
-                if (ofx_ptr_is_local(ctx, pay[k])) continue;
-                float2 *stage;
-                OFX_TRY(ofx_alloc(ctx, n, &stage));
-                OFX_TRY(ofx_copy_staged(ctx, stage, pay[k], n * sizeof(float2)));
-                pay[k] = stage;
-            }
-            f[g] = pay[0];       b[g] = pay[1];       occ_in[g] = d_occ_fwd[g0 + g];
-            f[cnt + g] = pay[1]; b[cnt + g] = pay[0]; occ_in[cnt + g] = d_occ_bwd[g0 + g];
+            void *fwd, *bwd;
+            OFX_TRY(ofx_stage_in(ctx, d_flo_fwd[g0 + g], n * sizeof(float2), true, &fwd));
+            OFX_TRY(ofx_stage_in(ctx, d_flo_bwd[g0 + g], n * sizeof(float2), true, &bwd));
+            f[g] = fwd;       b[g] = bwd;       occ_in[g] = d_occ_fwd[g0 + g];
+            f[cnt + g] = bwd; b[cnt + g] = fwd; occ_in[cnt + g] = d_occ_bwd[g0 + g];
         }
-        for (int z = 0; z < 2 * cnt; z++) {
-            occ[z] = occ_in[z];
-            if (ofx_ptr_is_local(ctx, occ_in[z])) continue;
-            unsigned char *stage;
-            OFX_TRY(ofx_alloc(ctx, n, &stage));
-            occ[z] = stage;
-        }
+        for (int z = 0; z < 2 * cnt; z++) OFX_TRY(ofx_stage_in(ctx, occ_in[z], n, false, &occ[z]));
         OFX_TRY(op_flow_consistency(ctx, 2 * cnt, f, b, occ, nx, ny, alpha, beta));
-        for (int z = 0; z < 2 * cnt; z++)
-            if (occ[z] != occ_in[z]) OFX_TRY(ofx_copy_staged(ctx, occ_in[z], occ[z], n));
+        for (int z = 0; z < 2 * cnt; z++) OFX_TRY(ofx_stage_out(ctx, occ_in[z], occ[z], n));
     }
     return OFX_OK;
 }

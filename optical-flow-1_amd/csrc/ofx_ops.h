@@ -190,7 +190,7 @@ int op_flow_pyramid(ofx_ctx *ctx, int G, const void *const *init, int nscales, d
 // bytes of arena scratch op_flow_pyramid takes per pair (the memory rule of ofx_tvl1_batch_group_size)
 double op_flow_pyramid_scratch_bytes(int nscales, double zfactor, const int *nxs, const int *nys);
 
-// ---- buffers that are not on the context's GPU (ofx_tvl1.hip) ----
+// ---- buffers that are not on the context's GPU (ofx_ops.hip; staged through the arena by ofx_pairs.h) ----
 // is p device memory of this context's GPU?  Everything else is reached through a staging copy:
 bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p);
 // dst <- src, one of them on this context's GPU, the other anywhere (ofx_staging_route), on the context's stream

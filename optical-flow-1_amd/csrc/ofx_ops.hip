@@ -1891,3 +1891,57 @@ OFX_INSTANTIATE(double)
 OFX_INSTANTIATE(float)
 // float storage fed with the doubles of a host image (the robust_expo host path rounds after the normalisation)
 template int op_normalize_sets<float, double>(ofx_ctx *, const OfxSrcPtrs &, const OfxDstPtrs &, int, int, size_t, int, double *, int);
+
+// ---- buffers that are not on the context's GPU ----
+// Is p device memory of this context's GPU?  Everything else -- another GPU's memory, pinned or pageable host memory -- is
+// reached through a staging copy (hipMemcpyDefault resolves the direction; between GPUs it is a peer copy over xGMI).
+bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void) hipGetLastError();                              // pageable host memory is unknown to the runtime
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == ctx->device;
+}
+// How a buffer that lives on `mem_device` (-1: host memory) reaches a context on `ctx_device`: 0 = in place, 1 = one
+// hipMemcpyDefault (host <-> device, or a peer copy over xGMI), 2 = two copies through a host bounce buffer because the two GPUs
+// cannot address each other (hipDeviceCanAccessPeer says no: another IOMMU group, peer access disabled, ...).  Pure decision,
+// exported so that the host-logic tests cover it without a GPU.
+extern "C" int ofx_staging_route(int ctx_device, int mem_device, int can_access_peer)
+{
+    if (mem_device == ctx_device) return 0;
+    if (mem_device < 0) return 1;
+    return can_access_peer ? 1 : 2;
+}
+// dst <- src (one of them on this context's GPU, the other anywhere), on the context's stream.  A route-2 copy is synchronous
+// and leaves a note in ofx_last_error (the call still succeeds).  UNEXECUTED on more than one GPU (no multi-GPU box in any round).
+int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
+{
+    const void *other = ofx_ptr_is_local(ctx, dst) ? src : dst;
+    int mem_device = -1, can = 1;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, other) == hipSuccess) {
+        if (a.type == hipMemoryTypeDevice) mem_device = a.device;
+    } else {
+        (void) hipGetLastError();
+    }
+    if (mem_device >= 0 && mem_device != ctx->device && hipDeviceCanAccessPeer(&can, ctx->device, mem_device) != hipSuccess) {
+        (void) hipGetLastError();
+        can = 0;
+    }
+    if (ofx_staging_route(ctx->device, mem_device, can) < 2) {
+        OFX_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream));
+        return OFX_OK;
+    }
+    void *bounce = nullptr;
+    OFX_HIP(ctx, hipHostMalloc(&bounce, bytes, hipHostMallocDefault));
+    hipError_t e = hipStreamSynchronize(ctx->stream);                                       // src may be this stream's product
+    if (e == hipSuccess) e = hipMemcpy(bounce, src, bytes, hipMemcpyDefault);
+    if (e == hipSuccess) e = hipMemcpy(dst, bounce, bytes, hipMemcpyDefault);
+    (void) hipHostFree(bounce);
+    if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "staging through the host failed: %s", hipGetErrorString(e));
+    snprintf(ctx->errmsg, sizeof(ctx->errmsg), "note: GPU %d cannot address GPU %d, buffers were staged through the host", ctx->device,
+             mem_device);
+    return OFX_OK;
+}

@@ -21,7 +21,7 @@
 #include "ofx_device.h"
 #include "ofx_loop.h"
 #include "ofx_sor_tile.h"
-#include "ofx_batch.h"
+#include "ofx_pairs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1055,78 +1055,6 @@ static int hs_single_scale_host(ofx_ctx *ctx, const double *I1, const double *I2
     return download_flow<T>(ctx, L.flow(0), u, v, n);
 }
 
-// The warm start of the two multiscale drivers (include/ofx.h): the payloads' own pyramid (op_flow_pyramid) in place of the zeros
-// of the coarsest level, its last level rounded once into U (pair g at U + g * n); a NULL entry of init gives that pair zeros.
-template <typename T>
-static int sor_start_flow(ofx_ctx *ctx, int G, const void *const *init, int nscales, double z, const std::vector<int> &nxs,
-                          const std::vector<int> &nys, typename Pix<T>::v2 *U, size_t n)
-{
-    void *dst[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) dst[g] = U + (size_t) g * n;
-    return op_flow_pyramid<typename Pix<T>::v2>(ctx, G, init, nscales, z, nxs.data(), nys.data(), dst);
-}
-
-// the start's own refusals, before any work: the alignment of every payload, then the Gaussians of its pyramid
-static int sor_start_check(ofx_ctx *ctx, const char *who, int n_pairs, const void *const *d_flo_init, int nx, int ny, int nscales,
-                           double z)
-{
-    if (!d_flo_init) return OFX_OK;
-    for (int g = 0; g < n_pairs; g++)
-        if (reinterpret_cast<uintptr_t>(d_flo_init[g]) % sizeof(float2))
-            return ofx_fail(ctx, OFX_ERR_ARG, "%s: start payload of pair %d is not 8-byte aligned", who, g);
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, z, nxs, nys));
-    return op_flow_pyramid_check(ctx, nscales, z, nxs.data(), nys.data());
-}
-
-// The buffers of a group as its solve uses them.  A start that is not on this context's GPU is read through a staging copy from
-// the arena, as the TV-L1 entries stage theirs; the video chains (stage_all) reach their frames and payloads the same way, which
-// is the front-ends' route.  The plain entries use the caller's frames and payloads in place, as they always did.
-struct SorGroupIO {
-    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
-    void *flo[OFX_MAX_GROUP];
-};
-static int sor_stage_in(ofx_ctx *ctx, const void *p, size_t bytes, bool fill, const void **out)
-{
-    *out = p;
-    if (!p || ofx_ptr_is_local(ctx, p)) return OFX_OK;
-    char *stage;
-    OFX_TRY(ofx_alloc(ctx, bytes, &stage));
-    *out = stage;
-    return fill ? ofx_copy_staged(ctx, stage, p, bytes) : OFX_OK;
-}
-static int sor_group_stage(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, const void *const *init_in,
-                           void *const *d_flo, int nx, int ny, bool stage_all, SorGroupIO &io)
-{
-    const size_t n = (size_t) nx * ny;
-    const int kind = ofx_src_kind(ctx);
-    const size_t pitch = nx > 0 ? ofx_src_pitch(ctx, nx) : 0;
-    // a frame's bytes as they lie: with a pitch, from its first row's start to its last row's end
-    const size_t span = pitch && ny > 0 ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
-    for (int g = 0; g < G; g++) {
-        io.a[g] = dI1[g];
-        io.b[g] = dI2[g];
-        io.flo[g] = d_flo[g];
-        io.init[g] = nullptr;
-        if (stage_all) {
-            const void *flo;
-            OFX_TRY(sor_stage_in(ctx, dI1[g], span, true, &io.a[g]));
-            OFX_TRY(sor_stage_in(ctx, dI2[g], span, true, &io.b[g]));
-            OFX_TRY(sor_stage_in(ctx, d_flo[g], n * sizeof(float2), false, &flo));
-            io.flo[g] = const_cast<void *>(flo);
-        }
-        if (init_in) OFX_TRY(sor_stage_in(ctx, init_in[g], n * sizeof(float2), true, &io.init[g]));
-    }
-    return OFX_OK;
-}
-// ... and back into the caller's payloads where the solve wrote a stage
-static int sor_group_unstage(ofx_ctx *ctx, int G, void *const *d_flo, const SorGroupIO &io, size_t n)
-{
-    for (int g = 0; g < G; g++)
-        if (io.flo[g] != d_flo[g]) OFX_TRY(ofx_copy_staged(ctx, d_flo[g], io.flo[g], n * sizeof(float2)));
-    return OFX_OK;
-}
-
 // src/horn_schunck_pyramidal.cpp:258-370 for G pairs in lockstep.  dI1[g] / dI2[g]: device images of storage type T.
 // On success lv[0].flow(g) holds the flow of pair g.
 template <typename T>
@@ -1139,32 +1067,19 @@ static int hs_pyramidal_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
     if (P.verbose && G == 1)
         fprintf(stderr, "Multiscale Horn-Schunck of a %dx%d pair\n\ta=%g ns=%d zf=%g nw=%d eps=%g mi=%d\n", nx, ny,
                 P.alpha, nscales, zfactor, P.warps, P.TOL, P.maxiter);
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
-    for (int g = 0; g < G; g++) {
-        ofx_stats_begin(&stats[g], nscales, P.warps);
-        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
-    }
-    lv.resize(nscales);
-    for (int s = 0; s < nscales; s++) OFX_TRY(hs_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true));
-    {                                                                                                  // :279-317
-        T *tmpA, *tmpB;                                   // all 2 G images of the group per launch (op_build_pyramid_group)
-        double *scr;
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nx * ny, &tmpA));
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nx * ny, &tmpB));
-        OFX_TRY(ofx_alloc(ctx, (size_t) G * op_pyramid_scratch_doubles(), &scr));
-        std::vector<T *> lA(nscales), lB(nscales);
-        for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }
-        OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI1, (const void *const *) dI2, nscales, zfactor,
-                                          HS_PRESMOOTH_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind,
-                                          pitch));
-    }
-    HsLevel<T> &C = lv[nscales - 1];
-    if (!init) {
-        OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                      // :320-323
-    } else {
-        OFX_TRY(sor_start_flow<T>(ctx, G, init, nscales, zfactor, nxs, nys, C.U, C.n()));
-    }
+    using V2 = typename Pix<T>::v2;
+    auto levels = [&](const std::vector<int> &nxs, const std::vector<int> &nys, T **lA, T **lB, V2 **U) -> int {
+        lv.resize(nscales);
+        for (int s = 0; s < nscales; s++) {
+            OFX_TRY(hs_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true));
+            lA[s] = lv[s].I1;
+            lB[s] = lv[s].I2;
+        }
+        *U = lv[nscales - 1].U;
+        return OFX_OK;
+    };
+    OFX_TRY(ofx_pyramid_head<T>(ctx, G, G, (const void *const *) dI1, (const void *const *) dI2, nx, ny, nscales, zfactor,
+                                HS_PRESMOOTH_SIGMA, P.warps, stats, kind, pitch, init, levels));               // :279-323
     for (int s = nscales - 1; s >= 0; s--) {                                                           // :326
         if (P.verbose && G == 1) fprintf(stderr, "Scale: %d %dx%d\n", s, lv[s].nx, lv[s].ny);
         OFX_TRY(hs_single_scale_dev<T>(ctx, lv[s], P, s, stats));
@@ -1190,35 +1105,84 @@ static int hs_pyramidal_host(ofx_ctx *ctx, const double *I1, const double *I2, d
     return download_flow<T>(ctx, lv[0].flow(0), u, v, n);
 }
 
-// What the three ofx_*_group_dev entries share: the checks of the pointer tables and the group size, then the solver's own
-// (check), then solve(st) under the group shell (ofx_group_records).
-template <class CheckFn, class SolveFn>
-static int sor_group_entry(ofx_ctx *ctx, const char *who, int n_pairs, const void *const *dI1, const void *const *dI2,
-                           void *const *d_flo, ofx_stats *stats_out, CheckFn check, SolveFn solve)
-{
-    if (!dI1 || !dI2 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer", who);
-    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "%s: a lockstep group holds 1..%d pairs (got %d)", who, OFX_MAX_GROUP, n_pairs);
-    for (int g = 0; g < n_pairs; g++)
-        if (!dI1[g] || !dI2[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer (pair %d)", who, g);
-    OFX_TRY(check());
-    return ofx_group_records(ctx, n_pairs, stats_out, solve);
-}
+// ---- the pair entries of Horn-Schunck and Brox, written once over ofx_pairs.h ----
+// A solver S brings: Params and Level<T>; who (opens its messages); check(ctx, P), its parameters' refusals; pyramid<T>, its
+// coarse-to-fine driver (hs_pyramidal_dev / brox_spatial_dev); flow<T>(L, g), where the flow of pair g lies in the finest level.
+struct HsPairs {
+    using Params = HsParams;
+    template <typename T> using Level = HsLevel<T>;
+    static constexpr const char *who = "hs";
+    static int check(ofx_ctx *ctx, const HsParams &P)
+    {
+        if (P.warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", P.warps);
+        if (P.maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
+        return OFX_OK;
+    }
+    template <typename T, class... A> static int pyramid(A &&...a) { return hs_pyramidal_dev<T>(a...); }
+    template <typename T> static const typename Pix<T>::v2 *flow(const HsLevel<T> &L, int g) { return L.flow(g); }
+};
 
-template <typename T>
-static int hs_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx,
-                           int ny, const HsParams &P, int nscales, double zfactor, ofx_stats *stats,
-                           const void *const *init_in = nullptr,     // G start payloads (NULL entry: zero start), or nullptr
-                           bool stage_all = false)                  // the video chain: frames and payloads may lie anywhere
+// stage -> pyramid -> payloads -> unstage.  stage_all: the video chain, whose frames and payloads may lie anywhere
+template <class S, typename T>
+static int sor_pair_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx, int ny,
+                           const typename S::Params &P, int nscales, double z, ofx_stats *stats,
+                           const void *const *init_in,      // G start payloads (NULL entry: zero start), or nullptr
+                           bool stage_all)
 {
     const size_t n = (size_t) nx * ny;
-    SorGroupIO io;
-    OFX_TRY(sor_group_stage(ctx, G, dI1, dI2, init_in, d_flo, nx, ny, stage_all, io));
-    std::vector<HsLevel<T>> lv;
-    OFX_TRY(hs_pyramidal_dev<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, zfactor, lv, stats,
-                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0, init_in ? io.init : nullptr));
-    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].flow(g), (float2 *) io.flo[g], n));
-    return sor_group_unstage(ctx, G, d_flo, io, n);
+    OfxPairIO io;
+    OFX_TRY(ofx_pairs_stage(ctx, G, dI1, dI2, init_in, d_flo, nx, ny, stage_all, io));
+    std::vector<typename S::template Level<T>> lv;
+    OFX_TRY(S::template pyramid<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, z, lv, stats, io.kind,
+                                   io.pitch, init_in ? io.init : nullptr));
+    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, S::template flow<T>(lv[0], g), (float2 *) io.flo[g], n));
+    return ofx_pairs_unstage(ctx, G, d_flo, io, n);
+}
+
+// the lockstep group behind ofx_*_group_dev (d_flo_init = nullptr), ofx_*_group_init_dev and every step of a chain (stage_all)
+template <class S>
+static int sor_pair_group(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2, const void *const *d_flo_init,
+                          void *const *d_flo, int nx, int ny, const typename S::Params &P, int nscales, double z,
+                          ofx_stats *stats_out, bool stage_all = false)
+{
+    OFX_ENTER(ctx);
+    auto check = [&]() -> int {
+        OFX_TRY(S::check(ctx, P));
+        OFX_TRY(ofx_pitch_check(ctx, S::who, nx));
+        return ofx_start_check(ctx, S::who, n_pairs, d_flo_init, nx, ny, nscales, z);
+    };
+    return ofx_pair_group_entry(ctx, S::who, n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
+        return ctx->precision == OFX_F64
+                   ? sor_pair_devapi<S, double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, z, st, d_flo_init, stage_all)
+                   : sor_pair_devapi<S, float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, z, st, d_flo_init, stage_all);
+    });
+}
+
+// ---- batches of pairs for the SOR solvers: lockstep groups over the contexts (ofx_run_groups, with the `concurrency` hint:
+// memory budgets are shared between the workers) ----
+// group size: option "lockstep" of ctxs[0], else as large as possible (16), evened out over the contexts
+static int sor_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs)
+{
+    return ofx_plan_lockstep(ctxs[0]->lockstep, OFX_MAX_GROUP, ofx_plan_even_rounds(n_pairs, n_ctx, OFX_MAX_GROUP));
+}
+
+// The batches behind ofx_*_batch_dev (d_flo_init = nullptr) and ofx_*_batch_init_dev: a start per pair where d_flo_init is a table
+// (NULL entry: that pair starts from zero).  d_flo_init[g] == d_flo[g] is allowed; a start that is ANOTHER pair's payload of the
+// same batch is not (groups run concurrently).  The start's scratch comes from the group's arena and does not enter the group size.
+template <class S>
+static int sor_pair_batch(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                          const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, const typename S::Params &P,
+                          int nscales, double z, double *work_pix_iters)
+{
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
+    if (n_pairs == 0) return OFX_OK;
+    OFX_TRY(ofx_batch_start_check(ctxs, n_ctx, S::who, n_pairs, d_flo_init, nx, ny, nscales, z));
+    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
+    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
+        return sor_pair_group<S>(c, cnt, dI1 + first, dI2 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nx, ny, P,
+                                 nscales, z, st);
+    });
 }
 
 extern "C" int ofx_hs_single_scale(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nx,
@@ -1252,97 +1216,23 @@ extern "C" int ofx_hs_pyramidal(ofx_ctx *ctx, const double *I1, const double *I2
     return s;
 }
 
-// the lockstep group behind ofx_hs_group_dev (d_flo_init = nullptr) and ofx_hs_group_init_dev
-static int hs_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2, const void *const *d_flo_init,
-                          void *const *d_flo, int nx, int ny, double alpha, int nscales, double zfactor, int warps, double TOL,
-                          int maxiter, ofx_stats *stats_out, bool stage_all = false)
-{
-    OFX_ENTER(ctx);
-    const HsParams P = {alpha, TOL, warps, maxiter, 0};
-    auto check = [&]() -> int {
-        if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs: warps=%d", warps);
-        if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs: maxiter > %d", OFX_HS_MAX_MAXITER);
-        OFX_TRY(ofx_pitch_check(ctx, "hs", nx));
-        return sor_start_check(ctx, "hs", n_pairs, d_flo_init, nx, ny, nscales, zfactor);
-    };
-    return sor_group_entry(ctx, "hs", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
-        return ctx->precision == OFX_F64
-                   ? hs_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init, stage_all)
-                   : hs_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init, stage_all);
-    });
-}
-
 extern "C" int ofx_hs_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
                                 void *const *d_flo, int nx, int ny, double alpha, int nscales, double zfactor, int warps,
                                 double TOL, int maxiter, ofx_stats *stats_out)
 {
-    return hs_group_entry(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter, stats_out);
+    return sor_pair_group<HsPairs>(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nx, ny, {alpha, TOL, warps, maxiter, 0}, nscales, zfactor,
+                                   stats_out);
 }
 
 extern "C" int ofx_hs_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
                                      const void *const *d_flo_init, void *const *d_flo, int nx, int ny, double alpha, int nscales,
                                      double zfactor, int warps, double TOL, int maxiter, ofx_stats *stats_out)
 {
-    return hs_group_entry(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
-                          stats_out);
+    return sor_pair_group<HsPairs>(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nx, ny, {alpha, TOL, warps, maxiter, 0}, nscales,
+                                   zfactor, stats_out);
 }
 
-// What the two video chains check before any work (include/ofx.h): the tables, then both pyramids -- sizes, the pre-smoothing
-// Gaussian of the frames and the Gaussians of the start's pyramid.
-static int sor_sequence_check(ofx_ctx *ctx, const char *who, int n_seq, int n_frames, const void *const *dF, void *const *d_flo,
-                              int nx, int ny, int nscales_first, int nscales_next, double z, double sigma)
-{
-    if (!dF || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL pointer", who);
-    if (n_seq < 1 || n_seq > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "%s: a lockstep group holds 1..%d sequences (got %d)", who, OFX_MAX_GROUP, n_seq);
-    if (n_frames < 2) return ofx_fail(ctx, OFX_ERR_ARG, "%s: %d frames (a sequence has at least 2)", who, n_frames);
-    const int steps = n_frames - 1;
-    for (int q = 0; q < n_seq; q++) {
-        for (int t = 0; t < n_frames; t++)
-            if (!dF[(size_t) q * n_frames + t]) return ofx_fail(ctx, OFX_ERR_ARG, "%s: NULL frame %d of sequence %d", who, t, q);
-        for (int t = 0; t < steps; t++) {
-            const void *p = d_flo[(size_t) q * steps + t];
-            if (!p || reinterpret_cast<uintptr_t>(p) % sizeof(float2))
-                return ofx_fail(ctx, OFX_ERR_ARG, "%s: payload %d of sequence %d NULL or not 8-byte aligned", who, t, q);
-        }
-    }
-    OFX_TRY(ofx_pitch_check(ctx, who, nx));
-    for (int k = 0; k < 2; k++) {
-        const int nscales = k ? nscales_next : nscales_first;
-        std::vector<int> nxs, nys;
-        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, z, nxs, nys));
-        GaussTaps taps;
-        if (ofx_gauss_taps(sigma, &taps) == OFX_OK && (taps.size >= nx || taps.size >= ny))
-            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
-        OFX_TRY(op_flow_pyramid_check(ctx, nscales, z, nxs.data(), nys.data()));
-    }
-    return OFX_OK;
-}
-
-// The chain itself: step t solves the pairs (F[q][t], F[q][t + 1]) of all sequences as one lockstep group through
-// step(t, a, b, init, out, st), from the payloads of step t - 1 where there is one.  Every step is a group entry on the context's
-// stream, so the start of step t is read after step t - 1 has written it and never leaves the device.  Frames and payloads that
-// are not on the context's GPU (the front-ends' host arrays) are staged step by step, as the TV-L1 chain stages them.
-template <class StepFn>
-static int sor_sequence_run(int n_seq, int n_frames, const void *const *dF, void *const *d_flo, ofx_stats *stats_out, StepFn step)
-{
-    const int steps = n_frames - 1;
-    std::vector<ofx_stats> st(n_seq);
-    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
-    void *out[OFX_MAX_GROUP];
-    for (int t = 0; t < steps; t++) {
-        for (int q = 0; q < n_seq; q++) {
-            a[q] = dF[(size_t) q * n_frames + t];
-            b[q] = dF[(size_t) q * n_frames + t + 1];
-            init[q] = t ? d_flo[(size_t) q * steps + t - 1] : nullptr;
-            out[q] = d_flo[(size_t) q * steps + t];
-        }
-        OFX_TRY(step(t, a, b, t ? init : nullptr, out, st.data()));
-        for (int q = 0; stats_out && q < n_seq; q++) stats_out[(size_t) q * steps + t] = st[q];
-    }
-    return OFX_OK;
-}
-
+// The video chain (ofx_chain_check, ofx_chain_walk): every step is a group entry with that step's scale and warp counts.
 extern "C" int ofx_hs_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nx,
                                          int ny, double alpha, int nscales_first, int nscales_next, double zfactor, int warps_first,
                                          int warps_next, double TOL, int maxiter, ofx_stats *stats_out)
@@ -1350,14 +1240,31 @@ extern "C" int ofx_hs_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, 
     OFX_ENTER(ctx);
     if (warps_first < 1 || warps_next < 1) return ofx_fail(ctx, OFX_ERR_ARG, "hs_sequence: warps=%d, %d", warps_first, warps_next);
     if (maxiter > OFX_HS_MAX_MAXITER) return ofx_fail(ctx, OFX_ERR_ARG, "hs_sequence: maxiter > %d", OFX_HS_MAX_MAXITER);
-    OFX_TRY(sor_sequence_check(ctx, "hs_sequence", n_seq, n_frames, dF, d_flo, nx, ny, nscales_first, nscales_next, zfactor,
-                               HS_PRESMOOTH_SIGMA));
-    return sor_sequence_run(n_seq, n_frames, dF, d_flo, stats_out,
-                            [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
-                                ofx_stats *st) {
-                                return hs_group_entry(ctx, n_seq, a, b, init, out, nx, ny, alpha, t ? nscales_next : nscales_first,
-                                                      zfactor, t ? warps_next : warps_first, TOL, maxiter, st, true);
-                            });
+    OFX_TRY(ofx_chain_check(ctx, "hs_sequence", n_seq, n_frames, dF, d_flo, nx, ny, nscales_first, nscales_next, zfactor,
+                            HS_PRESMOOTH_SIGMA));
+    return ofx_chain_walk(n_seq, n_frames, dF, d_flo, stats_out,
+                          [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
+                              ofx_stats *st) {
+                              return sor_pair_group<HsPairs>(ctx, n_seq, a, b, init, out, nx, ny,
+                                                             {alpha, TOL, t ? warps_next : warps_first, maxiter, 0},
+                                                             t ? nscales_next : nscales_first, zfactor, st, true);
+                          });
+}
+
+extern "C" int ofx_hs_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales, double zfactor,
+                                int warps, double TOL, int maxiter, double *work_pix_iters)
+{
+    return sor_pair_batch<HsPairs>(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nx, ny, {alpha, TOL, warps, maxiter, 0}, nscales,
+                                   zfactor, work_pix_iters);
+}
+
+extern "C" int ofx_hs_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
+                                     const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha,
+                                     int nscales, double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters)
+{
+    return sor_pair_batch<HsPairs>(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nx, ny, {alpha, TOL, warps, maxiter, 0},
+                                   nscales, zfactor, work_pix_iters);
 }
 
 // ============================================================================================
@@ -2476,31 +2383,19 @@ static int brox_spatial_dev(ofx_ctx *ctx, int G, const T *const *dI1, const T *c
                             const void *const *init = nullptr)     // G start payloads (NULL entry: zero start); nullptr: all zero
 {
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "brox: group of %d pairs", G);
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, nu, nxs, nys));
-    for (int g = 0; g < G; g++) {
-        ofx_stats_begin(&stats[g], nscales, P.inner_iter * P.outer_iter);
-        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
-    }
-    lv.resize(nscales);
-    for (int s = 0; s < nscales; s++) OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G));
-    {                                                                                              // :467-504
-        T *tmpA, *tmpB;                                   // all 2 G images of the group per launch (op_build_pyramid_group)
-        double *scr;
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nx * ny, &tmpA));
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * G * nx * ny, &tmpB));
-        OFX_TRY(ofx_alloc(ctx, (size_t) G * op_pyramid_scratch_doubles(), &scr));
-        std::vector<T *> lA(nscales), lB(nscales);
-        for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I1; lB[s] = lv[s].I2; }
-        OFX_TRY(op_build_pyramid_group<T>(ctx, G, (const void *const *) dI1, (const void *const *) dI2, nscales, nu,
-                                          BROX_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind, pitch));
-    }
-    BroxLevel<T> &C = lv[nscales - 1];
-    if (!init) {
-        OFX_TRY(op_fill2<T>(ctx, C.U, C.n() * G));                                                 // :507-509
-    } else {
-        OFX_TRY(sor_start_flow<T>(ctx, G, init, nscales, nu, nxs, nys, C.U, C.n()));
-    }
+    using V2 = typename Pix<T>::v2;
+    auto levels = [&](const std::vector<int> &nxs, const std::vector<int> &nys, T **lA, T **lB, V2 **U) -> int {
+        lv.resize(nscales);
+        for (int s = 0; s < nscales; s++) {
+            OFX_TRY(brox_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G));
+            lA[s] = lv[s].I1;
+            lB[s] = lv[s].I2;
+        }
+        *U = lv[nscales - 1].U;
+        return OFX_OK;
+    };
+    OFX_TRY(ofx_pyramid_head<T>(ctx, G, G, (const void *const *) dI1, (const void *const *) dI2, nx, ny, nscales, nu, BROX_SIGMA,
+                                P.inner_iter * P.outer_iter, stats, kind, pitch, init, levels));          // :467-509
     for (int s = nscales - 1; s >= 0; s--) {                                                      // :516
         if (P.verbose && G == 1) { printf("Scale: %d\n", s); fflush(stdout); }
         OFX_TRY(brox_single_scale_dev<T>(ctx, lv[s], P, s, stats));
@@ -2526,21 +2421,19 @@ static int brox_spatial_host(ofx_ctx *ctx, const double *I1, const double *I2, d
     return download_flow<T>(ctx, lv[0].U, u, v, n);
 }
 
-template <typename T>
-static int brox_group_devapi(ofx_ctx *ctx, int G, const void *const *dI1, const void *const *dI2, void *const *d_flo, int nx,
-                             int ny, const BroxParams &P, int nscales, double nu, ofx_stats *stats,
-                             const void *const *init_in = nullptr,   // G start payloads (NULL entry: zero start), or nullptr
-                             bool stage_all = false)                // the video chain: frames and payloads may lie anywhere
-{
-    const size_t n = (size_t) nx * ny;
-    SorGroupIO io;
-    OFX_TRY(sor_group_stage(ctx, G, dI1, dI2, init_in, d_flo, nx, ny, stage_all, io));
-    std::vector<BroxLevel<T>> lv;
-    OFX_TRY(brox_spatial_dev<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, nu, lv, stats,
-                                ofx_src_kind(ctx), nx > 0 ? ofx_src_pitch(ctx, nx) : 0, init_in ? io.init : nullptr));
-    for (int g = 0; g < G; g++) OFX_TRY(op_to_flo<T>(ctx, lv[0].U + g * n, (float2 *) io.flo[g], n));
-    return sor_group_unstage(ctx, G, d_flo, io, n);
-}
+// Brox's side of the pair entries (HsPairs above)
+struct BroxPairs {
+    using Params = BroxParams;
+    template <typename T> using Level = BroxLevel<T>;
+    static constexpr const char *who = "brox";
+    static int check(ofx_ctx *ctx, const BroxParams &P)
+    {
+        if (P.inner_iter < 0 || P.outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
+        return OFX_OK;
+    }
+    template <typename T, class... A> static int pyramid(A &&...a) { return brox_spatial_dev<T>(a...); }
+    template <typename T> static const typename Pix<T>::v2 *flow(const BroxLevel<T> &L, int g) { return L.U + g * L.n(); }
+};
 
 extern "C" int ofx_brox_spatial(ofx_ctx *ctx, const double *I1, const double *I2, double *u, double *v, int nxx,
                                 int nyy, double alpha, double gamma, int nscales, double nu, double TOL,
@@ -2824,32 +2717,12 @@ extern "C" int ofx_robust_expo_single_scale(ofx_ctx *ctx, const double *I1, cons
     return s;
 }
 
-// the lockstep group behind ofx_brox_group_dev (d_flo_init = nullptr) and ofx_brox_group_init_dev
-static int brox_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
-                            const void *const *d_flo_init, void *const *d_flo, int nxx, int nyy, double alpha, double gamma,
-                            int nscales, double nu, double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out,
-                            bool stage_all = false)
-{
-    OFX_ENTER(ctx);
-    const BroxParams P = {alpha, gamma, TOL, inner_iter, outer_iter, 0};
-    auto check = [&]() -> int {
-        if (inner_iter < 0 || outer_iter < 0) return ofx_fail(ctx, OFX_ERR_ARG, "brox: negative iteration count");
-        OFX_TRY(ofx_pitch_check(ctx, "brox", nxx));
-        return sor_start_check(ctx, "brox", n_pairs, d_flo_init, nxx, nyy, nscales, nu);
-    };
-    return sor_group_entry(ctx, "brox", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
-        return ctx->precision == OFX_F64
-                   ? brox_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st, d_flo_init, stage_all)
-                   : brox_group_devapi<float>(ctx, n_pairs, dI1, dI2, d_flo, nxx, nyy, P, nscales, nu, st, d_flo_init, stage_all);
-    });
-}
-
 extern "C" int ofx_brox_group_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
                                   void *const *d_flo, int nxx, int nyy, double alpha, double gamma, int nscales, double nu,
                                   double TOL, int inner_iter, int outer_iter, ofx_stats *stats_out)
 {
-    return brox_group_entry(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter,
-                            stats_out);
+    return sor_pair_group<BroxPairs>(ctx, n_pairs, dI1, dI2, nullptr, d_flo, nxx, nyy, {alpha, gamma, TOL, inner_iter, outer_iter, 0},
+                                     nscales, nu, stats_out);
 }
 
 extern "C" int ofx_brox_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *const *dI1, const void *const *dI2,
@@ -2857,8 +2730,8 @@ extern "C" int ofx_brox_group_init_dev(ofx_ctx *ctx, int n_pairs, const void *co
                                        double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter,
                                        ofx_stats *stats_out)
 {
-    return brox_group_entry(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
-                            outer_iter, stats_out);
+    return sor_pair_group<BroxPairs>(ctx, n_pairs, dI1, dI2, d_flo_init, d_flo, nxx, nyy,
+                                     {alpha, gamma, TOL, inner_iter, outer_iter, 0}, nscales, nu, stats_out);
 }
 
 extern "C" int ofx_brox_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, void *const *d_flo, int nxx,
@@ -2868,15 +2741,14 @@ extern "C" int ofx_brox_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames
     OFX_ENTER(ctx);
     if (inner_iter < 0 || outer_first < 0 || outer_next < 0)
         return ofx_fail(ctx, OFX_ERR_ARG, "brox_sequence: negative iteration count");
-    OFX_TRY(sor_sequence_check(ctx, "brox_sequence", n_seq, n_frames, dF, d_flo, nxx, nyy, nscales_first, nscales_next, nu,
-                               BROX_SIGMA));
-    return sor_sequence_run(n_seq, n_frames, dF, d_flo, stats_out,
-                            [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
-                                ofx_stats *st) {
-                                return brox_group_entry(ctx, n_seq, a, b, init, out, nxx, nyy, alpha, gamma,
-                                                        t ? nscales_next : nscales_first, nu, TOL, inner_iter,
-                                                        t ? outer_next : outer_first, st, true);
-                            });
+    OFX_TRY(ofx_chain_check(ctx, "brox_sequence", n_seq, n_frames, dF, d_flo, nxx, nyy, nscales_first, nscales_next, nu, BROX_SIGMA));
+    return ofx_chain_walk(n_seq, n_frames, dF, d_flo, stats_out,
+                          [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
+                              ofx_stats *st) {
+                              return sor_pair_group<BroxPairs>(ctx, n_seq, a, b, init, out, nxx, nyy,
+                                                               {alpha, gamma, TOL, inner_iter, t ? outer_next : outer_first, 0},
+                                                               t ? nscales_next : nscales_first, nu, st, true);
+                          });
 }
 
 // ofx_robust_expo_pyramid for the pairs of a lockstep group on device-resident images (include/ofx.h)
@@ -2894,7 +2766,7 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
         OFX_TRY(rexpo_pyramid_check(ctx, n_pairs, nxx, nyy, nzz, nscales, nu, nxs, nys));
         return ofx_pitch_check(ctx, "robust_expo", nxx * nzz);
     };
-    return sor_group_entry(ctx, "robust_expo", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
+    return ofx_pair_group_entry(ctx, "robust_expo", n_pairs, dI1, dI2, d_flo, stats_out, check, [&](ofx_stats *st) {
         BroxParams P = rexpo_params(method_type, rexpo_multiscale_alpha(alpha, nzz), gamma, lambda, TOL, inner_iter, outer_iter, 0);
         P.time_windows = ctx->profile;
         return ctx->precision == OFX_F64 ? rexpo_group_devapi<double>(ctx, n_pairs, dI1, dI2, d_flo, nzz, P, nscales, nu, nxs, nys, st)
@@ -2902,83 +2774,12 @@ extern "C" int ofx_robust_expo_group_dev(ofx_ctx *ctx, int n_pairs, const void *
     });
 }
 
-// ---- batches of pairs for the SOR solvers: lockstep groups over the contexts (ofx_run_groups, with the `concurrency` hint:
-// memory budgets are shared between the workers) ----
-// group size: option "lockstep" of ctxs[0], else as large as possible (16), evened out over the contexts
-static int sor_batch_group_size(ofx_ctx *const *ctxs, int n_ctx, int n_pairs)
-{
-    return ofx_plan_lockstep(ctxs[0]->lockstep, OFX_MAX_GROUP, ofx_plan_even_rounds(n_pairs, n_ctx, OFX_MAX_GROUP));
-}
-
-// The starts' refusals for the whole batch, before any group runs (groups run concurrently: a refusal inside one would find the
-// others at work).  The pair is named by its index in the batch, the reason is left in every context.
-static int sor_batch_start_check(ofx_ctx *const *ctxs, int n_ctx, const char *who, int n_pairs, const void *const *d_flo_init, int nx,
-                                 int ny, int nscales, double z)
-{
-    if (!d_flo_init) return OFX_OK;
-    int s = OFX_OK;
-    for (int w = 0; w < n_ctx; w++) {
-        const int sw = sor_start_check(ctxs[w], who, n_pairs, d_flo_init, nx, ny, nscales, z);
-        if (s == OFX_OK) s = sw;
-    }
-    return s;
-}
-
-// The batches behind ofx_*_batch_dev (d_flo_init = nullptr) and ofx_*_batch_init_dev: a start per pair where d_flo_init is a table
-// (NULL entry: that pair starts from zero).  d_flo_init[g] == d_flo[g] is allowed; a start that is ANOTHER pair's payload of the
-// same batch is not (groups run concurrently).  The start's scratch comes from the group's arena and does not enter the group size.
-static int hs_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
-                          const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales,
-                          double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters)
-{
-    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
-    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
-    if (n_pairs == 0) return OFX_OK;
-    OFX_TRY(sor_batch_start_check(ctxs, n_ctx, "hs", n_pairs, d_flo_init, nx, ny, nscales, zfactor));
-    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
-        return hs_group_entry(c, cnt, dI1 + first, dI2 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nx, ny,
-                              alpha, nscales, zfactor, warps, TOL, maxiter, st);
-    });
-}
-
-extern "C" int ofx_hs_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
-                                void *const *d_flo, int n_pairs, int nx, int ny, double alpha, int nscales, double zfactor,
-                                int warps, double TOL, int maxiter, double *work_pix_iters)
-{
-    return hs_batch_entry(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
-                          work_pix_iters);
-}
-
-extern "C" int ofx_hs_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
-                                     const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nx, int ny, double alpha,
-                                     int nscales, double zfactor, int warps, double TOL, int maxiter, double *work_pix_iters)
-{
-    return hs_batch_entry(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nx, ny, alpha, nscales, zfactor, warps, TOL, maxiter,
-                          work_pix_iters);
-}
-
-static int brox_batch_entry(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
-                            const void *const *d_flo_init, void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha,
-                            double gamma, int nscales, double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
-{
-    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
-    if (n_pairs < 0 || !dI1 || !dI2 || !d_flo) return OFX_ERR_ARG;
-    if (n_pairs == 0) return OFX_OK;
-    OFX_TRY(sor_batch_start_check(ctxs, n_ctx, "brox", n_pairs, d_flo_init, nxx, nyy, nscales, nu));
-    const int G = sor_batch_group_size(ctxs, n_ctx, n_pairs);
-    return ofx_run_groups(ctxs, n_ctx, n_pairs, G, 1, work_pix_iters, true, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) {
-        return brox_group_entry(c, cnt, dI1 + first, dI2 + first, d_flo_init ? d_flo_init + first : nullptr, d_flo + first, nxx,
-                                nyy, alpha, gamma, nscales, nu, TOL, inner_iter, outer_iter, st);
-    });
-}
-
 extern "C" int ofx_brox_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
                                   void *const *d_flo, int n_pairs, int nxx, int nyy, double alpha, double gamma, int nscales,
                                   double nu, double TOL, int inner_iter, int outer_iter, double *work_pix_iters)
 {
-    return brox_batch_entry(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
-                            outer_iter, work_pix_iters);
+    return sor_pair_batch<BroxPairs>(ctxs, n_ctx, dI1, dI2, nullptr, d_flo, n_pairs, nxx, nyy,
+                                     {alpha, gamma, TOL, inner_iter, outer_iter, 0}, nscales, nu, work_pix_iters);
 }
 
 extern "C" int ofx_brox_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
@@ -2986,10 +2787,11 @@ extern "C" int ofx_brox_batch_init_dev(ofx_ctx *const *ctxs, int n_ctx, const vo
                                        double alpha, double gamma, int nscales, double nu, double TOL, int inner_iter,
                                        int outer_iter, double *work_pix_iters)
 {
-    return brox_batch_entry(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nxx, nyy, alpha, gamma, nscales, nu, TOL, inner_iter,
-                            outer_iter, work_pix_iters);
+    return sor_pair_batch<BroxPairs>(ctxs, n_ctx, dI1, dI2, d_flo_init, d_flo, n_pairs, nxx, nyy,
+                                     {alpha, gamma, TOL, inner_iter, outer_iter, 0}, nscales, nu, work_pix_iters);
 }
 
+// the robust_expo batch: the contexts' agreement, group size and runner of the SOR batches (sor_pair_batch) around its own group
 extern "C" int ofx_robust_expo_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const *dI1, const void *const *dI2,
                                          void *const *d_flo, int n_pairs, int nxx, int nyy, int nzz, int method_type,
                                          double alpha, double gamma, double lambda, int nscales, double nu, double TOL,

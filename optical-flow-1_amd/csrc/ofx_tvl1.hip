@@ -33,7 +33,7 @@
 #include "ofx_ops.h"
 #include "ofx_device.h"
 #include "ofx_loop.h"
-#include "ofx_batch.h"
+#include "ofx_pairs.h"
 
 #include <chrono>
 #include <cmath>
@@ -1912,35 +1912,19 @@ static int tvl1_multiscale_dev(ofx_ctx *ctx, int G, const T *const *dI0, const T
     if (P.warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", P.warps);
     if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: group of %d pairs", G);
 
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    for (int g = 0; g < G; g++) {
-        ofx_stats_begin(&stats[g], nscales, P.warps);
-        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { stats[g].nx[s] = nxs[s]; stats[g].ny[s] = nys[s]; }
-    }
-    lv.resize(nscales);
-    for (int s = 0; s < nscales; s++) OFX_TRY(tvl1_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true, shared));
-    {                                                                                              // :255-275
-        T *tmpA, *tmpB;
-        double *scr;
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * Gp * nxx * nyy, &tmpA));
-        OFX_TRY(ofx_alloc(ctx, (size_t) 2 * Gp * nxx * nyy, &tmpB));
-        OFX_TRY(ofx_alloc(ctx, (size_t) Gp * op_pyramid_scratch_doubles(), &scr));
-        std::vector<T *> lA(nscales), lB(nscales);
-        for (int s = 0; s < nscales; s++) { lA[s] = lv[s].I0; lB[s] = shared ? lv[s].I0 + (size_t) shared * lv[s].n() : lv[s].I1; }
-        OFX_TRY(op_build_pyramid_group<T>(ctx, Gp, (const void *const *) dI0, (const void *const *) dI1, nscales, zfactor,
-                                          TVL1_PRESMOOTHING_SIGMA, nxs.data(), nys.data(), lA.data(), lB.data(), tmpA, tmpB, scr, kind,
-                                          pitch));
-    }
-    Tvl1Level<T> &C = lv[nscales - 1];
-    if (!init) {
-        OFX_TRY(op_fill2<T>(ctx, C.U[0], C.n() * G));                                            // :278-280
-    } else {
-        // the start in place of the zeros: the payloads' own pyramid (op_flow_pyramid), its last level rounded into U
-        void *dst[OFX_MAX_GROUP];
-        for (int g = 0; g < G; g++) dst[g] = C.U[0] + (size_t) g * C.n();
-        OFX_TRY(op_flow_pyramid<typename Pix<T>::v2>(ctx, G, init, nscales, zfactor, nxs.data(), nys.data(), dst));
-    }
+    using V2 = typename Pix<T>::v2;
+    auto levels = [&](const std::vector<int> &nxs, const std::vector<int> &nys, T **lA, T **lB, V2 **U) -> int {
+        lv.resize(nscales);
+        for (int s = 0; s < nscales; s++) {
+            OFX_TRY(tvl1_level_alloc<T>(ctx, lv[s], nxs[s], nys[s], G, true, shared));
+            lA[s] = lv[s].I0;
+            lB[s] = shared ? lv[s].I0 + (size_t) shared * lv[s].n() : lv[s].I1;
+        }
+        *U = lv[nscales - 1].U[0];
+        return OFX_OK;
+    };
+    OFX_TRY(ofx_pyramid_head<T>(ctx, G, Gp, (const void *const *) dI0, (const void *const *) dI1, nxx, nyy, nscales, zfactor,
+                                TVL1_PRESMOOTHING_SIGMA, P.warps, stats, kind, pitch, init, levels));     // :236-280
 
     for (int s = nscales - 1; s >= 0; s--) {                                                     // :283
         if (P.verbose && G == 1) fprintf(stderr, "Scale %d: %dx%d\n", s, lv[s].nx, lv[s].ny);
@@ -2005,109 +1989,26 @@ extern "C" int ofx_tvl1_multiscale(ofx_ctx *ctx, const double *I0, const double 
     return s;
 }
 
-// G device-resident pairs in lockstep; stats = G records
-// Is p device memory of this context's GPU?  Everything else -- another GPU's memory, pinned or pageable host memory -- is
-// reached through a staging copy (hipMemcpyDefault resolves the direction; between GPUs it is a peer copy over xGMI).
-bool ofx_ptr_is_local(const ofx_ctx *ctx, const void *p)
-{
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void) hipGetLastError();                              // pageable host memory is unknown to the runtime
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice && a.device == ctx->device;
-}
-// How a buffer that lives on `mem_device` (-1: host memory) reaches a context on `ctx_device`: 0 = in place, 1 = one
-// hipMemcpyDefault (host <-> device, or a peer copy over xGMI), 2 = two copies through a host bounce buffer because the two GPUs
-// cannot address each other (hipDeviceCanAccessPeer says no: another IOMMU group, peer access disabled, ...).  Pure decision,
-// exported so that the host-logic tests cover it without a GPU.
-extern "C" int ofx_staging_route(int ctx_device, int mem_device, int can_access_peer)
-{
-    if (mem_device == ctx_device) return 0;
-    if (mem_device < 0) return 1;
-    return can_access_peer ? 1 : 2;
-}
-// dst <- src (one of them on this context's GPU, the other anywhere), on the context's stream.  A route-2 copy is synchronous
-// and leaves a note in ofx_last_error (the call still succeeds).  UNEXECUTED on more than one GPU (no multi-GPU box in any round).
-int ofx_copy_staged(ofx_ctx *ctx, void *dst, const void *src, size_t bytes)
-{
-    const void *other = ofx_ptr_is_local(ctx, dst) ? src : dst;
-    int mem_device = -1, can = 1;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, other) == hipSuccess) {
-        if (a.type == hipMemoryTypeDevice) mem_device = a.device;
-    } else {
-        (void) hipGetLastError();
-    }
-    if (mem_device >= 0 && mem_device != ctx->device && hipDeviceCanAccessPeer(&can, ctx->device, mem_device) != hipSuccess) {
-        (void) hipGetLastError();
-        can = 0;
-    }
-    if (ofx_staging_route(ctx->device, mem_device, can) < 2) {
-        OFX_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream));
-        return OFX_OK;
-    }
-    void *bounce = nullptr;
-    OFX_HIP(ctx, hipHostMalloc(&bounce, bytes, hipHostMallocDefault));
-    hipError_t e = hipStreamSynchronize(ctx->stream);                                       // src may be this stream's product
-    if (e == hipSuccess) e = hipMemcpy(bounce, src, bytes, hipMemcpyDefault);
-    if (e == hipSuccess) e = hipMemcpy(dst, bounce, bytes, hipMemcpyDefault);
-    (void) hipHostFree(bounce);
-    if (e != hipSuccess) return ofx_fail(ctx, OFX_ERR_HIP, "staging through the host failed: %s", hipGetErrorString(e));
-    snprintf(ctx->errmsg, sizeof(ctx->errmsg), "note: GPU %d cannot address GPU %d, buffers were staged through the host", ctx->device,
-             mem_device);
-    return OFX_OK;
-}
-
-// Buffers that do not live on this context's GPU (a batch spread over several GPUs by ofx_tvl1_batch_dev, or host buffers) are
-// staged through the arena, on the context's stream.  In: *out = p itself where it is local, else an arena buffer of `bytes`
-// bytes -- filled from p (fill: what the solve reads) or left for the solve to write ...
-static int tvl1_stage_in(ofx_ctx *ctx, const void *p, size_t bytes, bool fill, void **out)
-{
-    *out = const_cast<void *>(p);
-    if (ofx_ptr_is_local(ctx, p)) return OFX_OK;
-    char *stage;
-    OFX_TRY(ofx_alloc(ctx, bytes, &stage));
-    *out = stage;
-    return fill ? ofx_copy_staged(ctx, stage, p, bytes) : OFX_OK;
-}
-// ... out: back into the caller's array where the solve wrote a stage
-static int tvl1_stage_out(ofx_ctx *ctx, void *p, const void *staged, size_t bytes)
-{
-    return staged != p ? ofx_copy_staged(ctx, p, staged, bytes) : OFX_OK;
-}
-
+// G device-resident pairs in lockstep; stats = G records.  Frames, payloads and starts that are not on this context's GPU (a
+// batch spread over several GPUs by ofx_tvl1_batch_dev, or host buffers) are staged through the arena (ofx_pairs_stage).
 template <typename T>
 static int tvl1_group_devapi(ofx_ctx *ctx, int G, const void *const *dI0_in, const void *const *dI1_in, void *const *d_flo_in,
                              int nx, int ny, const Tvl1Params &P, int nscales, double zfactor, ofx_stats *stats,
                              const void *const *init_in = nullptr)     // G start payloads (NULL entry: zero start), or nullptr
 {
     const size_t n = (size_t) nx * ny;
-    const int kind = ofx_src_kind(ctx);                      // the frames come in the context's "input" kind
     OFX_TRY(ofx_pitch_check(ctx, "tvl1", nx));
-    const size_t pitch = nx > 0 ? ofx_src_pitch(ctx, nx) : 0;
-    // a frame's bytes as they lie: with a pitch, from its first row's start to its last row's end
-    const size_t span = pitch && ny > 0 ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
-    void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP], *d_flo[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) {                            // a pitched frame keeps its pitch
-        OFX_TRY(tvl1_stage_in(ctx, dI0_in[g], span, true, &dI0[g]));
-        OFX_TRY(tvl1_stage_in(ctx, dI1_in[g], span, true, &dI1[g]));
-        OFX_TRY(tvl1_stage_in(ctx, d_flo_in[g], n * sizeof(float2), false, &d_flo[g]));
-    }
-    for (int g = 0; init_in && g < G; g++) {                 // a start, where the pair has one
-        init[g] = nullptr;
-        if (init_in[g]) OFX_TRY(tvl1_stage_in(ctx, init_in[g], n * sizeof(float2), true, &init[g]));
-    }
+    OfxPairIO io;                                            // the frames come in the context's "input" kind
+    OFX_TRY(ofx_pairs_stage(ctx, G, dI0_in, dI1_in, init_in, d_flo_in, nx, ny, true, io));
     std::vector<Tvl1Level<T>> lv;
-    OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv,
-                                   stats, kind, pitch, 0, init_in ? init : nullptr));
+    OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) io.a, (const T *const *) io.b, nx, ny, P, nscales, zfactor, lv, stats,
+                                   io.kind, io.pitch, 0, init_in ? io.init : nullptr));
     OfxGroupPtrs out;
-    for (int g = 0; g < OFX_MAX_GROUP; g++) { out.a[g] = g < G ? d_flo[g] : nullptr; out.b[g] = nullptr; }
+    for (int g = 0; g < OFX_MAX_GROUP; g++) { out.a[g] = g < G ? io.flo[g] : nullptr; out.b[g] = nullptr; }
     hipLaunchKernelGGL(k_tvl1_to_flo_g<T>, dim3((unsigned) ((n + 255) / 256), G), dim3(256), 0, ctx->stream, lv[0].Ut(), lv[0].cur,
                        out, n);
     OFX_LAUNCH_CHECK(ctx);
-    for (int g = 0; g < G; g++) OFX_TRY(tvl1_stage_out(ctx, d_flo_in[g], d_flo[g], n * sizeof(float2)));
-    return OFX_OK;
+    return ofx_pairs_unstage(ctx, G, d_flo_in, io, n);
 }
 
 extern "C" int ofx_tvl1_multiscale_dev(ofx_ctx *ctx, const void *dI0, const void *dI1, void *d_flo, int nx, int ny,
@@ -2131,21 +2032,10 @@ static int tvl1_group_entry(ofx_ctx *ctx, int n_pairs, const void *const *dI0, c
                             int warps, double epsilon, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
-    if (!dI0 || !dI1 || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: NULL pointer");
-    if (n_pairs < 1 || n_pairs > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: a lockstep group holds 1..%d pairs (got %d)", OFX_MAX_GROUP, n_pairs);
-    for (int g = 0; g < n_pairs; g++)
-        if (!dI0[g] || !dI1[g] || !d_flo[g]) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: NULL pointer (pair %d)", g);
-    if (d_flo_init) {                                           // the start's own refusals, before any work
-        for (int g = 0; g < n_pairs; g++)
-            if (reinterpret_cast<uintptr_t>(d_flo_init[g]) % sizeof(float2))
-                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: start payload of pair %d is not 8-byte aligned", g);
-        std::vector<int> nxs, nys;
-        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
-        OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
-    }
     const Tvl1Params P = make_params(ctx, tau, lambda, theta, warps, epsilon, 0);
-    return ofx_group_records(ctx, n_pairs, stats_out, [&](ofx_stats *st) {
+    // the start's refusals alone: warps and "input_pitch" are tested inside the solve, after them, as they always were
+    auto check = [&]() -> int { return ofx_start_check(ctx, "tvl1", n_pairs, d_flo_init, nx, ny, nscales, zfactor); };
+    return ofx_pair_group_entry(ctx, "tvl1", n_pairs, dI0, dI1, d_flo, stats_out, check, [&](ofx_stats *st) {
         return ctx->precision == OFX_F64
                    ? tvl1_group_devapi<double>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init)
                    : tvl1_group_devapi<float>(ctx, n_pairs, dI0, dI1, d_flo, nx, ny, P, nscales, zfactor, st, d_flo_init);
@@ -2178,46 +2068,15 @@ extern "C" int ofx_tvl1_sequence_group_dev(ofx_ctx *ctx, int n_seq, int n_frames
                                            double zfactor, int warps, double epsilon, ofx_stats *stats_out)
 {
     OFX_ENTER(ctx);
-    if (!dF || !d_flo) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: NULL pointer");
-    if (n_seq < 1 || n_seq > OFX_MAX_GROUP)
-        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: a lockstep group holds 1..%d sequences (got %d)", OFX_MAX_GROUP, n_seq);
-    if (n_frames < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: %d frames (a sequence has at least 2)", n_frames);
     if (warps < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: warps=%d", warps);
-    const int steps = n_frames - 1;
-    for (int q = 0; q < n_seq; q++) {
-        for (int t = 0; t < n_frames; t++)
-            if (!dF[(size_t) q * n_frames + t]) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: NULL frame %d of sequence %d", t, q);
-        for (int t = 0; t < steps; t++) {
-            const void *p = d_flo[(size_t) q * steps + t];
-            if (!p || reinterpret_cast<uintptr_t>(p) % sizeof(float2))
-                return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_sequence: payload %d of sequence %d NULL or not 8-byte aligned", t, q);
-        }
-    }
-    OFX_TRY(ofx_pitch_check(ctx, "tvl1_sequence", nx));
-    for (int k = 0; k < 2; k++) {                               // both pyramids, every Gaussian of either, before any work
-        const int nscales = k ? nscales_next : nscales_first;
-        std::vector<int> nxs, nys;
-        OFX_TRY(op_pyramid_sizes(ctx, nx, ny, nscales, zfactor, nxs, nys));
-        GaussTaps taps;
-        if (ofx_gauss_taps(TVL1_PRESMOOTHING_SIGMA, &taps) == OFX_OK && (taps.size >= nx || taps.size >= ny))
-            return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
-        OFX_TRY(op_flow_pyramid_check(ctx, nscales, zfactor, nxs.data(), nys.data()));
-    }
-    std::vector<ofx_stats> st(n_seq);
-    const void *a[OFX_MAX_GROUP], *b[OFX_MAX_GROUP], *init[OFX_MAX_GROUP];
-    void *out[OFX_MAX_GROUP];
-    for (int t = 0; t < steps; t++) {
-        for (int q = 0; q < n_seq; q++) {
-            a[q] = dF[(size_t) q * n_frames + t];
-            b[q] = dF[(size_t) q * n_frames + t + 1];
-            init[q] = t ? d_flo[(size_t) q * steps + t - 1] : nullptr;
-            out[q] = d_flo[(size_t) q * steps + t];
-        }
-        OFX_TRY(tvl1_group_entry(ctx, n_seq, a, b, t ? init : nullptr, out, nx, ny, tau, lambda, theta, t ? nscales_next : nscales_first,
-                                 zfactor, warps, epsilon, st.data()));
-        for (int q = 0; stats_out && q < n_seq; q++) stats_out[(size_t) q * steps + t] = st[q];
-    }
-    return OFX_OK;
+    OFX_TRY(ofx_chain_check(ctx, "tvl1_sequence", n_seq, n_frames, dF, d_flo, nx, ny, nscales_first, nscales_next, zfactor,
+                            TVL1_PRESMOOTHING_SIGMA));
+    return ofx_chain_walk(n_seq, n_frames, dF, d_flo, stats_out,
+                          [&](int t, const void *const *a, const void *const *b, const void *const *init, void *const *out,
+                              ofx_stats *st) {
+                              return tvl1_group_entry(ctx, n_seq, a, b, init, out, nx, ny, tau, lambda, theta,
+                                                      t ? nscales_next : nscales_first, zfactor, warps, epsilon, st);
+                          });
 }
 
 // The start's pyramid alone (include/ofx.h): op_flow_pyramid into the caller's arrays as doubles, in either precision.
@@ -2252,20 +2111,20 @@ static int tvl1_bidir_devapi(ofx_ctx *ctx, int Gp, const void *const *dI0_in, co
     const int kind = ofx_src_kind(ctx);
     OFX_TRY(ofx_pitch_check(ctx, "tvl1_bidir", nx));
     const size_t pitch = ofx_src_pitch(ctx, nx);
-    const size_t span = pitch ? (size_t) (ny - 1) * pitch + (size_t) nx * ofx_src_bytes(kind) : n * ofx_src_bytes(kind);
+    const size_t span = ofx_frame_span(nx, ny, pitch, ofx_src_bytes(kind));
     void *dI0[OFX_MAX_GROUP], *dI1[OFX_MAX_GROUP];
     void *flo_in[OFX_MAX_GROUP], *occ_in[OFX_MAX_GROUP], *flo[OFX_MAX_GROUP], *occ[OFX_MAX_GROUP];     // slot order
     for (int g = 0; g < Gp; g++) {
-        OFX_TRY(tvl1_stage_in(ctx, dI0_in[g], span, true, &dI0[g]));
-        OFX_TRY(tvl1_stage_in(ctx, dI1_in[g], span, true, &dI1[g]));
+        OFX_TRY(ofx_stage_in(ctx, dI0_in[g], span, true, &dI0[g]));
+        OFX_TRY(ofx_stage_in(ctx, dI1_in[g], span, true, &dI1[g]));
         flo_in[g] = d_flo_fwd[g];
         flo_in[Gp + g] = d_flo_bwd[g];
         occ_in[g] = d_occ_fwd[g];
         occ_in[Gp + g] = d_occ_bwd[g];
     }
     for (int z = 0; z < G; z++) {
-        OFX_TRY(tvl1_stage_in(ctx, flo_in[z], n * sizeof(float2), false, &flo[z]));
-        OFX_TRY(tvl1_stage_in(ctx, occ_in[z], n, false, &occ[z]));
+        OFX_TRY(ofx_stage_in(ctx, flo_in[z], n * sizeof(float2), false, &flo[z]));
+        OFX_TRY(ofx_stage_in(ctx, occ_in[z], n, false, &occ[z]));
     }
     std::vector<Tvl1Level<T>> lv;
     OFX_TRY(tvl1_multiscale_dev<T>(ctx, G, (const T *const *) dI0, (const T *const *) dI1, nx, ny, P, nscales, zfactor, lv, stats,
@@ -2279,8 +2138,8 @@ static int tvl1_bidir_devapi(ofx_ctx *ctx, int Gp, const void *const *dI0_in, co
     for (int z = 0; z < G; z++) against[z] = flo[(z + Gp) % G];
     OFX_TRY(op_flow_consistency(ctx, G, flo, against, occ, nx, ny, fb_alpha, fb_beta));
     for (int z = 0; z < G; z++) {
-        OFX_TRY(tvl1_stage_out(ctx, flo_in[z], flo[z], n * sizeof(float2)));
-        OFX_TRY(tvl1_stage_out(ctx, occ_in[z], occ[z], n));
+        OFX_TRY(ofx_stage_out(ctx, flo_in[z], flo[z], n * sizeof(float2)));
+        OFX_TRY(ofx_stage_out(ctx, occ_in[z], occ[z], n));
     }
     return OFX_OK;
 }
