@@ -165,6 +165,10 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *   "spin_us"        microseconds the host spins on a convergence poll's pinned record before it sleeps in
  *                         hipEventSynchronize (default 150; 0 = never)
  *   "warp_lds"       1/0  TV-L1 warp with the bicubic taps staged through LDS (default 1)
+ *   "apply_lds"      ofx_flow_warp_dev / ofx_flow_interpolate_dev: 1 = the bicubic taps staged through LDS (a workgroup whose taps
+ *                         do not fit its tile gathers from global memory), 0 = gathered from global memory alone, 2 (default) = by
+ *                         measurement: 1 for float and double frames, 0 for 8- and 16-bit frames.  Any other value is OFX_ERR_ARG.
+ *                         Results do not depend on it.
  *   "lockstep"       pairs per lockstep group in ofx_tvl1_batch_dev (default 0 = ofx_tvl1_batch_group_size's
  *                         rule: as large as possible, evened out over the contexts; at most 16)
  *   "mem_budget"     bytes the level arrays of all contexts of a batch may occupy when the group size is chosen
@@ -190,7 +194,8 @@ int   ofx_get_stats(const ofx_ctx *ctx, ofx_stats *out);
  * ofx_hs_group_init_dev / ofx_hs_batch_init_dev / ofx_hs_sequence_group_dev, ofx_brox_group_init_dev / ofx_brox_batch_init_dev /
  * ofx_brox_sequence_group_dev,
  * ofx_robust_expo_group_dev / _batch_dev, ofx_brox_temporal_dev / _group_dev / _batch_dev, ofx_tvl1occ_sequence_group_dev /
- * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev and ofx_pyramid_group_dev -- read
+ * _sequence_dev / _triples_group_dev / _triples_dev, ofx_normalize_frames_dev / ofx_normalize_frames2d_dev, ofx_pyramid_group_dev and
+ * ofx_flow_warp_dev / ofx_flow_interpolate_dev (which also WRITE that kind, and refuse OFX_IN_RGB8) -- read
  * elements of this kind wherever their
  * comments say "the context's storage precision"; a frame is aligned to its element (OFX_IN_RGB8: to a byte).  Every sample
  * converts exactly to double, so payloads, occlusion maps and iteration / sweep tables are BIT-IDENTICAL to the same call under
@@ -437,6 +442,54 @@ int ofx_tvl1_bidir_batch_dev(ofx_ctx *const *ctxs, int n_ctx, const void *const 
                              void *const *d_flo_fwd, void *const *d_flo_bwd, void *const *d_occ_fwd, void *const *d_occ_bwd,
                              int n_pairs, int nx, int ny, double tau, double lambda, double theta, int nscales, double zfactor,
                              int warps, double epsilon, double fb_alpha, double fb_beta, double *work_pix_iters);
+
+/* ---- a flow applied to frames on the device: warped frames and in-between frames ---------------------------------------------
+ * What consumes the payloads and maps above.  FRAMES (dSrc, dFill, dA, dB, dDst): ny rows of nx pixels of nz interleaved
+ * channels, nz = 1..4, of the element kind that option "input" selects -- OFX_IN_STORAGE (the context's double or float),
+ * OFX_IN_U8, OFX_IN_U16, OFX_IN_F32; OFX_IN_RGB8 is OFX_ERR_ARG (its meaning is "collapse to gray": an HWC byte image is OFX_IN_U8
+ * with nz = 3, as for ofx_robust_expo_group_dev).  The frames that are READ honour "input_pitch" (rows of nx * nz elements, the
+ * rules above; no byte outside the rows is read); dDst[g] has the same element kind, is written DENSE, is aligned to its element
+ * -- a byte image may sit at any byte address -- and no byte outside its nx * ny * nz elements is written.  PAYLOADS: as every
+ * *_dev solver writes them, nx * ny interleaved (u, v) float32, 8-byte aligned.  d_occ[g]: a byte map in the convention of
+ * ofx_flow_consistency_dev, 0 = keep, non-zero = flagged, at any alignment.
+ * All arithmetic in double, every operation rounded once, nothing contracted, association as written; every frame element
+ * converts exactly to double.
+ *     inside(x, y)       = x >= 0 && x <= nx - 1 && y >= 0 && y <= ny - 1          (NaN and Inf fail it, before any cast to int)
+ *     sample(I, x, y, k) = bicubic_interpolation_at_color(I, x, y, nx, ny, nz, k, false)   (src/bicubic_interpolation.h:30-43)
+ *     conv(x)            = x for double frames; (float) x for float frames; for U8 / U16 with max = 255 / 65535: NaN -> 0,
+ *                          x <= 0 -> 0, x >= max -> max, otherwise (int) (x + 0.5)
+ * ofx_flow_warp_dev, the backward warp of slot g at row i, column j:
+ *     (u, v) = flo[i][j];  x = j + u;  y = i + v
+ *     keep = inside(x, y) && (no map for this slot || occ[i * nx + j] == 0)
+ *     keep      : dst[i][j][k] = conv(sample(Src, x, y, k))
+ *     otherwise : dst[i][j][k] = Fill[i][j][k] copied unchanged (same kind and pitch as Src), or 0 where the slot has no fill frame
+ * d_occ and dFill may be NULL, and so may their entries.  A zero payload writes Src exactly.
+ * ofx_flow_interpolate_dev, the in-between frame at time t[g] in [0, 1] (t: a HOST array of n values, read before the call
+ * returns) from the two payloads of a bidirectional solve -- fwd: A -> B on A's grid, bwd: B -> A on B's grid -- with the flow
+ * approximation of Jiang et al., "Super SloMo", CVPR 2018, eq. 4:
+ *     s = 1 - t;  c0 = s * t;  c1 = t * t;  c2 = s * s
+ *     (u01, v01) = fwd[i][j];  (u10, v10) = bwd[i][j]
+ *     xa = j + (c1 * u10 - c0 * u01);  ya = i + (c1 * v10 - c0 * v01)              where this pixel is in A
+ *     xb = j + (c2 * u01 - c0 * u10);  yb = i + (c2 * v01 - c0 * v10)              ... and in B
+ *     ina = inside(xa, ya);  inb = inside(xb, yb)
+ *     o_k = ina && inb ? s * sample(A, xa, ya, k) + t * sample(B, xb, yb, k)
+ *         : ina ? sample(A, xa, ya, k) : inb ? sample(B, xb, yb, k) : s * A[i][j][k] + t * B[i][j][k]
+ *     dst[i][j][k] = conv(o_k)
+ * t = 0 writes A exactly and t = 1 writes B exactly (finite payloads).  The consistency maps take no part: gating the blend by
+ * them measured no better; they do their work in the warp, where a flagged pixel takes the fill frame.
+ * Both results are pure functions of the frames' values and the float payloads: for U8, U16 and F32 frames an f64 and an f32
+ * context write the same bytes, and option "apply_lds" changes nothing.
+ * n >= 1 slots of any number, OFX_MAX_GROUP = 16 per launch; several slots may name the same frames and payloads (three in-between
+ * frames of one pair in one launch).  A frame, payload, map or destination that is not on the context's GPU is staged as
+ * ofx_tvl1_batch_dev stages its buffers, a pitched frame as it lies.  Asynchronous on the context's stream.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: a NULL table or entry (but d_occ, dFill and their
+ * entries), n < 1, nx < 2 or ny < 2, nx * ny * nz beyond an int, nz outside 1..4, a t[g] outside [0, 1] or not finite, a payload
+ * that is not 8-byte aligned, a frame that is not aligned to its element, "input" = OFX_IN_RGB8, the refusals of "input_pitch",
+ * a dDst[g] equal to a frame pointer that its own slot reads. */
+int ofx_flow_warp_dev(ofx_ctx *ctx, int n, const void *const *dSrc, const void *const *d_flo, const void *const *d_occ,
+                      const void *const *dFill, void *const *dDst, int nx, int ny, int nz);
+int ofx_flow_interpolate_dev(ofx_ctx *ctx, int n, const void *const *dA, const void *const *dB, const void *const *d_flo_fwd,
+                             const void *const *d_flo_bwd, const double *t, void *const *dDst, int nx, int ny, int nz);
 
 /* Fixed-work inner loop only (src/tvl1flow.cpp:113-182 run exactly n_iter times on linearised
  * data, all arrays host double planes; u/p updated in place).  Returns the last error in *error.

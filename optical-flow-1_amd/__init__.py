@@ -137,7 +137,9 @@ def lib():
                                                                              C.POINTER(Stats)]),
         "ofx_tvl1_bidir_batch_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _i, _d, _d, _d, _i, _d, _i, _d, _d,
                                                                                         _d, C.POINTER(_d)]),
-        "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9 + [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
+        "ofx_flow_warp_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 5 + [_i, _i, _i]),
+        "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
+        "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
         "ofx_hs_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _i, _d, _i, _i]),
         "ofx_hs_pyramidal": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _i, _d, _i, _d, _i, _i]),
         "ofx_brox_spatial": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _d, _i, _d, _d, _i, _i, _i]),
@@ -689,6 +691,25 @@ class Ofx:
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_consistency_dev(self.h, n, arr(d_flo_fwd), arr(d_flo_bwd), arr(d_occ_fwd), arr(d_occ_bwd), nx, ny,
                                                  alpha, beta))
+
+    def flow_warp_dev(self, dSrc, d_flo, dDst, nx, ny, nz=1, d_occ=None, dFill=None):
+        """ofx_flow_warp_dev: lists of device pointers (ints), one entry per slot: dDst[g] receives frame dSrc[g] warped backwards
+        by payload d_flo[g].  d_occ / dFill: None, or one entry per slot (None / 0: no map / no fill frame for that slot); a pixel
+        that leaves the frame or that the map flags takes the fill frame's, or 0.  Frames are read under the options "input" and
+        "input_pitch", the result is dense.  Enqueues on the context's stream."""
+        n = len(dSrc)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_warp_dev(self.h, n, arr(dSrc), arr(d_flo), arr(d_occ), arr(dFill), arr(dDst), nx, ny, nz))
+
+    def flow_interpolate_dev(self, dA, dB, d_flo_fwd, d_flo_bwd, t, dDst, nx, ny, nz=1):
+        """ofx_flow_interpolate_dev: lists of device pointers (ints), one entry per slot: dDst[g] receives the frame at time t[g] in
+        [0, 1] between dA[g] and dB[g], from the payloads of both directions (tvl1_bidir_group_dev's).  Slots may share frames and
+        payloads.  Enqueues on the context's stream."""
+        n = len(dA)
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        ts = (_d * max(n, 1))(*[float(x) for x in t])
+        self._ck(self.L.ofx_flow_interpolate_dev(self.h, n, arr(dA), arr(dB), arr(d_flo_fwd), arr(d_flo_bwd), ts, arr(dDst), nx, ny,
+                                                 nz))
 
     def tvl1_bidir_group_dev(self, dI0, dI1, d_flo_fwd, d_flo_bwd, d_occ_fwd, d_occ_bwd, nx, ny, tau=0.25, lam=0.15, theta=0.3,
                              nscales=5, zfactor=0.5, warps=5, epsilon=0.01, fb_alpha=0.01, fb_beta=0.5):

@@ -342,6 +342,17 @@ int ofx_write_gray_bytes(const char *fname, const float *x, int w, int h)
     return rc;
 }
 
+int ofx_write_bytes_image(const char *fname, const unsigned char *bytes, int w, int h, int c)
+{
+    if (!fname || !bytes || w < 1 || h < 1 || (c != 1 && c != 3)) return 2;
+    FILE *f = fopen(fname, "wb");
+    if (!f) return 1;
+    const size_t n = (size_t) w * h * c;
+    int ok = fprintf(f, "P%d\n%d %d\n255\n", c == 1 ? 5 : 6, w, h) > 0;
+    ok = ok && fwrite(bytes, 1, n, f) == n;
+    return (fclose(f) == 0 && ok) ? 0 : 1;
+}
+
 int ofx_write_flo(const char *fname, const float *uv, int w, int h)
 {
     FILE *f = fopen(fname, "wb");

@@ -29,6 +29,9 @@ int ofx_write_flo(const char *fname, const float *uv, int w, int h);
  * through libpng16 (dlopen'ed), other names -> PGM (P2 up to 10000 pixels, P5 above).  0 ok, 1 I/O error, 2 not
  * representable here (TIFF name, non-byte samples) */
 int ofx_write_gray_bytes(const char *fname, const float *x, int w, int h);
+/* w*h pixels of c interleaved byte channels as binary PGM (c = 1: P5) or PPM (c = 3: P6), maxval 255, whatever the name.
+ * 0 ok, 1 I/O error, 2 not representable (another c, an empty image) */
+int ofx_write_bytes_image(const char *fname, const unsigned char *bytes, int w, int h, int c);
 /* returns a malloc'ed w*h*2 float array or NULL */
 float *ofx_read_flo(const char *fname, int *w, int *h);
 /* 1 if `s` ends with `suffix` */

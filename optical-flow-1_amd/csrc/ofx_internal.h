@@ -88,6 +88,8 @@ struct ofx_ctx {
     double tile_max_px; // ... for levels of at most this many pixels x pairs (0 = default 200 000)
     int gauss_fused;    // pyramids of lockstep groups: row + column pass of the Gaussian in one launch through LDS (1 default)
     int warp_lds;       // 1 (default): TV-L1 warp with the taps staged through LDS; 0: gathered from global memory
+    int apply_lds;      // ofx_flow_warp_dev / ofx_flow_interpolate_dev: 1 the taps staged through LDS, 0 gathered from global memory,
+                        // 2 (default) by measurement: LDS for float and double frames, global for 8- and 16-bit ones
     int chunk;
     int fuse3;          // TV-L1: three iterations per launch (k_tvl1_iter3): 0 never, 1 levels of >= fuse3_min_px pixels x pairs, 2 auto (default)
     double fuse3_min_px;
