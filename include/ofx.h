@@ -828,11 +828,17 @@ int ofx_solver_wrt_chi(ofx_ctx *ctx, const double *u1, const double *u2, double 
 int ofx_tvl1occ_multiscale(ofx_ctx *ctx, const double *I_1, const double *I0, const double *I1, const double *filtI0, double *u1,
                            double *u2, double *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
                            int nscales, double zfactor, int warps, double epsilon, int verbose);
-/* n_triples independent solves (e.g. the frames of a sequence), cut into lockstep groups of up to 16 consecutive triples
- * (option "lockstep" of ctxs[0]; fewer when the device memory -- option "mem_budget", default half of what is free -- does
- * not hold that many): the triples of a group share every kernel launch of a context, group q runs on context q mod n_ctx
- * (one host thread and one stream per context, all on one device).  Every result is bit-identical to the triple solved alone.
- * Arrays of n_triples host pointers.  Returns the first failing status (detail text on that context). */
+/* n_triples independent solves (e.g. the frames of a sequence) in lockstep groups of consecutive triples: the triples of a group
+ * share every kernel launch of a context, group q runs on context q mod n_ctx (one host thread and one stream per context, all on
+ * one device).  The group size and its memory rule are ofx_tvl1occ_triples_dev's below, the ONE rule of every tvl1occ batch entry:
+ * the table is built from the host pointers of the four roles -- equal ADDRESS means one plane, nothing else about the arrays is
+ * compared -- so D, a group's count of distinct planes, is 4 G for arrays that are all different, 3 G where filtI0 is I0, and
+ * G + 2 for the consecutive triples of a sequence passed as the same arrays, each of which is uploaded and built once per group.
+ * Every result is bit-identical to the triple solved alone.  Arrays of n_triples host pointers; host planes are dense doubles
+ * whatever the contexts' "input" and "input_pitch" options say.  Both host entries find everything they reject before any work
+ * (no output plane is written): sizes, nscales, warps, zfactor, theta, lambda, a coarsest level below 2x2, OFX_ERR_SIGMA for a
+ * level too small for its Gaussian, OFX_ERR_NOMEM where one triple does not fit.  Returns the first failing status (detail text
+ * on that context). */
 int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const double *const *I_1, const double *const *I0,
                       const double *const *I1, const double *const *filtI0, double *const *u1, double *const *u2,
                       double *const *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta, int nscales,
@@ -851,8 +857,9 @@ int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const doub
  *   d_occ[t]  n_frames - 2 device pointers: nxx * nyy bytes, 255 where the thresholded chi is 1, else 0 -- the bytes tvl1occflow
  *             writes as its occlusion map.  No alignment needed.
  * What is shared: no normalisation is applied to the images (the reference overwrites it, tvl1occflow.cpp:382-395), so the
- * presmoothed pyramid of a frame and its centred gradients depend on that frame alone.  A group keeps every frame once per level
- * and the three roles a frame plays in consecutive triples (I1, then I0 and filtI0, then I_1) are views into that array; the
+ * presmoothed pyramid of a frame and its centred gradients depend on that frame alone.  A group keeps every frame once per level;
+ * a sequence is the table of triples (t, t + 1, t + 2, filt = -1) of ofx_tvl1occ_triples_dev below, and the roles a frame plays in
+ * consecutive triples (I1, then I0 and filtI0, then I_1) are indices into that array -- the one layout of every tvl1occ entry.  The
  * pyramid, the gradients, the zoom-in of (u1, u2, chi) and the results take one launch per stage for the whole group.
  * ofx_tvl1occ_sequence_group_dev: one lockstep group, n_frames in 3 .. 18.  stats_out: NULL or n_frames - 2 records (level sizes,
  * iters[scale][warp], error, work_pix_iters, total_ms as ofx_tvl1occ_multiscale fills them).  Asynchronous on the context's stream
@@ -861,7 +868,7 @@ int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const doub
  * ofx_tvl1occ_sequence_dev: any n_frames >= 3 on one or several contexts of ONE device and one precision.  The triples are cut
  * into groups of G consecutive triples, group q = frames q G .. q G + cnt + 1 on ctxs[q % n_ctx], a worker thread per context; the
  * two frames neighbouring groups share are built by both.  G = the smallest of: option "lockstep" of ctxs[0] if positive; 16; what
- * the memory rule allows; ceil(triples / n_ctx).  The memory rule is ofx_tvl1occ_batch's for this layout, under option
+ * the memory rule allows; ceil(triples / n_ctx).  The memory rule is ofx_tvl1occ_triples_dev's with D = G + 2, under option
  * "mem_budget" (default: half of the free device memory), divided by n_ctx: a group of G triples takes, in doubles, G + 2 frames
  * and 3 G result planes per pyramid level, 2 (G + 2) + 27 G full-size planes and 13 G hyperplane-major ones, plus 5 %; if one
  * triple does not fit: OFX_ERR_NOMEM.  work_pix_iters: NULL or one double per triple.  Returns when every payload is complete.
@@ -891,8 +898,8 @@ int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, cons
  *   d_flo[k], d_occ[k]  n_triples payloads and maps as above (8-byte aligned | no alignment).
  * What is shared: as above, a plane's presmoothed pyramid and centred gradients depend on that plane alone, whatever role it plays
  * in whichever triple.  A group keeps each distinct referenced plane once per level and the roles of a triple are indices into
- * that array (a by-value table of 4 x 16 bytes, read by the two kernels that read images); every other stage is the sequence
- * entry's.
+ * that array (a by-value table of 4 x 16 bytes, read by the two kernels that read images).  The host entries and the sequence
+ * entries above are tables of this kind in front of the same group solve.
  * ofx_tvl1occ_triples_group_dev: one lockstep group, n_triples in 1 .. 16, hence at most 64 distinct planes: a group never fails
  * for having "too many frames".  stats_out: NULL or n_triples records, filled as the sequence group entry fills them.
  * Asynchronous on the context's stream in the same sense.
@@ -901,8 +908,8 @@ int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, cons
  * a plane that two groups share is built by both, so order the triples so that neighbours share frames (forward and backward
  * triple of one centre next to each other, centres in sequence order).  G = the smallest of: option "lockstep" of ctxs[0] if
  * positive; 16; ceil(n_triples / n_ctx); the largest G for which every group fits the memory rule under option "mem_budget"
- * (default: half of the free device memory) divided by n_ctx.  The memory rule is the sequence entry's with D, the group's own
- * count of distinct planes, in place of G + 2: in doubles, D + 3 G planes per pyramid level, 2 D + 27 G full-size planes and 13 G
+ * (default: half of the free device memory) divided by n_ctx.  The memory rule, the one of every tvl1occ batch entry, with D the
+ * group's own count of distinct planes: in doubles, D + 3 G planes per pyramid level, 2 D + 27 G full-size planes and 13 G
  * hyperplane-major ones, plus 5 %; if one triple does not fit: OFX_ERR_NOMEM.  work_pix_iters: NULL or one double per triple.
  * Returns when every payload is complete.
  * ofx_tvl1occ_triples_frames: the decision both entries build their tables with, pure host code (no context, no device).  Returns

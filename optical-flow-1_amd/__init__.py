@@ -306,7 +306,8 @@ def robust_expo_batch_dev(ctxs, dI1, dI2, d_flo, nx, ny, nz, method=1, alpha=50.
 
 def tvl1occ_batch(ctxs, triples, lam=0.15, alpha=0.01, beta=0.15, theta=0.3, nscales=3, zfactor=0.5, warps=2, epsilon=0.01, out=None):
     """ofx_tvl1occ_batch: triples = list of (I_1, I0, I1) or (I_1, I0, I1, filtI0) host images; lockstep groups of up to 16
-    consecutive triples, group q on ctxs[q % len(ctxs)] (one host thread per context inside the library).  Returns a list of
+    consecutive triples, group q on ctxs[q % len(ctxs)] (one host thread per context inside the library).  Planes are told apart
+    by address: triples that pass the same contiguous float64 array share one plane of their group.  Returns a list of
     (u1, u2, chi); out = such a list from an earlier call: its planes are reused (fresh planes are first touched -- page
     faults -- while the library writes them, which a benchmark loop would otherwise time)."""
     n = len(triples)

@@ -1,4 +1,4 @@
-// ofx_group_plan.h -- how many items (pairs, triples, sequences) a lockstep group of a batch holds, how many bytes a frame spans
+// ofx_group_plan.h -- how many items (pairs, triples, sequences) a lockstep group of a batch holds (by count and by memory), how many bytes a frame spans
 // and which pointers a step of a video chain gets.  Pure functions on ints and pointer tables and nothing but the standard
 // library, so a plain host compiler builds them (tests/group_plan_driver.cpp and tests/pair_plan_driver.cpp print them over grids).
 #pragma once
@@ -26,6 +26,24 @@ static inline int ofx_plan_even_rounds(int n_items, int n_ctx, int cap)
 static inline int ofx_plan_cap_per_ctx(int G, int n_items, int n_ctx)
 {
     return std::min(G, (n_items + n_ctx - 1) / n_ctx);
+}
+
+// Groups whose memory depends on what they hold: the largest G' <= G for which every group of a batch of n_items cut into groups
+// of G' consecutive items (the last one shorter) fits the budget, 0 if not even groups of one do.  distinct(first, cnt) = what a
+// group's memory depends on besides its count (TV-L1 with occlusions: its number of distinct planes), bytes(cnt, distinct) = that
+// memory.  *need = the largest group's bytes at the returned G' (at G' = 1 where 0 is returned).
+template <class DistinctFn, class BytesFn>
+static inline int ofx_plan_fit_groups(int G, int n_items, double budget, DistinctFn distinct, BytesFn bytes, double *need)
+{
+    for (*need = 0.0; G >= 1; G--) {
+        *need = 0.0;
+        for (int first = 0; first < n_items; first += G) {
+            const int cnt = std::min(G, n_items - first);
+            *need = std::max(*need, (double) bytes(cnt, distinct(first, cnt)));
+        }
+        if (*need <= budget) break;
+    }
+    return std::max(G, 0);
 }
 
 // A frame's bytes as they lie: ny rows of nx elements of elem_bytes bytes, `pitch` bytes from one row's start to the next's --

@@ -9,6 +9,9 @@
 #include "ofx_device.h"
 #include "ofx_batch.h"
 
+#include <functional>
+#include <unordered_map>
+
 #define OCC_IS_ZERO 1E-10      // src/tvl1occflow_constants.h:31
 #define OCC_THR_CHI 0.75       // src/tvl1occflow_constants.h:32
 #define OFX_MEDIAN_MAX_W 9     // largest window side of ofx_me_median_filtering
@@ -1153,14 +1156,16 @@ extern "C" int ofx_solver_wrt_u(ofx_ctx *ctx, double *u1, double *u2, const doub
 }
 
 // ==== TV-L1 with occlusions, the whole solve (src/tvl1occflow.cpp:144-329 single scale, :337-481 multiscale) ===================
-// Device-resident from the four uploaded images to the three downloaded planes.  The reference keeps the dual planes of
+// Device-resident from the planes a source brings in to the results a sink takes away.  The reference keeps the dual planes of
 // Solver_wrt_u and the dual variable of Solver_wrt_chi in function-local statics that it re-creates -- with operator
 // new[], uninitialised -- whenever the image width changes, i.e. once per pyramid level; its results are therefore only
 // defined on a heap that hands out zeros.  That is the semantics implemented here (state zeroed per level) and pinned by
 // the oracle against the reference built with a zero-filling operator new[] (oracle/ref_shim.cpp).
-// G independent triples are solved in lockstep (every array is [G][plane], every launch of the outer iteration serves all
-// triples that are still iterating, blockIdx.z = triple): one solve is a latency chain of ROF sweeps that keeps ny / 125
-// workgroups busy, so G of them cost hardly more time than one.
+// G independent triples are solved in lockstep (every array of the iteration is [G][plane], every launch of the outer iteration
+// serves all triples that are still iterating, blockIdx.z = triple): one solve is a latency chain of ROF sweeps that keeps
+// ny / 125 workgroups busy, so G of them cost hardly more time than one.  The images are kept once per DISTINCT plane of the
+// group, [D][plane], and a triple's four roles are indices into them (OccIdx): every entry -- host triples, a device-resident
+// sequence, indexed triples of a device-resident table -- is a table of triples in front of the one group solve below.
 #define OCC_EXT_MAX_ITERATIONS 20  // src/tvl1occflow_constants.h:35
 #define OCC_MAX_ITERATIONS_CHI 100 // :37
 #define OCC_MAX_ITERATIONS_U 10    // :36
@@ -1177,16 +1182,10 @@ OFX_DEV double occ_g_px(double ix, double iy)
     const double gggrad = sqrt(ix * ix + iy * iy);
     return 1. / (1. + OCC_G_FACTOR * gggrad);
 }
-__global__ void k_occ_g(const double *__restrict__ Ix, const double *__restrict__ Iy, double *__restrict__ g, size_t size)
-{
-    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= size) return;
-    g[i] = occ_g_px(Ix[i], Iy[i]);
-}
 
-// Role table of a group of indexed triples (ofx_tvl1occ_triples_group_dev): the level keeps D distinct planes once, [D][n], and
-// role r of triple g = blockIdx.z is plane idx.r[g] of them.  Passed by value; the index is uniform over a workgroup, so the
-// plane's base is scalar arithmetic on kernel arguments and the loads stay base + lane offset as in the kernels above.
+// Role table of a lockstep group (occ_triples_group): the level keeps the group's D distinct planes once, [D][n], and role r of
+// triple g = blockIdx.z is plane idx.r[g] of them.  Passed by value; the index is uniform over a workgroup, so the plane's base
+// is scalar arithmetic on kernel arguments and the loads stay base + lane offset as in the kernels above.
 struct alignas(4) OccIdx {
     unsigned char prev[OCC_MAX_GROUP], cur[OCC_MAX_GROUP], next[OCC_MAX_GROUP], filt[OCC_MAX_GROUP];
 };
@@ -1199,8 +1198,8 @@ OFX_DEV size_t occ_plane(const unsigned char (&role)[OCC_MAX_GROUP], size_t n)
     __builtin_memcpy(&w, static_cast<const unsigned char *>(__builtin_assume_aligned(role, 4)) + (z & ~3u), sizeof w);
     return (size_t) ((w >> (8 * (z & 3u))) & 0xffu) * n;
 }
-// k_occ_g with Ix, Iy = gx, gy [D][n] at the plane of role filt; g is [G][n], blockIdx.z = triple
-__global__ void k_occ_g_idx(const double *__restrict__ gx, const double *__restrict__ gy, double *__restrict__ g, int n, OccIdx idx)
+// Ix, Iy = gx, gy [D][n] at the plane of role filt; g is [G][n], blockIdx.z = triple
+__global__ void k_occ_g(const double *__restrict__ gx, const double *__restrict__ gy, double *__restrict__ g, int n, OccIdx idx)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1211,6 +1210,8 @@ __global__ void k_occ_g_idx(const double *__restrict__ gx, const double *__restr
 // the six warps of one warping step and what is derived from them (:214-248), one thread per pixel: I1, I1x, I1y sampled at
 // x + u, I_1, I_1x, I_1y at x - u (border_out = false), grad = |warped gradient|^2, rho_c = the constant part of the
 // linearised residual.  The warped intensities themselves are not used again and stay in registers.
+// I0 = I1 = I_1 = the level's planes [D][n], I1x = I_1x and I1y = I_1y their centred gradients: one pointer per use, as the
+// reference names them -- with three pointers in their place k_occ_prepare compiles to 70 VGPRs instead of 64 (a wave less per SIMD)
 struct OccPrep {
     const double *I0, *I1, *I1x, *I1y, *I_1, *I_1x, *I_1y, *u1, *u2;
     double *I1wx, *I1wy, *I_1wx, *I_1wy, *grad1, *grad3, *rho1_c, *rho3_c;
@@ -1225,7 +1226,7 @@ OFX_DEV double occ_sample(const double *__restrict__ in, const BicubicTaps &t, i
     return cubic_cell(c[0], c[1], c[2], c[3], t.fx);
 }
 // pixel (j, i) of the triple whose planes (u1 .. rho3_c) start at element o; its images start at elements oc (I0), of (I1 and its
-// gradients) and ob (I_1 and its gradients) of a's image arrays
+// gradients) and ob (I_1 and its gradients) of the level's planes
 OFX_DEV void occ_prepare_px(const OccPrep &a, size_t oc, size_t of, size_t ob, size_t o, int j, int i, int nx, int ny)
 {
     const size_t p = o + (size_t) i * nx + j;
@@ -1247,16 +1248,8 @@ OFX_DEV void occ_prepare_px(const OccPrep &a, size_t oc, size_t of, size_t ob, s
         a.rho3_c[p] = (w + wx * u1 + wy * u2 - i0);
     }
 }
-__global__ void k_occ_prepare(OccPrep a, int nx, int ny, OccGrp G)
-{
-    const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
-    size_t o;
-    if (j >= nx || i >= ny || !occ_grp(G, o)) return;
-    occ_prepare_px(a, o, o, o, o, j, i, nx, ny);
-}
-// ... of indexed triples: a.I0 = a.I1 = a.I_1 = the level's planes [D][n], a.I1x = a.I_1x and a.I1y = a.I_1y their gradients; the
-// triple's images are the planes of its roles
-__global__ void k_occ_prepare_idx(OccPrep a, OccIdx idx, int nx, int ny, OccGrp G)
+// the triple's images are the planes of its roles
+__global__ void k_occ_prepare(OccPrep a, OccIdx idx, int nx, int ny, OccGrp G)
 {
     const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
     size_t o;
@@ -1342,14 +1335,6 @@ __global__ __launch_bounds__(256) void k_occ_err_final(const double *__restrict_
     }
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
-__global__ void k_occ_scale2(double *__restrict__ a, double *__restrict__ b, size_t n, double s)
-{
-    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        a[i] *= s;
-        b[i] *= s;
-    }
-}
 __global__ void k_occ_threshold(double *__restrict__ chi, size_t n)
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -1380,18 +1365,11 @@ struct OccWork {
     }
 };
 
-// centred gradients of the level's images, [G][nx ny] like the images: the caller computes them (a group of host triples plane by
-// plane, a sequence once per frame).  filtx / filty are only read before the level's first iteration: they may be W.t1 / W.t2.
-struct OccGrad {
-    const double *filtx, *filty, *I1x, *I1y, *I_1x, *I_1y;
-};
-
-// one level of G triples, arrays [G][nx ny] on the device, u1 / u2 / chi in place; the level's dual state is zeroed here.
-// stats[g]: the record of triple g.  idx != nullptr: indexed triples -- I_1 = I0 = I1 = the level's planes [D][nx ny], D.I1x = D.I_1x
-// = D.filtx and D.I1y = D.I_1y = D.filty their gradients, and the two kernels that read images take the planes of the roles.
-int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I0, const double *I1, const OccGrad &D, double *u1,
-                         double *u2, double *chi, int nx, int ny, const OccParams &P, const OccWork &W, int scale, ofx_stats *stats,
-                         const OccIdx *idx = nullptr)
+// one level of G triples on the device: im = the level's D distinct planes [D][nx ny], gx / gy their centred gradients (the
+// caller computes them, once per plane), idx the roles -- read by the two kernels that read images; u1 / u2 / chi [G][nx ny] in
+// place; the level's dual state is zeroed here.  stats[g]: the record of triple g.
+int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *im, const double *gx, const double *gy, const OccIdx &idx, double *u1,
+                         double *u2, double *chi, int nx, int ny, const OccParams &P, const OccWork &W, int scale, ofx_stats *stats)
 {
     const size_t n = (size_t) nx * ny;
     const dim3 grid(ofx_cdiv(nx, 64), ofx_cdiv(ny, 4), G), block(64, 4);
@@ -1402,11 +1380,10 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     OFX_HIP(ctx, hipMemsetAsync(W.state, 0, 4 * nsk * G * sizeof(double), st));
     OFX_HIP(ctx, hipMemsetAsync(W.eta, 0, 2 * n * G * sizeof(double), st));
     double *eta1 = W.eta, *eta2 = W.eta + n * G;
-    if (idx) hipLaunchKernelGGL(k_occ_g_idx, g1, dim3(256), 0, st, D.filtx, D.filty, W.g, (int) n, *idx);
-    else hipLaunchKernelGGL(k_occ_g, dim3(occ_grid1d(n * G)), dim3(256), 0, st, D.filtx, D.filty, W.g, n * G);
+    hipLaunchKernelGGL(k_occ_g, g1, dim3(256), 0, st, gx, gy, W.g, (int) n, idx);
     OFX_HIP(ctx, hipMemcpyAsync(W.u1p, u1, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
     OFX_HIP(ctx, hipMemcpyAsync(W.u2p, u2, n * G * sizeof(double), hipMemcpyDeviceToDevice, st));
-    const OccPrep prep = {I0, I1, D.I1x, D.I1y, I_1, D.I_1x, D.I_1y, u1, u2, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.grad1, W.grad3,
+    const OccPrep prep = {im, im, gx, gy, im, gx, gy, u1, u2, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.grad1, W.grad3,
                           W.rho1_c, W.rho3_c};
     const OccV av = {u1, u2, chi, W.I1wx, W.I1wy, W.I_1wx, W.I_1wy, W.rho1_c, W.rho3_c, W.grad1, W.grad3,
                      W.v1, W.v2, W.vf1, W.vf2, W.vb1, W.vb2};
@@ -1418,8 +1395,7 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     double *h_err = ctx->h_aux;                                      // pinned, OFX_MAX_GROUP doubles, not the poll ring
     double *d_err = W.part + (size_t) OCC_ERR_BLOCKS * G;
     for (int w = 0; w < P.warps; w++) {
-        if (idx) hipLaunchKernelGGL(k_occ_prepare_idx, grid, block, 0, st, prep, *idx, nx, ny, OccGrp{n, all});
-        else hipLaunchKernelGGL(k_occ_prepare, grid, block, 0, st, prep, nx, ny, OccGrp{n, all});
+        hipLaunchKernelGGL(k_occ_prepare, grid, block, 0, st, prep, idx, nx, ny, OccGrp{n, all});
         OFX_LAUNCH_CHECK(ctx);
         int it[OCC_MAX_GROUP];
         double error[OCC_MAX_GROUP];
@@ -1464,175 +1440,12 @@ int occ_single_scale_dev(ofx_ctx *ctx, int G, const double *I_1, const double *I
     return OFX_OK;
 }
 
-// G triples (host planes) on one context
-int occ_group_impl(ofx_ctx *ctx, int G, const double *const *I_1, const double *const *I0, const double *const *I1,
-                   const double *const *filtI0, double *const *u1, double *const *u2, double *const *chi, int nxx, int nyy,
-                   const OccParams &P, int nscales, double zfactor, ofx_stats *stats);
-// An error return must not leave kernels or copies into the caller's planes in flight (the next call resets the arena they
-// work in): drain the stream first, as ofx_run_loop_group does for the iteration loops.
-int occ_group(ofx_ctx *ctx, int G, const double *const *I_1, const double *const *I0, const double *const *I1,
-              const double *const *filtI0, double *const *u1, double *const *u2, double *const *chi, int nxx, int nyy,
-              const OccParams &P, int nscales, double zfactor, ofx_stats *stats)
-{
-    const int s = occ_group_impl(ctx, G, I_1, I0, I1, filtI0, u1, u2, chi, nxx, nyy, P, nscales, zfactor, stats);
-    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);
-    return s;
-}
-int occ_group_impl(ofx_ctx *ctx, int G, const double *const *I_1, const double *const *I0, const double *const *I1,
-                   const double *const *filtI0, double *const *u1, double *const *u2, double *const *chi, int nxx, int nyy,
-                   const OccParams &P, int nscales, double zfactor, ofx_stats *stats)
-{
-    const double t0 = ofx_now_ms();
-    std::vector<int> nxs, nys;
-    OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    if (nxs[nscales - 1] < 2 || nys[nscales - 1] < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: coarsest level %dx%d", nxs[nscales - 1], nys[nscales - 1]);
-    for (int g = 0; g < G; g++) {
-        ofx_stats &S = stats[g];
-        S = ofx_stats{};
-        S.nscales = nscales;
-        S.nsolves = P.warps;
-        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { S.nx[s] = nxs[s]; S.ny[s] = nys[s]; }
-    }
-    const size_t size = (size_t) nxx * nyy;
-    double *gr[4];                                          // centred gradients of I1 and I_1, a level uses them as [G][n_s]
-    for (int k = 0; k < 4; k++) OFX_TRY(ofx_alloc(ctx, size * G, &gr[k]));
-    OccWork W;
-    OFX_TRY(W.alloc(ctx, size, rof_skew_elems(nxx, nyy), G));
-    struct Lv { double *im[4], *u1, *u2, *chi; };           // im: I_1, I0, I1, filtI0; every array [G][n_s]
-    std::vector<Lv> lv(nscales);
-    for (int s = 0; s < nscales; s++) {
-        const size_t n = (size_t) nxs[s] * nys[s] * G;
-        for (int k = 0; k < 4; k++) OFX_TRY(ofx_alloc(ctx, n, &lv[s].im[k]));
-        OFX_TRY(ofx_alloc(ctx, n, &lv[s].u1));
-        OFX_TRY(ofx_alloc(ctx, n, &lv[s].u2));
-        OFX_TRY(ofx_alloc(ctx, n, &lv[s].chi));
-    }
-    hipStream_t st = ctx->stream;
-    // :382-395 call image_normalization_4 and then overwrite its output with the raw images: no normalisation
-    const double *const *host[4] = {I_1, I0, I1, filtI0};
-    for (int g = 0; g < G; g++)
-        for (int k = 0; k < 4; k++) {
-            OFX_HIP(ctx, hipMemcpyAsync(lv[0].im[k] + g * size, host[k][g], size * sizeof(double), hipMemcpyHostToDevice, st));
-            OFX_TRY(op_gaussian_planes<double>(ctx, 1, 1, lv[0].im[k] + g * size, nullptr, size, W.t1, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
-        }
-    for (int s = 1; s < nscales; s++) {
-        const size_t np = (size_t) nxs[s - 1] * nys[s - 1], n = (size_t) nxs[s] * nys[s];
-        for (int g = 0; g < G; g++)
-            for (int k = 0; k < 4; k++)
-                OFX_TRY(op_zoom_out_channels_planes<double>(ctx, 1, 1, lv[s - 1].im[k] + g * np, nullptr, lv[s].im[k] + g * n, nullptr, W.t1,
-                                                            W.t2, nxs[s - 1], nys[s - 1], 1, zfactor));
-    }
-    {
-        const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1] * G;
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u1, 0, n * sizeof(double), st));
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u2, 0, n * sizeof(double), st));
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].chi, 0, n * sizeof(double), st));
-    }
-    for (int s = nscales - 1; s >= 0; s--) {
-        if (P.verbose && G == 1) fprintf(stderr, "Scale %d: %dx%d\n", s, nxs[s], nys[s]);
-        for (int g = 0; g < G; g++) {                       // once per level: plane by plane
-            const size_t o = (size_t) g * nxs[s] * nys[s];
-            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[3] + o, W.t1 + o, W.t2 + o, nxs[s], nys[s]));
-            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[2] + o, gr[0] + o, gr[1] + o, nxs[s], nys[s]));
-            OFX_TRY(op_centered_gradient<double>(ctx, lv[s].im[0] + o, gr[2] + o, gr[3] + o, nxs[s], nys[s]));
-        }
-        OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].im[0], lv[s].im[1], lv[s].im[2], OccGrad{W.t1, W.t2, gr[0], gr[1], gr[2], gr[3]},
-                                     lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P, W, s, stats));
-        if (s) {
-            const double fx = (double) nxs[s - 1] / nxs[s], fy = (double) nys[s - 1] / nys[s];
-            const size_t n = (size_t) nxs[s - 1] * nys[s - 1], nc = (size_t) nxs[s] * nys[s];
-            for (int g = 0; g < G; g++) {
-                OFX_TRY(op_resample<double>(ctx, lv[s].u1 + g * nc, lv[s - 1].u1 + g * n, nxs[s], nys[s], nxs[s - 1], nys[s - 1], fx, fy));
-                OFX_TRY(op_resample<double>(ctx, lv[s].u2 + g * nc, lv[s - 1].u2 + g * n, nxs[s], nys[s], nxs[s - 1], nys[s - 1], fx, fy));
-                OFX_TRY(op_resample<double>(ctx, lv[s].chi + g * nc, lv[s - 1].chi + g * n, nxs[s], nys[s], nxs[s - 1], nys[s - 1], fx, fy));
-            }
-            hipLaunchKernelGGL(k_occ_scale2, dim3(occ_grid1d(n * G)), dim3(256), 0, st, lv[s - 1].u1, lv[s - 1].u2, n * G, (double) 1.0 / zfactor);
-        } else {
-            hipLaunchKernelGGL(k_occ_threshold, dim3(occ_grid1d(size * G)), dim3(256), 0, st, lv[0].chi, size * G);
-        }
-        OFX_LAUNCH_CHECK(ctx);
-    }
-    Dev d{ctx};
-    for (int g = 0; g < G; g++) {
-        OFX_TRY(d.out(lv[0].u1 + g * size, u1[g], size));
-        OFX_TRY(d.out(lv[0].u2 + g * size, u2[g], size));
-        OFX_TRY(d.out(lv[0].chi + g * size, chi[g], size));
-    }
-    OFX_TRY(d.sync());
-    const double ms = ofx_now_ms() - t0;
-    for (int g = 0; g < G; g++) stats[g].total_ms = ms;
-    return OFX_OK;
-}
-
-int occ_check_args(ofx_ctx *ctx, int nxx, int nyy, double lambda, double theta, int nscales, double zfactor, int warps)
-{
-    if (nxx < 2 || nyy < 2 || (long long) nxx * nyy > 0x3fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: bad size %dx%d", nxx, nyy);
-    if (nscales < 1 || warps < 1 || warps > OFX_MAX_SOLVES) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: nscales=%d warps=%d", nscales, warps);
-    if (!(zfactor > 0.0 && zfactor < 1.0)) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: zfactor=%g", zfactor);
-    if (!(theta > 0.0) || !(lambda > 0.0)) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: theta=%g lambda=%g", theta, lambda);
-    return OFX_OK;
-}
-
 }   // namespace
 
-extern "C" int ofx_tvl1occ_multiscale(ofx_ctx *ctx, const double *I_1, const double *I0, const double *I1, const double *filtI0,
-                                      double *u1, double *u2, double *chi, int nxx, int nyy, double lambda, double alpha,
-                                      double beta, double theta, int nscales, double zfactor, int warps, double epsilon,
-                                      int verbose)
-{
-    OFX_ENTER(ctx);
-    if (!I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: NULL pointer");
-    OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, verbose};
-    return occ_group(ctx, 1, &I_1, &I0, &I1, &filtI0, &u1, &u2, &chi, nxx, nyy, P, nscales, zfactor, &ctx->stats);
-}
-
-// Several independent triples (e.g. the frames of a sequence): cut into lockstep groups of up to 16 consecutive triples (fewer
-// when the device memory the contexts may use -- option "mem_budget" -- does not hold that many), group q on context
-// q mod n_ctx, one host thread per context; all contexts on one device.
-extern "C" int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const double *const *I_1, const double *const *I0,
-                                 const double *const *I1, const double *const *filtI0, double *const *u1, double *const *u2,
-                                 double *const *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
-                                 int nscales, double zfactor, int warps, double epsilon)
-{
-    if (n_triples < 0 || !I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return OFX_ERR_ARG;
-    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE));
-    if (n_triples == 0) return OFX_OK;
-    // group size: option "lockstep" of ctxs[0], else as many as fit.  Per triple: 7 planes per pyramid level (occ_group: 4 images,
-    // u1, u2, chi) + 31 full-size row-major (OccWork's 27, 4 of gradients) and 13 hyperplane-major planes + 2 of Gaussian / zoom scratch
-    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
-    {
-        ofx_ctx *ctx = ctxs[0];
-        OFX_ENTER(ctx);
-        OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-        double budget;
-        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
-        std::vector<int> nxs, nys;
-        OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-        double level_px = 0.0;
-        for (int s = 0; s < nscales; s++) level_px += (double) nxs[s] * nys[s];
-        const double per = 8.0 * (7.0 * level_px + 33.0 * nxx * nyy + 13.0 * (double) rof_skew_elems(nxx, nyy)) * 1.05;
-        const int fit = (int) (budget / per);
-        if (fit < 1) return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ batch: %.1f GB per triple, %.1f GB per context available", per / 1e9, budget / 1e9);
-        if (G > fit) G = fit;
-    }
-    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
-    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
-    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, nullptr, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
-        OFX_ENTER(ctx);
-        const int s = occ_group(ctx, cnt, I_1 + first, I0 + first, I1 + first, filtI0 + first, u1 + first, u2 + first, chi + first, nxx, nyy,
-                                P, nscales, zfactor, st);
-        ctx->stats = st[0];
-        return s;
-    });
-}
-
-// ==== the same solve over a device-resident sequence (ofx_tvl1occ_sequence_group_dev / _dev) =====================================
-// Triple t of F frames is (F[t], F[t + 1], F[t + 2]) with filtI0 = F[t + 1].  No normalisation is applied (above), so the
-// presmoothed pyramid of a frame and its centred gradients depend on that frame alone: a level keeps the G + 2 frames of a
-// group of G consecutive triples ONCE, [G + 2][n_s], and their gradients likewise; the arrays of the triples are views at an
-// offset -- I_1 = base, I0 = filtI0 = base + n_s, I1 = base + 2 n_s, each again [G][n_s] with stride n_s, which is how the
-// iteration kernels address a group.  Every stage outside the level solver is one launch for all frames / triples.
+// ==== where a group's planes come from and where its results go =====================================================================
+// The planes are the caller's table: device-resident planes in the context's "input" kind, storage type and row pitch (the *_dev
+// entries), or dense host doubles (ofx_tvl1occ_multiscale / _batch).  The results are .flo payloads and byte maps on the device, or
+// host planes of doubles.
 struct OccSeqIn {
     const void *f[OCC_MAX_GROUP + 2];
 };
@@ -1640,7 +1453,7 @@ struct OccSeqOut {
     float2 *flo[OCC_MAX_GROUP];
     unsigned char *occ[OCC_MAX_GROUP];
 };
-// the caller's frames, in their storage type, into the finest level (exact: float -> double); blockIdx.z = frame.  Frames of
+// the caller's planes, in their storage type, into the finest level (exact: float -> double); blockIdx.z = plane.  Planes of
 // the byte kinds (context option "input") go through op_convert_sources_in instead.
 template <typename TIN> __global__ void k_occ_seq_in(OccSeqIn in, double *__restrict__ dst, int n)
 {
@@ -1648,7 +1461,7 @@ template <typename TIN> __global__ void k_occ_seq_in(OccSeqIn in, double *__rest
     if (i >= n) return;
     dst[(size_t) blockIdx.z * n + i] = ldw(static_cast<const TIN *>(in.f[blockIdx.z]) + i);
 }
-// ... from frames whose rows are R.pitch bytes apart (context option "input_pitch"): a thread keeps its column over four rows of
+// ... from planes whose rows are R.pitch bytes apart (context option "input_pitch"): a thread keeps its column over four rows of
 // its tile (rows_tile, ofx_device.h)
 template <typename TIN> __global__ __launch_bounds__(256) void k_occ_seq_in_p(OccSeqIn in, double *__restrict__ dst, OfxRows R)
 {
@@ -1695,12 +1508,97 @@ __global__ __launch_bounds__(256) void k_occ_seq_out(const double *__restrict__ 
 
 namespace {
 
-// what must hold before any work: the pyramid's sizes, its coarsest level, room for both Gaussians on the levels they
-// smooth (op_gaussian_planes' rule, which the host entries meet while they build the pyramid), and the frames' row pitch
-int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zfactor, std::vector<int> &nxs, std::vector<int> &nys)
+// source(ctx, D, frames, dst): planes frames[0 .. D) of the caller's table into dst [D][nxx nyy], on the context's stream
+using OccSource = std::function<int(ofx_ctx *, int, const int *, double *)>;
+// sink(ctx, first, G, u1, u2, chi): the finest level's results [G][nxx nyy] to triples first .. first + G - 1 of the caller's arrays
+using OccSink = std::function<int(ofx_ctx *, int, int, const double *, const double *, double *)>;
+
+template <typename TIN> void occ_seq_in_launch(hipStream_t st, const OccSeqIn &in, int cnt, double *dst, int nxx, int nyy, size_t pitch)
 {
+    if (pitch) {
+        const OfxRows R = op_rows_geom(nxx, nyy, pitch, false);
+        hipLaunchKernelGGL(k_occ_seq_in_p<TIN>, dim3(R.tiles, 1, cnt), dim3(256), 0, st, in, dst, R);
+    } else {
+        hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d((size_t) nxx * nyy), 1, cnt), dim3(256), 0, st, in, dst, nxx * nyy);
+    }
+}
+// device-resident planes: the context's "input" kind, "input_pitch" and storage type say how they lie
+OccSource occ_source_dev(const void *const *dF, int nxx, int nyy)
+{
+    return [=](ofx_ctx *ctx, int D, const int *frames, double *dst) -> int {
+        const int kind = ofx_src_kind(ctx);
+        const size_t size = (size_t) nxx * nyy, pitch = ofx_src_pitch(ctx, nxx);
+        for (int k0 = 0; k0 < D; k0 += OCC_MAX_GROUP + 2) {    // OccSeqIn holds 18 pointers: a sequence's frames are one launch, 64 planes four
+            const int cnt = D - k0 < OCC_MAX_GROUP + 2 ? D - k0 : OCC_MAX_GROUP + 2;
+            if (kind != OFX_SRC_F64 && kind != OFX_SRC_F32) {  // a byte kind
+                OfxSrcPtrs src = {};
+                OfxDstPtrs to = {};
+                for (int k = 0; k < cnt; k++) { src.p[k] = dF[frames[k0 + k]]; to.p[k] = dst + (k0 + k) * size; }
+                OFX_TRY(op_convert_sources_in<double>(ctx, kind, src, to, cnt, nxx, nyy, pitch));
+                continue;
+            }
+            OccSeqIn in = {};
+            for (int k = 0; k < cnt; k++) in.f[k] = dF[frames[k0 + k]];
+            if (kind == OFX_SRC_F64) occ_seq_in_launch<double>(ctx->stream, in, cnt, dst + k0 * size, nxx, nyy, pitch);
+            else occ_seq_in_launch<float>(ctx->stream, in, cnt, dst + k0 * size, nxx, nyy, pitch);
+        }
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    };
+}
+// host planes: dense doubles whatever the context's "input" and "input_pitch" say; each distinct plane straight into its slot
+OccSource occ_source_host(const double *const *planes, size_t size)
+{
+    return [=](ofx_ctx *ctx, int D, const int *frames, double *dst) -> int {
+        for (int d = 0; d < D; d++)
+            OFX_HIP(ctx, hipMemcpyAsync(dst + d * size, planes[frames[d]], size * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return OFX_OK;
+    };
+}
+// payloads and maps on the device; asynchronous on the context's stream
+OccSink occ_sink_dev(void *const *d_flo, void *const *d_occ, int nxx, int nyy)
+{
+    return [=](ofx_ctx *ctx, int first, int G, const double *u1, const double *u2, double *chi) -> int {
+        const int size = nxx * nyy;
+        OccSeqOut out = {};
+        for (int g = 0; g < G; g++) {
+            out.flo[g] = static_cast<float2 *>(d_flo[first + g]);
+            out.occ[g] = static_cast<unsigned char *>(d_occ[first + g]);
+        }
+        hipLaunchKernelGGL(k_occ_seq_out, dim3(ofx_cdiv(ofx_cdiv(size + 3, 4), 256), 1, G), dim3(256), 0, ctx->stream, u1, u2,
+                           (const double *) chi, out, size);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    };
+}
+// host planes of doubles, chi thresholded to {0, 1} as the reference does; complete on return
+OccSink occ_sink_host(double *const *h_u1, double *const *h_u2, double *const *h_chi, size_t size)
+{
+    return [=](ofx_ctx *ctx, int first, int G, const double *u1, const double *u2, double *chi) -> int {
+        hipLaunchKernelGGL(k_occ_threshold, dim3(occ_grid1d(size * G)), dim3(256), 0, ctx->stream, chi, size * G);
+        OFX_LAUNCH_CHECK(ctx);
+        Dev d{ctx};
+        for (int g = 0; g < G; g++) {
+            OFX_TRY(d.out(u1 + g * size, h_u1[first + g], size));
+            OFX_TRY(d.out(u2 + g * size, h_u2[first + g], size));
+            OFX_TRY(d.out(chi + g * size, h_chi[first + g], size));
+        }
+        return d.sync();
+    };
+}
+
+// What every entry checks before any work, after its own pointer tables: the arguments, the pyramid's sizes, the row pitch of
+// device-resident planes (dev_planes; host planes are dense whatever the context's options say), the coarsest level, and room
+// for both Gaussians on the levels they smooth (op_gaussian_planes' rule).
+int occ_check(ofx_ctx *ctx, bool dev_planes, int nxx, int nyy, const OccParams &P, int nscales, double zfactor, std::vector<int> &nxs,
+              std::vector<int> &nys)
+{
+    if (nxx < 2 || nyy < 2 || (long long) nxx * nyy > 0x3fffffffLL) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: bad size %dx%d", nxx, nyy);
+    if (nscales < 1 || P.warps < 1 || P.warps > OFX_MAX_SOLVES) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: nscales=%d warps=%d", nscales, P.warps);
+    if (!(zfactor > 0.0 && zfactor < 1.0)) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: zfactor=%g", zfactor);
+    if (!(P.theta > 0.0) || !(P.lambda > 0.0)) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: theta=%g lambda=%g", P.theta, P.lambda);
     OFX_TRY(op_pyramid_sizes(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    OFX_TRY(ofx_pitch_check(ctx, "tvl1occ", nxx));
+    if (dev_planes) OFX_TRY(ofx_pitch_check(ctx, "tvl1occ", nxx));
     if (nxs[nscales - 1] < 2 || nys[nscales - 1] < 2) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: coarsest level %dx%d", nxs[nscales - 1], nys[nscales - 1]);
     for (int s = 0; s < nscales; s++) {
         const double sigma = s ? 0.6 * sqrt(1.0 / (zfactor * zfactor) - 1.0) : OCC_PRESMOOTHING_SIGMA;     // smooths level s - 1 | 0
@@ -1712,6 +1610,132 @@ int occ_seq_pyramid_check(ofx_ctx *ctx, int nxx, int nyy, int nscales, double zf
             return ofx_fail(ctx, OFX_ERR_SIGMA, "GaussianSmooth: sigma too large (radius %d, image %dx%d)", taps.size, nx, ny);
     }
     return OFX_OK;
+}
+
+// ==== the group solve ================================================================================================================
+// G <= OCC_MAX_GROUP triples tr of a table of n_planes planes in lockstep on one context; everything checked by the caller
+// (occ_check gave nxs, nys).  No normalisation is applied (:382-395 call image_normalization_4 and then overwrite its output with
+// the raw images), so a plane's presmoothed pyramid and centred gradients depend on that plane alone, whatever role it plays in
+// whichever triple: a level keeps the group's D distinct planes once, [D][n_s], and their gradients likewise; (u1, u2, chi) are
+// [G][n_s].  Every stage outside the level solver is one launch for all planes / triples.  `first`: where the group's triples
+// stand in the caller's arrays (the sink's).  stats_out: NULL or G records; the shell is ofx_group_records'.
+int occ_triples_group(ofx_ctx *ctx, int n_planes, int G, const ofx_occ_triple *tr, int first, const OccSource &source, const OccSink &sink,
+                      const OccParams &P, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys, ofx_stats *stats_out)
+{
+    int frames[4 * OCC_MAX_GROUP];
+    unsigned char roles[OCC_MAX_GROUP][4];
+    const int D = ofx_tvl1occ_triples_frames(n_planes, G, tr, frames, &roles[0][0]);
+    if (D < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: bad index table");
+    OccIdx idx = {};
+    for (int g = 0; g < G; g++) {
+        idx.prev[g] = roles[g][0];
+        idx.cur[g] = roles[g][1];
+        idx.next[g] = roles[g][2];
+        idx.filt[g] = roles[g][3];
+    }
+    return ofx_group_records(ctx, G, stats_out, [&](ofx_stats *stats) -> int {
+        const int nscales = (int) nxs.size(), nxx = nxs[0], nyy = nys[0];
+        for (int g = 0; g < G; g++) {
+            ofx_stats &S = stats[g];
+            S = ofx_stats{};
+            S.nscales = nscales;
+            S.nsolves = P.warps;
+            for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { S.nx[s] = nxs[s]; S.ny[s] = nys[s]; }
+        }
+        const size_t size = (size_t) nxx * nyy;
+        OccWork W;
+        OFX_TRY(W.alloc(ctx, size, rof_skew_elems(nxx, nyy), G));
+        double *gx, *gy;                                        // centred gradients of the level's planes, [D][n_s]; before the first
+        OFX_TRY(ofx_alloc(ctx, size * D, &gx));                 // level is solved: the scratch of the Gaussian and the zoom-out
+        OFX_TRY(ofx_alloc(ctx, size * D, &gy));
+        struct Lv { double *fr, *u1, *u2, *chi; };              // fr: [D][n_s], the others [G][n_s]
+        std::vector<Lv> lv(nscales);
+        for (int s = 0; s < nscales; s++) {
+            const size_t n = (size_t) nxs[s] * nys[s];
+            OFX_TRY(ofx_alloc(ctx, n * D, &lv[s].fr));
+            OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u1));
+            OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u2));
+            OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].chi));
+        }
+        OFX_TRY(source(ctx, D, frames, lv[0].fr));
+        OFX_TRY(op_gaussian_planes<double>(ctx, D, D, lv[0].fr, nullptr, size, gx, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
+        for (int s = 1; s < nscales; s++)
+            OFX_TRY(op_zoom_out_channels_planes<double>(ctx, D, D, lv[s - 1].fr, nullptr, lv[s].fr, nullptr, gx, gy, nxs[s - 1], nys[s - 1], 1, zfactor));
+        {
+            const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1] * G;
+            OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u1, 0, n * sizeof(double), ctx->stream));
+            OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u2, 0, n * sizeof(double), ctx->stream));
+            OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].chi, 0, n * sizeof(double), ctx->stream));
+        }
+        for (int s = nscales - 1; s >= 0; s--) {
+            if (P.verbose && G == 1) fprintf(stderr, "Scale %d: %dx%d\n", s, nxs[s], nys[s]);
+            OFX_TRY(op_centered_gradient_planes<double>(ctx, D, lv[s].fr, gx, gy, nxs[s], nys[s]));
+            OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, gx, gy, idx, lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P, W, s, stats));
+            if (s)
+                OFX_TRY(op_zoom_in_planes3<double>(ctx, G, lv[s].u1, lv[s].u2, lv[s].chi, lv[s - 1].u1, lv[s - 1].u2, lv[s - 1].chi, nxs[s], nys[s],
+                                                   nxs[s - 1], nys[s - 1], (double) 1.0 / zfactor));
+        }
+        return sink(ctx, first, G, lv[0].u1, lv[0].u2, lv[0].chi);
+    });
+}
+
+// ==== the batch planner ==============================================================================================================
+// bytes of a lockstep group of G triples over D planes: per level D planes and 3 G of (u1, u2, chi); full size 2 D of gradients /
+// scratch and OccWork's 27 G; 13 G hyperplane-major planes; plus 5 %
+struct OccDevMem {
+    double level_px, full, skew;
+    OccDevMem(const std::vector<int> &nxs, const std::vector<int> &nys) : level_px(0.0)
+    {
+        for (size_t s = 0; s < nxs.size(); s++) level_px += (double) nxs[s] * nys[s];
+        full = (double) nxs[0] * nys[0];
+        skew = (double) rof_skew_elems(nxs[0], nys[0]);
+    }
+    double bytes(int G, int D) const { return 8.0 * 1.05 * ((D + 3.0 * G) * level_px + (2.0 * D + 27.0 * G) * full + 13.0 * G * skew); }
+};
+
+// Any number of triples of a table of n_planes planes, after the entry's own refusals on ctxs[0] (`who` names the entry in the
+// texts): groups of G consecutive triples in the caller's order, group q on context q mod n_ctx, a host thread per context.
+// G: option "lockstep" of ctxs[0], at most 16, no more than evens the groups out over the contexts, and the largest such G for
+// which every group fits OccDevMem's rule with its own count of distinct planes.  A plane that two groups share is built by both.
+int occ_triples_batch(ofx_ctx *const *ctxs, int n_ctx, const char *who, bool dev_planes, int n_planes, int n_triples,
+                      const ofx_occ_triple *tr, const OccSource &source, const OccSink &sink, int nxx, int nyy, const OccParams &P,
+                      int nscales, double zfactor, double *work_pix_iters)
+{
+    ofx_ctx *ctx = ctxs[0];
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_check(ctx, dev_planes, nxx, nyy, P, nscales, zfactor, nxs, nys));
+    double budget, need;
+    OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
+    const OccDevMem mem(nxs, nys);
+    const int cap = ofx_plan_cap_per_ctx(ofx_plan_lockstep(ctx->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP), n_triples, n_ctx);
+    const int G = ofx_plan_fit_groups(
+        cap, n_triples, budget, [&](int first, int cnt) { return ofx_tvl1occ_triples_frames(n_planes, cnt, tr + first, nullptr, nullptr); },
+        [&](int cnt, int D) { return mem.bytes(cnt, D); }, &need);
+    if (G < 1) return ofx_fail(ctx, OFX_ERR_NOMEM, "%s: %.2f GB for one triple, %.2f GB per context available", who, need / 1e9, budget / 1e9);
+    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, work_pix_iters, false, [&](ofx_ctx *c, int first, int cnt, ofx_stats *st) -> int {
+        OFX_ENTER(c);
+        return occ_triples_group(c, n_planes, cnt, tr + first, first, source, sink, P, zfactor, nxs, nys, st);
+    });
+}
+
+// the table of host triples: a plane is an address -- equal pointers are one plane, in order of first appearance (triples in order,
+// roles I_1, I0, I1, filtI0); nothing else about the arrays is compared
+void occ_host_table(int n_triples, const double *const *I_1, const double *const *I0, const double *const *I1, const double *const *filtI0,
+                    std::vector<const double *> &planes, std::vector<ofx_occ_triple> &tr)
+{
+    std::unordered_map<const double *, int> at;
+    auto index = [&](const double *p) {
+        const auto it = at.emplace(p, (int) planes.size());
+        if (it.second) planes.push_back(p);
+        return it.first->second;
+    };
+    tr.resize(n_triples);
+    for (int k = 0; k < n_triples; k++) {
+        tr[k].prev = index(I_1[k]);
+        tr[k].cur = index(I0[k]);
+        tr[k].next = index(I1[k]);
+        tr[k].filt = index(filtI0[k]);
+    }
 }
 
 // pointer arrays of a sequence of n_frames frames: no NULL, the frames aligned to their element, the payloads to a float2
@@ -1727,200 +1751,13 @@ int occ_seq_check_ptrs(ofx_ctx *ctx, int n_frames, const void *const *dF, void *
             return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: result pointer of triple %d NULL or misaligned", t);
     return OFX_OK;
 }
-
-// G triples over the F planes dF in lockstep; sizes checked by the caller.  idx == nullptr: the consecutive triples of a sequence,
-// F = G + 2, the roles are views at an offset; else F distinct planes (at most 4 G) and the roles of triple g are idx's.
-template <typename TIN>
-int occ_planes_group_impl(ofx_ctx *ctx, int kind, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
-                          const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
-                          ofx_stats *stats, size_t pitch)       // bytes between the rows of the planes dF, 0 = dense
+// the table of a sequence: triple t = frames (t, t + 1, t + 2), g from the middle one
+std::vector<ofx_occ_triple> occ_seq_table(int n_frames)
 {
-    const int nxx = nxs[0], nyy = nys[0];
-    for (int g = 0; g < G; g++) {
-        ofx_stats &S = stats[g];
-        S = ofx_stats{};
-        S.nscales = nscales;
-        S.nsolves = P.warps;
-        for (int s = 0; s < nscales && s < OFX_MAX_SCALES; s++) { S.nx[s] = nxs[s]; S.ny[s] = nys[s]; }
-    }
-    const size_t size = (size_t) nxx * nyy;
-    OccWork W;
-    OFX_TRY(W.alloc(ctx, size, rof_skew_elems(nxx, nyy), G));
-    double *gx, *gy;                                        // centred gradients of the level's frames, [F][n_s]; before the first
-    OFX_TRY(ofx_alloc(ctx, size * F, &gx));                 // level is solved: the scratch of the Gaussian and the zoom-out
-    OFX_TRY(ofx_alloc(ctx, size * F, &gy));
-    struct Lv { double *fr, *u1, *u2, *chi; };              // fr: [F][n_s], the others [G][n_s]
-    std::vector<Lv> lv(nscales);
-    for (int s = 0; s < nscales; s++) {
-        const size_t n = (size_t) nxs[s] * nys[s];
-        OFX_TRY(ofx_alloc(ctx, n * F, &lv[s].fr));
-        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u1));
-        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].u2));
-        OFX_TRY(ofx_alloc(ctx, n * G, &lv[s].chi));
-    }
-    hipStream_t st = ctx->stream;
-    for (int k0 = 0; k0 < F; k0 += OCC_MAX_GROUP + 2) {     // OccSeqIn holds 18 pointers: a sequence's frames are one launch, 64 planes four
-        const int cnt = F - k0 < OCC_MAX_GROUP + 2 ? F - k0 : OCC_MAX_GROUP + 2;
-        if (kind != OFX_SRC_F64 && kind != OFX_SRC_F32) {   // a byte kind
-            OfxSrcPtrs src = {};
-            OfxDstPtrs dst = {};
-            for (int k = 0; k < cnt; k++) { src.p[k] = dF[k0 + k]; dst.p[k] = lv[0].fr + (k0 + k) * size; }
-            OFX_TRY(op_convert_sources_in<double>(ctx, kind, src, dst, cnt, nxx, nyy, pitch));
-            continue;
-        }
-        OccSeqIn in = {};
-        for (int k = 0; k < cnt; k++) in.f[k] = dF[k0 + k];
-        if (pitch) {
-            const OfxRows R = op_rows_geom(nxx, nyy, pitch, false);
-            hipLaunchKernelGGL(k_occ_seq_in_p<TIN>, dim3(R.tiles, 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, R);
-            continue;
-        }
-        hipLaunchKernelGGL(k_occ_seq_in<TIN>, dim3(occ_grid1d(size), 1, cnt), dim3(256), 0, st, in, lv[0].fr + k0 * size, (int) size);
-    }
-    OFX_LAUNCH_CHECK(ctx);
-    OFX_TRY(op_gaussian_planes<double>(ctx, F, F, lv[0].fr, nullptr, size, gx, nxx, nyy, OCC_PRESMOOTHING_SIGMA));
-    for (int s = 1; s < nscales; s++)
-        OFX_TRY(op_zoom_out_channels_planes<double>(ctx, F, F, lv[s - 1].fr, nullptr, lv[s].fr, nullptr, gx, gy, nxs[s - 1], nys[s - 1], 1, zfactor));
-    {
-        const size_t n = (size_t) nxs[nscales - 1] * nys[nscales - 1] * G;
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u1, 0, n * sizeof(double), st));
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].u2, 0, n * sizeof(double), st));
-        OFX_HIP(ctx, hipMemsetAsync(lv[nscales - 1].chi, 0, n * sizeof(double), st));
-    }
-    for (int s = nscales - 1; s >= 0; s--) {
-        const size_t n = (size_t) nxs[s] * nys[s];
-        OFX_TRY(op_centered_gradient_planes<double>(ctx, F, lv[s].fr, gx, gy, nxs[s], nys[s]));
-        if (idx) {
-            OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr, lv[s].fr, OccGrad{gx, gy, gx, gy, gx, gy}, lv[s].u1, lv[s].u2, lv[s].chi,
-                                         nxs[s], nys[s], P, W, s, stats, idx));
-        } else {
-            const OccGrad D = {gx + n, gy + n, gx + 2 * n, gy + 2 * n, gx, gy};
-            OFX_TRY(occ_single_scale_dev(ctx, G, lv[s].fr, lv[s].fr + n, lv[s].fr + 2 * n, D, lv[s].u1, lv[s].u2, lv[s].chi, nxs[s], nys[s], P,
-                                         W, s, stats));
-        }
-        if (s)
-            OFX_TRY(op_zoom_in_planes3<double>(ctx, G, lv[s].u1, lv[s].u2, lv[s].chi, lv[s - 1].u1, lv[s - 1].u2, lv[s - 1].chi, nxs[s], nys[s],
-                                               nxs[s - 1], nys[s - 1], (double) 1.0 / zfactor));
-    }
-    OccSeqOut out = {};
-    for (int g = 0; g < G; g++) { out.flo[g] = static_cast<float2 *>(d_flo[g]); out.occ[g] = static_cast<unsigned char *>(d_occ[g]); }
-    hipLaunchKernelGGL(k_occ_seq_out, dim3(ofx_cdiv(ofx_cdiv((int) size + 3, 4), 256), 1, G), dim3(256), 0, st, (const double *) lv[0].u1,
-                       (const double *) lv[0].u2, (const double *) lv[0].chi, out, (int) size);
-    OFX_LAUNCH_CHECK(ctx);
-    return OFX_OK;
+    std::vector<ofx_occ_triple> tr(n_frames - 2);
+    for (int t = 0; t < n_frames - 2; t++) tr[t] = {t, t + 1, t + 2, -1};
+    return tr;
 }
-
-// a checked group on its context: the storage type, the records (stats_out: NULL or G of them), nothing in flight after an error
-int occ_planes_group(ofx_ctx *ctx, int G, int F, const void *const *dF, const OccIdx *idx, void *const *d_flo, void *const *d_occ,
-                     const OccParams &P, int nscales, double zfactor, const std::vector<int> &nxs, const std::vector<int> &nys,
-                     ofx_stats *stats_out)
-{
-    const int kind = ofx_src_kind(ctx);                     // the frames come in the context's "input" kind
-    const size_t pitch = ofx_src_pitch(ctx, nxs[0]);
-    return ofx_group_records(ctx, G, stats_out, [&](ofx_stats *st) {
-        return kind == OFX_SRC_F64
-                   ? occ_planes_group_impl<double>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch)
-                   : occ_planes_group_impl<float>(ctx, kind, G, F, dF, idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, st, pitch);
-    });
-}
-
-// bytes of a lockstep group of G triples over D planes: per level D planes and 3 G of (u1, u2, chi); full size 2 D of gradients /
-// scratch and OccWork's 27 G; 13 G hyperplane-major planes; plus 5 %
-struct OccDevMem {
-    double level_px, full, skew;
-    OccDevMem(const std::vector<int> &nxs, const std::vector<int> &nys) : level_px(0.0)
-    {
-        for (size_t s = 0; s < nxs.size(); s++) level_px += (double) nxs[s] * nys[s];
-        full = (double) nxs[0] * nys[0];
-        skew = (double) rof_skew_elems(nxs[0], nys[0]);
-    }
-    double bytes(int G, int D) const { return 8.0 * 1.05 * ((D + 3.0 * G) * level_px + (2.0 * D + 27.0 * G) * full + 13.0 * G * skew); }
-};
-
-}   // namespace
-
-extern "C" int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo,
-                                              void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
-                                              double theta, int nscales, double zfactor, int warps, double epsilon,
-                                              ofx_stats *stats_out)
-{
-    OFX_ENTER(ctx);
-    if (n_frames < 3 || n_frames > OCC_MAX_GROUP + 2)
-        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: a lockstep group holds 3..%d frames (got %d)", OCC_MAX_GROUP + 2, n_frames);
-    OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
-    OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-    std::vector<int> nxs, nys;
-    OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
-    return occ_planes_group(ctx, n_frames - 2, n_frames, dF, nullptr, d_flo, d_occ, P, nscales, zfactor, nxs, nys, stats_out);
-}
-
-// Any number of frames: groups of G consecutive triples, group q = frames q G .. q G + cnt + 1 on context q mod n_ctx, a host
-// thread per context.  G: option "lockstep" of ctxs[0], at most 16, what the memory budget holds, and no more than evens the
-// groups out over the contexts.  Memory of a group, ofx_tvl1occ_batch's rule for this layout (OccDevMem with D = G + 2): per level
-// G + 2 frames and 3 G of (u1, u2, chi); full size 2 (G + 2) of gradients / scratch and OccWork's 27 G; 13 G hyperplane-major planes.
-extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
-                                        void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
-                                        double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
-{
-    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
-    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
-    {
-        ofx_ctx *ctx = ctxs[0];
-        OFX_ENTER(ctx);
-        if (n_frames < 3) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: %d frames (at least 3)", n_frames);
-        OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
-        OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-        std::vector<int> nxs, nys;
-        OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-        double budget;
-        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
-        const OccDevMem mem(nxs, nys);
-        while (G >= 1 && mem.bytes(G, G + 2) > budget) G--;
-        if (G < 1)
-            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ sequence: %.2f GB for one triple, %.2f GB per context available", mem.bytes(1, 3) / 1e9, budget / 1e9);
-    }
-    const int n_triples = n_frames - 2;
-    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
-    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, work_pix_iters, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
-        return ofx_tvl1occ_sequence_group_dev(ctx, cnt + 2, dF + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta, theta,
-                                              nscales, zfactor, warps, epsilon, st);
-    });
-}
-
-// ==== ... over indexed triples of a table of device-resident planes (ofx_tvl1occ_triples_group_dev / _dev) =======================
-// Triple k is (dF[prev], dF[cur], dF[next]) with filtI0 = dF[filt] (filt = -1: cur).  A plane's pyramid and gradients depend on
-// that plane alone whatever its role, so a group keeps its D distinct referenced planes once per level, [D][n_s], exactly as a
-// sequence keeps its G + 2 frames; what differs is that a role is "plane idx.role[g]" (OccIdx) instead of a view at an offset,
-// in the two kernels that read images.
-
-// distinct referenced indices in order of first appearance (triples in order, roles prev, cur, next, filt) and the position of
-// every role among them; pure host code
-extern "C" int ofx_tvl1occ_triples_frames(int n_frames, int n_triples, const ofx_occ_triple *tr, int *frames_out,
-                                          unsigned char *roles_out)
-{
-    if (n_frames < 1 || n_triples < 0 || (n_triples > 0 && !tr)) return -OFX_ERR_ARG;
-    std::vector<int> seen;
-    for (int k = 0; k < n_triples; k++) {
-        const int role[4] = {tr[k].prev, tr[k].cur, tr[k].next, tr[k].filt < 0 ? tr[k].cur : tr[k].filt};
-        if (tr[k].filt < -1) return -OFX_ERR_ARG;
-        for (int r = 0; r < 4; r++) {
-            if (role[r] < 0 || role[r] >= n_frames) return -OFX_ERR_ARG;
-            size_t pos = 0;
-            while (pos < seen.size() && seen[pos] != role[r]) pos++;
-            if (pos == seen.size()) seen.push_back(role[r]);
-            if (roles_out) {
-                if (pos > 255) return -OFX_ERR_ARG;             // a position is a byte: at most 64 triples with a role table
-                roles_out[4 * k + r] = (unsigned char) pos;
-            }
-        }
-    }
-    if (frames_out)
-        for (size_t d = 0; d < seen.size(); d++) frames_out[d] = seen[d];
-    return (int) seen.size();
-}
-
-namespace {
 
 // the tables of n_triples indexed triples: no NULL array, every index inside the table (filt may be -1), every referenced plane
 // aligned to its element, the payloads to a float2; the maps need no alignment
@@ -1948,6 +1785,104 @@ int occ_tri_check(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_tripl
 
 }   // namespace
 
+// ==== the entries: a table of triples, a source and a sink in front of the group solve / the batch planner ==========================
+// distinct referenced indices in order of first appearance (triples in order, roles prev, cur, next, filt) and the position of
+// every role among them; pure host code
+extern "C" int ofx_tvl1occ_triples_frames(int n_frames, int n_triples, const ofx_occ_triple *tr, int *frames_out,
+                                          unsigned char *roles_out)
+{
+    if (n_frames < 1 || n_triples < 0 || (n_triples > 0 && !tr)) return -OFX_ERR_ARG;
+    std::vector<int> seen;
+    for (int k = 0; k < n_triples; k++) {
+        const int role[4] = {tr[k].prev, tr[k].cur, tr[k].next, tr[k].filt < 0 ? tr[k].cur : tr[k].filt};
+        if (tr[k].filt < -1) return -OFX_ERR_ARG;
+        for (int r = 0; r < 4; r++) {
+            if (role[r] < 0 || role[r] >= n_frames) return -OFX_ERR_ARG;
+            size_t pos = 0;
+            while (pos < seen.size() && seen[pos] != role[r]) pos++;
+            if (pos == seen.size()) seen.push_back(role[r]);
+            if (roles_out) {
+                if (pos > 255) return -OFX_ERR_ARG;             // a position is a byte: at most 64 triples with a role table
+                roles_out[4 * k + r] = (unsigned char) pos;
+            }
+        }
+    }
+    if (frames_out)
+        for (size_t d = 0; d < seen.size(); d++) frames_out[d] = seen[d];
+    return (int) seen.size();
+}
+
+// ---- host triples: planes are told apart by address ------------------------------------------------------------------------------
+extern "C" int ofx_tvl1occ_multiscale(ofx_ctx *ctx, const double *I_1, const double *I0, const double *I1, const double *filtI0,
+                                      double *u1, double *u2, double *chi, int nxx, int nyy, double lambda, double alpha,
+                                      double beta, double theta, int nscales, double zfactor, int warps, double epsilon,
+                                      int verbose)
+{
+    OFX_ENTER(ctx);
+    if (!I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ: NULL pointer");
+    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, verbose};
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_check(ctx, false, nxx, nyy, P, nscales, zfactor, nxs, nys));
+    std::vector<const double *> planes;
+    std::vector<ofx_occ_triple> tr;
+    occ_host_table(1, &I_1, &I0, &I1, &filtI0, planes, tr);
+    const size_t size = (size_t) nxx * nyy;
+    return occ_triples_group(ctx, (int) planes.size(), 1, tr.data(), 0, occ_source_host(planes.data(), size),
+                             occ_sink_host(&u1, &u2, &chi, size), P, zfactor, nxs, nys, &ctx->stats);
+}
+
+// Several independent triples: groups and memory are occ_triples_batch's.  Consecutive triples of a sequence passed as the same
+// arrays share their planes: a group of G of them uploads and builds G + 2 planes.
+extern "C" int ofx_tvl1occ_batch(ofx_ctx *const *ctxs, int n_ctx, int n_triples, const double *const *I_1, const double *const *I0,
+                                 const double *const *I1, const double *const *filtI0, double *const *u1, double *const *u2,
+                                 double *const *chi, int nxx, int nyy, double lambda, double alpha, double beta, double theta,
+                                 int nscales, double zfactor, int warps, double epsilon)
+{
+    if (n_triples < 0 || !I_1 || !I0 || !I1 || !filtI0 || !u1 || !u2 || !chi) return OFX_ERR_ARG;
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE));
+    if (n_triples == 0) return OFX_OK;
+    OFX_ENTER(ctxs[0]);
+    std::vector<const double *> planes;
+    std::vector<ofx_occ_triple> tr;
+    occ_host_table(n_triples, I_1, I0, I1, filtI0, planes, tr);
+    const size_t size = (size_t) nxx * nyy;
+    return occ_triples_batch(ctxs, n_ctx, "tvl1occ batch", false, (int) planes.size(), n_triples, tr.data(),
+                             occ_source_host(planes.data(), size), occ_sink_host(u1, u2, chi, size), nxx, nyy,
+                             OccParams{lambda, alpha, beta, theta, epsilon, warps, 0}, nscales, zfactor, nullptr);
+}
+
+// ---- a device-resident sequence: triple t = frames (t, t + 1, t + 2) ---------------------------------------------------------------
+extern "C" int ofx_tvl1occ_sequence_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                                              void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
+                                              double theta, int nscales, double zfactor, int warps, double epsilon,
+                                              ofx_stats *stats_out)
+{
+    OFX_ENTER(ctx);
+    if (n_frames < 3 || n_frames > OCC_MAX_GROUP + 2)
+        return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: a lockstep group holds 3..%d frames (got %d)", OCC_MAX_GROUP + 2, n_frames);
+    OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
+    const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_check(ctx, true, nxx, nyy, P, nscales, zfactor, nxs, nys));
+    return occ_triples_group(ctx, n_frames, n_frames - 2, occ_seq_table(n_frames).data(), 0, occ_source_dev(dF, nxx, nyy),
+                             occ_sink_dev(d_flo, d_occ, nxx, nyy), P, zfactor, nxs, nys, stats_out);
+}
+
+extern "C" int ofx_tvl1occ_sequence_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, void *const *d_flo,
+                                        void *const *d_occ, int nxx, int nyy, double lambda, double alpha, double beta,
+                                        double theta, int nscales, double zfactor, int warps, double epsilon, double *work_pix_iters)
+{
+    OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
+    ofx_ctx *ctx = ctxs[0];
+    OFX_ENTER(ctx);
+    if (n_frames < 3) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ sequence: %d frames (at least 3)", n_frames);
+    OFX_TRY(occ_seq_check_ptrs(ctx, n_frames, dF, d_flo, d_occ));
+    return occ_triples_batch(ctxs, n_ctx, "tvl1occ sequence", true, n_frames, n_frames - 2, occ_seq_table(n_frames).data(),
+                             occ_source_dev(dF, nxx, nyy), occ_sink_dev(d_flo, d_occ, nxx, nyy), nxx, nyy,
+                             OccParams{lambda, alpha, beta, theta, epsilon, warps, 0}, nscales, zfactor, work_pix_iters);
+}
+
+// ---- indexed triples of a table of device-resident planes: planes are told apart by index ------------------------------------------
 extern "C" int ofx_tvl1occ_triples_group_dev(ofx_ctx *ctx, int n_frames, const void *const *dF, int n_triples,
                                              const ofx_occ_triple *tr, void *const *d_flo, void *const *d_occ, int nxx, int nyy,
                                              double lambda, double alpha, double beta, double theta, int nscales, double zfactor,
@@ -1957,29 +1892,13 @@ extern "C" int ofx_tvl1occ_triples_group_dev(ofx_ctx *ctx, int n_frames, const v
     if (n_triples < 1 || n_triples > OCC_MAX_GROUP)
         return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: a lockstep group holds 1..%d triples (got %d)", OCC_MAX_GROUP, n_triples);
     OFX_TRY(occ_tri_check(ctx, n_frames, dF, n_triples, tr, d_flo, d_occ));
-    OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-    std::vector<int> nxs, nys;
-    OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-    int frames[4 * OCC_MAX_GROUP];
-    unsigned char roles[OCC_MAX_GROUP][4];
-    const int D = ofx_tvl1occ_triples_frames(n_frames, n_triples, tr, frames, &roles[0][0]);
-    if (D < 1) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1occ triples: bad index table");
-    const void *planes[4 * OCC_MAX_GROUP];
-    for (int d = 0; d < D; d++) planes[d] = dF[frames[d]];
-    OccIdx idx = {};
-    for (int g = 0; g < n_triples; g++) {
-        idx.prev[g] = roles[g][0];
-        idx.cur[g] = roles[g][1];
-        idx.next[g] = roles[g][2];
-        idx.filt[g] = roles[g][3];
-    }
     const OccParams P = {lambda, alpha, beta, theta, epsilon, warps, 0};
-    return occ_planes_group(ctx, n_triples, D, planes, &idx, d_flo, d_occ, P, nscales, zfactor, nxs, nys, stats_out);
+    std::vector<int> nxs, nys;
+    OFX_TRY(occ_check(ctx, true, nxx, nyy, P, nscales, zfactor, nxs, nys));
+    return occ_triples_group(ctx, n_frames, n_triples, tr, 0, occ_source_dev(dF, nxx, nyy), occ_sink_dev(d_flo, d_occ, nxx, nyy), P,
+                             zfactor, nxs, nys, stats_out);
 }
 
-// Any number of triples: groups of G consecutive triples in the caller's order, group q on context q mod n_ctx.  G: option
-// "lockstep" of ctxs[0], at most 16, no more than evens the groups out over the contexts, and the largest such G for which every
-// group fits OccDevMem's rule with its own count of distinct planes.  A plane that two groups share is built by both.
 extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_frames, const void *const *dF, int n_triples,
                                        const ofx_occ_triple *tr, void *const *d_flo, void *const *d_occ, int nxx, int nyy,
                                        double lambda, double alpha, double beta, double theta, int nscales, double zfactor, int warps,
@@ -1988,33 +1907,10 @@ extern "C" int ofx_tvl1occ_triples_dev(ofx_ctx *const *ctxs, int n_ctx, int n_fr
     OFX_TRY(ofx_batch_check_ctxs(ctxs, n_ctx, OFX_SAME_DEVICE | OFX_SAME_FORMAT));
     if (n_triples < 0) return OFX_ERR_ARG;
     if (n_triples == 0) return OFX_OK;
-    int G = ofx_plan_lockstep(ctxs[0]->lockstep, OCC_MAX_GROUP, OCC_MAX_GROUP);
-    G = ofx_plan_cap_per_ctx(G, n_triples, n_ctx);              // even the groups out over the contexts
-    {
-        ofx_ctx *ctx = ctxs[0];
-        OFX_ENTER(ctx);
-        OFX_TRY(occ_tri_check(ctx, n_frames, dF, n_triples, tr, d_flo, d_occ));
-        OFX_TRY(occ_check_args(ctx, nxx, nyy, lambda, theta, nscales, zfactor, warps));
-        std::vector<int> nxs, nys;
-        OFX_TRY(occ_seq_pyramid_check(ctx, nxx, nyy, nscales, zfactor, nxs, nys));
-        double budget;
-        OFX_TRY(ofx_batch_budget(ctx, n_ctx, &budget));
-        const OccDevMem mem(nxs, nys);
-        double need = 0.0;
-        for (; G >= 1; G--) {                                 // the largest G whose groups all fit
-            need = 0.0;
-            for (int first = 0; first < n_triples; first += G) {
-                const int cnt = n_triples - first < G ? n_triples - first : G;
-                const double b = mem.bytes(cnt, ofx_tvl1occ_triples_frames(n_frames, cnt, tr + first, nullptr, nullptr));
-                if (b > need) need = b;
-            }
-            if (need <= budget) break;
-        }
-        if (G < 1)
-            return ofx_fail(ctx, OFX_ERR_NOMEM, "tvl1occ triples: %.2f GB for one triple, %.2f GB per context available", need / 1e9, budget / 1e9);
-    }
-    return ofx_run_groups(ctxs, n_ctx, n_triples, G, 1, work_pix_iters, false, [&](ofx_ctx *ctx, int first, int cnt, ofx_stats *st) {
-        return ofx_tvl1occ_triples_group_dev(ctx, n_frames, dF, cnt, tr + first, d_flo + first, d_occ + first, nxx, nyy, lambda, alpha, beta,
-                                             theta, nscales, zfactor, warps, epsilon, st);
-    });
+    ofx_ctx *ctx = ctxs[0];
+    OFX_ENTER(ctx);
+    OFX_TRY(occ_tri_check(ctx, n_frames, dF, n_triples, tr, d_flo, d_occ));
+    return occ_triples_batch(ctxs, n_ctx, "tvl1occ triples", true, n_frames, n_triples, tr, occ_source_dev(dF, nxx, nyy),
+                             occ_sink_dev(d_flo, d_occ, nxx, nyy), nxx, nyy, OccParams{lambda, alpha, beta, theta, epsilon, warps, 0},
+                             nscales, zfactor, work_pix_iters);
 }

@@ -264,7 +264,7 @@ def test_errors_leave_the_outputs_untouched(ofx_mod, gpu64, gpu32, synth):
                 assert text in str(e.value), (text, str(e.value))
 
     for over in (dict(nscales=0), dict(warps=0), dict(warps=65), dict(zfactor=1.0), dict(zfactor=0.0), dict(theta=0.0), dict(lam=0.0)):
-        both((1,), F, MIXED, P, O, **over)                   # occ_check_args
+        both((1,), F, MIXED, P, O, **over)                   # occ_check's arguments
     both((1,), F, MIXED, P, O, x=1, y=ny)                    # bad size
     both((1, 2), F, MIXED, P, O, nscales=9)                  # a pyramid that cannot be built / coarsest level
     both((2,), F, MIXED, P, O, nscales=6)                    # 6 x 5 is too small for the zoom Gaussian

@@ -1,6 +1,7 @@
 """The grouping arithmetic of every batch entry (csrc/ofx_group_plan.h), pinned without a GPU: tests/group_plan_driver.cpp is built
 with the host C++ compiler against the header alone and prints the three rules over a grid; every line is compared with the
-restatement below.  Payloads do not depend on the group size, so this is the only pin on the group sizes of the SOR, occlusion
+restatement below.  The memory-bound group size of the TV-L1-with-occlusions batches (ofx_plan_fit_groups behind the cap per
+context) is compared, for a sequence, with the rule the sequence entry had before the three batch entries shared one planner.  Payloads do not depend on the group size, so this is the only pin on the group sizes of the SOR, occlusion
 and temporal-Brox batches (the TV-L1 batch's are also asserted on the GPU, tests/test_gpu_tvl1.py::test_batch_entry_point)."""
 import os
 import subprocess
@@ -34,15 +35,20 @@ RULES = {"lockstep": lockstep, "even_rounds": even_rounds, "cap_per_ctx": cap_pe
 
 
 @pytest.fixture(scope="module")
-def table():
-    """(rule, a, b, c) -> value, as the compiled header gives it"""
+def driver():
     out = os.path.join(HERE, "_build", "group_plan_driver")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", CSRC,
            os.path.join(HERE, "group_plan_driver.cpp"), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([out], capture_output=True, text=True)
+    return out
+
+
+@pytest.fixture(scope="module")
+def table(driver):
+    """(rule, a, b, c) -> value, as the compiled header gives it"""
+    r = subprocess.run([driver], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     t = {}
     for line in r.stdout.split("\n"):
@@ -80,3 +86,38 @@ def test_lockstep_clamps(table):
     assert table[("lockstep", 40, 16, 16)] == 16
     assert table[("lockstep", 3, 16, 16)] == 3
     assert table[("lockstep", 0, 16, 11)] == 11 and table[("lockstep", -1, 16, 1)] == 1
+
+
+def occ_bytes(G, D):
+    """the driver's memory rule: OccDevMem's without its 5 %, 64 x 48, two levels -- whole numbers, exact in a double"""
+    level_px, full, skew = 64 * 48 + 32 * 24, 64 * 48, (2 * 47 + 64) * 48
+    return 8.0 * ((D + 3.0 * G) * level_px + (2.0 * D + 27.0 * G) * full + 13.0 * G * skew)
+
+
+def old_sequence_rule(n_triples, n_ctx, lock, budget):
+    """ofx_tvl1occ_sequence_dev before the shared planner: shrink the lockstep size until a group of G triples over G + 2 frames
+    fits, THEN cap it per context; 0 = OFX_ERR_NOMEM"""
+    G = lockstep(lock, 16, 16)
+    while G >= 1 and occ_bytes(G, G + 2) > budget:
+        G -= 1
+    return cap_per_ctx(G, n_triples, n_ctx) if G >= 1 else 0
+
+
+@pytest.mark.parametrize("fits", [0, 1, 5, 20])
+def test_the_planner_gives_a_sequence_the_old_group_size(driver, fits):
+    """budgets that hold no triple, 1, 5 and more than a full group of 16; the planner caps per context FIRST and then takes the
+    largest G whose groups (cnt triples over cnt + 2 planes, the last one shorter) all fit: the same G, because bytes(G, G + 2)
+    grows with G and the cap is a min.  `need`, the figure of the OFX_ERR_NOMEM text, is the largest group's bytes."""
+    budget = occ_bytes(fits, fits + 2) if fits else 0.5 * occ_bytes(1, 3)
+    r = subprocess.run([driver, "occ_sequence", str(fits)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    seen = set()
+    for line in r.stdout.split("\n"):
+        if line:
+            rule, n, c, lock, G, need = line.split()
+            n, c, lock, G = int(n), int(c), int(lock), int(G)
+            assert rule == "occ_sequence" and G == old_sequence_rule(n, c, lock, budget), (n, c, lock, fits, G)
+            assert float(need) == occ_bytes(max(G, 1), max(G, 1) + 2), (n, c, lock, fits, need)
+            assert G == min(lockstep(lock, 16, 16), fits, cdiv(n, c))
+            seen.add((n, c, lock))
+    assert seen == {(n, c, lock) for n in range(1, 201) for c in range(1, 5) for lock in (0, 1, 4, 16, 99)}

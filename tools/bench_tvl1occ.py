@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """TV-L1 with occlusions, whole solve: GPU (ofx_tvl1occ_multiscale) against the CPU reference / oracle on one triple.
     python tools/bench_tvl1occ.py [--size 640x480] [--cpu ref|oracle|none] [--check] [--batch CTX:TRIPLES] [--sequence CTX:FRAMES]
-                                  [--triples CTX:FRAMES]
+                                  [--triples CTX:FRAMES] [--reps N]
 One JSON line per size.  --sequence: the frames of synth.sequence on the device through ofx_tvl1occ_sequence_dev against
-ofx_tvl1occ_batch on the same triples from host planes, in one process, both warmed, median of three.  --triples: for every
+ofx_tvl1occ_batch on the same triples from host planes, in one process, both warmed, median of --reps runs (default three).  --triples: for every
 inner frame t the forward triple (t - 1, t, t + 1) followed by the backward triple (t + 1, t, t - 1), 2 (FRAMES - 2) triples,
 through ofx_tvl1occ_triples_dev against ofx_tvl1occ_batch in the same way; with --check every payload and map must equal the
-host batch's.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
+host batch's.  Every leg reports the CRC-32 of all its results, for A/B runs of two trees.  The CPU side is test infrastructure (oracle/), timed here only as the baseline beside the GPU."""
 import argparse
 import importlib
 import json
@@ -14,6 +14,7 @@ import math
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -29,12 +30,23 @@ ap.add_argument("--warps", type=int, default=2)
 ap.add_argument("--batch", default="", help="contexts:triples, e.g. 4:8 -- also time a batch of independent triples")
 ap.add_argument("--sequence", default="", help="contexts:frames, e.g. 3:50 -- time the device-resident sequence entry against the host batch")
 ap.add_argument("--triples", default="", help="contexts:frames, e.g. 3:48 -- time forward + backward triples through the indexed-triples entry against the host batch")
+ap.add_argument("--reps", type=int, default=3, help="timed runs of the --batch, --sequence and --triples legs; the median is reported")
 ap.add_argument("--opt", action="append", default=[], help="name=value for every context (e.g. rof_pipe=0)")
 a = ap.parse_args()
 if a.sequence or a.triples:
     import torch                # torch brings its own HIP runtime and has to see the device before libofx.so does
     torch.cuda.init()
 ctx = ofx.Ofx(0, ofx.F64)
+median = lambda xs: sorted(xs)[len(xs) // 2]
+
+
+def crc(arrays):
+    c = 0
+    for x in arrays:
+        c = zlib.crc32(np.ascontiguousarray(x).tobytes(), c)
+    return "%08x" % c
+
+
 for o in a.opt:
     ctx.set_option(o.split("=")[0], float(o.split("=")[1]))
 for size in a.size or ["320x240"]:
@@ -75,10 +87,14 @@ for size in a.size or ["320x240"]:
                 c_.set_option(o.split("=")[0], float(o.split("=")[1]))
         triples = [tuple(synth.sequence(nx, ny, 3, k + 1)) for k in range(n_tr)]
         res_b = ofx.tvl1occ_batch(ctxs, triples, **kw)                                          # warm every context, arena, result planes
-        t = time.perf_counter()
-        ofx.tvl1occ_batch(ctxs, triples, out=res_b, **kw)
-        bt = time.perf_counter() - t
-        rec["batch"] = {"contexts": n_ctx, "triples": n_tr, "seconds": round(bt, 4), "s_per_triple": round(bt / n_tr, 4)}
+        t_b = []
+        for _ in range(a.reps):
+            t = time.perf_counter()
+            ofx.tvl1occ_batch(ctxs, triples, out=res_b, **kw)
+            t_b.append(time.perf_counter() - t)
+        bt = median(t_b)
+        rec["batch"] = {"contexts": n_ctx, "triples": n_tr, "seconds": round(bt, 4), "s_per_triple": round(bt / n_tr, 5),
+                        "s_repetitions": [round(x, 4) for x in t_b], "crc": crc(p for r_ in res_b for p in r_)}
     if a.sequence:
         n_ctx, n_fr = (int(v) for v in a.sequence.split(":"))
         ctxs = [ofx.Ofx(0, ofx.F64) for _ in range(n_ctx)]
@@ -97,18 +113,19 @@ for size in a.size or ["320x240"]:
         run_seq()                                                                               # warm both paths on every context
         res_b = ofx.tvl1occ_batch(ctxs, triples, **kw)
         t_seq, t_host = [], []
-        for _ in range(3):                                                                      # interleaved
+        for _ in range(a.reps):                                                                 # interleaved
             t = time.perf_counter()
             run_seq()
             t_seq.append(time.perf_counter() - t)
             t = time.perf_counter()
             ofx.tvl1occ_batch(ctxs, triples, out=res_b, **kw)
             t_host.append(time.perf_counter() - t)
-        s_seq, s_host = sorted(t_seq)[1] / n_tr, sorted(t_host)[1] / n_tr
+        s_seq, s_host = median(t_seq) / n_tr, median(t_host) / n_tr
         rec["sequence"] = {"contexts": n_ctx, "frames": n_fr, "triples": n_tr,
                            "sequence_s_per_triple": round(s_seq, 5), "host_batch_s_per_triple": round(s_host, 5),
                            "host_over_sequence": round(s_host / s_seq, 3),
-                           "sequence_s_repetitions": [round(x, 4) for x in t_seq], "host_batch_s_repetitions": [round(x, 4) for x in t_host]}
+                           "sequence_s_repetitions": [round(x, 4) for x in t_seq], "host_batch_s_repetitions": [round(x, 4) for x in t_host],
+                           "crc": crc([d_flo.cpu().numpy(), d_occ.cpu().numpy()]), "host_batch_crc": crc(p for r_ in res_b for p in r_)}
         if a.check:
             flo, occ = d_flo.cpu().numpy(), d_occ.cpu().numpy()
             worst = 0.0
@@ -137,18 +154,19 @@ for size in a.size or ["320x240"]:
         run_tri()                                                                               # warm both paths on every context
         res_b = ofx.tvl1occ_batch(ctxs, host, **kw)
         t_tri, t_host = [], []
-        for _ in range(3):                                                                      # interleaved
+        for _ in range(a.reps):                                                                 # interleaved
             t = time.perf_counter()
             run_tri()
             t_tri.append(time.perf_counter() - t)
             t = time.perf_counter()
             ofx.tvl1occ_batch(ctxs, host, out=res_b, **kw)
             t_host.append(time.perf_counter() - t)
-        s_tri, s_host = sorted(t_tri)[1] / n_tr, sorted(t_host)[1] / n_tr
+        s_tri, s_host = median(t_tri) / n_tr, median(t_host) / n_tr
         rec["triples"] = {"contexts": n_ctx, "frames": n_fr, "triples": n_tr,
                           "triples_s_per_triple": round(s_tri, 5), "host_batch_s_per_triple": round(s_host, 5),
                           "host_over_triples": round(s_host / s_tri, 3),
-                          "triples_s_repetitions": [round(x, 4) for x in t_tri], "host_batch_s_repetitions": [round(x, 4) for x in t_host]}
+                          "triples_s_repetitions": [round(x, 4) for x in t_tri], "host_batch_s_repetitions": [round(x, 4) for x in t_host],
+                          "crc": crc([d_flo.cpu().numpy(), d_occ.cpu().numpy()]), "host_batch_crc": crc(p for r_ in res_b for p in r_)}
         if a.check:
             flo, occ = d_flo.cpu().numpy(), d_occ.cpu().numpy()
             bad = [k for k, (u_, v_, c_) in enumerate(res_b)
