@@ -138,6 +138,7 @@ def lib():
         "ofx_tvl1_bidir_batch_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _i, _d, _d, _d, _i, _d, _i, _d, _d,
                                                                                         _d, C.POINTER(_d)]),
         "ofx_flow_warp_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 5 + [_i, _i, _i]),
+        "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
         "ofx_hs_single_scale": (_i, [_vp, _dp, _dp, _dp, _dp, _i, _i, _d, _i, _d, _i, _i]),
@@ -701,6 +702,16 @@ class Ofx:
         n = len(dSrc)
         arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_warp_dev(self.h, n, arr(dSrc), arr(d_flo), arr(d_occ), arr(dFill), arr(dDst), nx, ny, nz))
+
+    def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
+        """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part
+        T = f - alpha S of the one-channel frame dSrc[g], S its ROF structure part after n_iter projection steps (Wedel et al.
+        2009); dStruct: None, or one entry per slot (None / 0: no structure frame for that slot).  Frames are read under the
+        options "input" and "input_pitch"; the results are dense frames of the storage precision.  Enqueues on the context's
+        stream."""
+        n = len(dSrc)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_structure_texture_dev(self.h, n, arr(dSrc), arr(dTex), arr(dStruct), nx, ny, theta, alpha, n_iter))
 
     def flow_interpolate_dev(self, dA, dB, d_flo_fwd, d_flo_bwd, t, dDst, nx, ny, nz=1):
         """ofx_flow_interpolate_dev: lists of device pointers (ints), one entry per slot: dDst[g] receives the frame at time t[g] in

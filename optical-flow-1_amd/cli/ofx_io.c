@@ -353,6 +353,17 @@ int ofx_write_bytes_image(const char *fname, const unsigned char *bytes, int w, 
     return (fclose(f) == 0 && ok) ? 0 : 1;
 }
 
+int ofx_write_pfm(const char *fname, const float *x, int w, int h)
+{
+    if (!fname || !x || w < 1 || h < 1) return 2;
+    FILE *f = fopen(fname, "wb");
+    if (!f) return 1;
+    const size_t n = (size_t) w * h;
+    int ok = fprintf(f, "Pf\n%d %d\n-1.0\n", w, h) > 0;       /* read_pfm: the scale is parsed and ignored, the floats taken as they lie */
+    ok = ok && fwrite(x, sizeof(float), n, f) == n;
+    return (fclose(f) == 0 && ok) ? 0 : 1;
+}
+
 int ofx_write_flo(const char *fname, const float *uv, int w, int h)
 {
     FILE *f = fopen(fname, "wb");

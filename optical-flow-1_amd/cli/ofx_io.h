@@ -32,6 +32,10 @@ int ofx_write_gray_bytes(const char *fname, const float *x, int w, int h);
 /* w*h pixels of c interleaved byte channels as binary PGM (c = 1: P5) or PPM (c = 3: P6), maxval 255, whatever the name.
  * 0 ok, 1 I/O error, 2 not representable (another c, an empty image) */
 int ofx_write_bytes_image(const char *fname, const unsigned char *bytes, int w, int h, int c);
+/* a one-channel float image as PFM ("Pf"), the way ofx_read_image_double reads one: header "Pf\n<w> <h>\n-1.0\n", then the w*h
+ * floats as they lie in memory, first row first (no vertical flip, no byte swap).  Any float goes through unchanged.  0 ok,
+ * 1 I/O error, 2 an empty image */
+int ofx_write_pfm(const char *fname, const float *x, int w, int h);
 /* returns a malloc'ed w*h*2 float array or NULL */
 float *ofx_read_flo(const char *fname, int *w, int *h);
 /* 1 if `s` ends with `suffix` */

@@ -93,6 +93,7 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->lockstep = 0;
     ctx->warp_lds = 1;
     ctx->apply_lds = 2;         // by measurement: LDS tiles for float and double frames, global gathers for 8- and 16-bit ones
+    ctx->st_fuse = 0;
     ctx->gauss_fused = 1;
     ctx->relaxed_dual = 0;
     ctx->tile = 0;              // measured: no faster than the marching strips on the small levels, off by default
@@ -236,6 +237,12 @@ extern "C" int ofx_set_option(ofx_ctx *ctx, const char *name, double value)
     if (!strcmp(name, "apply_lds")) {
         if (value != 0 && value != 1 && value != 2) return ofx_fail(ctx, OFX_ERR_ARG, "apply_lds must be 0, 1 or 2");
         ctx->apply_lds = (int) value;
+        return OFX_OK;
+    }
+    if (!strcmp(name, "st_fuse")) {
+        if (!(value >= 0 && value <= OFX_ST_MAX_FUSE) || value != (double) (int) value)
+            return ofx_fail(ctx, OFX_ERR_ARG, "st_fuse must be 0 (default) or 1..%d", OFX_ST_MAX_FUSE);
+        ctx->st_fuse = (int) value;
         return OFX_OK;
     }
     if (!strcmp(name, "nt_stores")) { ctx->nt_stores = (int) value; return (value >= 0 && value <= 2) ? OFX_OK : ofx_fail(ctx, OFX_ERR_ARG, "nt_stores = 0 | 1 | 2"); }
