@@ -13,6 +13,7 @@
 
 #include "ofx_internal.h"
 #include "ofx_device.h"
+#include "ofx_loop_plan.h"
 
 #define OFX_CRIT_MEAN      0   // error = sum / size           (TV-L1, tvl1flow.cpp:162)
 #define OFX_CRIT_SQRT_MEAN 1   // error = sqrt(sum / size)     (HS :230, Brox :389)
@@ -67,12 +68,82 @@ int ofx_loop_finalize_group(ofx_ctx *ctx, const LoopSpec &L, int G, int slots_pe
 int ofx_loop_finalize_cursor(ofx_ctx *ctx, const LoopSpec &L, int G, int slots_per_problem, int launch_end, int max_range,
                              OfxIterState *host_slot, int seq);
 int ofx_loop_wait_poll(ofx_ctx *ctx, int slot, int G, int seq);
-static inline int ofx_poll_seq(const ofx_ctx *ctx) { return (int) (ctx->poll_seq & 0x3FFFFFFF) + 1; }
+
+// ---- polls: the one way a loop learns where it stands --------------------------------------------------------------------------
+// A poll = a finalize kernel behind the launches it covers, writing G records into a slot of the pinned ring, and an event
+// behind it.  ofx_poll_issue takes the next sequence number (before it advances the count: every site the same) and slot, has
+// finalize(host_slot, seq) enqueue the kernel and records the event; ofx_poll_read waits and copies the G records out -- `spin`:
+// on the records' sequence numbers first (ofx_loop_wait_poll: a loop with a chunk of lookahead), else on the event alone (the
+// exact SOR batches, which have nothing in flight behind the poll).
+struct OfxPoll { int slot, seq; };
+template <class FinalizeFn> static int ofx_poll_issue(ofx_ctx *ctx, FinalizeFn finalize, OfxPoll *p)
+{
+    p->seq = (int) (ctx->poll_seq & 0x3FFFFFFF) + 1;
+    p->slot = (int) (ctx->poll_seq++ % OFX_NPOLL);
+    OFX_TRY(finalize(&ctx->h_state[p->slot * OFX_MAX_GROUP], p->seq));
+    OFX_HIP(ctx, hipEventRecord(ctx->ev_poll[p->slot], ctx->stream));
+    return OFX_OK;
+}
+static int ofx_poll_read(ofx_ctx *ctx, const OfxPoll &p, int G, bool spin, OfxIterState *out)
+{
+    if (spin) OFX_TRY(ofx_loop_wait_poll(ctx, p.slot, G, p.seq));
+    else OFX_HIP(ctx, hipEventSynchronize(ctx->ev_poll[p.slot]));
+    for (int g = 0; g < G; g++) out[g] = ctx->h_state[p.slot * OFX_MAX_GROUP + g];
+    return OFX_OK;
+}
+
+// What ofx_run_loop_group and ofx_run_loop_cursor share: the error slots and the state of G problems (problem g accumulates into
+// err slots g * (L.max_iter + 1) + k; + 1: the scratch slot for a re-run's errors), the pump (ofx_loop_plan.h) and the timing.
+// more() / enqueue(S, per, &poll) -- a chunk of launches and its poll -- feed the pump; decide(fin) gets the G final records.
+// A context that has the device to itself keeps two polls outstanding (the one the host waits for and one chunk of lookahead,
+// so the GPU never idles while the host reads a poll) at the price of one chunk of no-op launches behind the stopping
+// iteration.  When other contexts share the device (option "concurrency" > 1) their work fills such gaps, so nothing is
+// launched speculatively: one outstanding poll.
+template <class MoreFn, class EnqueueFn, class DecideFn>
+static int ofx_loop_drive_impl(ofx_ctx *ctx, const LoopSpec &L, int G, MoreFn more, EnqueueFn enqueue, DecideFn decide, float *ms_out)
+{
+    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "loop group of %d problems", G);
+    const int per = L.max_iter + 1;
+    OFX_TRY(ofx_loop_reserve(ctx, G * per));
+    LoopSpec S = L;
+    if (S.fixed) S.thr = -1.0;          // error >= 0 always passes `error > -1`
+    OFX_TRY(ofx_loop_clear(ctx, (size_t) G * per));
+    if (ms_out) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
+    OfxPoll poll[2];
+    OfxIterState fin[OFX_MAX_GROUP];
+    bool stopped = false;
+    OFX_TRY(ofx_loop_pump(
+        ctx->concurrency > 1 ? 1 : 2, more, [&](int i) -> int { return enqueue(S, per, &poll[i]); },
+        [&](int i, bool *all) -> int {
+            OFX_TRY(ofx_poll_read(ctx, poll[i], G, true, fin));
+            *all = true;
+            for (int g = 0; g < G; g++) *all = *all && fin[g].done;
+            return OFX_OK;
+        },
+        &stopped));
+    if (!stopped) return ofx_fail(ctx, OFX_ERR_HIP, "iteration loop ended without a final state");
+    OFX_TRY(decide(fin));
+    if (ms_out) {
+        OFX_HIP(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
+        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_t1));
+        OFX_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev_t0, ctx->ev_t1));
+    }
+    return OFX_OK;
+}
+// An error return must not leave launches or a poll of this loop in flight: the next API call resets the arena these
+// kernels work in.  (Stream order already protects the next call's own kernels; the drain makes it hold for anything
+// else the caller does with the context.)
+template <class MoreFn, class EnqueueFn, class DecideFn>
+static int ofx_loop_drive(ofx_ctx *ctx, const LoopSpec &L, int G, MoreFn more, EnqueueFn enqueue, DecideFn decide, float *ms_out)
+{
+    const int s = ofx_loop_drive_impl(ctx, L, G, more, enqueue, decide, ms_out);
+    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);
+    return s;
+}
 
 // Runs the loop for G independent problems of the same size in LOCKSTEP (TV-L1: G image pairs solved by
-// the same launches, blockIdx.y = problem; the SOR solvers use G = 1).  Problem g accumulates into err slots
-// g * (L.max_iter + 1) + k and stops on its own test -- its launches turn into no-ops while the others
-// continue; the host stops enqueueing when every problem is done.
+// the same launches, blockIdx.y = problem; the SOR solvers use G = 1).  Problem g stops on its own test -- its launches turn
+// into no-ops while the others continue; the host stops enqueueing when every problem is done.
 //   launch(k, count, thr) must enqueue every kernel of sweeps k .. k+count-1 of ALL problems on ctx->stream
 // (count is 2 only when L.pairs and at least two sweeps remain; pairs always start at an even k); kernels
 // take (ctx->d_err, k, thr) and use the helpers above (L.fuse > 2: count is up to L.fuse, units start at multiples of it, and
@@ -84,106 +155,31 @@ static inline int ofx_poll_seq(const ofx_ctx *ctx) { return (int) (ctx->poll_seq
 // state (L.afac, or bit g of amask0 for a loop that stopped in its very first launch) need no redo: took_alt[g] = 1
 // tells the caller to continue from that stored state.  Returns the reference's n and error per problem.
 template <class LaunchFn, class RedoFn>
-static int ofx_run_loop_group_impl(ofx_ctx *ctx, const LoopSpec &L, int G, LaunchFn launch, RedoFn redo, int *n_out,
-                                   double *err_out, float *ms_out, unsigned amask0, int *took_alt);
-
-// An error return must not leave launches or a poll of this loop in flight: the next API call resets the arena these
-// kernels work in.  (Stream order already protects the next call's own kernels; the drain makes it hold for anything
-// else the caller does with the context.)
-template <class LaunchFn, class RedoFn>
 static int ofx_run_loop_group(ofx_ctx *ctx, const LoopSpec &L, int G, LaunchFn launch, RedoFn redo, int *n_out,
                               double *err_out, float *ms_out, unsigned amask0 = 0, int *took_alt = nullptr)
 {
-    const int s = ofx_run_loop_group_impl(ctx, L, G, launch, redo, n_out, err_out, ms_out, amask0, took_alt);
-    if (s != OFX_OK) (void) hipStreamSynchronize(ctx->stream);
-    return s;
-}
-
-template <class LaunchFn, class RedoFn>
-static int ofx_run_loop_group_impl(ofx_ctx *ctx, const LoopSpec &L, int G, LaunchFn launch, RedoFn redo, int *n_out,
-                                   double *err_out, float *ms_out, unsigned amask0, int *took_alt)
-{
-    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "loop group of %d problems", G);
-    const int per = L.max_iter + 1;                      // +1: scratch slot for the redo's error
-    OFX_TRY(ofx_loop_reserve(ctx, G * per));
-    LoopSpec S = L;
-    if (S.fixed) S.thr = -1.0;          // error >= 0 always passes `error > -1`
-    OFX_TRY(ofx_loop_clear(ctx, (size_t) G * per));
-    if (ms_out) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-
-    // head / tail count the polls issued / consumed.  A context that has the device to itself keeps two
-    // outstanding (the one the host waits for and one chunk of lookahead, so the GPU never idles while the
-    // host reads a poll) at the price of one chunk of no-op launches behind the stopping iteration.  When
-    // other contexts share the device (option "concurrency" > 1) their work fills such gaps, so nothing is
-    // launched speculatively: one outstanding poll.
-    const int max_out = ctx->concurrency > 1 ? 1 : 2;
-    int launched = 0, head = 0, tail = 0, slot_of[2] = {0, 0}, seq_of[2] = {0, 0};
-    bool stop = false;
-    OfxIterState fin[OFX_MAX_GROUP];
-    int chunk = S.chunk < 1 ? 1 : S.chunk;
-    const int F = S.fuse > 2 ? S.fuse : (S.pairs ? 2 : 1);       // sweeps per launch unit; units start at multiples of F
-    chunk = (chunk + F - 1) / F * F;
-    for (;;) {
-        while (launched < S.max_iter && head - tail < max_out) {
-            const int first = launched;
-            const int c = (S.max_iter - launched < chunk) ? S.max_iter - launched : chunk;
-            while (launched < first + c) {
-                const int cnt = (first + c - launched < F) ? first + c - launched : F;
-                OFX_TRY(launch(launched, cnt, S.thr));
-                launched += cnt;
-            }
-            const int seq = ofx_poll_seq(ctx);
-            const int slot = (int) (ctx->poll_seq++ % OFX_NPOLL);
-            OFX_TRY(ofx_loop_finalize_group(ctx, S, G, per, first, launched, &ctx->h_state[slot * OFX_MAX_GROUP], seq));
-            slot_of[head & 1] = slot;
-            seq_of[head & 1] = seq;
-            OFX_HIP(ctx, hipEventRecord(ctx->ev_poll[slot], ctx->stream));
-            head++;
-        }
-        if (tail == head) break;
-        const int slot = slot_of[tail & 1];
-        OFX_TRY(ofx_loop_wait_poll(ctx, slot, G, seq_of[tail & 1]));
-        bool all = true;
+    const int F = ofx_loop_unit_size(L.pairs, L.fuse);
+    OfxChunkSchedule sched(L.max_iter, L.chunk, F);
+    auto enqueue = [&](const LoopSpec &S, int per, OfxPoll *p) -> int {
+        OFX_TRY(sched.next([&](int k, int cnt) -> int { return launch(k, cnt, S.thr); }));
+        return ofx_poll_issue(ctx, [&](OfxIterState *slot, int seq) -> int {
+            return ofx_loop_finalize_group(ctx, S, G, per, sched.first, sched.launched, slot, seq); }, p);
+    };
+    auto decide = [&](const OfxIterState *fin) -> int {
+        int redo_k[OFX_MAX_GROUP];
+        bool any_redo = false;
         for (int g = 0; g < G; g++) {
-            fin[g] = ctx->h_state[slot * OFX_MAX_GROUP + g];
-            all = all && fin[g].done;
+            const bool inside = ofx_loop_inside(fin[g].n, F, L.max_iter);
+            const bool stored = ofx_loop_took_alt(inside, F, took_alt != nullptr, fin[g].apred, fin[g].n, (amask0 >> g) & 1u);
+            if (took_alt) took_alt[g] = stored ? 1 : 0;
+            redo_k[g] = inside && !stored ? fin[g].n - 1 : -1;
+            any_redo = any_redo || redo_k[g] >= 0;
+            n_out[g] = fin[g].n;
+            err_out[g] = fin[g].error;
         }
-        tail++;
-        if (all) {
-            // A poll still in flight covers launches that are no-ops (their stopping test already
-            // fails); it is not drained -- stream order keeps it ahead of whatever is enqueued next.
-            stop = true;
-            break;
-        }
-    }
-    if (!stop) return ofx_fail(ctx, OFX_ERR_HIP, "iteration loop ended without a final state");
-    int redo_k[OFX_MAX_GROUP];
-    bool any_redo = false;
-    for (int g = 0; g < G; g++) {
-        // the loop ended inside launch unit j = (n - 1) / F unless n is that unit's last sweep (units are F sweeps, the last
-        // one of the loop what is left of max_iter): F = 2 -> n odd and not max_iter
-        bool r = false;
-        if (F > 1 && fin[g].n > 0) {
-            const int k0 = (fin[g].n - 1) / F * F, cnt = (S.max_iter - k0 < F) ? S.max_iter - k0 : F;
-            r = fin[g].n - k0 != cnt;
-        }
-        const bool stored = r && F == 2 && took_alt && (fin[g].apred || (fin[g].n == 1 && ((amask0 >> g) & 1u)));
-        if (took_alt) took_alt[g] = stored ? 1 : 0;
-        r = r && !stored;
-        redo_k[g] = r ? fin[g].n - 1 : -1;
-        any_redo = any_redo || r;
-    }
-    if (any_redo) OFX_TRY(redo(redo_k));
-    if (ms_out) OFX_HIP(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-    for (int g = 0; g < G; g++) {
-        n_out[g] = fin[g].n;
-        err_out[g] = fin[g].error;
-    }
-    if (ms_out) {
-        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_t1));
-        OFX_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev_t0, ctx->ev_t1));
-    }
-    return OFX_OK;
+        return any_redo ? redo(redo_k) : OFX_OK;
+    };
+    return ofx_loop_drive(ctx, L, G, [&] { return sched.more(); }, enqueue, decide, ms_out);
 }
 
 // single problem (the SOR solvers); redo(k) as above for the one problem
@@ -201,59 +197,27 @@ static int ofx_run_loop(ofx_ctx *ctx, const LoopSpec &L, LaunchFn launch, RedoFn
 // previous error says the stop is near -- fewer iterations computed past the stop, fewer re-runs) and logs where it started.  A
 // launch looks max_unit error slots back, so every launch behind the stop is a no-op.  The host only counts
 // launches: launch(L, thr) enqueues launch L for all problems; units_per_chunk launches, then one finalize kernel (which learns
-// the iteration range from the device state), polled one chunk behind as in ofx_run_loop_group.  On return unit_out[g] / k0_out[g] /
-// ucnt_out[g] describe the launch unit that contains iteration n_g - 1; when n_g - k0 < ucnt the loop ended INSIDE that unit and
-// redo(n_of, k0_of, unit_of) -- called once, entries -1 for the problems that need nothing -- must re-run its first n - k0
+// the iteration range from the device state), polled one chunk behind as in ofx_run_loop_group.  On return unit_out[g] is the
+// launch unit that contains iteration n_g - 1 (-1: none ran); when the loop ended INSIDE that unit (inside_out[g]),
+// redo(n_of, k0_of, unit_of) -- called once, n_of -1 for the problems that need nothing -- must re-run its first n - k0
 // iterations from the unit's input buffers.
 template <class LaunchFn, class RedoFn>
 static int ofx_run_loop_cursor(ofx_ctx *ctx, const LoopSpec &L, int G, int units_per_chunk, int max_unit, LaunchFn launch, RedoFn redo,
                                int *n_out, double *err_out, int *unit_out, int *inside_out, float *ms_out)
 {
-    if (G < 1 || G > OFX_MAX_GROUP) return ofx_fail(ctx, OFX_ERR_ARG, "loop group of %d problems", G);
-    const int per = L.max_iter + 1;
-    OFX_TRY(ofx_loop_reserve(ctx, G * per));
-    LoopSpec S = L;
-    if (S.fixed) S.thr = -1.0;
-    OFX_TRY(ofx_loop_clear(ctx, (size_t) G * per));
-    if (ms_out) OFX_HIP(ctx, hipEventRecord(ctx->ev_t0, ctx->stream));
-    const int max_out = ctx->concurrency > 1 ? 1 : 2;
     const int upc = units_per_chunk < 1 ? 1 : units_per_chunk;
-    int launches = 0, head = 0, tail = 0, slot_of[2] = {0, 0}, seq_of[2] = {0, 0};
-    bool stop = false;
-    OfxIterState fin[OFX_MAX_GROUP];
-    int status = OFX_OK;
-    for (;;) {
-        while (launches < OFX_ULOG && head - tail < max_out) {
-            const int c = OFX_ULOG - launches < upc ? OFX_ULOG - launches : upc;
-            for (int i = 0; i < c && status == OFX_OK; i++) status = launch(launches++, S.thr);
-            if (status != OFX_OK) break;
-            const int seq = ofx_poll_seq(ctx);
-            const int slot = (int) (ctx->poll_seq++ % OFX_NPOLL);
-            status = ofx_loop_finalize_cursor(ctx, S, G, per, launches, c * max_unit, &ctx->h_state[slot * OFX_MAX_GROUP], seq);
-            if (status != OFX_OK) break;
-            slot_of[head & 1] = slot;
-            seq_of[head & 1] = seq;
-            if (hipEventRecord(ctx->ev_poll[slot], ctx->stream) != hipSuccess) { status = ofx_fail(ctx, OFX_ERR_HIP, "event record failed"); break; }
-            head++;
-        }
-        if (status != OFX_OK || tail == head) break;
-        const int slot = slot_of[tail & 1];
-        status = ofx_loop_wait_poll(ctx, slot, G, seq_of[tail & 1]);
-        if (status != OFX_OK) break;
-        bool all = true;
-        for (int g = 0; g < G; g++) {
-            fin[g] = ctx->h_state[slot * OFX_MAX_GROUP + g];
-            all = all && fin[g].done;
-        }
-        tail++;
-        if (all) { stop = true; break; }
-    }
-    if (status == OFX_OK && !stop) status = ofx_fail(ctx, OFX_ERR_HIP, "iteration loop ended without a final state");
-    if (status == OFX_OK) {
+    int launches = 0;
+    auto enqueue = [&](const LoopSpec &S, int per, OfxPoll *p) -> int {
+        const int c = OFX_ULOG - launches < upc ? OFX_ULOG - launches : upc;
+        for (int i = 0; i < c; i++) OFX_TRY(launch(launches++, S.thr));
+        return ofx_poll_issue(ctx, [&](OfxIterState *slot, int seq) -> int {
+            return ofx_loop_finalize_cursor(ctx, S, G, per, launches, c * max_unit, slot, seq); }, p);
+    };
+    auto decide = [&](const OfxIterState *fin) -> int {
         int n_of[OFX_MAX_GROUP], k0_of[OFX_MAX_GROUP], u_of[OFX_MAX_GROUP];
         bool any = false;
         for (int g = 0; g < G; g++) {
-            const bool inside = fin[g].n > 0 && fin[g].n - fin[g].k0 < fin[g].ucnt;
+            const bool inside = ofx_loop_inside_cursor(fin[g].n, fin[g].k0, fin[g].ucnt);
             n_of[g] = inside ? fin[g].n : -1;
             k0_of[g] = fin[g].k0;
             u_of[g] = fin[g].unit;
@@ -263,16 +227,7 @@ static int ofx_run_loop_cursor(ofx_ctx *ctx, const LoopSpec &L, int G, int units
             unit_out[g] = fin[g].n > 0 ? fin[g].unit : -1;
             if (inside_out) inside_out[g] = inside ? 1 : 0;
         }
-        if (any) status = redo(n_of, k0_of, u_of);
-    }
-    if (status != OFX_OK) {
-        (void) hipStreamSynchronize(ctx->stream);       // nothing of this loop in flight when the caller resets the arena
-        return status;
-    }
-    if (ms_out) {
-        OFX_HIP(ctx, hipEventRecord(ctx->ev_t1, ctx->stream));
-        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_t1));
-        OFX_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev_t0, ctx->ev_t1));
-    }
-    return OFX_OK;
+        return any ? redo(n_of, k0_of, u_of) : OFX_OK;
+    };
+    return ofx_loop_drive(ctx, L, G, [&] { return launches < OFX_ULOG; }, enqueue, decide, ms_out);
 }

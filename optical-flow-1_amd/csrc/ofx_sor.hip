@@ -618,14 +618,13 @@ static int sor_window_loop(ofx_ctx *ctx, int G, int size, int ny, double TOL, in
             OFX_TRY(launch(w, B, (int) (s_hi - s_lo + 1), active, per * OFX_NSHARD));
         }
         LS.max_iter = ns;
-        const int seq = ofx_poll_seq(ctx);
-        const int slot = (int) (ctx->poll_seq++ % OFX_NPOLL);
-        OFX_TRY(ofx_loop_finalize_group(ctx, LS, G, per, 0, ns, &ctx->h_state[slot * OFX_MAX_GROUP], seq));
-        OFX_HIP(ctx, hipEventRecord(ctx->ev_poll[slot], ctx->stream));
-        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_poll[slot]));
+        OfxPoll poll;
+        OfxIterState fin[OFX_MAX_GROUP];
+        OFX_TRY(ofx_poll_issue(ctx, [&](OfxIterState *slot, int seq) -> int { return ofx_loop_finalize_group(ctx, LS, G, per, 0, ns, slot, seq); }, &poll));
+        OFX_TRY(ofx_poll_read(ctx, poll, G, false, fin));       // nothing in flight behind it: the event alone
         for (int g = 0; g < G; g++) {
             if (!((active >> g) & 1u)) continue;
-            const OfxIterState st = ctx->h_state[slot * OFX_MAX_GROUP + g];
+            const OfxIterState &st = fin[g];
             if (st.n < ns) OFX_TRY(take(g, st.n));              // stopped inside the batch: the state is snapshot n - 1
             n_out[g] = niter + st.n;
             err_out[g] = st.error;
@@ -667,12 +666,11 @@ static int sor_exact_loop(ofx_ctx *ctx, int size, double TOL, int maxiter, int q
             OFX_TRY(launch_plane(t, s_lo, s_hi - s_lo + 1));
         }
         LS.max_iter = ns;
-        const int slot = (int) (ctx->poll_seq++ % OFX_NPOLL);
-        OFX_TRY(ofx_loop_finalize_group(ctx, LS, 1, 0, 0, ns, &ctx->h_state[slot * OFX_MAX_GROUP], ofx_poll_seq(ctx)));
-        OFX_HIP(ctx, hipEventRecord(ctx->ev_poll[slot], ctx->stream));
-        OFX_HIP(ctx, hipEventSynchronize(ctx->ev_poll[slot]));
-        *out = ctx->h_state[slot * OFX_MAX_GROUP];
-        return OFX_OK;
+        // (this loop used to take the sequence number behind the increment of the count, one more than the other loops' polls
+        // carry; nothing waits on the number here -- the read below waits on the event alone -- so nothing observable changed)
+        OfxPoll poll;
+        OFX_TRY(ofx_poll_issue(ctx, [&](OfxIterState *slot, int seq) -> int { return ofx_loop_finalize_group(ctx, LS, 1, 0, 0, ns, slot, seq); }, &poll));
+        return ofx_poll_read(ctx, poll, 1, false, out);
     };
     while (error > TOL && niter < maxiter) {
         const int b = (maxiter - niter < batch) ? maxiter - niter : batch;

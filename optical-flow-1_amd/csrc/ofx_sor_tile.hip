@@ -358,8 +358,13 @@ __global__ __launch_bounds__(64 * NW) void k_hs_tile(typename Pix<T>::v2 *U0, ty
     }
 }
 
-static_assert(OFX_MAX_GROUP * 4 <= 64, "4 bits of `nit` per pair of a lockstep group");
-static_assert(OFX_MAX_GROUP <= 32, "one bit of incode / runmask per pair of a lockstep group");
+// the packed code of the buffers that hold the results of loops of niter[g] sweeps in units of K
+static unsigned sor_tile_result(const OfxUnitTable<2> &units, const int *niter, int K)
+{
+    int ran[OFX_MAX_GROUP];
+    for (int g = 0; g < units.G; g++) ran[g] = ofx_loop_units(niter[g], K);
+    return units.result(ran);
+}
 
 template <typename T, int K, int TH, int NW>
 static int hs_tile_launch(ofx_ctx *ctx, int G, typename Pix<T>::v2 *U0, typename Pix<T>::v2 *U1, const typename Pix<T>::v2 *A,
@@ -412,8 +417,7 @@ int ofx_hs_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *U0, typename Pix
         S.chunk = units * K;
     }
     const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
-    const unsigned b0 = *cur & all;
+    const OfxUnitTable<2> units(G, *cur);     // unit j = sweeps j K .. reads the buffer pair g started in when j is even
     // tile geometry (option "sor_tile": 0 = default): 1 = 128 x 32 pixels on 16 waves (one cell row per wave), 2 = 128 x 32 on 8,
     // 3 = 128 x 48 on 12
     const int geom = ctx->sor_tile > 0 ? ctx->sor_tile : 2;
@@ -435,32 +439,13 @@ int ofx_hs_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *U0, typename Pix
 #undef HST_GEOM
 #undef HST_GO
     };
-    auto launch = [&](int k, int cnt, double thr) -> int {
-        // unit j = k / K reads the buffer pair g started in when j is even
-        const unsigned flip = ((k / K) & 1) ? all : 0u;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
-        return go(k, 1, k, thr, b0 ^ flip, all, nit);
-    };
+    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, thr, units.code(k / K), units.all(), units.nit(cnt)); };
     auto redo = [&](const int *k_of) -> int {
-        unsigned incode = 0, runmask = 0;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) {
-            if (k_of[g] < 0) continue;
-            const int n = k_of[g] + 1, j = (n - 1) / K;
-            runmask |= 1u << g;
-            incode |= (((b0 >> g) ^ (unsigned) j) & 1u) << g;
-            nit |= (unsigned long long) (n - j * K) << (4 * g);
-        }
-        return go(0, 0, S.max_iter, -1.0, incode, runmask, nit);     // no stopping test; errors into the scratch slot
+        const auto r = units.redo(k_of, K);
+        return go(0, 0, S.max_iter, -1.0, r.incode, r.runmask, r.nit);     // no stopping test; errors into the scratch slot
     };
     OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, niter, error, ms));
-    unsigned c = 0;
-    for (int g = 0; g < G; g++) {
-        const unsigned units = (unsigned) ((niter[g] + K - 1) / K);
-        c |= (((b0 >> g) ^ units) & 1u) << g;
-    }
-    *cur = c;
+    *cur = sor_tile_result(units, niter, K);
     return OFX_OK;
 }
 
@@ -1025,7 +1010,7 @@ int ofx_brox_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename 
         S.chunk = units * K;
     }
     const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
+    const OfxUnitTable<2> units(G, 0u);       // unit j reads DU0 when j is even (every pair starts in DU0)
     auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit) -> int {
         switch (K) {
         case 1: return brox_tile_launch<T, 1, 32, 16>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, alpha, thr, incode, runmask, nit, err_stride);
@@ -1033,27 +1018,13 @@ int ofx_brox_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename 
         default: return brox_tile_launch<T, 4, 32, 16>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, alpha, thr, incode, runmask, nit, err_stride);
         }
     };
-    auto launch = [&](int k, int cnt, double thr) -> int {
-        const unsigned flip = ((k / K) & 1) ? all : 0u;      // unit j reads DU0 when j is even (every pair starts in DU0)
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
-        return go(k, 1, k, thr, flip, all, nit);
-    };
+    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, thr, units.code(k / K), units.all(), units.nit(cnt)); };
     auto redo = [&](const int *k_of) -> int {
-        unsigned incode = 0, runmask = 0;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) {
-            if (k_of[g] < 0) continue;
-            const int n = k_of[g] + 1, j = (n - 1) / K;
-            runmask |= 1u << g;
-            incode |= ((unsigned) j & 1u) << g;
-            nit |= (unsigned long long) (n - j * K) << (4 * g);
-        }
-        return go(0, 0, S.max_iter, -1.0, incode, runmask, nit);
+        const auto r = units.redo(k_of, K);
+        return go(0, 0, S.max_iter, -1.0, r.incode, r.runmask, r.nit);
     };
     OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, niter, error, ms));
-    unsigned in1 = 0;
-    for (int g = 0; g < G; g++) in1 |= ((unsigned) ((niter[g] + K - 1) / K) & 1u) << g;
+    const unsigned in1 = sor_tile_result(units, niter, K);
     if (in1) {
         const size_t npix = (size_t) nx * ny;
         hipLaunchKernelGGL((k_copy_pairs<typename Pix<T>::v2>), dim3((unsigned) ((npix + 255) / 256), G), dim3(256), 0, ctx->stream,
@@ -1369,7 +1340,9 @@ int ofx_broxt_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename
         };
         return ofx_run_loop_group(ctx, S, G, launch, [](const int *) { return OFX_OK; }, niter, error, ms);
     }
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
+    // unit j = sweeps j K .. j K + K - 1 reads DU0 when j is even (every sequence starts in DU0; one that has stopped leaves at
+    // the kernel's own test, before it writes)
+    const OfxUnitTable<2> units(G, 0u);
     auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit) -> int {
         switch (K) {
         case 1: return broxt_tile_launch<T, 1>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, nz, alpha, thr, incode, runmask, nit, err_stride);
@@ -1377,29 +1350,14 @@ int ofx_broxt_tile_solve(ofx_ctx *ctx, int G, typename Pix<T>::v2 *DU0, typename
         default: return broxt_tile_launch<T, 4>(ctx, G, DU0, DU1, CO, Dm, Ps, k0, check, slot0, nx, ny, nz, alpha, thr, incode, runmask, nit, err_stride);
         }
     };
-    // unit j = sweeps j K .. j K + K - 1 reads DU0 when j is even (every sequence starts in DU0; one that has stopped leaves at
-    // the kernel's own test, before it writes)
-    auto launch = [&](int k, int cnt, double thr) -> int {
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
-        return go(k, 1, k, thr, ((k / K) & 1) ? all : 0u, all, nit);
-    };
+    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, thr, units.code(k / K), units.all(), units.nit(cnt)); };
     // the sequences that stopped inside a launch unit: its first sweeps again from the unit's input, each in its own phase
     auto redo = [&](const int *k_of) -> int {
-        unsigned incode = 0, runmask = 0;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) {
-            if (k_of[g] < 0) continue;
-            const int n = k_of[g] + 1, j = (n - 1) / K;
-            runmask |= 1u << g;
-            incode |= ((unsigned) j & 1u) << g;
-            nit |= (unsigned long long) (n - j * K) << (4 * g);
-        }
-        return go(0, 0, S.max_iter, -1.0, incode, runmask, nit);
+        const auto r = units.redo(k_of, K);
+        return go(0, 0, S.max_iter, -1.0, r.incode, r.runmask, r.nit);
     };
     OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, niter, error, ms));
-    unsigned in1 = 0;
-    for (int g = 0; g < G; g++) in1 |= ((unsigned) ((niter[g] + K - 1) / K) & 1u) << g;
+    const unsigned in1 = sor_tile_result(units, niter, K);
     if (in1) {
         const size_t n1 = (size_t) nx * ny * nz;
         hipLaunchKernelGGL((k_copy_pairs<v2>), dim3((unsigned) ((n1 + 255) / 256), G), dim3(256), 0, ctx->stream, (const v2 *) DU1, DU0, n1, in1);

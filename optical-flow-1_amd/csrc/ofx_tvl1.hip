@@ -1411,46 +1411,13 @@ static int tvl1_pick_rows(const ofx_ctx *ctx, int nx, int ny, int G)
     return 1;
 }
 
-// Strip height of the fused two-iteration kernel.  A wave of a strip of r rows executes r + 3 marching
-// steps (+ ~2 steps of start-up).  At 142 VGPRs the chip holds 3 waves per SIMD = 3072 waves at once, so a
-// launch of W waves takes k = ceil(W / 3072) rounds of about (r + 5) step times.  The best strip height is
-// therefore the SMALLEST r whose wave count still fits k rounds exactly (1080p: r = 12 -> 32 x 90 = 2880
-// waves, one round; r = 8 -> 4320 waves = 1.4 rounds is 9 % slower), minimised over k.  Measured on the
-// bench workload at every pyramid level: profiles/r01_g_rows2_on_bench_workload.txt.  A lockstep group of
-// G pairs is G times the waves of one pair.
+// Strip height of the fused two-iteration kernel: the model of ofx_pick_strip_rows (ofx_loop_plan.h) with r + 3 marching steps
+// per strip of r rows + ~2 of start-up, and 3 waves per SIMD at 142 VGPRs.  Measured on the bench workload at every pyramid level:
+// profiles/r01_g_rows2_on_bench_workload.txt.
 static int tvl1_pick_rows2(const ofx_ctx *ctx, int nx, int ny, int G)
 {
     if (ctx->rows_per_wave2 > 0) return ctx->rows_per_wave2;
-    const long strips_pad = (long) ofx_cdiv(ofx_cdiv(nx, STRIP2_OUT), 4) * 4 * G;
-    const int rmax = 24;
-    int best = rmax;
-    long best_cost = -1;
-    if (ctx->concurrency > 1) {
-        // Several contexts share the device (option "concurrency"): other pairs' waves fill this launch's
-        // partial rounds, so what counts is the total work  ~ ceil(W / 1024 SIMDs) * (r + 5)  -- taller
-        // strips, less halo recomputation (measured with 4 pairs in flight: +8 % job throughput over the
-        // single-pair choice).
-        static const int cand[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 20, 24};
-        for (int r : cand) {
-            const long waves = strips_pad * ofx_cdiv(ny, r);
-            const long slots = ctx->rows_slots > 0 ? ctx->rows_slots : 1024;
-            const long cost = ((waves + slots - 1) / slots) * (r + 5);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
-        }
-        return best;
-    }
-    const long slots = 1024L * OFX_ITER2_WAVES;
-    for (int k = 1; k <= 4; k++) {
-        for (int r = 1; r <= rmax; r++) {
-            if (strips_pad * ofx_cdiv(ny, r) > k * slots) continue;
-            const long cost = (long) k * (r + 5);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
-            break;
-        }
-    }
-    // very short strips triple the halo work; keep 3 rows as long as that still leaves >= 512 waves
-    if (best < 3 && strips_pad * ofx_cdiv(ny, 3) >= 512) best = 3;
-    return best;
+    return ofx_pick_strip_rows(ofx_strip_model2(STRIP2_OUT, OFX_ITER2_WAVES), nx, ny, G, ctx->concurrency, ctx->rows_slots, INT_MAX);
 }
 
 static int tvl1_pick_chunk(const ofx_ctx *ctx, int nx, int ny, int G)
@@ -1473,19 +1440,9 @@ static int tvl1_pick_tile(const ofx_ctx *ctx, int nx, int ny, int G)
     return ctx->tile == 6 ? 6 : 4;
 }
 
-template <typename T> struct Tvl1Level;
-struct Tvl1Params;
-template <typename T>
-static int tvl1_run_iterations_tile(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int K, int *n_out,
-                                    double *err_out, float *ms_out, int *alt_out);
-template <typename T>
-static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int N, int *n_out, double *err_out,
-                                   float *ms_out, int *alt_out);
-
 // strip height of the three- / four-iteration kernel: tvl1_pick_rows2's model with r + 7 / r + 9 marching steps per strip
 static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G, int N = 3)
 {
-    const int depth = 2 * N + 1;                            // marching steps of a strip beyond its rows
     if (ctx->rows_per_wave3 > 0) return ctx->rows_per_wave3;
     {   // A/B knob only: OFX_ROWS3="ny:rows/ny:rows" forces the strip height on the levels of the given heights
         static const char *tab = getenv("OFX_ROWS3");
@@ -1496,32 +1453,7 @@ static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G, int N = 3)
             if (q) q++;
         }
     }
-    const long strips_pad = (long) ofx_cdiv(ofx_cdiv(nx, STRIP3_OUT), 4) * 4 * G;
-    const int rmax = 32;
-    int best = rmax;
-    long best_cost = -1;
-    if (ctx->concurrency > 1) {
-        static const int cand[] = {2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32, 36, 40, 48, 54, 64, 72, 80, 96};
-        for (int r : cand) {
-            if (r > ctx->rows3_max) break;
-            const long waves = strips_pad * ofx_cdiv(ny, r);
-            const long slots = ctx->rows_slots > 0 ? ctx->rows_slots : 1024;
-            const long cost = ((waves + slots - 1) / slots) * (r + depth);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
-        }
-        return best;
-    }
-    const long slots = 1024L * OFX_ITER3_WAVES;
-    for (int k = 1; k <= 4; k++) {
-        for (int r = 1; r <= rmax; r++) {
-            if (strips_pad * ofx_cdiv(ny, r) > k * slots) continue;
-            const long cost = (long) k * (r + depth);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = r; }
-            break;
-        }
-    }
-    if (best < 4 && strips_pad * ofx_cdiv(ny, 4) >= 512) best = 4;
-    return best;
+    return ofx_pick_strip_rows(ofx_strip_model3(N, STRIP3_OUT, OFX_ITER3_WAVES), nx, ny, G, ctx->concurrency, ctx->rows_slots, ctx->rows3_max);
 }
 
 // pixels x pairs from which option fuse4 = 2 takes four iterations per launch.  On the job (four contexts, 1080p, groups of 5;
@@ -1530,6 +1462,139 @@ static int tvl1_pick_rows3(const ofx_ctx *ctx, int nx, int ny, int G, int N = 3)
 #ifndef TVL1_FUSE4_AUTO_PX
 #define TVL1_FUSE4_AUTO_PX 2e6
 #endif
+// What the iteration launches of one loop share whichever kernel runs them: the scalars, which instantiation of a kernel
+// family, and where unit j of pair g finds its buffers -- unit j reads buffer (b_g + j) % 3 of the rotation and writes
+// (b_g + j + 1) % 3 (OfxUnitTable, ofx_loop_plan.h).
+template <typename T> struct Tvl1Launch {
+    double l_t, taut, theta;
+    bool strict;            // the reference's dual update bit for bit (double storage, option "relaxed_dual" off)
+    bool nt_stores;         // one launch touches 15 storage elements per pixel; beyond the Infinity Cache its output is streamed out
+    int err_stride;
+    OfxUnitTable<3> units;
+    Tvl1Launch(const ofx_ctx *ctx, const Tvl1Level<T> &L, const Tvl1Params &P)
+        : l_t(P.lambda * P.theta), taut(P.tau / P.theta), theta(P.theta), strict(sizeof(T) == sizeof(double) && !ctx->relaxed_dual),
+          nt_stores(ctx->nt_stores ? ctx->nt_stores == 1 : (double) L.nx * L.ny * L.G * 15.0 * sizeof(T) > 300e6),
+          err_stride((P.max_iter + 1) * OFX_NSHARD), units(L.G, L.cur)
+    {
+    }
+    // fam(NT, STRICT) names a kernel family's instantiation for two std::bool_constant values; float storage has no strict ones
+    template <class Fam> auto kernel(Fam fam) const -> decltype(fam(std::false_type{}, std::false_type{}))
+    {
+        if constexpr (sizeof(T) == sizeof(double)) {
+            if (strict) return nt_stores ? fam(std::true_type{}, std::true_type{}) : fam(std::false_type{}, std::true_type{});
+        }
+        return nt_stores ? fam(std::true_type{}, std::false_type{}) : fam(std::false_type{}, std::false_type{});
+    }
+    // the loops are over: the results are where ran[g] units (+ took_alt[g]) left them
+    void done(Tvl1Level<T> &L, const int *ran, const int *took_alt, const int *n_out) const
+    {
+        L.cur = units.result(ran, took_alt);
+        for (int g = 0; g < L.G; g++) L.last_n[g] = n_out[g];
+    }
+};
+
+// tvl1_run_iterations through k_tvl1_tile: launch unit j = iterations [j K, j K + K); a loop that ends inside a unit is finished
+// by one more launch that re-runs the unit's first n - j K iterations from its input (every pair with its own count).
+template <typename T>
+static int tvl1_run_iterations_tile(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Launch<T> &A, LoopSpec S, int K, int *n_out,
+                                    double *err_out, float *ms_out, int *alt_out)
+{
+    const int nx = L.nx, ny = L.ny, G = L.G;
+    const int OW = 64 - 2 * K, OH = TILE_RH - 2 * K;
+    const int tiles_x = ofx_cdiv(nx, OW), tiles_y = ofx_cdiv(ny, OH);
+    const dim3 grid((unsigned) (tiles_x * tiles_y), G), block(64 * TILE_RH);
+    S.pairs = false;
+    S.fuse = K;
+    S.afac = 0.0;
+    // a launch of K iterations takes ~2 us + K x 1.5 us whatever the level's size; one poll per ~40 us
+    if (ctx->chunk <= 0) S.chunk = 6 * K;
+    auto kern = A.kernel([&](auto, auto ST) { return K == 6 ? k_tvl1_tile<T, decltype(ST)::value, 6> : k_tvl1_tile<T, decltype(ST)::value, 4>; });
+    auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit) -> int {
+        hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k0, check,
+                           slot0, nx, ny, tiles_x, A.l_t, A.theta, A.taut, thr, incode, runmask, nit, A.err_stride);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    };
+    auto launch = [&](int k, int cnt, double thr) -> int { return go(k, 1, k, thr, A.units.code(k / K), A.units.all(), A.units.nit(cnt)); };
+    auto redo = [&](const int *k_of) -> int {
+        const auto r = A.units.redo(k_of, K);
+        // no stopping test; the errors go to the scratch slot behind the loop's own (all K of them into it: never read)
+        return go(0, 0, S.max_iter, -1.0, r.incode, r.runmask, r.nit);
+    };
+    OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out));
+    int ran[OFX_MAX_GROUP];
+    for (int g = 0; g < G; g++) {
+        ran[g] = ofx_loop_units(n_out[g], K);
+        if (alt_out) alt_out[g] = 0;
+    }
+    A.done(L, ran, nullptr, n_out);
+    return OFX_OK;
+}
+
+// tvl1_run_iterations through k_tvl1_iter3 (N = 3) or k_tvl1_iter4 (N = 4) as a CURSOR loop (ofx_loop.h): launch number j is
+// unit j and runs N iterations -- fewer once the loop is about to stop (tvl1_unit) --, so where a
+// unit starts is device state.  A loop that still ends inside a unit is finished by one more launch that re-runs the unit's first
+// n - k0 iterations from its input (every pair with its own count).  Option "fuse3_cursor" = 0: the round-3 scheme, fixed units of
+// N iterations with the iteration index passed from the host.
+template <typename T>
+static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Launch<T> &A, LoopSpec S, int N, int *n_out, double *err_out,
+                                   float *ms_out, int *alt_out)
+{
+    const int nx = L.nx, ny = L.ny, G = L.G;
+    const int rows = tvl1_pick_rows3(ctx, nx, ny, G, N);
+    const int strips_x = ofx_cdiv(nx, STRIP3_OUT), strips_pad = ofx_cdiv(strips_x, 4) * 4;
+    const dim3 grid((unsigned) (strips_pad / 4) * ofx_cdiv(ny, rows), G), block(256);
+    S.pairs = false;
+    S.fuse = N;
+    S.afac = 0.0;
+    const bool cursor = ctx->fuse3_cursor != 0 && !S.fixed;
+    // the error decays by 6-14 % per iteration near the threshold: within afac2 the loop has a handful of iterations left,
+    // within afac1 the next one is the last more often than not (A/B on one box, profiles/r04_ab_cursor_loop.txt: fixed units of three 68.1k, cursor loop 71.2-71.6k Mpix*warp-iters/s whatever the two ratios in 1.08-1.2 / 1.3-2.0; 1.2 leaves the fewest re-runs)
+    const double afac2 = ctx->fuse3_afac2 > 0 ? ctx->fuse3_afac2 : 1.5, afac1 = ctx->fuse3_afac1 > 0 ? ctx->fuse3_afac1 : 1.2;
+    // units of four have a third ratio, within which a unit runs three iterations (option "fuse4_afac3").  Measured on the job
+    // (profiles/r05_iter4_ab.txt): 1.6 costs 0.5 %, 2.4 costs 2.5 % against none -- three iterations in the four-iteration kernel
+    // cost as much per iteration as k_tvl1_iter3, and a wasted fourth less than that.  0 (default) = afac2: never three.
+    const double afac3 = ctx->fuse4_afac3 > 0 ? ctx->fuse4_afac3 : afac2;
+    auto kern = A.kernel([&](auto NT, auto ST) {
+        return N == 4 ? k_tvl1_iter4<T, decltype(NT)::value, decltype(ST)::value> : k_tvl1_iter3<T, decltype(NT)::value, decltype(ST)::value>;
+    });
+    auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit, OfxLoopDev *dev,
+                  int launch) -> int {
+        hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k0, check,
+                           slot0, nx, ny, rows, strips_x, strips_pad, A.l_t, A.theta, A.taut, thr, incode, runmask, nit, A.err_stride, dev,
+                           launch, afac1, afac2, afac3, S.max_iter);
+        OFX_LAUNCH_CHECK(ctx);
+        return OFX_OK;
+    };
+    // a re-run: no stopping test, errors into the scratch slot
+    auto rerun = [&](const OfxUnitTable<3>::Redo &r) -> int { return go(0, 0, S.max_iter, -1.0, r.incode, r.runmask, r.nit, nullptr, 0); };
+    int ran[OFX_MAX_GROUP];                 // units up to the one that contains iteration n - 1: the result is its output
+    int inside[OFX_MAX_GROUP];
+    if (cursor) {
+        // (ctx->d_state is read at launch time: the loop driver may re-allocate the state block before the first launch)
+        auto launch = [&](int j, double thr) -> int {
+            return go(0, 1, 0, thr, A.units.code((unsigned) j), A.units.all(), 0ull, reinterpret_cast<OfxLoopDev *>(ctx->d_state), j);
+        };
+        auto redo = [&](const int *n_of, const int *k0_of, const int *u_of) -> int { return rerun(A.units.redo(n_of, k0_of, u_of)); };
+        const int upc = (S.chunk + N - 1) / N < 1 ? 1 : (S.chunk + N - 1) / N;
+        OFX_TRY(ofx_run_loop_cursor(ctx, S, G, upc, N, launch, redo, n_out, err_out, ran, inside, ms_out));
+        for (int g = 0; g < G; g++) ran[g]++;                       // unit_out: the unit's number, -1 when nothing ran
+    } else {
+        auto launch = [&](int k, int cnt, double thr) -> int {
+            return go(k, 1, k, thr, A.units.code((unsigned) (k / N)), A.units.all(), A.units.nit(cnt), nullptr, 0);
+        };
+        auto redo = [&](const int *k_of) -> int { return rerun(A.units.redo(k_of, N)); };
+        OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out));
+        for (int g = 0; g < G; g++) {
+            ran[g] = ofx_loop_units(n_out[g], N);
+            inside[g] = ofx_loop_inside(n_out[g], N, S.max_iter) ? 1 : 0;
+        }
+    }
+    for (int g = 0; g < G && alt_out; g++) alt_out[g] = inside[g] ? 1 : 0;      // ended inside a unit: its first iterations were re-run
+    A.done(L, ran, nullptr, n_out);
+    return OFX_OK;
+}
+
 // The inner loop of one warp (src/tvl1flow.cpp:111-182) for all pairs of the group in lockstep.  On return
 // L.cur points at the halves holding the results; n_out[g] / err_out[g] are what the reference prints.
 template <typename T>
@@ -1539,7 +1604,7 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
 {
     const int nx = L.nx, ny = L.ny, G = L.G;
     if ((long long) nx * ny >= (1LL << 27)) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1: image larger than 2^27 pixels");
-    const double l_t = P.lambda * P.theta, taut = P.tau / P.theta, theta = P.theta;
+    const Tvl1Launch<T> A(ctx, L, P);
     const bool pairs = ctx->fuse2 != 0;
     // geometry of the one-iteration kernel (also used for a trailing single iteration and the redo)
     const int rows = tvl1_pick_rows(ctx, nx, ny, G);
@@ -1561,7 +1626,7 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
     // small levels: K iterations per launch on 2-D tiles (k_tvl1_tile) instead of the marching strips
     const int tileK = tvl1_pick_tile(ctx, nx, ny, G);
     if (unit_out) *unit_out = tileK ? tileK : (pairs ? 2 : 1);
-    if (tileK) return tvl1_run_iterations_tile<T>(ctx, L, P, S, tileK, n_out, err_out, ms_out, alt_out);
+    if (tileK) return tvl1_run_iterations_tile<T>(ctx, L, A, S, tileK, n_out, err_out, ms_out, alt_out);
     // Three iterations per launch (k_tvl1_iter3; option "fuse3": 0 never, 1 on every level of at least fuse3_min_px pixels x
     // pairs, 2 = by measurement, the default).  Measured on one box, interleaved (profiles/r03_q_ab_three_iterations_per_launch.txt):
     // the tolerance mode's job 55.8k -> 61.8k Mpix*warp-iters/s, fixed work 79.8k -> 103.7k; the strict mode, bound by FP64 issue
@@ -1569,10 +1634,9 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
     // of r + 7 instead of r + 5 marching steps): so 2 = not strict, pairs in lockstep or contexts sharing the device, and a level
     // of at least 500 000 pixels x pairs.
     {
-        const bool strict_mode = sizeof(T) == sizeof(double) && !ctx->relaxed_dual;
         const double px = (double) nx * ny * G;
         const bool tri = ctx->fuse3 == 1 ? px >= ctx->fuse3_min_px
-                                         : (ctx->fuse3 == 2 && !strict_mode && (G >= 2 || ctx->concurrency > 1) &&
+                                         : (ctx->fuse3 == 2 && !A.strict && (G >= 2 || ctx->concurrency > 1) &&
                                             px >= (ctx->fuse3_min_px > 0 ? ctx->fuse3_min_px : 5e5));
         // Four per launch (k_tvl1_iter4; option "fuse4": 0 never, 1 on every level of at least fuse4_min_px pixels x pairs,
         // 2 = by measurement, the default): where three would run by the rule above and the level has at least
@@ -1582,22 +1646,12 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
                                              px >= (ctx->fuse4_min_px > 0 ? ctx->fuse4_min_px : TVL1_FUSE4_AUTO_PX));
         if (pairs && (tri || quad)) {
             if (unit_out) *unit_out = quad ? 4 : 3;
-            return tvl1_run_iterations_tri<T>(ctx, L, P, S, quad ? 4 : 3, n_out, err_out, ms_out, alt_out);
+            return tvl1_run_iterations_tri<T>(ctx, L, A, S, quad ? 4 : 3, n_out, err_out, ms_out, alt_out);
         }
     }
-    const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
-    // one launch touches 15 storage elements per pixel; beyond the Infinity Cache its output is streamed out
-    const bool nt_stores = ctx->nt_stores ? ctx->nt_stores == 1 : (double) nx * ny * G * 15.0 * sizeof(T) > 300e6;
-    // Launch unit j (a fused pair of iterations, or a single one) of pair g reads buffer (b_g + j) % 3 of the rotation
-    // and writes (b_g + j + 1) % 3; (b_g + j + 2) % 3 receives the intermediate state of a fused pair (tvl1_store_a).
-    unsigned b0[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) b0[g] = L.curidx(g);
-    auto code_of = [&](unsigned unit) -> unsigned {
-        unsigned c = 0;
-        for (int g = 0; g < G; g++) c |= ((b0[g] + unit) % 3u) << (2 * g);
-        return c;
-    };
+    // A launch unit is a fused pair of iterations, or a single one; the third buffer of the rotation, (b_g + j + 2) % 3, receives
+    // the intermediate state of a fused pair (tvl1_store_a).
+    const int F = pairs ? 2 : 1;
     // intermediate state: stored when the previous error is within this factor of the threshold ...
     // (option "store_a": 0 = never, 2 = always -- 1e300 stands for "any error" -- for the tests)
     const bool sa = pairs && !P.fixed && ctx->store_a != 0;
@@ -1607,27 +1661,21 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
     if (sa)
         for (int g = 0; g < G; g++)
             if (ctx->store_a == 2 || (L.last_n[g] >= 1 && L.last_n[g] <= 2)) amask0 |= 1u << g;
-    // strict: the reference's dual update bit for bit (double storage, option "relaxed_dual" off)
-    const bool strict = sizeof(T) == sizeof(double) && !ctx->relaxed_dual;
+    auto kern1 = A.kernel([](auto, auto ST) { return k_tvl1_iter<T, decltype(ST)::value>; });
+    auto kern2 = A.kernel([](auto NT, auto ST) { return k_tvl1_iter2<T, decltype(NT)::value, decltype(ST)::value>; });
     auto single = [&](unsigned incode, unsigned runmask, int check, int slot, double thr) -> int {
-        auto kern = k_tvl1_iter<T, false>;
-        if constexpr (sizeof(T) == sizeof(double)) { if (strict) kern = k_tvl1_iter<T, true>; }
-        hipLaunchKernelGGL(kern, dim3(gx1, G), block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R,
-                           ctx->d_err, check, slot, nx, ny, rows, strips_x, strips_pad, l_t, theta, taut, thr, incode, runmask,
-                           err_stride);
+        hipLaunchKernelGGL(kern1, dim3(gx1, G), block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R,
+                           ctx->d_err, check, slot, nx, ny, rows, strips_x, strips_pad, A.l_t, A.theta, A.taut, thr, incode, runmask,
+                           A.err_stride);
         OFX_LAUNCH_CHECK(ctx);
         return OFX_OK;
     };
     auto launch = [&](int k, int cnt, double thr) -> int {
-        const unsigned incode = code_of((unsigned) (pairs ? k / 2 : k));
-        if (cnt == 1) return single(incode, all, k, k, thr);
+        const unsigned incode = A.units.code((unsigned) (k / F));
+        if (cnt == 1) return single(incode, A.units.all(), k, k, thr);
         const unsigned amask = k == 0 ? amask0 : 0u;
-        auto kern = nt_stores ? k_tvl1_iter2<T, true, false> : k_tvl1_iter2<T, false, false>;
-        if constexpr (sizeof(T) == sizeof(double)) {
-            if (strict) kern = nt_stores ? k_tvl1_iter2<T, true, true> : k_tvl1_iter2<T, false, true>;
-        }
-        hipLaunchKernelGGL(kern, grid2, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k, nx,
-                           ny, rows2, strips2_x, strips2_pad, l_t, theta, taut, thr, incode, amask, S.afac, err_stride);
+        hipLaunchKernelGGL(kern2, grid2, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k, nx,
+                           ny, rows2, strips2_x, strips2_pad, A.l_t, A.theta, A.taut, thr, incode, amask, S.afac, A.err_stride);
         OFX_LAUNCH_CHECK(ctx);
         return OFX_OK;
     };
@@ -1635,203 +1683,18 @@ static int tvl1_run_iterations(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &
     // buffer: recompute that iteration alone (no stopping test, error into the scratch slot) from the unit's input
     // buffer into its output buffer -- one launch for all of them (runmask)
     auto redo = [&](const int *k_of) -> int {
-        unsigned incode = 0, runmask = 0;
-        for (int g = 0; g < G; g++) {
-            if (k_of[g] < 0) continue;
-            runmask |= 1u << g;
-            incode |= ((b0[g] + (unsigned) (k_of[g] / 2)) % 3u) << (2 * g);
-        }
-        return single(incode, runmask, 0, S.max_iter, -1.0);
+        const auto r = A.units.redo(k_of, F);
+        return single(r.incode, r.runmask, 0, S.max_iter, -1.0);
     };
-    int took_alt[OFX_MAX_GROUP];
+    int took_alt[OFX_MAX_GROUP], ran[OFX_MAX_GROUP];
     OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out, amask0, took_alt));
-    unsigned cur = 0;
     for (int g = 0; g < G; g++) {
-        const unsigned units = (unsigned) (pairs ? (n_out[g] + 1) / 2 : n_out[g]);
-        // normally the result is the output of the last unit = the input of the next; a loop that stopped on the first
-        // iteration of a pair whose intermediate state was stored continues from the unit's third buffer instead
-        cur |= ((b0[g] + units + (took_alt[g] ? 1u : 0u)) % 3u) << (2 * g);
-        L.last_n[g] = n_out[g];
-        if (alt_out) alt_out[g] = (pairs && (n_out[g] & 1) && n_out[g] != S.max_iter) ? (took_alt[g] ? 2 : 1) : 0;
+        ran[g] = ofx_loop_units(n_out[g], F);
+        if (alt_out) alt_out[g] = ofx_loop_inside(n_out[g], F, S.max_iter) ? (took_alt[g] ? 2 : 1) : 0;
     }
-    L.cur = cur;
-    return OFX_OK;
-}
-
-static_assert(OFX_MAX_GROUP * 4 <= 64 && OFX_MAX_GROUP * 2 <= 32,
-              "k_tvl1_tile / k_tvl1_iter3 pack 4 bits of iteration count (`nit`, 64 bits) and 2 bits of buffer index (`incode`, 32 bits) per pair");
-// tvl1_run_iterations through k_tvl1_tile: launch unit j = iterations [j K, j K + K) reads buffer (b_g + j) % 3 and writes
-// (b_g + j + 1) % 3; a loop that ends inside a unit is finished by one more launch that re-runs the unit's first n - j K
-// iterations from its input (every pair with its own count).
-template <typename T>
-static int tvl1_run_iterations_tile(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int K, int *n_out,
-                                    double *err_out, float *ms_out, int *alt_out)
-{
-    const int nx = L.nx, ny = L.ny, G = L.G;
-    const double l_t = P.lambda * P.theta, taut = P.tau / P.theta, theta = P.theta;
-    const bool strict = sizeof(T) == sizeof(double) && !ctx->relaxed_dual;
-    const int OW = 64 - 2 * K, OH = TILE_RH - 2 * K;
-    const int tiles_x = ofx_cdiv(nx, OW), tiles_y = ofx_cdiv(ny, OH);
-    const dim3 grid((unsigned) (tiles_x * tiles_y), G), block(64 * TILE_RH);
-    S.pairs = false;
-    S.fuse = K;
-    S.afac = 0.0;
-    // a launch of K iterations takes ~2 us + K x 1.5 us whatever the level's size; one poll per ~40 us
-    if (ctx->chunk <= 0) S.chunk = 6 * K;
-    const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
-    unsigned b0[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) b0[g] = L.curidx(g);
-    auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit) -> int {
-        auto kern = K == 6 ? k_tvl1_tile<T, false, 6> : k_tvl1_tile<T, false, 4>;
-        if constexpr (sizeof(T) == sizeof(double)) {
-            if (strict) kern = K == 6 ? k_tvl1_tile<T, true, 6> : k_tvl1_tile<T, true, 4>;
-        }
-        hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k0, check,
-                           slot0, nx, ny, tiles_x, l_t, theta, taut, thr, incode, runmask, nit, err_stride);
-        OFX_LAUNCH_CHECK(ctx);
-        return OFX_OK;
-    };
-    auto launch = [&](int k, int cnt, double thr) -> int {
-        unsigned incode = 0;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) {
-            incode |= ((b0[g] + (unsigned) (k / K)) % 3u) << (2 * g);
-            nit |= (unsigned long long) cnt << (4 * g);
-        }
-        return go(k, 1, k, thr, incode, all, nit);
-    };
-    auto redo = [&](const int *k_of) -> int {
-        unsigned incode = 0, runmask = 0;
-        unsigned long long nit = 0;
-        for (int g = 0; g < G; g++) {
-            if (k_of[g] < 0) continue;
-            const int n = k_of[g] + 1, j = (n - 1) / K;
-            runmask |= 1u << g;
-            incode |= ((b0[g] + (unsigned) j) % 3u) << (2 * g);
-            nit |= (unsigned long long) (n - j * K) << (4 * g);
-        }
-        // no stopping test; the errors go to the scratch slot behind the loop's own (all K of them into it: never read)
-        return go(0, 0, S.max_iter, -1.0, incode, runmask, nit);
-    };
-    int took_alt[OFX_MAX_GROUP];
-    OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out, 0u, took_alt));
-    unsigned cur = 0;
-    for (int g = 0; g < G; g++) {
-        const unsigned units = (unsigned) ((n_out[g] + K - 1) / K);
-        cur |= ((b0[g] + units) % 3u) << (2 * g);
-        L.last_n[g] = n_out[g];
-        if (alt_out) alt_out[g] = 0;
-    }
-    L.cur = cur;
-    return OFX_OK;
-}
-
-// tvl1_run_iterations through k_tvl1_iter3 (N = 3) or k_tvl1_iter4 (N = 4) as a CURSOR loop (ofx_loop.h): launch L reads buffer
-// (b_g + L) % 3 of the rotation and writes (b_g + L + 1) % 3 and runs N iterations -- fewer once the loop is about to stop
-// (tvl1_unit) --, so where a
-// unit starts is device state.  A loop that still ends inside a unit is finished by one more launch that re-runs the unit's first
-// n - k0 iterations from its input (every pair with its own count).  Option "fuse3_cursor" = 0: the round-3 scheme, fixed units of
-// N iterations with the iteration index passed from the host.
-template <typename T>
-static int tvl1_run_iterations_tri(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params &P, LoopSpec S, int N, int *n_out, double *err_out,
-                                   float *ms_out, int *alt_out)
-{
-    const int nx = L.nx, ny = L.ny, G = L.G;
-    const double l_t = P.lambda * P.theta, taut = P.tau / P.theta, theta = P.theta;
-    const bool strict = sizeof(T) == sizeof(double) && !ctx->relaxed_dual;
-    const int rows = tvl1_pick_rows3(ctx, nx, ny, G, N);
-    const int strips_x = ofx_cdiv(nx, STRIP3_OUT), strips_pad = ofx_cdiv(strips_x, 4) * 4;
-    const dim3 grid((unsigned) (strips_pad / 4) * ofx_cdiv(ny, rows), G), block(256);
-    const bool nt_stores = ctx->nt_stores ? ctx->nt_stores == 1 : (double) nx * ny * G * 15.0 * sizeof(T) > 300e6;
-    S.pairs = false;
-    S.fuse = N;
-    S.afac = 0.0;
-    const int err_stride = (S.max_iter + 1) * OFX_NSHARD;
-    const unsigned all = (G >= 32) ? 0xFFFFFFFFu : ((1u << G) - 1u);
-    unsigned b0[OFX_MAX_GROUP];
-    for (int g = 0; g < G; g++) b0[g] = L.curidx(g);
-    const bool cursor = ctx->fuse3_cursor != 0 && !S.fixed;
-    // the error decays by 6-14 % per iteration near the threshold: within afac2 the loop has a handful of iterations left,
-    // within afac1 the next one is the last more often than not (A/B on one box, profiles/r04_ab_cursor_loop.txt: fixed units of three 68.1k, cursor loop 71.2-71.6k Mpix*warp-iters/s whatever the two ratios in 1.08-1.2 / 1.3-2.0; 1.2 leaves the fewest re-runs)
-    const double afac2 = ctx->fuse3_afac2 > 0 ? ctx->fuse3_afac2 : 1.5, afac1 = ctx->fuse3_afac1 > 0 ? ctx->fuse3_afac1 : 1.2;
-    // units of four have a third ratio, within which a unit runs three iterations (option "fuse4_afac3").  Measured on the job
-    // (profiles/r05_iter4_ab.txt): 1.6 costs 0.5 %, 2.4 costs 2.5 % against none -- three iterations in the four-iteration kernel
-    // cost as much per iteration as k_tvl1_iter3, and a wasted fourth less than that.  0 (default) = afac2: never three.
-    const double afac3 = ctx->fuse4_afac3 > 0 ? ctx->fuse4_afac3 : afac2;
-    auto go = [&](int k0, int check, int slot0, double thr, unsigned incode, unsigned runmask, unsigned long long nit, OfxLoopDev *dev,
-                  int launch) -> int {
-        auto kern = nt_stores ? k_tvl1_iter3<T, true, false> : k_tvl1_iter3<T, false, false>;
-        if (N == 4) kern = nt_stores ? k_tvl1_iter4<T, true, false> : k_tvl1_iter4<T, false, false>;
-        if constexpr (sizeof(T) == sizeof(double)) {
-            if (strict) kern = nt_stores ? k_tvl1_iter3<T, true, true> : k_tvl1_iter3<T, false, true>;
-            if (strict && N == 4) kern = nt_stores ? k_tvl1_iter4<T, true, true> : k_tvl1_iter4<T, false, true>;
-        }
-        hipLaunchKernelGGL(kern, grid, block, 0, ctx->stream, L.Ut(), L.P1t(), L.P2t(), L.A, (const T *) L.R, ctx->d_err, k0, check,
-                           slot0, nx, ny, rows, strips_x, strips_pad, l_t, theta, taut, thr, incode, runmask, nit, err_stride, dev, launch,
-                           afac1, afac2, afac3, S.max_iter);
-        OFX_LAUNCH_CHECK(ctx);
-        return OFX_OK;
-    };
-    auto code_of_unit = [&](unsigned unit) -> unsigned {
-        unsigned c = 0;
-        for (int g = 0; g < G; g++) c |= ((b0[g] + unit) % 3u) << (2 * g);
-        return c;
-    };
-    int unit_of[OFX_MAX_GROUP];
-    int inside[OFX_MAX_GROUP];
-    if (cursor) {
-        // (ctx->d_state is read at launch time: the loop driver may re-allocate the state block before the first launch)
-        auto launch = [&](int Lidx, double thr) -> int {
-            return go(0, 1, 0, thr, code_of_unit((unsigned) Lidx), all, 0ull, reinterpret_cast<OfxLoopDev *>(ctx->d_state), Lidx);
-        };
-        auto redo = [&](const int *n_of, const int *k0_of, const int *u_of) -> int {
-            unsigned incode = 0, runmask = 0;
-            unsigned long long nit = 0;
-            for (int g = 0; g < G; g++) {
-                if (n_of[g] < 0) continue;
-                runmask |= 1u << g;
-                incode |= ((b0[g] + (unsigned) u_of[g]) % 3u) << (2 * g);
-                nit |= (unsigned long long) (n_of[g] - k0_of[g]) << (4 * g);
-            }
-            return go(0, 0, S.max_iter, -1.0, incode, runmask, nit, nullptr, 0);    // no stopping test; errors into the scratch slot
-        };
-        const int upc = (S.chunk + N - 1) / N < 1 ? 1 : (S.chunk + N - 1) / N;
-        // the cursor loop reserves G * (max_iter + 1) slots itself; make sure the state block it clears is the large one
-        OFX_TRY(ofx_run_loop_cursor(ctx, S, G, upc, N, launch, redo, n_out, err_out, unit_of, inside, ms_out));
-    } else {
-        auto launch = [&](int k, int cnt, double thr) -> int {
-            unsigned long long nit = 0;
-            for (int g = 0; g < G; g++) nit |= (unsigned long long) cnt << (4 * g);
-            return go(k, 1, k, thr, code_of_unit((unsigned) (k / N)), all, nit, nullptr, 0);
-        };
-        auto redo = [&](const int *k_of) -> int {
-            unsigned incode = 0, runmask = 0;
-            unsigned long long nit = 0;
-            for (int g = 0; g < G; g++) {
-                if (k_of[g] < 0) continue;
-                const int n = k_of[g] + 1, j = (n - 1) / N;
-                runmask |= 1u << g;
-                incode |= ((b0[g] + (unsigned) j) % 3u) << (2 * g);
-                nit |= (unsigned long long) (n - j * N) << (4 * g);
-            }
-            return go(0, 0, S.max_iter, -1.0, incode, runmask, nit, nullptr, 0);
-        };
-        int took_alt[OFX_MAX_GROUP];
-        OFX_TRY(ofx_run_loop_group(ctx, S, G, launch, redo, n_out, err_out, ms_out, 0u, took_alt));
-        for (int g = 0; g < G; g++) {
-            unit_of[g] = n_out[g] > 0 ? (n_out[g] - 1) / N : -1;
-            inside[g] = (n_out[g] % N != 0 && n_out[g] != S.max_iter) ? 1 : 0;
-        }
-    }
-    unsigned cur = 0;
-    for (int g = 0; g < G; g++) {
-        const unsigned units = (unsigned) (unit_of[g] + 1);        // the result is the output of the unit that contains iteration n - 1
-        cur |= ((b0[g] + units) % 3u) << (2 * g);
-        L.last_n[g] = n_out[g];
-        if (alt_out) alt_out[g] = inside[g] ? 1 : 0;               // ended inside a unit: its first iterations were re-run
-    }
-    L.cur = cur;
+    // normally the result is the output of the last unit = the input of the next; a loop that stopped on the first
+    // iteration of a pair whose intermediate state was stored continues from the unit's third buffer instead
+    A.done(L, ran, took_alt, n_out);
     return OFX_OK;
 }
 
