@@ -169,6 +169,12 @@ int   ofx_set_option(ofx_ctx *ctx, const char *name, double value);
  *                         do not fit its tile gathers from global memory), 0 = gathered from global memory alone, 2 (default) = by
  *                         measurement: 1 for float and double frames, 0 for 8- and 16-bit frames.  Any other value is OFX_ERR_ARG.
  *                         Results do not depend on it.
+ *   "tvl1_median"    TV-L1 (every entry but the solvers with occlusions, which have the reference's own median): 3 | 5 = after the
+ *                         inner loop of EVERY warp at EVERY level, u1 and u2 of every pair become their 3x3 | 5x5 median (Wedel et
+ *                         al. 2009, section 3.2; "Median of a flow" below, without a map), the last warp included, so the flow that
+ *                         zoom_in takes up and the final payload are filtered; the dual variables stay as they are.  0 (default) =
+ *                         off: not one launch more.  Any other value is OFX_ERR_ARG and leaves the option as it was.  Iteration
+ *                         tables and ofx_stats keep their meaning.  The front-ends read OFX_TVL1_MEDIAN=3|5 for it.
  *   "st_fuse"        ofx_structure_texture_dev: iterations per kernel launch on LDS tiles with a halo of that many pixels: 0 (default) =
  *                         chosen by measurement, 1 .. OFX_ST_MAX_FUSE = that many (1 = one launch per iteration, the A/B
  *                         baseline).  Any other value is OFX_ERR_ARG.  Results do not depend on it.
@@ -494,6 +500,38 @@ int ofx_flow_warp_dev(ofx_ctx *ctx, int n, const void *const *dSrc, const void *
                       const void *const *dFill, void *const *dDst, int nx, int ny, int nz);
 int ofx_flow_interpolate_dev(ofx_ctx *ctx, int n, const void *const *dA, const void *const *dB, const void *const *d_flo_fwd,
                              const void *const *d_flo_bwd, const double *t, void *const *dDst, int nx, int ny, int nz);
+
+/* ---- Median of a flow: outliers removed, flagged vectors filled from their neighbours -----------------------------------------
+ * What cleans a payload between ofx_flow_consistency_dev and ofx_flow_warp_dev.  d_flo_in[g], d_flo_out[g]: payloads as every
+ * *_dev solver writes them, nx * ny interleaved (u, v) float32, 8-byte aligned.  d_occ[g]: a byte map in the convention of
+ * ofx_flow_consistency_dev, 0 = valid, non-zero = flagged, at any byte alignment; d_occ and its entries may be NULL.
+ * For each component on its own, at row i, column j:
+ *   - The window is W x W around the pixel, W = wsize.
+ *   - Indices are mirrored with repetition of the border sample: -k -> k - 1, n - 1 + k -> n - k (the rule of
+ *     me_median_filtering, src/utils.cpp:150-213).  It needs W / 2 <= nx and W / 2 <= ny.
+ *   - A mirrored position counts as often as it occurs.
+ * Unmasked result: the output is element [W * W / 2] of the sorted window.
+ * Masked result, where the slot has a map:
+ *   - Only window positions whose map byte is 0 take part.
+ *   - The output is element [cnt / 2] of the cnt sorted valid values.
+ *   - If cnt = 0, the input value is copied unchanged.
+ *   - A flagged pixel with valid neighbours is therefore filled from them.  A valid pixel is filtered among valid ones only.
+ * Order: -Inf < finite < +Inf < NaN, which is what np.sort does.
+ *   - All NaNs are equal.
+ *   - -0.0 equals +0.0, and which of two equal values is emitted cannot be told.
+ *   - So results are compared with == plus equal NaN positions.
+ *   - A NaN in one window comes out where and only where the definition puts it.
+ * No arithmetic happens on the values.  The result is a selection, exact in every precision: a pure function of the floats and the
+ * bytes, the same bytes from an f64 and an f32 context.  An all-zero map gives what no map gives; an all-flagged map returns the
+ * input.  No byte outside a destination's nx * ny * 8 is written.
+ * n >= 1 slots of any number, OFX_MAX_GROUP = 16 per launch; several slots may read the same payload.  A payload, map or
+ * destination that is not on the context's GPU is staged as ofx_flow_warp_dev stages its buffers.  Asynchronous on the context's
+ * stream.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: a NULL table or entry (but d_occ and its entries),
+ * n < 1, nx < 2 or ny < 2, nx * ny beyond an int, wsize not in {3, 5, 7}, wsize / 2 > min(nx, ny), a payload that is not 8-byte
+ * aligned, a d_flo_out[g] equal to the payload that its own slot reads. */
+int ofx_flow_median_dev(ofx_ctx *ctx, int n, const void *const *d_flo_in, const void *const *d_occ, void *const *d_flo_out, int nx,
+                        int ny, int wsize);
 
 /* ---- structure-texture decomposition on the device: frames for an illumination-robust flow -----------------------------------
  * dTex[g] receives the texture part T = f - alpha * S of frame dSrc[g], S being the structure part: the ROF (total variation)

@@ -138,6 +138,7 @@ def lib():
         "ofx_tvl1_bidir_batch_dev": (_i, [C.POINTER(_vp), _i] + [C.POINTER(_vp)] * 6 + [_i, _i, _i, _d, _d, _d, _i, _d, _i, _d, _d,
                                                                                         _d, C.POINTER(_d)]),
         "ofx_flow_warp_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 5 + [_i, _i, _i]),
+        "ofx_flow_median_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _i]),
         "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
@@ -702,6 +703,15 @@ class Ofx:
         n = len(dSrc)
         arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_warp_dev(self.h, n, arr(dSrc), arr(d_flo), arr(d_occ), arr(dFill), arr(dDst), nx, ny, nz))
+
+    def flow_median_dev(self, d_flo_in, d_flo_out, nx, ny, wsize=5, d_occ=None):
+        """ofx_flow_median_dev: lists of device pointers (ints), one entry per slot: payload d_flo_out[g] receives the wsize x wsize
+        median (3, 5 or 7; per component, borders mirrored) of payload d_flo_in[g].  d_occ: None, or one entry per slot (None / 0:
+        no map for that slot); with a map only the positions it leaves at 0 take part, so flagged vectors are filled from their
+        valid neighbours.  Enqueues on the context's stream."""
+        n = len(d_flo_in)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_median_dev(self.h, n, arr(d_flo_in), arr(d_occ), arr(d_flo_out), nx, ny, wsize))
 
     def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
         """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part

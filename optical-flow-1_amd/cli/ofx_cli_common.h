@@ -11,7 +11,8 @@
 
 /* OFX_DEVICE = GPU index (default 0); OFX_PRECISION = f64 (default, strict) | f32 (float storage); OFX_TOLERANCE=1: the f64
  * tolerance mode of the TV-L1 dual update (option relaxed_dual; not byte-identical .flo files); OFX_SOR_TOLERANCE=1: the tolerance
- * mode of the SOR solvers (option sor_exact = 0); OFX_STATS: see cli_write_stats */
+ * mode of the SOR solvers (option sor_exact = 0); OFX_TVL1_MEDIAN=3|5: TV-L1 with a median filter on the flow after every warp
+ * (option tvl1_median; unset: the bytes stay what they are); OFX_STATS: see cli_write_stats */
 static ofx_ctx *cli_context(void)
 {
     const char *d = getenv("OFX_DEVICE"), *p = getenv("OFX_PRECISION");
@@ -28,6 +29,12 @@ static ofx_ctx *cli_context(void)
     /* OFX_SOR_TOLERANCE=1: Horn-Schunck / Brox, spatial and temporal (brox_temporal: 3-D red-black), with re-ordered
      * sweeps inside the AEPE < 1e-4 bar (option sor_exact = 0) */
     if (getenv("OFX_SOR_TOLERANCE")) ofx_set_option(ctx, "sor_exact", atoi(getenv("OFX_SOR_TOLERANCE")) != 0 ? 0 : 1);
+    /* OFX_TVL1_MEDIAN=3|5: the TV-L1 front-ends filter the flow after every warp (option tvl1_median); any other value is an error */
+    if (getenv("OFX_TVL1_MEDIAN") && ofx_set_option(ctx, "tvl1_median", atoi(getenv("OFX_TVL1_MEDIAN"))) != OFX_OK) {
+        fprintf(stderr, "ERROR: OFX_TVL1_MEDIAN=%s: %s\n", getenv("OFX_TVL1_MEDIAN"), ofx_last_error(ctx));
+        ofx_ctx_destroy(ctx);
+        return NULL;
+    }
     return ctx;
 }
 

@@ -94,6 +94,7 @@ extern "C" int ofx_ctx_create(ofx_ctx **out, int device, int precision)
     ctx->warp_lds = 1;
     ctx->apply_lds = 2;         // by measurement: LDS tiles for float and double frames, global gathers for 8- and 16-bit ones
     ctx->st_fuse = 0;
+    ctx->tvl1_median = 0;
     ctx->gauss_fused = 1;
     ctx->relaxed_dual = 0;
     ctx->tile = 0;              // measured: no faster than the marching strips on the small levels, off by default
@@ -234,6 +235,11 @@ extern "C" int ofx_set_option(ofx_ctx *ctx, const char *name, double value)
     if (!strcmp(name, "relaxed_dual")) { ctx->relaxed_dual = value != 0; return OFX_OK; }
     if (!strcmp(name, "gauss_fused")) { ctx->gauss_fused = (value == 2 || value == 3) ? (int) value : (value != 0); return OFX_OK; }   // 2: the generic-radius fused kernel; 3: radius-templated, zoom_out not fused
     if (!strcmp(name, "warp_lds")) { ctx->warp_lds = value != 0; return OFX_OK; }
+    if (!strcmp(name, "tvl1_median")) {
+        if (value != 0 && value != 3 && value != 5) return ofx_fail(ctx, OFX_ERR_ARG, "tvl1_median must be 0, 3 or 5");
+        ctx->tvl1_median = (int) value;
+        return OFX_OK;
+    }
     if (!strcmp(name, "apply_lds")) {
         if (value != 0 && value != 1 && value != 2) return ofx_fail(ctx, OFX_ERR_ARG, "apply_lds must be 0, 1 or 2");
         ctx->apply_lds = (int) value;

@@ -90,6 +90,7 @@ struct ofx_ctx {
     int warp_lds;       // 1 (default): TV-L1 warp with the taps staged through LDS; 0: gathered from global memory
     int apply_lds;      // ofx_flow_warp_dev / ofx_flow_interpolate_dev: 1 the taps staged through LDS, 0 gathered from global memory,
                         // 2 (default) by measurement: LDS for float and double frames, global for 8- and 16-bit ones
+    int tvl1_median;    // TV-L1: 3 | 5 = the flow of every pair is median-filtered (ofx_median.hip) after the inner loop of every warp; 0 (default) off
     int st_fuse;        // ofx_structure_texture_dev: iterations per launch, 1 .. OFX_ST_MAX_FUSE; 0 (default) = the measured best (ofx_texture.hip)
     int chunk;
     int fuse3;          // TV-L1: three iterations per launch (k_tvl1_iter3): 0 never, 1 levels of >= fuse3_min_px pixels x pairs, 2 auto (default)

@@ -209,7 +209,19 @@ int op_flow_consistency_check(ofx_ctx *ctx, const char *who, int nx, int ny, dou
 int op_flow_consistency(ofx_ctx *ctx, int slots, const void *const *f, const void *const *b, void *const *occ, int nx, int ny,
                         double alpha, double beta);
 
-#define OFX_LAUNCH_CHECK(ctx)                                                                   \
+// ---- the median of a flow (ofx_median.hip) -----------------------------------------------------------------------------------------
+struct OfxMedianSlots {
+    const void          *in[OFX_MAX_GROUP];      // nx * ny interleaved (u, v) pairs
+    const unsigned char *occ[OFX_MAX_GROUP];     // NULL: no map for the slot
+    void                *out[OFX_MAX_GROUP];     // never the slot's `in`
+};
+// The wsize x wsize median of include/ofx.h ("Median of a flow") of slots <= OFX_MAX_GROUP flows in one launch; esize = 4 | 8: the
+// elements are floats (wsize 3, 5, 7) or doubles (3, 5).  The pointers are memory of the context's GPU, aligned to a pair.
+int op_flow_median(ofx_ctx *ctx, int esize, int wsize, int slots, const OfxMedianSlots &S, int nx, int ny);
+// ... and out[z] copied back over in[z], n pairs each, in one launch
+int op_median_copy_back(ofx_ctx *ctx, int esize, int slots, const OfxMedianSlots &S, size_t n);
+
+#define OFX_LAUNCH_CHECK(ctx)                                                                  \
     do {                                                                                         \
         hipError_t e__ = hipGetLastError();                                                      \
         if (e__ != hipSuccess)                                                                   \

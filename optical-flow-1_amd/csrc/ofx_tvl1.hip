@@ -1753,6 +1753,14 @@ static int tvl1_single_scale_dev(ofx_ctx *ctx, Tvl1Level<T> &L, const Tvl1Params
             }
             S.work_pix_iters += (double) it[g] * nx * ny;
         }
+        // option "tvl1_median" (Wedel et al. 2009, section 3.2): u of every pair becomes its W x W median, component by component,
+        // from the buffer its loop ended in; the duals stay.  A (rewritten by the next warp, dead until then) is the scratch.
+        if (ctx->tvl1_median) {
+            OfxMedianSlots M = {};
+            for (int g = 0; g < G; g++) { M.in[g] = L.Ucur(g); M.out[g] = L.A + (size_t) g * n; }
+            OFX_TRY(op_flow_median(ctx, (int) sizeof(T), ctx->tvl1_median, G, M, nx, ny));
+            OFX_TRY(op_median_copy_back(ctx, (int) sizeof(T), G, M, n));
+        }
     }
     return OFX_OK;
 }
