@@ -533,6 +533,68 @@ int ofx_flow_interpolate_dev(ofx_ctx *ctx, int n, const void *const *dA, const v
 int ofx_flow_median_dev(ofx_ctx *ctx, int n, const void *const *d_flo_in, const void *const *d_occ, void *const *d_flo_out, int nx,
                         int ny, int wsize);
 
+/* ---- Flows composed along a sequence: long-range flows and point tracks ---------------------------------------------------------
+ * "Where did this pixel of frame 0 go by frame k?"  The step payloads of a video (ofx_tvl1_sequence_group_dev and its kin) are
+ * chained on the device: follow a point through the step flows, sample each flow at the sub-pixel position reached, stop where the
+ * consistency map flags the position (Sundaram, Brox, Keutzer, "Dense point trajectories by GPU-accelerated large displacement
+ * optical flow", ECCV 2010).  PAYLOADS: as every *_dev solver writes them, nx * ny interleaved (u, v) float32, 8-byte aligned.
+ * MAPS: bytes in the convention of ofx_flow_consistency_dev, 0 = valid, non-zero = flagged / lost, at ANY byte alignment, written
+ * dense with 0 and 255.  No byte outside a destination is written.
+ * All arithmetic in double, every operation rounded once, nothing contracted, association as written:
+ *     inside(x, y)     = x >= 0 && x <= nx - 1 && y >= 0 && y <= ny - 1            (NaN and Inf fail it, before any cast to int)
+ *     sample(S, x, y)  = (bicubic_interpolation_at_color(S, x, y, nx, ny, 2, 0, false), (..., 1, false)), S = a step payload as a
+ *                        2-channel interleaved image of doubles converted exactly from its floats: the sampling of
+ *                        ofx_flow_consistency_dev
+ *     flagged(M, x, y) = for an inside position and a map M: x0 = (int) x, x1 = x0 + (x > x0), y0 = (int) y, y1 = y0 + (y > y0);
+ *                        true if any of M[y0][x0], M[y0][x1], M[y1][x0], M[y1][x1] is non-zero.  At an integer position only the
+ *                        pixel itself counts; no index leaves the map; without a map it is false.
+ *     advance(p, S, M) = one step of a point at the inside position p = (x, y): flagged(M, x, y) -> lost; otherwise (bu, bv) =
+ *                        sample(S, x, y), q = (x + bu, y + bv); !inside(q) -> lost (a NaN or Inf in the step lands here);
+ *                        otherwise the point moves to q.
+ * ofx_flow_compose_dev, one step for slot g at row i, column j:
+ *     (U, V) = ab[i][j];  m = occ_ab[i][j]      (a NULL d_flo_ab table or entry: the zero flow; a NULL d_occ_ab table or entry: 0)
+ *     m != 0 || !inside(j + U, i + V) :  ac[i][j] = ab[i][j] bit for bit, occ_ac[i][j] = 255
+ *     f = flagged(occ_bc, j + U, i + V);  (bu, bv) = sample(bc, j + U, i + V);  Un = (float) (U + bu);  Vn = (float) (V + bv)
+ *     f || !inside(j + Un, i + Vn)    :  ac[i][j] = ab[i][j] bit for bit, occ_ac[i][j] = 255
+ *     otherwise                       :  ac[i][j] = (Un, Vn), occ_ac[i][j] = 0
+ * A lost vector stays where it was lost and stays lost.  With the zero flow for ab the result is bc itself wherever bc's vector
+ * stays inside and is unflagged.  An all-zero bc returns ab with lost vectors flagged.
+ * d_occ_bc, d_occ_ac and their entries may be NULL (no map / the map is not wanted).  d_flo_ac[g] == d_flo_ab[g] and d_occ_ac[g] ==
+ * d_occ_ab[g] are allowed -- a pixel reads only its own element of them: the streaming use, one accumulated payload advanced step
+ * by step.  d_flo_ac[g] == d_flo_bc[g] is refused (and d_occ_ac[g] == d_occ_bc[g]): the step is read at other pixels.
+ * n >= 1 slots of any number, OFX_MAX_GROUP = 16 per launch.
+ * ofx_flow_accumulate_dev, the chain: tables laid out like d_flo of ofx_tvl1_sequence_group_dev, step t of sequence q is element
+ * q * n_steps + t.
+ *     acc[q][0] = compose(zero flow, step[q][0]);  acc[q][t] = compose(acc[q][t - 1], step[q][t])
+ * with occ_acc[q][t] the map of that call and occ_step[q][t] the step's own map.  Every payload and map is bit for bit what the
+ * chained ofx_flow_compose_dev calls write: n_steps launches over all sequences.  n_seq >= 1 of any number, n_steps >= 1.
+ * d_occ_step and d_occ_acc may be NULL, tables or entries; without d_occ_acc the lost state still travels from step to step,
+ * through the context's workspace.  acc[q][t] may be acc[q][t - 1] (only the last payload is wanted); it may not be a step payload
+ * that the chain has yet to read.  A chain backwards in time is the backward payloads handed over in reverse order: step[q][t] =
+ * the payload of frame k - t -> frame k - t - 1 gives acc[q][t] = frame k -> frame k - t - 1 on frame k's grid.
+ * acc[q][k - 1] with its map goes into ofx_flow_warp_dev (frame k registered onto frame 0), into ofx_flow_median_dev (lost vectors
+ * filled from surviving neighbours) and into ofx_tvl1_group_init_dev as the start of a direct 0 -> k solve.
+ * ofx_flow_tracks_dev, sparse query points kept in double, no float rounding between steps.  d_xy0[q]: n_pts interleaved (x, y)
+ * doubles; d_xy[q]: (n_steps + 1) * n_pts interleaved doubles, step-major (position t of point k at 2 * (t * n_pts + k));
+ * d_len[q]: n_pts int32.  Per point:
+ *     p_0 = xy0;  !inside(p_0): len = -1 and every p_t = p_0 bit for bit
+ *     p_{t+1} = advance(p_t, step[q][t], occ_step[q][t]) while the point lives
+ *     the first lost step t sets len = t and every later position repeats p_t;  a point that survives has len = n_steps
+ * One launch marches all steps, a thread owns a point; the step pointers go through a device table, whose upload the call awaits
+ * (it waits for the stream's earlier work), the march itself is asynchronous.
+ * All three are pure functions of the floats, the bytes and the query doubles: the same bytes from an f64 and an f32 context.
+ * A payload, map, position array or destination that is not on the context's GPU is staged as ofx_flow_warp_dev stages its
+ * buffers.  Asynchronous on the context's stream.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: a NULL d_flo_bc / d_flo_ac / d_flo_step / d_flo_acc /
+ * d_xy0 / d_xy / d_len table or entry, n < 1, n_seq < 1, n_steps < 1, n_pts < 1, nx < 2 or ny < 2, nx * ny beyond an int, a payload
+ * or position array that is not 8-byte aligned, a d_len[q] that is not 4-byte aligned, the refused aliases. */
+int ofx_flow_compose_dev(ofx_ctx *ctx, int n, const void *const *d_flo_ab, const void *const *d_occ_ab, const void *const *d_flo_bc,
+                         const void *const *d_occ_bc, void *const *d_flo_ac, void *const *d_occ_ac, int nx, int ny);
+int ofx_flow_accumulate_dev(ofx_ctx *ctx, int n_seq, int n_steps, const void *const *d_flo_step, const void *const *d_occ_step,
+                            void *const *d_flo_acc, void *const *d_occ_acc, int nx, int ny);
+int ofx_flow_tracks_dev(ofx_ctx *ctx, int n_seq, int n_steps, const void *const *d_flo_step, const void *const *d_occ_step, int n_pts,
+                        const void *const *d_xy0, void *const *d_xy, void *const *d_len, int nx, int ny);
+
 /* ---- structure-texture decomposition on the device: frames for an illumination-robust flow -----------------------------------
  * dTex[g] receives the texture part T = f - alpha * S of frame dSrc[g], S being the structure part: the ROF (total variation)
  * smoothing of f by n_iter steps of Chambolle's projection -- the preprocessing of Wedel, Pock, Zach, Bischof, Cremers, "An

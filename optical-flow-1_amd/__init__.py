@@ -139,6 +139,9 @@ def lib():
                                                                                         _d, C.POINTER(_d)]),
         "ofx_flow_warp_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 5 + [_i, _i, _i]),
         "ofx_flow_median_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _i]),
+        "ofx_flow_compose_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 6 + [_i, _i]),
+        "ofx_flow_accumulate_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 4 + [_i, _i]),
+        "ofx_flow_tracks_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 2 + [_i] + [C.POINTER(_vp)] * 3 + [_i, _i]),
         "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
@@ -712,6 +715,48 @@ class Ofx:
         n = len(d_flo_in)
         arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_median_dev(self.h, n, arr(d_flo_in), arr(d_occ), arr(d_flo_out), nx, ny, wsize))
+
+    def flow_compose_dev(self, d_flo_bc, d_flo_ac, nx, ny, d_flo_ab=None, d_occ_ab=None, d_occ_bc=None, d_occ_ac=None):
+        """ofx_flow_compose_dev: lists of device pointers (ints), one entry per slot: payload d_flo_ac[g] receives the flow a -> c,
+        payload d_flo_ab[g] followed by payload d_flo_bc[g] sampled where ab's vector lands.  d_flo_ab: None or entries None / 0: the
+        zero flow.  d_occ_ab / d_occ_bc: None, or one entry per slot (None / 0: no map): vectors lost before this step, and the
+        step's own flagged positions.  d_occ_ac: None, or where the lost vectors are flagged (255).  d_flo_ac[g] may be d_flo_ab[g]
+        and d_occ_ac[g] may be d_occ_ab[g].  Enqueues on the context's stream."""
+        n = len(d_flo_bc)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_compose_dev(self.h, n, arr(d_flo_ab), arr(d_occ_ab), arr(d_flo_bc), arr(d_occ_bc), arr(d_flo_ac),
+                                             arr(d_occ_ac), nx, ny))
+
+    @staticmethod
+    def _step_tables(who, tables):
+        """[sequence][step] lists (or None) -> (n_seq, n_steps, flat ctypes tables or None)"""
+        n_seq = len(tables[0])
+        n_steps = len(tables[0][0]) if n_seq else 0
+        for t in tables:
+            if t is not None and (len(t) != n_seq or any(len(s) != n_steps for s in t)):
+                raise ValueError(who + ": every table needs one entry per sequence and step")
+        arr = lambda t: None if t is None else (_vp * max(n_seq * n_steps, 1))(*[p for s in t for p in s])
+        return n_seq, n_steps, [arr(t) for t in tables]
+
+    def flow_accumulate_dev(self, d_flo_step, d_flo_acc, nx, ny, d_occ_step=None, d_occ_acc=None):
+        """ofx_flow_accumulate_dev: d_flo_step[q] = the device pointers (ints) of the step payloads of sequence q (t -> t + 1, as
+        tvl1_sequence_group_dev writes them), d_flo_acc[q][t] receives the flow 0 -> t + 1 on frame 0's grid.  d_occ_step / d_occ_acc:
+        None, or tables of the same shape (entries None / 0: no map): the steps' consistency maps, and where the vectors lost by
+        step t are flagged.  Enqueues on the context's stream."""
+        n_seq, n_steps, (step, acc, occ_step, occ_acc) = self._step_tables("flow_accumulate_dev", [d_flo_step, d_flo_acc, d_occ_step,
+                                                                                                   d_occ_acc])
+        self._ck(self.L.ofx_flow_accumulate_dev(self.h, n_seq, n_steps, step, occ_step, acc, occ_acc, nx, ny))
+
+    def flow_tracks_dev(self, d_flo_step, n_pts, d_xy0, d_xy, d_len, nx, ny, d_occ_step=None):
+        """ofx_flow_tracks_dev: n_pts query points per sequence followed through its step payloads in double.  d_xy0[q]: n_pts
+        interleaved (x, y) float64; d_xy[q] receives (n_steps + 1) * n_pts positions, step-major; d_len[q] n_pts int32: -1 = the
+        start is outside, t < n_steps = lost in step t (later positions repeat the last one), n_steps = survived.  Enqueues on
+        the context's stream."""
+        n_seq, n_steps, (step, occ_step) = self._step_tables("flow_tracks_dev", [d_flo_step, d_occ_step])
+        if len(d_xy0) != n_seq or len(d_xy) != n_seq or len(d_len) != n_seq:
+            raise ValueError("flow_tracks_dev: one d_xy0, d_xy and d_len per sequence")
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_tracks_dev(self.h, n_seq, n_steps, step, occ_step, n_pts, arr(d_xy0), arr(d_xy), arr(d_len), nx, ny))
 
     def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
         """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part
