@@ -595,6 +595,64 @@ int ofx_flow_accumulate_dev(ofx_ctx *ctx, int n_seq, int n_steps, const void *co
 int ofx_flow_tracks_dev(ofx_ctx *ctx, int n_seq, int n_steps, const void *const *d_flo_step, const void *const *d_occ_step, int n_pts,
                         const void *const *d_xy0, void *const *d_xy, void *const *d_len, int nx, int ny);
 
+/* ---- Track seeds and dense point trajectories ----------------------------------------------------------------------------------
+ * Where the tracks of ofx_flow_tracks_dev should start, and new tracks while a clip runs: the seeding of Sundaram, Brox, Keutzer
+ * (ECCV 2010).  Points are placed on a grid of step x step cells, kept where the smaller eigenvalue of the smoothed structure
+ * tensor reaches a fraction of its image mean, and every new frame is seeded again in the cells that no live track occupies.
+ * FRAMES: ONE-channel frames of the element kind that option "input" selects (all five kinds; OFX_IN_RGB8 collapses to gray),
+ * read under "input_pitch" exactly as ofx_structure_texture_dev reads them.  PAYLOADS and MAPS: as ofx_flow_tracks_dev takes them.
+ * All arithmetic in double whatever the context's precision, every operation rounded once, nothing contracted, association as
+ * written, sqrt correctly rounded:
+ *     f          = (double) sample
+ *     (gx, gy)   = centered_gradient(f)               src/operators.cpp, nz = 1, its border rule: what ofx_centered_gradient computes
+ *     a = gx * gx;  b = gx * gy;  c = gy * gy
+ *     A, B, C    = gaussian(a | b | c, nx, ny, rho)   src/operators.cpp:506-624 with its defaults (reflecting boundary, window 5):
+ *                                                     size = (int) (5 * rho) + 1 taps, rows of the whole plane, then columns, the
+ *                                                     coefficients computed on the host with libm as ofx_gaussian has them
+ *     d = A - C;  e = B + B;  r = sqrt(d * d + e * e)
+ *     lam2       = 0.5 * ((A + C) - r)
+ *     sum64(v)   = p[l] = v[l] + v[l + 64] + v[l + 128] + ... left to right, l = 0 .. 63 (a lane without an element is +0.0);
+ *                  then for s = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + s] for l < s; the value is p[0]
+ *     mean       = sum64([sum64(row i of lam2) for i = 0 .. ny - 1]) / (double) (nx * ny)
+ *     tau        = frac * mean
+ * CELLS are step x step pixels; cell (ca, cb) has the candidate pixel x = ca * step + step / 2, y = cb * step + step / 2 (integer
+ * division), none where that lies beyond nx - 1 or ny - 1.  A candidate has STRUCTURE when lam2[y][x] >= tau (a NaN fails).  A
+ * point p OCCUPIES cell ((int) px / step, (int) py / step) when inside(p) of the section above holds; other points occupy
+ * nothing.  The SEEDS of a frame are the candidates with structure in unoccupied cells, as (x, y) doubles in row-major cell order,
+ * cb outer: the order is part of the result, the same from run to run (a scan, no atomics).
+ * ofx_track_structure_dev: d_lam2[g] receives lam2 of frame dF[g] as nx * ny doubles, d_mean[g] its mean as one double.  d_lam2 and
+ * d_mean may be NULL, tables or entries.  The inspection hook of the fused kernel.
+ * ofx_track_seed_dev: the seeds of n frames.  d_xy_occ: NULL, or a table (NULL entries allowed) of n_occ interleaved (x, y) doubles
+ * per slot that occupy cells.  d_xy_new[g] receives at most cap seeds; d_count[g] two int32: the seeds written, and the seeds
+ * dropped for lack of room -- the last in cell order.  No byte beyond the seeds written is touched.
+ * ofx_track_sequence_dev: n_seq clips of n_frames frames, tables laid out like those of ofx_flow_accumulate_dev: frame f of clip
+ * q at q * n_frames + f, step t at q * (n_frames - 1) + t; d_occ_step optional, table or entries.  d_xy[q]: n_frames * cap
+ * interleaved doubles, frame-major (slot k at frame f at 2 * (f * cap + k)); d_t0[q], d_len[q]: cap int32; d_count[q]: two int32,
+ * slots used and seeds dropped.  The slots start as the seeds of frame 0 with t0 = 0.  For t = 0 .. n_frames - 2:
+ *     every live slot moves by advance(p, step[t], occ_step[t]); a slot lost there keeps len = t - t0 and is dead from frame t + 1 on;
+ *     then the survivors' positions at frame t + 1 occupy cells;
+ *     then the seeds of frame t + 1 are appended in cell order with t0 = t + 1.
+ * A slot that survives to the end has len = n_frames - 1 - t0.  Every used slot has all n_frames positions written: the frames
+ * before t0 repeat the birth position bit for bit, the frames after the loss repeat the last one.  Slots beyond the count are not
+ * written at all.  The slots born at frame 0 are bit for bit the tracks of ofx_flow_tracks_dev from the seeds of frame 0.
+ * Counts and tables stay on the device between the steps: the call makes no host synchronisation; its launches are sized by cap
+ * and the cell count and read the counters on the device.  Up to OFX_MAX_GROUP = 16 frames or clips share every launch, any n.
+ * Pure functions of the samples, floats, map bytes and doubles: the same bytes from an f64 and an f32 context on the same sample
+ * values.  Buffers that are not on the context's GPU are staged as ofx_flow_warp_dev stages them.  Asynchronous on the context's
+ * stream.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: NULL required tables or entries; n, n_seq or cap < 1,
+ * n_occ < 0, n_frames < 2, step < 1, nx < 2 or ny < 2, nx * ny beyond an int; rho not finite or <= 0, or more than
+ * OFX_TRACK_MAX_SIZE taps; frac not finite or < 0; misaligned frames, doubles or int32s; the refusals of "input_pitch"; an output
+ * that is an input of the call or another output of its slot.  OFX_ERR_SIGMA under ofx_zoom_out's rule: size >= nx or size >= ny. */
+#define OFX_TRACK_MAX_SIZE 11   /* the largest (int) (5 * rho) + 1: rho below 2.2 */
+int ofx_track_structure_dev(ofx_ctx *ctx, int n, const void *const *dF, void *const *d_lam2, void *const *d_mean, int nx, int ny,
+                            double rho);
+int ofx_track_seed_dev(ofx_ctx *ctx, int n, const void *const *dF, const void *const *d_xy_occ, int n_occ, void *const *d_xy_new,
+                       void *const *d_count, int cap, int nx, int ny, double rho, double frac, int step);
+int ofx_track_sequence_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *const *dF, const void *const *d_flo_step,
+                           const void *const *d_occ_step, int cap, void *const *d_xy, void *const *d_t0, void *const *d_len,
+                           void *const *d_count, int nx, int ny, double rho, double frac, int step);
+
 /* ---- structure-texture decomposition on the device: frames for an illumination-robust flow -----------------------------------
  * dTex[g] receives the texture part T = f - alpha * S of frame dSrc[g], S being the structure part: the ROF (total variation)
  * smoothing of f by n_iter steps of Chambolle's projection -- the preprocessing of Wedel, Pock, Zach, Bischof, Cremers, "An

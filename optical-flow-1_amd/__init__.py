@@ -142,6 +142,9 @@ def lib():
         "ofx_flow_compose_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 6 + [_i, _i]),
         "ofx_flow_accumulate_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 4 + [_i, _i]),
         "ofx_flow_tracks_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 2 + [_i] + [C.POINTER(_vp)] * 3 + [_i, _i]),
+        "ofx_track_structure_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d]),
+        "ofx_track_seed_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 2 + [_i] + [C.POINTER(_vp)] * 2 + [_i, _i, _i, _d, _d, _i]),
+        "ofx_track_sequence_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 3 + [_i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d, _i]),
         "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
@@ -757,6 +760,41 @@ class Ofx:
             raise ValueError("flow_tracks_dev: one d_xy0, d_xy and d_len per sequence")
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_tracks_dev(self.h, n_seq, n_steps, step, occ_step, n_pts, arr(d_xy0), arr(d_xy), arr(d_len), nx, ny))
+
+    def track_structure_dev(self, dF, nx, ny, rho=1.0, d_lam2=None, d_mean=None):
+        """ofx_track_structure_dev: lists of device pointers (ints), one entry per frame: d_lam2[g] receives the smaller eigenvalue
+        of the structure tensor of frame dF[g] smoothed with a Gaussian of rho (nx * ny float64), d_mean[g] its image mean (one
+        float64); either may be None, or hold None / 0 entries.  Frames are read under the options "input" and "input_pitch".
+        Enqueues on the context's stream."""
+        n = len(dF)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_track_structure_dev(self.h, n, arr(dF), arr(d_lam2), arr(d_mean), nx, ny, rho))
+
+    def track_seed_dev(self, dF, d_xy_new, d_count, cap, nx, ny, rho=1.0, frac=0.1, step=4, d_xy_occ=None, n_occ=0):
+        """ofx_track_seed_dev: the track seeds of the frames dF[g]: the candidates of the step x step cells whose lam2 reaches frac
+        times its image mean, in cell order, without the cells that one of the n_occ points of d_xy_occ[g] (interleaved float64;
+        None / 0: none) occupies.  d_xy_new[g] receives at most cap interleaved (x, y) float64, d_count[g] two int32: seeds
+        written and seeds dropped.  Enqueues on the context's stream."""
+        n = len(dF)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_track_seed_dev(self.h, n, arr(dF), arr(d_xy_occ), n_occ, arr(d_xy_new), arr(d_count), cap, nx, ny, rho,
+                                           frac, step))
+
+    def track_sequence_dev(self, dF, d_flo_step, cap, d_xy, d_t0, d_len, d_count, nx, ny, rho=1.0, frac=0.1, step=4, d_occ_step=None):
+        """ofx_track_sequence_dev: dense point trajectories of device-resident clips.  dF[q]: the frames of clip q, d_flo_step[q] its
+        step payloads (t -> t + 1), d_occ_step: None or the steps' maps (entries None / 0: no map).  Tracks start at the seeds of
+        frame 0, move by the advance rule of flow_tracks_dev, and every later frame is seeded again in the cells that no live
+        track occupies.  d_xy[q] receives n_frames * cap positions, frame-major; d_t0[q] and d_len[q] cap int32 (birth frame and
+        steps lived), d_count[q] two int32: slots used and seeds dropped.  Enqueues on the context's stream."""
+        n_seq, n_steps, (step_t, occ_t) = self._step_tables("track_sequence_dev", [d_flo_step, d_occ_step])
+        n_frames = n_steps + 1
+        if len(dF) != n_seq or any(len(f) != n_frames for f in dF):
+            raise ValueError("track_sequence_dev: every clip needs one frame more than it has steps")
+        if any(len(t) != n_seq for t in (d_xy, d_t0, d_len, d_count)):
+            raise ValueError("track_sequence_dev: one d_xy, d_t0, d_len and d_count per clip")
+        arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_track_sequence_dev(self.h, n_seq, n_frames, arr([p for f in dF for p in f]), step_t, occ_t, cap, arr(d_xy),
+                                               arr(d_t0), arr(d_len), arr(d_count), nx, ny, rho, frac, step))
 
     def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
         """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part

@@ -8,7 +8,9 @@
 //     sample(S, x, y)  = bicubic_interpolation_at_color(S, x, y, nx, ny, 2, 0 / 1, false): flow_check's sample (ofx_flow.hip), both
 //                        channels of a tap in one 8-byte load
 //     flagged(M, x, y) = a non-zero byte among the up to four map pixels around an inside position; false without a map
+// These three and advance() are ofx_advance.h's, shared with ofx_tracks.hip.
 // Pure functions of the float payloads, the byte maps and the double query points: the same bytes in every storage precision.
+#include "ofx_advance.h"
 #include "ofx_device.h"
 #include "ofx_ops.h"
 #include "ofx_pairs.h"
@@ -35,37 +37,6 @@ struct OfxComposeSlots {
     float2              *ac[OFX_MAX_GROUP];
     unsigned char       *occ_ac[OFX_MAX_GROUP];  // NULL: the map is not wanted
 };
-
-OFX_DEV bool cp_inside(double x, double y, int nx, int ny)
-{
-    return x >= 0.0 && x <= (double) (nx - 1) && y >= 0.0 && y <= (double) (ny - 1);
-}
-
-// (x, y) inside: x0 <= nx - 1, and x > x0 only where x0 <= nx - 2 -- no index leaves the map
-OFX_DEV bool cp_flagged(const unsigned char *__restrict__ M, double x, double y, int nx)
-{
-    if (!M) return false;
-    const int x0 = (int) x, y0 = (int) y;
-    const int x1 = x0 + (x > (double) x0 ? 1 : 0), y1 = y0 + (y > (double) y0 ? 1 : 0);
-    const size_t r0 = (size_t) y0 * nx, r1 = (size_t) y1 * nx;
-    return (M[r0 + x0] | M[r0 + x1] | M[r1 + x0] | M[r1 + x1]) != 0;
-}
-
-OFX_DEV double2 cp_sample(const float2 *__restrict__ S, double x, double y, int nx, int ny)
-{
-    const BicubicTaps t = bicubic_taps(x, y, nx, ny);
-    double c1[4], c2[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const double2 v0 = ldw2(S + (size_t) t.row[0] * nx + t.col[k]);
-        const double2 v1 = ldw2(S + (size_t) t.row[1] * nx + t.col[k]);
-        const double2 v2 = ldw2(S + (size_t) t.row[2] * nx + t.col[k]);
-        const double2 v3 = ldw2(S + (size_t) t.row[3] * nx + t.col[k]);
-        c1[k] = cubic_cell(v0.x, v1.x, v2.x, v3.x, t.fy);
-        c2[k] = cubic_cell(v0.y, v1.y, v2.y, v3.y, t.fy);
-    }
-    return make_double2(cubic_cell(c1[0], c1[1], c1[2], c1[3], t.fx), cubic_cell(c2[0], c2[1], c2[2], c2[3], t.fx));
-}
 
 // ---- one step, dense --------------------------------------------------------------------------------------------------------------
 //     (U, V) = ab[i][j] (zero without ab);  m = occ_ab[i][j] (0 without it)
@@ -163,14 +134,8 @@ __global__ __launch_bounds__(256) void k_flow_tracks(const void *const *__restri
     int l = alive ? n_steps : -1;
     for (int t = 0; t < n_steps; t++) {
         if (alive) {
-            bool lose = has_occ && cp_flagged(static_cast<const unsigned char *>(occ[t]), x, y, nx);
-            if (!lose) {
-                const double2 b = cp_sample(static_cast<const float2 *>(flo[t]), x, y, nx, ny);
-                const double qx = x + b.x, qy = y + b.y;
-                if (cp_inside(qx, qy, nx, ny)) { x = qx; y = qy; }
-                else lose = true;
-            }
-            if (lose) { alive = false; l = t; }
+            const unsigned char *M = has_occ ? static_cast<const unsigned char *>(occ[t]) : nullptr;
+            if (!cp_advance(static_cast<const float2 *>(flo[t]), M, x, y, nx, ny)) { alive = false; l = t; }
         }
         const size_t o = 2 * ((size_t) (t + 1) * n_pts + k);
         xy[o] = x;
