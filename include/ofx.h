@@ -653,6 +653,83 @@ int ofx_track_sequence_dev(ofx_ctx *ctx, int n_seq, int n_frames, const void *co
                            const void *const *d_occ_step, int cap, void *const *d_xy, void *const *d_t0, void *const *d_len,
                            void *const *d_count, int nx, int ny, double rho, double frac, int step);
 
+/* ---- The dominant motion of a flow: a robust parametric fit ---------------------------------------------------------------------
+ * How much of a flow is the camera's?  A global motion model -- a translation, a similarity or an affine map -- is fitted to a .flo
+ * payload by iteratively re-weighted least squares with Tukey's biweight (Odobez, Bouthemy, "Robust multiresolution estimation of
+ * parametric motion models", JVCIR 1995); the model's flow, the camera-compensated residual flow and the pixels that disagree with
+ * the model -- the moving foreground -- are what Wang, Schmid, "Action recognition with improved trajectories" (ICCV 2013) build on.
+ * PAYLOADS and MAPS: as ofx_flow_compose_dev takes them: nx * ny interleaved (u, v) float32, 8-byte aligned; bytes at ANY
+ * alignment, 0 = valid, written dense with 0 and 255.  No byte outside a destination is written.  A RECORD is OFX_MOTION_REC = 16
+ * doubles, 8-byte aligned.
+ * All arithmetic in double whatever the context's precision, every operation rounded once, nothing contracted, division correctly
+ * rounded, association as written.  At row i, column j:
+ *     cx = 0.5 * (nx - 1);  cy = 0.5 * (ny - 1);  h = 0.5 * max(nx, ny);  X = (j - cx) / h;  Y = (i - cy) / h
+ *     theta = (t0, a, b, t1, c, d);  mu = (t0 + a * X) + b * Y;  mv = (t1 + c * X) + d * Y          the model's flow
+ *     valid(i, j) = the map byte is 0 (no map: true) && u - u == 0 && v - v == 0                    (NaN and Inf vectors are not)
+ * The WEIGHT of a valid pixel under theta and a cut-off C, in this order:
+ *     du = u - mu;  dv = v - mv;  r2 = du * du + dv * dv;  C2 = C * C
+ *     r2 < C2:  q = 1.0 - r2 / C2;  w = q * q        otherwise w = 0        an unweighted fit has w = 1 on every valid pixel
+ * The twelve MOMENTS:
+ *     S1 = sum w;        SX = sum w * X;          SY = sum w * Y
+ *     SXX = sum (w * X) * X;  SXY = sum (w * X) * Y;  SYY = sum (w * Y) * Y
+ *     U1 = sum w * u;    UX = sum (w * u) * X;    UY = sum (w * u) * Y;    V1, VX, VY the same with v
+ * where an invalid pixel contributes +0.0 to every sum (its terms are not evaluated: a NaN vector poisons nothing) and "sum" is
+ * sum64 over the rows of sum64 over the terms of a row, exactly as the mean of ofx_track_structure_dev is defined above: no
+ * atomics, the order is part of the result, the same from run to run.
+ * The SOLVE, with eps = 1e-12; a fit is DEGENERATE where one of its tests fails, and a NaN fails every test:
+ *     translation:  t0 = U1 / S1;  t1 = V1 / S1;  a = b = c = d = 0                                  test: S1 > 0
+ *     similarity (b = -c, d = a):
+ *         Q = SXX + SYY;  D = Q - (SX * SX + SY * SY) / S1
+ *         a = ((UX + VY) - (SX * U1 + SY * V1) / S1) / D;   c = ((VX - UY) - (SX * V1 - SY * U1) / S1) / D
+ *         t0 = ((U1 - SX * a) + SY * c) / S1;               t1 = ((V1 - SY * a) - SX * c) / S1      tests: S1 > 0, D > eps * Q
+ *     affine: the u and the v system share the matrix [S1 SX SY; SX SXX SXY; SY SXY SYY]; elimination without pivoting:
+ *         l10 = SX / S1;  l20 = SY / S1;  a11 = SXX - l10 * SX;  a12 = SXY - l10 * SY;  a22 = SYY - l20 * SY
+ *         l21 = a12 / a11;  p2 = a22 - l21 * a12
+ *         per right side (r0, r1, r2) = (U1, UX, UY) -> (t0, a, b) and (V1, VX, VY) -> (t1, c, d):
+ *         y1 = r1 - l10 * r0;  y2 = (r2 - l20 * r0) - l21 * y1;  z2 = y2 / p2;  z1 = (y1 - a12 * z2) / a11
+ *         z0 = ((r0 - SX * z1) - SY * z2) / S1;  the solution is (z0, z1, z2)          tests: S1 > 0, a11 > eps * SXX, p2 > eps * SYY
+ * The SCHEDULE of ofx_flow_motion_fit_dev: n_fits >= 1 fits per slot.  A slot without an initial record (a NULL d_motion_init table
+ * or entry) starts from theta = 0 and its fit 0 is unweighted; a slot with one starts from that record's [0..5] and its fit 0 is
+ * weighted from it.  Every later fit is weighted from the theta of the fit before.  The t-th WEIGHTED fit of a slot (t = 0, 1, ...)
+ * uses C_t = max(c_last, c_first * 2^-t), the scaling exact.  A degenerate fit keeps the theta it started from -- for fit 0 the
+ * initial record's theta, or zeros -- and all later fits of the slot are skipped.  The schedule is decided on the device, through
+ * a flag in the record that the kernels of the later fits read: the call makes no host synchronisation.  Launches per call and
+ * chunk of up to OFX_MAX_GROUP = 16 slots: two for each fit and one for the outputs; any n >= 1.
+ * The RECORD d_motion[g]:
+ *     [0..5]   theta
+ *     [6..11]  the same map on pixel indices, u = p0 + p1 * j + p2 * i, v = q0 + q1 * j + q2 * i:
+ *              p1 = a / h;  p2 = b / h;  p0 = (t0 - p1 * cx) - p2 * cy;  q0, q1, q2 likewise from t1, c, d
+ *     [12]     S1 of the last completed fit (0 if none)        [13]  fits completed
+ *     [14]     the cut-off of the inlier map, c_last           [15]  1.0 if the call stopped on a degenerate fit, otherwise 0.0
+ * The OUTPUTS, under the final theta and C = c_last (ofx_flow_motion_fit_dev) or under [0..5] of the record d_motion[g] and C =
+ * cutoff (ofx_flow_motion_apply_dev: a record may also come from the caller, for example a smoothed camera path):
+ *     d_flo_model[g]:  ((float) mu, (float) mv)
+ *     d_flo_resid[g]:  ((float) (u - mu), (float) (v - mv))     the camera-compensated flow; a NaN stays NaN
+ *     d_inlier[g]:     0 where valid && r2 < C2, otherwise 255   the moving foreground and the flagged pixels together
+ * A payload that is exactly the model flow of some theta, on valid pixels, has an all-zero inlier map.  The residual payload in
+ * place turns a flow into the camera-compensated flow.  The model payload goes into ofx_flow_warp_dev as it is.  A slot whose map
+ * flags every pixel returns the starting theta with [15] = 1.
+ * d_occ, d_motion_init, d_flo_model, d_flo_resid and d_inlier may be NULL, tables or entries; in the apply entry d_flo too, then
+ * only the model payload can be asked for.  d_flo_resid[g] == d_flo[g] is allowed where no other slot reads that payload -- a pixel
+ * reads only its own element; every other alias between an output and an input of the call, or between two outputs of a slot, is
+ * refused.  Pure functions of the floats, the bytes and the doubles: the same bytes from an f64 and an f32 context.  A buffer that
+ * is not on the context's GPU is staged as ofx_flow_warp_dev stages its buffers.  Asynchronous on the context's stream.
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: NULL required tables or entries (d_flo and d_motion
+ * of the fit entry, d_motion of the apply entry); n < 1, n_fits < 1; a model that is not one of the three; nx < 2 or ny < 2, nx * ny
+ * beyond an int; c_first, c_last or cutoff not finite or <= 0; c_first < c_last; payloads or records that are not 8-byte aligned;
+ * the refused aliases; the apply entry asked for a residual or a map without d_flo. */
+#define OFX_MOTION_TRANSLATION 2
+#define OFX_MOTION_SIMILARITY  4
+#define OFX_MOTION_AFFINE      6
+#define OFX_MOTION_REC 16       /* doubles per motion record */
+int ofx_flow_motion_fit_dev(ofx_ctx *ctx, int n, const void *const *d_flo, const void *const *d_occ,
+                            const void *const *d_motion_init, void *const *d_motion, int model, int n_fits,
+                            double c_first, double c_last, void *const *d_flo_model, void *const *d_flo_resid,
+                            void *const *d_inlier, int nx, int ny);
+int ofx_flow_motion_apply_dev(ofx_ctx *ctx, int n, const void *const *d_motion, const void *const *d_flo,
+                              const void *const *d_occ, double cutoff, void *const *d_flo_model,
+                              void *const *d_flo_resid, void *const *d_inlier, int nx, int ny);
+
 /* ---- structure-texture decomposition on the device: frames for an illumination-robust flow -----------------------------------
  * dTex[g] receives the texture part T = f - alpha * S of frame dSrc[g], S being the structure part: the ROF (total variation)
  * smoothing of f by n_iter steps of Chambolle's projection -- the preprocessing of Wedel, Pock, Zach, Bischof, Cremers, "An

@@ -22,6 +22,8 @@ F64, F32 = 0, 1
 # option "input": the element kind of the frames that the *_dev entries read (OFX_IN_* of include/ofx.h)
 IN_STORAGE, IN_U8, IN_U16, IN_F32, IN_RGB8 = 0, 1, 2, 3, 4
 MAX_SCALES, MAX_SOLVES = 32, 64
+# the motion models of flow_motion_fit_dev (OFX_MOTION_* of include/ofx.h) and the doubles of a motion record
+MOTION_TRANSLATION, MOTION_SIMILARITY, MOTION_AFFINE, MOTION_REC = 2, 4, 6, 16
 
 _STATUS = {1: "invalid argument", 2: "GaussianSmooth: sigma too large", 3: "out of memory",
            4: "HIP runtime error", 5: "no usable gfx950 device"}
@@ -145,6 +147,8 @@ def lib():
         "ofx_track_structure_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d]),
         "ofx_track_seed_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 2 + [_i] + [C.POINTER(_vp)] * 2 + [_i, _i, _i, _d, _d, _i]),
         "ofx_track_sequence_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 3 + [_i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d, _i]),
+        "ofx_flow_motion_fit_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d] + [C.POINTER(_vp)] * 3 + [_i, _i]),
+        "ofx_flow_motion_apply_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_d] + [C.POINTER(_vp)] * 3 + [_i, _i]),
         "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
@@ -795,6 +799,29 @@ class Ofx:
         arr = lambda xs: (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_track_sequence_dev(self.h, n_seq, n_frames, arr([p for f in dF for p in f]), step_t, occ_t, cap, arr(d_xy),
                                                arr(d_t0), arr(d_len), arr(d_count), nx, ny, rho, frac, step))
+
+    def flow_motion_fit_dev(self, d_flo, d_motion, nx, ny, model=MOTION_AFFINE, n_fits=8, c_first=16.0, c_last=1.0, d_occ=None,
+                            d_motion_init=None, d_flo_model=None, d_flo_resid=None, d_inlier=None):
+        """ofx_flow_motion_fit_dev: lists of device pointers (ints), one entry per slot: record d_motion[g] (MOTION_REC float64)
+        receives the dominant motion of payload d_flo[g] -- a TRANSLATION, SIMILARITY or AFFINE model fitted by n_fits rounds of
+        re-weighted least squares with Tukey's biweight, the cut-off halved from c_first down to c_last.  d_occ: None, or one map
+        per slot (None / 0: none); d_motion_init: None, or records to start from.  d_flo_model / d_flo_resid / d_inlier: None, or
+        where the model's flow, the camera-compensated flow (may be d_flo[g] itself) and the map of the pixels that disagree with
+        the model (255) go.  Enqueues on the context's stream."""
+        n = len(d_flo)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_motion_fit_dev(self.h, n, arr(d_flo), arr(d_occ), arr(d_motion_init), arr(d_motion), model, n_fits,
+                                                c_first, c_last, arr(d_flo_model), arr(d_flo_resid), arr(d_inlier), nx, ny))
+
+    def flow_motion_apply_dev(self, d_motion, nx, ny, cutoff=1.0, d_flo=None, d_occ=None, d_flo_model=None, d_flo_resid=None,
+                              d_inlier=None):
+        """ofx_flow_motion_apply_dev: the outputs of flow_motion_fit_dev under given records d_motion[g] (its own, or the caller's:
+        a smoothed camera path) and the cut-off `cutoff`.  Without d_flo only the model payloads can be asked for.  Enqueues on the
+        context's stream."""
+        n = len(d_motion)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_motion_apply_dev(self.h, n, arr(d_motion), arr(d_flo), arr(d_occ), cutoff, arr(d_flo_model),
+                                                  arr(d_flo_resid), arr(d_inlier), nx, ny))
 
     def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
         """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part

@@ -16,6 +16,7 @@
 #include "ofx_device.h"
 #include "ofx_ops.h"
 #include "ofx_pairs.h"
+#include "ofx_sum64.h"
 
 #include <climits>
 #include <cmath>
@@ -133,22 +134,7 @@ __global__ __launch_bounds__(TK_NT) void k_trk_structure(OfxTrkFrames P, int nx,
     }
 }
 
-// ---- sum64 ------------------------------------------------------------------------------------------------------------------------
-//     p[l] = v[l] + v[l + 64] + v[l + 128] + ...   left to right, l = 0 .. 63; a lane without an element holds +0.0
-//     for s = 32, 16, 8, 4, 2, 1:  p[l] = p[l] + p[l + s] for l < s;  the value is p[0]
-// A wave is the 64 lanes: the order is fixed, so is the result.  Lanes at and above s add what no lower lane reads again.
-OFX_DEV double tk_sum64(const double *__restrict__ v, int n)
-{
-    const int l = (int) threadIdx.x & 63;
-    double p = 0.0;
-    if (l < n) {
-        p = v[l];
-        for (int j = l + 64; j < n; j += 64) p = p + v[j];
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) p = p + __shfl_down(p, s, 64);
-    return p;
-}
+// ---- the mean: sum64 (ofx_sum64.h) over the rows of sum64 over a row ---------------------------------------------------------------
 // one wave per row of lam2: rows[z * ny + i]
 __global__ __launch_bounds__(256) void k_trk_rowsum(OfxTrkFrames P, double *__restrict__ rows, int nx, int ny)
 {
