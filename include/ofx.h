@@ -730,6 +730,77 @@ int ofx_flow_motion_apply_dev(ofx_ctx *ctx, int n, const void *const *d_motion, 
                               const void *const *d_occ, double cutoff, void *const *d_flo_model,
                               void *const *d_flo_resid, void *const *d_inlier, int nx, int ny);
 
+/* ---- Measure and show a flow: error statistics and image encodings ---------------------------------------------------------------
+ * How good is a flow, and what does it look like?  ofx_flow_error_dev compares .flo payloads with their ground truth on the device:
+ * end-point error, Barron's angular error, outlier rates (Middlebury's R-x, KITTI's Fl) and a histogram to take percentiles from.
+ * ofx_flow_encode_dev turns payloads into images: Middlebury's colour wheel (Baker et al., "A database and evaluation methodology
+ * for optical flow", IJCV 2011; colorcode.cpp of its flow-code), the bounded 8-bit x / y coding that two-stream action-recognition
+ * pipelines store, and KITTI's 16-bit coding; ofx_flow_decode_dev reads the latter two back.
+ * PAYLOADS, MAPS, SLOTS as ofx_flow_motion_fit_dev takes them: nx * ny interleaved (u, v) float32, 8-byte aligned; bytes at ANY
+ * alignment, 0 = valid; any n >= 1, OFX_MAX_GROUP = 16 per launch.  A buffer that is not on the context's GPU is staged as
+ * ofx_flow_warp_dev stages its buffers.  Asynchronous on the context's stream, no host synchronisation inside.
+ * All arithmetic in double whatever the context's precision, every operation rounded once, nothing contracted, division and sqrt
+ * correctly rounded, association as written.  Pure functions of the floats and bytes: the same bytes from an f64 and an f32
+ * context.  No byte outside a destination is written.
+ *     fin(x) = (x - x == 0);   shown(u, v) = fin(u) && fin(v) && |u| <= 1e9 && |v| <= 1e9     (Middlebury's unknown marker is not)
+ *
+ * ofx_flow_error_dev.  thr_abs, thr_rel: HOST arrays of n_thr (0 .. 8) values, read before the call returns.  d_occ, d_epe and
+ * d_hist may be NULL, as tables or as entries.  Per pixel, (u, v) the estimate d_flo[g], (gu, gv) the truth d_flo_gt[g]:
+ *     known = (map byte == 0 or no map) && shown(gu, gv);   bad = known && !(fin(u) && fin(v));   good = known && !bad
+ *     good:  du = u - gu;  dv = v - gv;  e2 = du * du + dv * dv;  e = sqrt(e2);  gm = sqrt(gu * gu + gv * gv)
+ *            num = (u * gu + v * gv) + 1.0;   den = sqrt((u * u + v * v) + 1.0) * sqrt((gu * gu + gv * gv) + 1.0)
+ *            c = num / den;  c > 1 -> 1;  c < -1 -> -1;  ae = acos(c)          Barron's angular error in radians, the library's acos
+ *     out_k = bad || (good && e > thr_abs[k] && e > thr_rel[k] * gm)            R1.0 is (1, 0), KITTI's Fl is (3, 0.05)
+ *     bin   = bad ? n_bins - 1 : (q = e / bin_w;  q >= n_bins ? n_bins - 1 : (int) q)         counted over the known pixels
+ * The sums Se = sum e, S2 = sum e2, Sa = sum ae run over the good pixels: a pixel that is not good contributes +0.0 by a select
+ * (its terms are not evaluated), and "sum" is sum64 over the rows of sum64 over the terms of a row, exactly as the moments of
+ * ofx_flow_motion_fit_dev: no floating-point atomics, the order is part of the result.  Counts and the maximum are order-free.
+ * The RECORD d_rec[g]: OFX_ERROR_REC = 16 doubles, 8-byte aligned; ng = [0] - [1]; where ng = 0, [2..7] are 0.0:
+ *     [0] known pixels     [1] bad pixels     [2] Se / ng     [3] sqrt(S2 / ng)     [4] (Sa / ng) * 57.29577951308232  (degrees)
+ *     [5] max e over the good pixels     [6] Se     [7] Sa     (a caller pools slots exactly from [0], [1], [6] and [7])
+ *     [8 + k] the count of out_k; 0.0 for k >= n_thr
+ * d_epe[g]: one float32 per pixel, 4-byte aligned: (float) e where good, +Inf where bad, the quiet NaN 0x7FC00000 elsewhere.
+ * d_hist[g]: n_bins uint32, 4-byte aligned, written, not accumulated.
+ *
+ * ofx_flow_encode_dev / ofx_flow_decode_dev.  Destinations are dense; bytes may sit at any byte address, uint16 images are 2-byte
+ * aligned.  vis = (map byte == 0 or no map) && shown(u, v).
+ * OFX_ENC_WHEEL_RGB8: 3 bytes per pixel, R G B.  maxrad = scale where scale > 0; where scale == 0 the slot's own
+ * max sqrt(u * u + v * v) over its vis pixels, 1.0 if that is 0 or no pixel is vis: found on the device and read by the encode
+ * launch, the call awaits nothing.  A pixel that is not vis is (0, 0, 0).  The wheel has 55 integer RGB entries, six segments,
+ * entry i of a segment, integer divisions:
+ *     RY 15: (255, 255*i/15, 0)       YG 6: (255 - 255*i/6, 255, 0)     GC 4:  (0, 255, 255*i/4)
+ *     CB 11: (0, 255 - 255*i/11, 255)  BM 13: (255*i/13, 0, 255)          MR 6:  (255, 0, 255 - 255*i/6)
+ *     fx = u / maxrad;  fy = v / maxrad;  rad = sqrt(fx * fx + fy * fy);  a = atan2(-fy, -fx) / 3.141592653589793
+ *     fk = (a + 1.0) / 2.0 * 54.0;  k0 = (int) fk;  k1 = (k0 + 1) % 55;  f = fk - k0
+ *     per channel b:  c0 = wheel[k0][b] / 255.0;  c1 = wheel[k1][b] / 255.0;  col = (1.0 - f) * c0 + f * c1
+ *                     rad <= 1 ? col = 1.0 - rad * (1.0 - col) : col = col * 0.75;   byte = (int) (255.0 * col)
+ * The zero vector is white; at scale = 4 the vector (1, 0) is (255, 191, 191) and (-1, 0) is (191, 243, 255).
+ * OFX_ENC_BOUND_U8: 2 bytes per pixel, x then y; scale = the bound B > 0.  Per component f of a vis pixel: f <= -B gives 0,
+ * f >= B gives 255, otherwise (int) (255.0 * (f + B) / (2.0 * B) + 0.5); a pixel that is not vis gets the code of 0.0, 128.
+ * Decoded: f = (float) ((code * (2.0 * B)) / 255.0 - B), the map all 0.
+ * OFX_ENC_KITTI_U16: 3 uint16 per pixel; scale must be 0.  A vis pixel is (q(u), q(v), 1) with x = f * 64.0 + 32768.0: x <= 0
+ * gives 0, x >= 65535 gives 65535, otherwise (int) (x + 0.5); a pixel that is not vis is (0, 0, 0).  Decoded, where the third
+ * value is not 0: f = (float) ((code - 32768.0) / 64.0), map 0; otherwise the payload is (NaN, NaN) and the map 255 -- the error
+ * entry then treats it as unknown even without the map.  d_occ of the decode entry may be NULL, as a table or as entries.
+ *
+ * OFX_ERR_ARG before any work, nothing written, the reason in ofx_last_error: a NULL required table or entry (d_flo, d_flo_gt,
+ * d_rec; d_flo, dDst; dSrc, d_flo); n < 1; nx < 2 or ny < 2, nx * ny beyond an int; n_thr outside 0 .. 8, n_thr > 0 with a NULL
+ * threshold array, a threshold that is negative or not finite; d_hist given with n_bins outside 1 .. 65536 or bin_w not finite or
+ * <= 0; a misaligned payload, record, EPE map, histogram or uint16 image; any output equal to, or overlapping, an input or
+ * another output of the call; a kind that is not one of the three, a scale that is not finite or < 0, scale == 0 for BOUND,
+ * scale != 0 for KITTI, WHEEL in the decode entry. */
+#define OFX_ERROR_REC 16        /* doubles per error record */
+#define OFX_ENC_WHEEL_RGB8 1
+#define OFX_ENC_BOUND_U8   2
+#define OFX_ENC_KITTI_U16  3
+int ofx_flow_error_dev(ofx_ctx *ctx, int n, const void *const *d_flo, const void *const *d_flo_gt, const void *const *d_occ,
+                       int n_thr, const double *thr_abs, const double *thr_rel, void *const *d_rec, void *const *d_epe,
+                       void *const *d_hist, int n_bins, double bin_w, int nx, int ny);
+int ofx_flow_encode_dev(ofx_ctx *ctx, int n, const void *const *d_flo, const void *const *d_occ, int kind, double scale,
+                        void *const *dDst, int nx, int ny);
+int ofx_flow_decode_dev(ofx_ctx *ctx, int n, const void *const *dSrc, int kind, double scale, void *const *d_flo,
+                        void *const *d_occ, int nx, int ny);
+
 /* ---- structure-texture decomposition on the device: frames for an illumination-robust flow -----------------------------------
  * dTex[g] receives the texture part T = f - alpha * S of frame dSrc[g], S being the structure part: the ROF (total variation)
  * smoothing of f by n_iter steps of Chambolle's projection -- the preprocessing of Wedel, Pock, Zach, Bischof, Cremers, "An

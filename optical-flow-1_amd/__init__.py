@@ -24,6 +24,9 @@ IN_STORAGE, IN_U8, IN_U16, IN_F32, IN_RGB8 = 0, 1, 2, 3, 4
 MAX_SCALES, MAX_SOLVES = 32, 64
 # the motion models of flow_motion_fit_dev (OFX_MOTION_* of include/ofx.h) and the doubles of a motion record
 MOTION_TRANSLATION, MOTION_SIMILARITY, MOTION_AFFINE, MOTION_REC = 2, 4, 6, 16
+# the doubles of an error record of flow_error_dev and the encodings of flow_encode_dev / flow_decode_dev (OFX_ENC_*)
+ERROR_REC = 16
+ENC_WHEEL_RGB8, ENC_BOUND_U8, ENC_KITTI_U16 = 1, 2, 3
 
 _STATUS = {1: "invalid argument", 2: "GaussianSmooth: sigma too large", 3: "out of memory",
            4: "HIP runtime error", 5: "no usable gfx950 device"}
@@ -149,6 +152,10 @@ def lib():
         "ofx_track_sequence_dev": (_i, [_vp, _i, _i] + [C.POINTER(_vp)] * 3 + [_i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d, _i]),
         "ofx_flow_motion_fit_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [_i, _i, _d, _d] + [C.POINTER(_vp)] * 3 + [_i, _i]),
         "ofx_flow_motion_apply_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_d] + [C.POINTER(_vp)] * 3 + [_i, _i]),
+        "ofx_flow_error_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, C.POINTER(_d), C.POINTER(_d)] + [C.POINTER(_vp)] * 3 +
+                               [_i, _d, _i, _i]),
+        "ofx_flow_encode_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 2 + [_i, _d, C.POINTER(_vp), _i, _i]),
+        "ofx_flow_decode_dev": (_i, [_vp, _i, C.POINTER(_vp), _i, _d] + [C.POINTER(_vp)] * 2 + [_i, _i]),
         "ofx_structure_texture_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 3 + [_i, _i, _d, _d, _i]),
         "ofx_flow_interpolate_dev": (_i, [_vp, _i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_d), C.POINTER(_vp), _i, _i, _i]),
         "ofx_tvl1_iterations": (_i, [_vp] + [_dp] * 9+ [_i, _i, _d, _d, _d, _i, C.POINTER(_d)]),
@@ -822,6 +829,38 @@ class Ofx:
         arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
         self._ck(self.L.ofx_flow_motion_apply_dev(self.h, n, arr(d_motion), arr(d_flo), arr(d_occ), cutoff, arr(d_flo_model),
                                                   arr(d_flo_resid), arr(d_inlier), nx, ny))
+
+    def flow_error_dev(self, d_flo, d_flo_gt, d_rec, nx, ny, thr_abs=(), thr_rel=(), d_occ=None, d_epe=None, d_hist=None, n_bins=0,
+                       bin_w=0.0):
+        """ofx_flow_error_dev: lists of device pointers (ints), one entry per slot: record d_rec[g] (ERROR_REC float64) receives the
+        error statistics of payload d_flo[g] against the truth d_flo_gt[g]: known and bad pixels, mean and RMS end-point error,
+        mean angular error in degrees, the maximum, the two sums, and for each threshold pair (thr_abs[k], thr_rel[k]) -- up to 8
+        -- the count of outliers.  d_occ: None, or one map per slot (None / 0: none).  d_epe: None, or where the per-pixel error
+        (float32) goes; d_hist: None, or n_bins uint32 per slot for the histogram of bin width bin_w.  Enqueues on the context's
+        stream."""
+        n = len(d_flo)
+        if len(thr_abs) != len(thr_rel):
+            raise ValueError("flow_error_dev: one thr_rel per thr_abs")
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        thr = lambda xs: (_d * max(len(xs), 1))(*[float(x) for x in xs])
+        self._ck(self.L.ofx_flow_error_dev(self.h, n, arr(d_flo), arr(d_flo_gt), arr(d_occ), len(thr_abs), thr(thr_abs), thr(thr_rel),
+                                           arr(d_rec), arr(d_epe), arr(d_hist), n_bins, bin_w, nx, ny))
+
+    def flow_encode_dev(self, d_flo, dDst, nx, ny, kind=ENC_WHEEL_RGB8, scale=0.0, d_occ=None):
+        """ofx_flow_encode_dev: lists of device pointers (ints), one entry per slot: dDst[g] receives payload d_flo[g] as an image:
+        ENC_WHEEL_RGB8 (3 bytes per pixel, Middlebury's colour wheel; scale: the radius of full saturation, 0: the payload's own
+        maximum), ENC_BOUND_U8 (2 bytes per pixel; scale: the bound) or ENC_KITTI_U16 (3 uint16 per pixel; scale 0).  d_occ: None,
+        or one map per slot (None / 0: none): flagged pixels are coded as not shown.  Enqueues on the context's stream."""
+        n = len(d_flo)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_encode_dev(self.h, n, arr(d_flo), arr(d_occ), kind, scale, arr(dDst), nx, ny))
+
+    def flow_decode_dev(self, dSrc, d_flo, nx, ny, kind, scale=0.0, d_occ=None):
+        """ofx_flow_decode_dev: payload d_flo[g] from the ENC_BOUND_U8 or ENC_KITTI_U16 image dSrc[g]; d_occ: None, or where the
+        maps go (255 where a 16-bit pixel is marked invalid).  Enqueues on the context's stream."""
+        n = len(dSrc)
+        arr = lambda xs: None if xs is None else (_vp * max(len(xs), 1))(*xs)
+        self._ck(self.L.ofx_flow_decode_dev(self.h, n, arr(dSrc), kind, scale, arr(d_flo), arr(d_occ), nx, ny))
 
     def structure_texture_dev(self, dSrc, dTex, nx, ny, theta=16.0, alpha=0.95, n_iter=100, dStruct=None):
         """ofx_structure_texture_dev: lists of device pointers (ints), one entry per slot: dTex[g] receives the texture part
